@@ -40,7 +40,6 @@ import tempfile
 import time
 
 # read by the HIP / HSA runtimes when they initialise, so set before anything touches the GPU
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")          # concurrent kernels from several streams (pipelined leg)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # RCCL / cross-process sharing on this driver
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +65,7 @@ NODE_TEST_VALU = 213
 TRI_TEST_VALU = 70
 L1_BYTES_PER_CLK_CU = 64.0  # vector L1 (TCP) data path per CU and clock (guide, cache hierarchy)
 CUS = 256
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
 
 
 def baseline_metric():
@@ -182,6 +182,12 @@ def parse():
     ap.add_argument("--kernel-variant", default="0", help="trx_set_kernel_variant word (tuning / A-B runs; 0 = the product's defaults)")
     ap.add_argument("--dump-frame", default="", help="rank 0 writes the last timed frame (int64 {t, prim} records, "
                                                       ".npy) here, with the scene's flat buffers next to it (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path computed in its LAST timed step, the hit record of every pixel, "
+                         "row-major and all finite: DIR/hit.npy (float32, 1 = hit, 0 = miss), DIR/t.npy (float32 hit distance, "
+                         "0 where the ray missed: the record's +inf) and DIR/prim.npy (triangle index as float64, 4294967295 = "
+                         "miss); beyond 64 MB a fixed, seeded sample of pixels, their indices in DIR/pixel.npy.  The inputs are "
+                         "seeded, so two builds compare output for output")
     return ap.parse_args()
 
 
@@ -539,6 +545,8 @@ def main():
     for s in streams:
         scene.check(s.cuda_stream)
     frame = state["last"]
+    # the last timed step's frame, copied out before the replay and the repeats below write the same buffers again
+    dumped = frame.detach().cpu() if rank == 0 and args.dump_outputs else None
     region_kernel_ms = None
     if one_pair:
         region_kernel_ms = r0.elapsed_time(r1) / args.steps   # average launch duration over the timed region, gaps included
@@ -1330,6 +1338,17 @@ def main():
                  instance_offsets=flat.instance_offsets, tlas_start=np.uint32(flat.tlas_start),
                  view=np.frombuffer(bytes(view), dtype=np.uint8), width=np.uint32(w), height=np.uint32(h),
                  **entry_nodes(flat))
+    if dumped is not None:
+        hits = D.int64_to_hits(dumped)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        if hits.size * 16 > DUMP_BYTES:   # frames beyond 64 MB: a fixed, seeded sample of pixels, their indices in pixel.npy
+            pixel = np.sort(np.random.default_rng(0).choice(hits.size, DUMP_BYTES // 24, replace=False))
+            hits = hits[pixel]
+            np.save(os.path.join(args.dump_outputs, "pixel.npy"), pixel.astype(np.float64))
+        hit = hits["prim"] != T.MISS_PRIM   # a miss carries t = +inf in the record: written as t = 0 beside hit = 0
+        np.save(os.path.join(args.dump_outputs, "hit.npy"), hit.astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "t.npy"), np.where(hit, hits["t"], np.float32(0)).astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "prim.npy"), hits["prim"].astype(np.float64))
     # CPU baseline: the oracle (a port, not the reference binary) on the host cores, rank 0 at N=1 only; it is
     # the only place this file touches oracle/ (as the thing timed beside the GPU, and as the frame's checker)
     if rank == 0 and world == 1 and not args.no_cpu_baseline and args.sim_shards == 1:

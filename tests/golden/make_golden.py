@@ -5,15 +5,7 @@ be executed, so these fixtures are produced by this repo'
 CPU oracle: `bf_*` arrays come from the BVH-independent brute-force query
 (every ray against every triangle), `orc_*` arrays from the CWBVH restatement.
 Each .npz carries its INPUTS (80-byte nodes, triangles, instance table, view)
-and the expected outputs, so the tests do not depend on the builder or on
-/root/reference being present.
-
-The `ref_*` fixtures are built from the two small OBJ assets the reference ships
-(assets/obj/cornell_box.obj, assets/obj/box.obj) with the cameras of their .ron scene
-files.  The reference's licences do not cover its assets (README.md:99), so these
-fixtures hold NO geometry: only the asset's name, SHA-256 digests of the rebuilt
-buffers, the view and the expected hit buffers.  Tests rebuild the inputs from the
-mounted reference checkout and skip where it is absent.
+and the expected outputs, so the tests do not depend on the builder.
 
 Run from the repo root:  python tests/golden/make_golden.py [name-substring ...]
 """
@@ -63,31 +55,14 @@ def tie_scene():
 
 
 ONLY = sys.argv[1:]
-REF_ASSETS = "/root/reference/assets"
 
 
-def ron_camera(path):
-    """eye / look_at / fov of a tray_racing scene file (assets/scenes/*.ron)."""
-    import re
-    txt = open(path).read()
-    vec = lambda key: [float(x) for x in re.search(key + r":\s*\(([^)]*)\)", txt).group(1).split(",")]
-    return vec("eye"), vec("look_at"), float(re.search(r"fov:\s*([-0-9.]+)", txt).group(1))
-
-
-def save(name, flat, view, w, h, extra, asset=None, use_tlas=False):
+def save(name, flat, view, w, h, extra):
     if ONLY and not any(o in name for o in ONLY):
         return
     osc = O.Scene.from_flat(flat)
-    if asset is None:
-        out = dict(nodes=flat.nodes, tri_verts=flat.tri_verts, instance_offsets=flat.instance_offsets,
-                   tlas_start=np.uint32(flat.tlas_start), width=np.uint32(w), height=np.uint32(h))
-    else:
-        # built from one of the reference's OBJ assets: the licences do not cover assets (README.md:99), so the
-        # geometry stays out of the repository; the fixture names the asset and pins the rebuilt buffers by digest
-        import hashlib
-        sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-        out = dict(asset=asset, use_tlas=np.uint32(use_tlas), n_tris=np.uint64(flat.n_tris), n_nodes=np.uint64(flat.n_nodes),
-                   tri_sha256=sha(flat.tri_verts), nodes_sha256=sha(flat.nodes), width=np.uint32(w), height=np.uint32(h))
+    out = dict(nodes=flat.nodes, tri_verts=flat.tri_verts, instance_offsets=flat.instance_offsets,
+               tlas_start=np.uint32(flat.tlas_start), width=np.uint32(w), height=np.uint32(h))
     if view is not None:
         ov = O.view_from_bytes(view)
         out["view"] = view_bytes(view)
@@ -164,8 +139,7 @@ def main():
         return e
 
     save("kitchen_tlas_f16_56x40", flat, view, 56, 40, f16_extra)
-    # 5b. stand-ins for the two ref_* fixtures below that need no reference checkout (so they also run on the GPU box):
-    #     a 14-triangle, two-object scene - one box and a ground quad, the triangle count and object split of
+    # 5b. a 14-triangle, two-object scene - one box and a ground quad, the triangle count and object split of
     #     assets/obj/box.obj - through a TLAS with the camera of assets/scenes/box.ron; the Cornell-class box with the
     #     camera of assets/scenes/cornell_box.ron is fixture 1 above
     def quad(a, b, c, d):
@@ -179,18 +153,6 @@ def main():
     counts = np.array([12, 2], dtype=np.uint64)
     flat = T.flat_build(verts, counts, use_tlas=True)
     save("box14_tlas_48", flat, T.view_from_camera((3.0, 1.5, 1.4), (-3.9438584, 1.5, -1.7303504), 90.0, 48, 48), 48, 48, None)
-    # 6./7. the reference's own small assets (the only geometry it ships), its loader rules and its cameras
-    if os.path.exists(os.path.join(REF_ASSETS, "obj", "cornell_box.obj")):
-        verts, counts = T.load_meshs(os.path.join(REF_ASSETS, "obj", "cornell_box.obj"))
-        eye, look, fov = ron_camera(os.path.join(REF_ASSETS, "scenes", "cornell_box.ron"))
-        flat = T.flat_build(verts, counts)
-        save("ref_cornell_box_64", flat, T.view_from_camera(eye, look, fov, 64, 64), 64, 64, None, asset="cornell_box.obj")
-        verts, counts = T.load_meshs(os.path.join(REF_ASSETS, "obj", "box.obj"))
-        eye, look, fov = ron_camera(os.path.join(REF_ASSETS, "scenes", "box.ron"))
-        flat = T.flat_build(verts, counts, use_tlas=True)
-        save("ref_box_tlas_48", flat, T.view_from_camera(eye, look, fov, 48, 48), 48, 48, None, asset="box.obj", use_tlas=True)
-    else:
-        print("reference assets not mounted: ref_* fixtures left as they are")
 
 
 if __name__ == "__main__":

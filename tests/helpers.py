@@ -14,29 +14,49 @@ def make_scene(T, O, name, n, w, h, tlas=False, seed=1):
     return flat, view, osc, O.view_from_bytes(view)
 
 
-REF_ASSETS = "/root/reference/assets"
-
-
 def golden_inputs(T, g):
-    """(nodes, tri_verts, instance_offsets, tlas_start) of a golden fixture.  Fixtures made from the reference's own
-    OBJ assets carry no geometry ("MIT & Apache 2.0 Licenses don't apply to assets", README.md:99): only the asset's
-    name, the expected outputs and SHA-256 digests of the buffers; their inputs are rebuilt from the mounted
-    reference checkout (deterministic loader + builder) and checked against the digests, or the test is skipped."""
-    import hashlib
-    import os
+    """(nodes, tri_verts, instance_offsets, tlas_start) of a golden fixture: every fixture carries its own inputs."""
+    return g["nodes"], g["tri_verts"], g["instance_offsets"], int(g["tlas_start"])
 
-    import pytest
-    if "nodes" in g.files:
-        return g["nodes"], g["tri_verts"], g["instance_offsets"], int(g["tlas_start"])
-    path = os.path.join(REF_ASSETS, "obj", str(g["asset"]))
-    if not os.path.exists(path):
-        pytest.skip("fixture built from %s: the reference checkout is not mounted here" % g["asset"])
-    verts, counts = T.load_meshs(path)
-    flat = T.flat_build(verts, counts, use_tlas=bool(g["use_tlas"]))
-    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-    assert sha(flat.tri_verts) == str(g["tri_sha256"]), "loader / builder no longer reproduce the fixture's triangles"
-    assert sha(flat.nodes) == str(g["nodes_sha256"]), "builder output changed: regenerate tests/golden (make_golden.py ref_)"
-    return flat.nodes, flat.tri_verts, flat.instance_offsets, flat.tlas_start
+
+def obj_text(scene):
+    """OBJ text standing in for the reference's two small assets (assets/obj/<scene>.obj), which this repository does
+    not carry: `cornell_box` = the Cornell-class stand-in of cornell_64, every triangle by relative indices, one `o` per
+    object; `box` = the 14-triangle two-object box of box14_tlas_48 (one box, one ground quad), faces as quads."""
+    if scene == "cornell_box":
+        import tray_racing_amd as T
+        verts, counts = T.gen_scene("cornell", 0, 1)
+        lines, k = ["# Cornell-class stand-in"], 0
+        for i, n in enumerate(counts):
+            lines.append("o part%d" % i)
+            for tri in verts[k:k + int(n)]:
+                lines += ["v %.9g %.9g %.9g" % tuple(float(x) for x in tri[j:j + 3]) for j in (0, 3, 6)]
+                lines.append("f -3 -2 -1")
+            k += int(n)
+        return "\n".join(lines) + "\n"
+    return """# box and ground
+o box
+v -1 0 -1
+v 1 0 -1
+v 1 0 1
+v -1 0 1
+v -1 2 -1
+v 1 2 -1
+v 1 2 1
+v -1 2 1
+f 1 2 3 4
+f 5 8 7 6
+f 1 5 6 2
+f 2 6 7 3
+f 3 7 8 4
+f 4 8 5 1
+o ground
+v -6 -0.001 -6
+v 6 -0.001 -6
+v 6 -0.001 6
+v -6 -0.001 6
+f 9 10 11 12
+"""
 
 
 def bits(a):
