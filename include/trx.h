@@ -230,6 +230,49 @@ int trx_scene_get_instance_transform(const trx_scene *scene, uint32_t instance_i
 /* The world-to-object rows the kernels use: 3 rows of {m0 m1 m2 t}; x' = ((m0*x + m1*y) + m2*z) + t. */
 int trx_scene_get_instance_world_to_object(const trx_scene *scene, uint32_t instance_id, float out_rows[12]);
 
+/* ---- refit: geometry moves, topology stays ------------------------------------------------------------------------
+ * A refit gives the scene new f32 vertices for every triangle record, in the scene's record order (the layout of
+ * trx_flat.tri_verts, TRX_TRI_VERTS_36: 9 floats per record; object-order vertices map through trx_flat.tri_source),
+ * and then
+ *  - rewrites the 48-byte device triangle records exactly as trx_scene_create does for TRX_TRI_VERTS_36;
+ *  - recomputes every node's quantisation frame (p, e) and the quantised bytes of every used child slot, bottom-up,
+ *    with the builder's rules: a leaf child's box is the f32 min / max over the three vertices of each of its
+ *    triangles; an inner child's box is the exact union of that child node's own child boxes (kept in f32, never
+ *    decoded from the bytes); the frame and bytes follow the builder's encoder; a TLAS leaf child's box is the union of
+ *    its primitives' boxes, primitive k's box being the refit box of BLAS node instance_offsets[k] + entry[k] - with
+ *    instance transforms, its 8 corners taken through object_to_world[k] and padded as trx_flat_build_instanced pads
+ *    them, without transforms used as it is (as trx_flat_build's TLAS does).
+ * It keeps imask, child_base_idx, primitive_base_idx, child_meta, the bytes of empty slots, the instance table and the
+ * entry nodes.  So a refit with the vertices (and transforms) a scene was built from returns its nodes byte for byte for
+ * single-level builds without pre-splitting (trx_set_build_split(0), the default), trx_flat_build TLAS builds without
+ * re-braiding (trx_set_build_rebraid(0)) and trx_flat_build_instanced scenes.  Pre-split and re-braided scenes get boxes
+ * that bound everything they must but are not the build's bytes (a split reference gets its whole triangle's box, an
+ * entry subtree its exact box instead of the decoded, outward-rounded one).  The tree was built for the old geometry:
+ * walks cost more as the geometry moves away from it, and when to rebuild is the caller's decision.
+ *
+ * Moving instances: trx_scene_set_instance_transforms, then a refit (with the unchanged vertices) - the TLAS boxes then
+ * bound the moved instances.  A vertex refit of a two-level scene refits its TLAS too.
+ * Refused with TRX_ERR_INVALID, the scene left unchanged: a count other than the scene's triangle count, a null pointer,
+ * a non-finite coordinate, a scene created from TRX_TRI_F16_24.
+ * Ordering: every launch enqueued on the scene before the call sees the old geometry in full, every launch enqueued
+ * after it returns the new one; both forms return once the refit has finished on the device.  The scene's ray services
+ * (trx_traverse1) are stopped for the refit; callers arriving meanwhile wait and restart them. */
+/* tri_verts (host memory): n_tris * 9 floats. */
+int trx_scene_refit(trx_scene *scene, const float *tri_verts, uint64_t n_tris);
+/* The same from device memory on the scene's device (e.g. a torch tensor), ordered on `stream` (NULL = null stream).
+ * A pointer that is not a device allocation of the scene's device, or whose allocation ends before n_tris * 36 bytes,
+ * is refused (TRX_ERR_INVALID) before anything reads it. */
+int trx_scene_refit_dev(trx_scene *scene, const float *d_tri_verts, uint64_t n_tris, void *stream);
+/* The node buffer as the kernels now see it (n_nodes * 80 B), for checking and for handing to other consumers. */
+int trx_scene_read_nodes(trx_scene *scene, void *out_nodes, uint64_t n_nodes);
+/* Host twin, no device needed: `nodes` (n_nodes * 80 B) refitted over tri_verts into out_nodes (may equal nodes), the
+ * bytes trx_scene_refit produces.  instance_offsets / n_instances / tlas_start as for trx_scene_create; entry_nodes
+ * (n_instances, or NULL = node 0) and object_to_world (n_instances column-major 4x4, or NULL = no transforms) as the
+ * scene setters take them. */
+int trx_refit_nodes(const void *nodes, uint64_t n_nodes, const float *tri_verts, uint64_t n_tris,
+                    const uint32_t *instance_offsets, uint32_t n_instances, uint32_t tlas_start,
+                    const uint32_t *entry_nodes, const float *object_to_world, void *out_nodes);
+
 /* ---- camera ---------------------------------------------------------------
  * ViewUniform::from_camera (src/main.rs:602-616): proj_inv =
  * inverse(perspective_infinite_reverse_rh(fov_deg->rad, w/h, 0.01)),

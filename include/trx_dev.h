@@ -56,6 +56,12 @@ int trx_debug_traverse1_stats(trx_scene *scene, uint64_t *out_launches, uint64_t
 int trx_debug_service_stats(trx_scene *scene, uint64_t *out_rays, uint64_t *out_starts, uint64_t *out_call_ns,
                             uint64_t *out_walk_ticks, uint64_t *out_walk_trips);
 
+/* The scene's derived launch words as the kernels get them: exp_exact (0, 1 or 2: which exact shortcuts the node test may
+ * take, trx_scene_create / trx_scene_refit derive it from the node bytes), the scene diagonal that scales camera-cut
+ * detection, and the number of height levels of the refit's cached schedule (0 before the first refit).  Any pointer may
+ * be NULL. */
+int trx_debug_scene_info(trx_scene *scene, uint32_t *out_exp_exact, float *out_scene_diag, uint32_t *out_refit_levels);
+
 /* Measuring aid: the reference's CPU pixel loop over the literal Traversable::traverse (src/rt_cpu/rt_cpu.rs:35-57) -
  * `threads` host threads, thread k calls trx_traverse1 for rays k, k + threads, ... - with the loop's wall-clock seconds and
  * the launches its calls shared. */

@@ -98,6 +98,10 @@ SIGNATURES = {
     "trx_scene_set_instance_transforms": (_i, [_P, _P, _u32]),
     "trx_scene_get_instance_transform": (_i, [_P, _u32, _P]),
     "trx_scene_get_instance_world_to_object": (_i, [_P, _u32, _P]),
+    "trx_scene_refit": (_i, [_P, _P, _u64]),
+    "trx_scene_refit_dev": (_i, [_P, _P, _u64, _P]),
+    "trx_scene_read_nodes": (_i, [_P, _P, _u64]),
+    "trx_refit_nodes": (_i, [_P, _u64, _P, _u64, _P, _u32, _u32, _P, _P, _P]),
     "trx_view_from_camera": (_i, [C.POINTER(_f), C.POINTER(_f), _f, _f, _f, C.POINTER(View)]),
     "trx_trace_primary_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _P, _P]),
     "trx_trace_primary_inst_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _P, _P, _P]),
@@ -122,6 +126,7 @@ SIGNATURES = {
     "trx_trace_rays_inst": (_i, [_P, _P, _u64, _u32, _P, _P, C.POINTER(_f)]),
     "trx_traverse1": (_i, [_P, C.POINTER(Ray), _u32, C.POINTER(RayHit)]),
     "trx_debug_traverse1_stats": (_i, [_P, C.POINTER(_u64), C.POINTER(_u64)]),
+    "trx_debug_scene_info": (_i, [_P, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_u32)]),
     "trx_debug_fetch_rate": (_i, [_P, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "trx_debug_copy_rate": (_i, [_i, _u64, _u32, C.POINTER(C.c_double)]),
     "trx_debug_service_stats": (_i, [_P] + [C.POINTER(_u64)] * 5),

@@ -35,7 +35,7 @@ int fail_msg(int code, const char *fmt, ...) {
 }
 } // namespace trx
 
-namespace {
+namespace trxapi {
 
 // Structural validation of untrusted node buffers: a kernel that walks a
 // malformed tree would read out of bounds (and can take the GPU down), so
@@ -90,6 +90,10 @@ int validate_nodes(const CwbvhNode *nodes, uint64_t n_nodes, uint64_t n_tris, co
     }
     return TRX_OK;
 }
+
+} // namespace trxapi
+
+namespace {
 
 float half_to_float(uint16_t h) {
     uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1f, man = h & 0x3ffu, bits;
@@ -216,6 +220,7 @@ int trx_scene_create(const void *bvh_bytes, uint64_t n_nodes, const void *tri_by
     s->n_inst = n_instances;
     s->tlas_start = tlas_start;
     s->tlas = n_instances > 0;
+    s->tri_format = tri_format;
 
     std::vector<TriDev> tris(std::max<uint64_t>(n_tris, 1));
     convert_tris(tri_bytes, n_tris, tri_format, tris.data());
@@ -326,6 +331,7 @@ void trx_scene_destroy(trx_scene *s) {
         if (fl.ao_inst) (void)hipFree(fl.ao_inst);
     }
     delete s->comb;
+    refit_state_free(s);
     delete s;
 }
 
@@ -342,6 +348,8 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     }
     // trx_frame_loop's record buffers (four primary, one AO; instance ids beside them on two-level scenes)
     bytes += s->loop.records * (FrameLoop::kBuffers + 1) * (sizeof(trx_hit) + (s->tlas ? sizeof(uint32_t) : 0));
+    // trx_scene_refit's schedule and node boxes (after the first refit)
+    bytes += refit_state_bytes(s);
     return bytes;
 }
 int trx_scene_device(const trx_scene *s) { return s ? s->device : -1; }
@@ -352,13 +360,17 @@ int trx_scene_set_geometry_ranges(trx_scene *s, const uint32_t *blas_tri_start, 
     return TRX_OK;
 }
 
+} // extern "C"
+
 // The scene under a launch slot's frozen tile order changed (instances moved, entry nodes replaced): the next frame of
 // every slot files a new order even if its camera has not moved - an order learnt for other geometry is only stale, never
 // wrong, but a static camera would replay it for ever.  Call with s->mu held.
-static void forget_tile_orders(trx_scene *s) {
+void trxapi::forget_tile_orders(trx_scene *s) {
     for (Slot &sl : s->slots)
         for (auto &o : sl.order) o.have_views = false;
 }
+
+extern "C" {
 
 // Entry nodes: TLAS primitive k starts its BLAS walk at node entry_nodes[k] of the BLAS at instance_offsets[k] instead
 // of node 0, so one BLAS can be referenced as several subtrees (re-braiding: a BLAS whose box spans the scene no longer
@@ -368,6 +380,7 @@ int trx_scene_set_instance_entry_nodes(trx_scene *s, const uint32_t *entry_nodes
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
     HIP_TRY(hipSetDevice(s->device));
     uint32_t *fresh = nullptr;
+    std::vector<uint32_t> host_copy;
     if (entry_nodes && n) {
         if (!s->tlas) return fail(TRX_ERR_INVALID, "entry nodes need a TLAS scene");
         if (n != s->n_inst) return fail(TRX_ERR_INVALID, "%u entry nodes for %u instances", n, s->n_inst);
@@ -379,6 +392,11 @@ int trx_scene_set_instance_entry_nodes(trx_scene *s, const uint32_t *entry_nodes
             const uint32_t seg_end = it == seg.end() ? s->tlas_start : *it;
             if ((uint64_t)s->h_inst[k] + entry_nodes[k] >= seg_end)
                 return fail(TRX_ERR_FORMAT, "instance %u: entry node %u leaves its BLAS [%u, %u)", k, entry_nodes[k], s->h_inst[k], seg_end);
+        }
+        try { // (host copy for the refit's schedule, which follows the walk into the entry nodes; taken before the swap)
+            host_copy.assign(entry_nodes, entry_nodes + n);
+        } catch (const std::exception &) {
+            return fail(TRX_ERR_OOM, "host allocation failed");
         }
         HIP_TRY(hipMalloc(&fresh, (size_t)n * sizeof(uint32_t)));
         const hipError_t e = hipMemcpy(fresh, entry_nodes, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -392,6 +410,8 @@ int trx_scene_set_instance_entry_nodes(trx_scene *s, const uint32_t *entry_nodes
         std::lock_guard<std::mutex> lock(s->mu);
         old = s->d_inst_entry;
         s->d_inst_entry = fresh;
+        s->h_inst_entry.swap(host_copy); // (no-throw: device and host copies change together)
+        s->inst_entry_version++;
         forget_tile_orders(s);
     }
     HIP_TRY(hipDeviceSynchronize());

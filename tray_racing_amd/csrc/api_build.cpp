@@ -1,6 +1,7 @@
 // api_build.cpp - host side: builders, the flat-buffer assembly of cwbvh_gpu_runner (src/rt_gpu/mod.rs:16-112),
 // scene generators and loaders.
 #include "api_internal.h"
+#include "refit_gpu.h"
 
 namespace {
 
@@ -503,24 +504,9 @@ static int flat_build_impl(const float *verts, const uint64_t *object_tri_counts
             if (instance_object) {
                 tlas_boxes.assign(n_instances, Aabb{});
                 for (uint32_t k = 0; k < n_instances; k++) {
-                    const Aabb &bb = blas_aabb[blas_of_object[instance_object[k]]];
-                    Aabb wb;
-                    for (int a = 0; a < 3; a++) { wb.mn[a] = 3.402823466e+38f; wb.mx[a] = -3.402823466e+38f; }
-                    for (int c = 0; c < 8; c++) {
-                        const float p[3] = {c & 1 ? bb.mx[0] : bb.mn[0], c & 2 ? bb.mx[1] : bb.mn[1], c & 4 ? bb.mx[2] : bb.mn[2]};
-                        float q[3] = {p[0], p[1], p[2]};
-                        if (instance_o2w) {
-                            const float *m = instance_o2w + (size_t)k * 16;
-                            for (int r = 0; r < 3; r++) q[r] = m[r] * p[0] + m[4 + r] * p[1] + m[8 + r] * p[2] + m[12 + r];
-                        }
-                        for (int a = 0; a < 3; a++) { wb.mn[a] = std::min(wb.mn[a], q[a]); wb.mx[a] = std::max(wb.mx[a], q[a]); }
-                    }
-                    for (int a = 0; a < 3; a++) {
-                        const float pad = 1e-5f * (std::max(std::fabs(wb.mn[a]), std::fabs(wb.mx[a])) + (wb.mx[a] - wb.mn[a])) + 1e-30f;
-                        wb.mn[a] -= pad;
-                        wb.mx[a] += pad;
-                    }
-                    tlas_boxes[k] = wb;
+                    // (the rule trx_scene_refit applies to the refitted BLAS boxes, refit_gpu.h)
+                    instance_world_box(blas_aabb[blas_of_object[instance_object[k]]], instance_o2w ? instance_o2w + (size_t)k * 16 : nullptr,
+                                       tlas_boxes[k]);
                 }
             }
             // TLAS over the BLAS boxes (src/cwbvh.rs:114,132); instance table in TLAS

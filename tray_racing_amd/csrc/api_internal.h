@@ -5,6 +5,7 @@
 //   api_trace.cpp    the trace / count / bench / diagnostic entry points (device-resident and host-buffer forms)
 //   api_traverse.cpp Traversable::traverse for one ray (concurrent callers share launches) and for batches
 //   api_build.cpp    builders, flat-buffer assembly (cwbvh_gpu_runner's host half), scene generators and loaders
+//   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -57,6 +58,7 @@ extern std::atomic<uint32_t> g_variant; // tuning aid (trx_set_kernel_variant), 
     } while (0)
 
 constexpr int kSlots = 8;
+struct RefitState; // api_refit.cpp
 constexpr uint32_t kDefaultWavesPerBlock = 1;
 
 struct Slot {
@@ -255,6 +257,10 @@ struct trx_scene {
     // the kernels use them, and their device copy; empty / null = identity
     std::vector<float> inst_o2w, inst_w2o;
     float4 *d_inst_xform = nullptr;
+    uint32_t tri_format = 0;                 // trx_tri_format the scene was created from (trx_scene_refit takes the f32 ones)
+    std::vector<uint32_t> h_inst_entry;      // host copy of the entry nodes (empty = node 0 everywhere) ...
+    uint64_t inst_entry_version = 0;         // ... bumped whenever they are set: the refit's cached schedule follows them
+    trxapi::RefitState *refit = nullptr;     // trx_scene_refit: schedule, node boxes, stream (api_refit.cpp; created on first use)
 };
 
 struct trx_bvh {
@@ -269,6 +275,14 @@ void fill_view(const trx_view *v, trx::ViewDev &out);
 int enqueue(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream, trx::SlotCounters **ctr_out);
 int image_params(trx::TraceParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard);
 int read_overflow(trx_scene *s, trx::SlotCounters *ctr);
+// structural validation of an untrusted node buffer (api.cpp): every index a walk can form is in range
+int validate_nodes(const CwbvhNode *nodes, uint64_t n_nodes, uint64_t n_tris, const uint32_t *inst, uint32_t n_inst,
+                   uint32_t tlas_start);
+// the scene under the launch slots' learnt tile orders changed: the next frame of every slot files a new order (s->mu held)
+void forget_tile_orders(trx_scene *s);
+// trx_scene_refit's per-scene state (api_refit.cpp)
+void refit_state_free(trx_scene *s);
+uint64_t refit_state_bytes(const trx_scene *s);
 // explicit rays (api_trace.cpp; trx_traverse1's batches launch through it)
 int trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
                     trx::SlotCounters **ctr, bool any_hit = false, uint32_t *d_inst = nullptr, uint32_t *over_host = nullptr,

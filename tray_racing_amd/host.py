@@ -251,6 +251,31 @@ def pack_tris_f16(tri_verts):
     return out
 
 
+# ---- refit (host twin) ----------------------------------------------------------------
+
+def record_order_verts(flat, object_verts):
+    """Object-order vertices (what the build was given, [n, 9]) in the scene's triangle-record order: flat.tri_source
+    names the input triangle of every record (pre-split references repeat theirs)."""
+    return np.ascontiguousarray(np.asarray(object_verts, dtype=np.float32).reshape(-1, 9)[flat.tri_source])
+
+
+def refit_nodes(flat, tri_verts, object_to_world=None, nodes=None):
+    """trx_refit_nodes, the host twin of Scene.refit (no GPU): `nodes` (default flat.nodes) refitted over tri_verts
+    (record order) with flat's instance table and entry nodes; object_to_world [n_instances, 16] or None.  Returns the
+    new [n_nodes, 20] u32 buffer."""
+    lib = L.load()
+    src = np.ascontiguousarray(flat.nodes if nodes is None else nodes, dtype=np.uint32).reshape(-1, 20)
+    v = np.ascontiguousarray(tri_verts, dtype=np.float32).reshape(-1, 9)
+    inst = flat.instance_offsets
+    entry = getattr(flat, "instance_entry", None)
+    xf = None if object_to_world is None else np.ascontiguousarray(object_to_world, dtype=np.float32).reshape(-1, 16)
+    out = np.empty_like(src)
+    L.check(lib.trx_refit_nodes(_ptr(src), src.shape[0], _ptr(v), v.shape[0], _ptr(inst) if inst.size else None, inst.size,
+                                flat.tlas_start, _ptr(entry) if entry is not None else None,
+                                _ptr(xf) if xf is not None else None, _ptr(out)))
+    return out
+
+
 # ---- device scene ---------------------------------------------------------------------
 
 class Scene:
@@ -297,6 +322,37 @@ class Scene:
         out = np.zeros((n, 12), dtype=np.float32)
         for k in range(n):
             L.check(self._lib.trx_scene_get_instance_world_to_object(self._h, k, _ptr(out[k])))
+        return out
+
+    def refit(self, tri_verts):
+        """New vertices for every triangle record, in record order ([n_tris, 9] f32; record_order_verts maps object-order
+        vertices): trx_scene_refit for a numpy array, trx_scene_refit_dev on torch.cuda.current_stream() for a tensor on
+        the GPU.  Nodes and records are rewritten in place, the topology kept (include/trx.h, "refit")."""
+        n = self.flat.n_tris
+        if hasattr(tri_verts, "data_ptr") and getattr(tri_verts, "is_cuda", False):
+            import torch
+            if tri_verts.dtype != torch.float32 or tri_verts.numel() != n * 9:
+                raise L.TrxError(L.TRX_ERR_INVALID, "refit needs %d x 9 float32 vertices" % n)
+            dev = self._lib.trx_scene_device(self._h)
+            if tri_verts.device.index != dev:   # (the library refuses it too: the kernels read the tensor on the scene's device)
+                raise L.TrxError(L.TRX_ERR_INVALID, "vertices on %s for a scene on device %d" % (tri_verts.device, dev))
+            t = tri_verts.contiguous()
+            L.check(self._lib.trx_scene_refit_dev(self._h, C.c_void_p(t.data_ptr()), n,
+                                                  C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
+            return
+        v = np.ascontiguousarray(tri_verts, dtype=np.float32).reshape(-1, 9)
+        L.check(self._lib.trx_scene_refit(self._h, _ptr(v), v.shape[0]))
+
+    def info(self):
+        """The scene's derived launch words (trx_debug_scene_info): exp_exact, scene_diag and the refit schedule's level count."""
+        e, d, lv = C.c_uint32(), C.c_float(), C.c_uint32()
+        L.check(self._lib.trx_debug_scene_info(self._h, C.byref(e), C.byref(d), C.byref(lv)))
+        return {"exp_exact": e.value, "scene_diag": d.value, "refit_levels": lv.value}
+
+    def read_nodes(self):
+        """[n_nodes, 20] u32: the node buffer as the kernels now see it (trx_scene_read_nodes)."""
+        out = np.empty((self.flat.n_nodes, 20), dtype=np.uint32)
+        L.check(self._lib.trx_scene_read_nodes(self._h, _ptr(out), out.shape[0]))
         return out
 
     def close(self):
