@@ -117,6 +117,27 @@ typedef struct trx_hit {
     uint32_t prim;
 } trx_hit;
 
+/* Hit attributes, 24 B per hit record (trx_hit_attributes_*): what a renderer shades a hit with, beyond t and prim -
+ * the reference's triangle test writes barycentric = float2(u, v) when it commits (query.hlsl:89-129), and its
+ * Intersectable trait has compute_barycentric / compute_normal (traversable/src/lib.rs:31-43).
+ *  u, v    the barycentrics the committing triangle test computed, over the 48-byte record {v0, e1 = v0 - v1,
+ *          e2 = v2 - v0, ng = cross(e1, e2)}: c = v0 - o, r = cross(d, c), det = dot(ng, d), u = dot(r, e2) * (1 / det),
+ *          v = dot(r, e1) * (1 / det), every dot (x*x' + y*y') + z*z' without contraction.  (o, d) is the ray that test
+ *          saw: the world ray with every zero direction component replaced by FLT_EPSILON, or - on a scene with instance
+ *          transforms - the world ray as given taken through the instance's world-to-object rows
+ *          (trx_scene_get_instance_world_to_object) and then fixed the same way.
+ *          Convention (DXR's): u weights v1 and v weights v2, the hit point is (1 - u - v) * v0 + u * v1 + v * v2.
+ *  normal  the record's ng - with instance transforms first taken to world space by the transpose of the instance's
+ *          world-to-object rows - times 1 / sqrtf(dot(ng, ng)): the world-space unit geometric normal, NOT flipped toward
+ *          the ray (the AO pass's normal before its flip).
+ * A record whose prim is not a triangle of the scene (a miss: prim = 0xFFFFFFFF), or whose instance id is outside the
+ * instance table on a scene with instance transforms, gets all-zero bits.  t is not looked at. */
+typedef struct trx_hit_attr {
+    float u, v;
+    float normal[3];
+    uint32_t _pad; /* written as 0 */
+} trx_hit_attr;
+
 /* Mirror of obvhs RayHit {primitive_id, geometry_id, instance_id, t}
  * (fields: embree/src/embree_managed.rs:52-57) for the Traversable shim. */
 typedef struct trx_rayhit {
@@ -378,6 +399,26 @@ int trx_trace_rays_inst_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_
 int trx_trace_occluded_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays,
                            uint32_t semantics, uint8_t *d_flags, void *stream);
 
+/* Hit attributes (trx_hit_attr) of hit records already traced: one 24-byte record per hit record, a post-pass that reads
+ * the hits, rebuilds each ray and recomputes the committed triangle test's u, v and the normal.  The attributes depend
+ * only on the committed triangle and the ray, so no semantics word is taken (under TRX_SEM_TIE_FIRST another triangle may
+ * have been committed; its attributes follow it).
+ *  d_inst  the instance id of every record (the *_inst_dev trace calls write them), REQUIRED when the scene has instance
+ *          transforms - without it the call returns TRX_ERR_INVALID before anything is enqueued; ignored (may be NULL)
+ *          on every other scene.
+ * Ordering: these launches are ordered with trx_scene_refit* as trace launches are - a refit called after this call has
+ * returned waits for the attribute pass, which sees the old geometry in full.
+ * trx_hit_attributes_rays_dev: d_rays / d_hits / d_inst / d_attr hold n_rays records each (the hits of trx_trace_rays*_dev
+ * over these rays, or any hit records over them). */
+int trx_hit_attributes_rays_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, const trx_hit *d_hits,
+                                const uint32_t *d_inst, trx_hit_attr *d_attr, void *stream);
+/* The same for a primary frame: d_hits / d_inst laid out by `shard` exactly as trx_trace_primary*_dev wrote them (image
+ * layout or TRX_LAYOUT_SHARD), d_attr laid out alike; the primary rays are regenerated from `view`.  In image layout the
+ * records of pixels outside the shard are left untouched. */
+int trx_hit_attributes_primary_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                   trx_shard shard, const trx_hit *d_hits, const uint32_t *d_inst, trx_hit_attr *d_attr,
+                                   void *stream);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,
@@ -431,6 +472,10 @@ int trx_trace_primary_ao_inst(trx_scene *scene, const trx_view *view, uint32_t w
                               uint32_t *out_primary_inst, trx_hit *out_ao, uint32_t *out_ao_inst, float *out_ms);
 int trx_trace_rays_inst(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, uint32_t semantics,
                         trx_hit *out_hits, uint32_t *out_inst, float *out_ms);
+/* trx_trace_rays_inst followed by trx_hit_attributes_rays_dev over its hits: out_attr gets one trx_hit_attr per ray
+ * (out_hits, out_inst, out_attr may each be NULL); out_ms is the hipEvent time of both passes. */
+int trx_trace_rays_attr(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, uint32_t semantics, trx_hit *out_hits,
+                        uint32_t *out_inst, trx_hit_attr *out_attr, float *out_ms);
 /* Host-buffer form of trx_trace_occluded_dev. */
 int trx_trace_occluded(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, uint32_t semantics,
                        uint8_t *out_flags, float *out_ms);

@@ -48,6 +48,11 @@ class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_uint32)]
 
 
+class HitAttr(C.Structure):
+    """trx_hit_attr: barycentrics (u weights v1, v weights v2) and world-space unit geometric normal of a hit."""
+    _fields_ = [("u", C.c_float), ("v", C.c_float), ("normal", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
 class RayHit(C.Structure):
     _fields_ = [("primitive_id", C.c_uint32), ("geometry_id", C.c_uint32), ("instance_id", C.c_uint32),
                 ("t", C.c_float)]
@@ -113,6 +118,8 @@ SIGNATURES = {
     "trx_trace_rays_dev": (_i, [_P, _P, _u64, _u32, _P, _P]),
     "trx_trace_rays_inst_dev": (_i, [_P, _P, _u64, _u32, _P, _P, _P]),
     "trx_trace_occluded_dev": (_i, [_P, _P, _u64, _u32, _P, _P]),
+    "trx_hit_attributes_rays_dev": (_i, [_P, _P, _u64, _P, _P, _P, _P]),
+    "trx_hit_attributes_primary_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _P, _P, _P, _P]),
     "trx_trace_occluded": (_i, [_P, _P, _u64, _u32, _P, C.POINTER(_f)]),
     "trx_count_primary": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _P, C.POINTER(Stats)]),
     "trx_count_ao": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _f, _P, _P, C.POINTER(Stats)]),
@@ -124,6 +131,7 @@ SIGNATURES = {
     "trx_trace_primary_ao_inst": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _f, _P, _P, _P, _P, C.POINTER(_f)]),
     "trx_trace_rays": (_i, [_P, _P, _u64, _u32, _P, C.POINTER(_f)]),
     "trx_trace_rays_inst": (_i, [_P, _P, _u64, _u32, _P, _P, C.POINTER(_f)]),
+    "trx_trace_rays_attr": (_i, [_P, _P, _u64, _u32, _P, _P, _P, C.POINTER(_f)]),
     "trx_traverse1": (_i, [_P, C.POINTER(Ray), _u32, C.POINTER(RayHit)]),
     "trx_debug_traverse1_stats": (_i, [_P, C.POINTER(_u64), C.POINTER(_u64)]),
     "trx_debug_scene_info": (_i, [_P, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_u32)]),

@@ -304,6 +304,7 @@ void trx_scene_destroy(trx_scene *s) {
     if (s->d_scratch_ia) (void)hipFree(s->d_scratch_ia);
     if (s->d_scratch_ib) (void)hipFree(s->d_scratch_ib);
     if (s->d_scratch_rays) (void)hipFree(s->d_scratch_rays);
+    if (s->d_scratch_attr) (void)hipFree(s->d_scratch_attr);
     if (s->d_wave_times) (void)hipFree(s->d_wave_times);
     if (s->d_inst_xform) (void)hipFree(s->d_inst_xform);
     for (Slot &sl : s->slots) {

@@ -1,0 +1,118 @@
+// api_attr.cpp - hit attributes (include/trx.h, trx_hit_attr): the post-pass that turns hit records into the barycentrics
+// and the world-space geometric normal of the committed triangle test (k_hit_attr, kernels.hip).  Its launches take a
+// launch slot of the scene like the traversal kernels do, so trx_scene_refit waits for them.
+#include "api_internal.h"
+
+namespace {
+
+// One k_hit_attr pass over p.n_items records (split into launches of at most 2^30 for rays), on a launch slot.
+int enqueue_attr(trx_scene *s, HitAttrParams &p, int mode, uint64_t n, const uint32_t *d_inst, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    const bool xf = s->tlas && s->d_inst_xform;
+    if (xf && !d_inst)
+        return fail(TRX_ERR_INVALID, "this scene has instance transforms: the attribute pass needs the instance id of every "
+                                     "hit (the trace's d_inst) to take the ray into object space and the normal to world space");
+    if (n == 0) return TRX_OK;
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, stream, slot)) return rc;
+    p.tris = s->d_tris;
+    p.inst_xform = xf ? s->d_inst_xform : nullptr;
+    p.inst = xf ? d_inst : nullptr;
+    p.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull);
+    p.n_inst = s->n_inst;
+    slot->last_stream = stream;
+    slot->last_use = ++s->launches;
+    if (mode == kAttrRays) {
+        const uint64_t chunk = 1ull << 30;
+        const HitAttrParams base = p;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            p = base;
+            p.rays = base.rays + off;
+            p.hits = base.hits + off;
+            p.inst = base.inst ? base.inst + off : nullptr;
+            p.out = base.out + off;
+            p.n_items = (uint32_t)std::min(chunk, n - off);
+            HIP_TRY(launch_hit_attr(p, mode, stream));
+        }
+    } else {
+        HIP_TRY(launch_hit_attr(p, mode, stream));
+    }
+    HIP_TRY(hipEventRecord(slot->done, stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int trx_hit_attributes_rays_dev(trx_scene *s, const trx_ray *d_rays, uint64_t n, const trx_hit *d_hits,
+                                const uint32_t *d_inst, trx_hit_attr *d_attr, void *stream) {
+    if (!s || (n && (!d_rays || !d_hits || !d_attr))) return fail(TRX_ERR_INVALID, "null argument");
+    HitAttrParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.rays = d_rays;
+    p.hits = d_hits;
+    p.out = d_attr;
+    return enqueue_attr(s, p, kAttrRays, n, d_inst, (hipStream_t)stream);
+}
+
+int trx_hit_attributes_primary_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard,
+                                   const trx_hit *d_hits, const uint32_t *d_inst, trx_hit_attr *d_attr, void *stream) {
+    if (!s || !d_hits || !d_attr) return fail(TRX_ERR_INVALID, "null argument");
+    TraceParams t; // (the image geometry exactly as the trace derives it)
+    std::memset(&t, 0, sizeof(t));
+    int rc = image_params(t, view, w, h, shard);
+    if (rc) return rc;
+    HitAttrParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.hits = d_hits;
+    p.out = d_attr;
+    p.n_items = t.n_items;
+    p.width = t.width;
+    p.height = t.height;
+    p.tiles_x = t.tiles_x;
+    p.shard_index = t.shard_index;
+    p.shard_count = t.shard_count;
+    p.compact = t.compact;
+    p.view = t.views[0];
+    return enqueue_attr(s, p, kAttrPrimary, t.n_items, d_inst, (hipStream_t)stream);
+}
+
+int trx_trace_rays_attr(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, trx_hit *out_hits, uint32_t *out_inst,
+                        trx_hit_attr *out_attr, float *out_ms) {
+    if (!s || (n && !rays)) return fail(TRX_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
+    if (n == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    int rc = ensure_scratch(s, n, n);
+    if (rc) return rc;
+    if (n > s->scratch_attr) {
+        if (s->d_scratch_attr) (void)hipFree(s->d_scratch_attr);
+        s->d_scratch_attr = nullptr;
+        s->scratch_attr = 0;
+        HIP_TRY(hipMalloc(&s->d_scratch_attr, n * sizeof(trx_hit_attr)));
+        s->scratch_attr = n;
+    }
+    // (two-level scenes always trace the instance ids: the attribute pass needs them under instance transforms)
+    uint32_t *d_inst = s->tlas ? s->d_scratch_ia : nullptr;
+    HIP_TRY(hipMemcpy(s->d_scratch_rays, rays, n * sizeof(trx_ray), hipMemcpyHostToDevice));
+    HIP_TRY(hipEventRecord(s->ev0, nullptr));
+    rc = trx_trace_rays_inst_dev(s, s->d_scratch_rays, n, sem, s->d_scratch_a, d_inst, nullptr);
+    if (rc) return rc;
+    rc = trx_hit_attributes_rays_dev(s, s->d_scratch_rays, n, s->d_scratch_a, d_inst, s->d_scratch_attr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s->ev1, nullptr));
+    HIP_TRY(hipEventSynchronize(s->ev1));
+    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
+    if (out_hits) HIP_TRY(hipMemcpy(out_hits, s->d_scratch_a, n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+    if (out_inst) {
+        if (d_inst) HIP_TRY(hipMemcpy(out_inst, d_inst, n * 4, hipMemcpyDeviceToHost));
+        else std::memset(out_inst, 0xff, n * 4);
+    }
+    if (out_attr) HIP_TRY(hipMemcpy(out_attr, s->d_scratch_attr, n * sizeof(trx_hit_attr), hipMemcpyDeviceToHost));
+    return trx_scene_check(s, nullptr);
+}
+
+} // extern "C"

@@ -6,6 +6,7 @@
 //   api_traverse.cpp Traversable::traverse for one ray (concurrent callers share launches) and for batches
 //   api_build.cpp    builders, flat-buffer assembly (cwbvh_gpu_runner's host half), scene generators and loaders
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
+//   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -246,6 +247,8 @@ struct trx_scene {
     uint32_t *d_scratch_ia = nullptr, *d_scratch_ib = nullptr; // instance ids beside scratch_a / scratch_b
     trx_ray *d_scratch_rays = nullptr;
     uint64_t scratch_hits = 0, scratch_rays = 0;
+    trx_hit_attr *d_scratch_attr = nullptr; // trx_trace_rays_attr's attribute records (api_attr.cpp)
+    uint64_t scratch_attr = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<uint32_t> blas_tri_start; // geometry_id lookup for trx_traverse1
     FrameLoop loop;                // trx_frame_loop
@@ -271,6 +274,8 @@ namespace trxapi {
 
 int ensure_scratch(trx_scene *s, uint64_t hits, uint64_t rays);
 void fill_view(const trx_view *v, trx::ViewDev &out);
+// The launch slot a kernel enqueued on `stream` runs on, set up and waited for (api_launch.cpp; s->mu held)
+int acquire_slot(trx_scene *s, hipStream_t stream, Slot *&out);
 // Enqueues one traversal kernel on a launch slot of the scene (api_launch.cpp)
 int enqueue(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream, trx::SlotCounters **ctr_out);
 int image_params(trx::TraceParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard);

@@ -39,17 +39,10 @@ void fill_view(const trx_view *v, ViewDev &out) {
     out.pad = 0.f;
 }
 
-// Enqueue one traversal kernel on a launch slot.  Slots make the scene
-// re-entrant (Traversable requires Sync, src/rt_cpu/rt_cpu.rs:17-20): a slot is
-// reused only after the stream has waited for its previous kernel.
-int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream,
-            SlotCounters **ctr_out) {
-    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
-    HIP_TRY(hipSetDevice(s->device));
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (s->d_inst_xform && mode == kModeAo && !p.primary_inst)
-        return fail(TRX_ERR_INVALID, "this scene has instance transforms: the AO pass needs the primary pass's instance ids "
-                                     "(trx_trace_ao_inst_dev) to take the hit normal into world space");
+// Picks the launch slot of the scene a kernel enqueued on `stream` runs on, sets it up on first use and makes `stream`
+// wait for the slot's previous kernel when that ran on another stream (s->mu held).  The caller records slot.done after
+// its launch: trx_scene_refit waits on that event of every slot.
+int acquire_slot(trx_scene *s, hipStream_t stream, Slot *&out) {
     // A stream keeps its slot: its launches are ordered anyway, and the slot's tile-order feedback
     // stays with the caller's frame loop.  Otherwise take an unused slot, else the oldest one, and
     // make the stream wait for that slot's last kernel.
@@ -65,23 +58,6 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     }
     Slot &slot = s->slots[pick];
     const bool same_stream = slot.used && slot.last_stream == stream;
-    const uint32_t variant = g_variant.load(std::memory_order_relaxed);
-    // tuning overrides (trx_set_kernel_variant): bits 8..12 waves per CU, bits 16..19 waves per workgroup
-    uint32_t wpb = (variant >> 16) & 0x7u; // (bit 19: the tile-order feedback does not tune itself off, see below)
-    // incoherent single-level passes (AO, explicit rays) run two waves to a workgroup, so that the second can hand its last rays to the first
-    // when both are draining (kernels.hip, "drain"); an explicit 1 or 4 here switches that off
-    // (two-level scenes: explicit rays only, see kMerge in kernels.hip)
-    const bool merge_default = (wpb != 1 && wpb != 2 && wpb != 4) && mode != kModePrimary && mode != kModeFused && mode != kModeService &&
-                               (!s->tlas || mode == kModeRays) && !count;
-    if (wpb != 1 && wpb != 2 && wpb != 4) wpb = merge_default ? 2u : kDefaultWavesPerBlock;
-    if (mode == kModeService) wpb = 2u; // a walker and a porter (kernels.h, kSvcRays); n_items = 64 per WAVE of the grid
-    const uint32_t per_cu = (variant >> 8) & 0x1fu;
-    int grid = per_cu ? (int)(std::min(per_cu, 32u) * (uint32_t)s->cu_count) : s->grid;
-    // no more waves than chunks of work: a batch of one ray (trx_traverse1) is a one-wave launch with a
-    // one-wave spill area
-    const uint64_t n_chunks = ((uint64_t)p.n_items + 63u) >> 6;
-    if ((uint64_t)grid > n_chunks) grid = (int)std::max<uint64_t>(n_chunks, 1);
-    grid = std::max((int)wpb, (grid + (int)wpb - 1) / (int)wpb * (int)wpb);
     if (!slot.ctr) {
         // all or nothing: a slot is either fully usable or untouched
         SlotCounters *ctr = nullptr;
@@ -103,6 +79,41 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
         slot.done = done;
     }
     if (slot.used && !same_stream) HIP_TRY(hipStreamWaitEvent(stream, slot.done, 0));
+    out = &slot;
+    return TRX_OK;
+}
+
+// Enqueue one traversal kernel on a launch slot.  Slots make the scene
+// re-entrant (Traversable requires Sync, src/rt_cpu/rt_cpu.rs:17-20): a slot is
+// reused only after the stream has waited for its previous kernel.
+int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream,
+            SlotCounters **ctr_out) {
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->d_inst_xform && mode == kModeAo && !p.primary_inst)
+        return fail(TRX_ERR_INVALID, "this scene has instance transforms: the AO pass needs the primary pass's instance ids "
+                                     "(trx_trace_ao_inst_dev) to take the hit normal into world space");
+    Slot *slot_p = nullptr;
+    if (int rc = acquire_slot(s, stream, slot_p)) return rc;
+    Slot &slot = *slot_p;
+    const uint32_t variant = g_variant.load(std::memory_order_relaxed);
+    // tuning overrides (trx_set_kernel_variant): bits 8..12 waves per CU, bits 16..19 waves per workgroup
+    uint32_t wpb = (variant >> 16) & 0x7u; // (bit 19: the tile-order feedback does not tune itself off, see below)
+    // incoherent single-level passes (AO, explicit rays) run two waves to a workgroup, so that the second can hand its last rays to the first
+    // when both are draining (kernels.hip, "drain"); an explicit 1 or 4 here switches that off
+    // (two-level scenes: explicit rays only, see kMerge in kernels.hip)
+    const bool merge_default = (wpb != 1 && wpb != 2 && wpb != 4) && mode != kModePrimary && mode != kModeFused && mode != kModeService &&
+                               (!s->tlas || mode == kModeRays) && !count;
+    if (wpb != 1 && wpb != 2 && wpb != 4) wpb = merge_default ? 2u : kDefaultWavesPerBlock;
+    if (mode == kModeService) wpb = 2u; // a walker and a porter (kernels.h, kSvcRays); n_items = 64 per WAVE of the grid
+    const uint32_t per_cu = (variant >> 8) & 0x1fu;
+    int grid = per_cu ? (int)(std::min(per_cu, 32u) * (uint32_t)s->cu_count) : s->grid;
+    // no more waves than chunks of work: a batch of one ray (trx_traverse1) is a one-wave launch with a
+    // one-wave spill area
+    const uint64_t n_chunks = ((uint64_t)p.n_items + 63u) >> 6;
+    if ((uint64_t)grid > n_chunks) grid = (int)std::max<uint64_t>(n_chunks, 1);
+    grid = std::max((int)wpb, (grid + (int)wpb - 1) / (int)wpb * (int)wpb);
     if (slot.spill_waves < (uint32_t)grid) {
         // stack spill area (entries kLdsStack.. of every lane), sized for the grid actually launched; growing it
         // waits for the slot's previous kernel, which may still be writing the old one

@@ -179,6 +179,22 @@ struct TraceParams {
     ViewDev views[kMaxBatchFrames];
 };
 
+// Hit attributes (k_hit_attr, trx_hit_attributes_*): one lane per hit record, no traversal.
+enum HitAttrMode : int { kAttrRays = 0, kAttrPrimary = 1 };
+struct HitAttrParams {
+    const float4 *tris;       // the scene's 48-byte records
+    const float4 *inst_xform; // world-to-object rows per instance, or null (no instance transforms)
+    const trx_ray *rays;      // kAttrRays
+    const trx_hit *hits;
+    const uint32_t *inst;     // instance id per record (read only with inst_xform)
+    trx_hit_attr *out;
+    uint32_t n_items;         // kAttrRays: records; kAttrPrimary: the shard's tiles * 64, in tile order
+    uint32_t n_tris, n_inst;
+    uint32_t width, height, tiles_x, shard_index, shard_count, compact; // kAttrPrimary, as in TraceParams
+    ViewDev view;
+};
+hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream);
+
 // Resident waves the persistent kernel should be launched with on `device`.
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count);
 

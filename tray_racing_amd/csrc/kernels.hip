@@ -829,7 +829,105 @@ int node_variant(uint32_t sem) {
     return ((sem & TRX_SEM_NODE_RCP) ? 1 : 0) | ((sem & TRX_SEM_NODE_FMA) ? 2 : 0);
 }
 
+// Hit attributes (include/trx.h, trx_hit_attr): one lane per hit record.  The ray the committing triangle test saw is
+// rebuilt - the explicit ray, or the primary ray of the record's pixel; with instance transforms the world ray as given
+// through the instance's world-to-object rows (trace_walk_plain.inc) - and the test's u, v are recomputed with
+// intersect_tri's operations; the normal is the AO pass's before its flip (trace_refill.inc).  A gather: 8 B of hit,
+// 4 B of instance id, 48 B of triangle (and 48 B of rows) per record, 24 B written.  Primary frames are walked in the
+// tile order of the trace (64 lanes = one 8x8 tile), so a wave's hits are the same tile's.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_items) return;
+    uint32_t rec = item;
+    float ox, oy, oz, dx, dy, dz;
+    if constexpr (MODE == kAttrPrimary) {
+        const uint32_t local_tile = item >> 6, k = item & 63u;
+        const uint32_t tile = local_tile * P.shard_count + P.shard_index;
+        const uint32_t ty = tile / P.tiles_x;
+        const uint32_t px = (tile - ty * P.tiles_x) * 8u + (k & 7u), py = ty * 8u + (k >> 3);
+        if (px >= P.width || py >= P.height) return; // (the trace writes no record for it either)
+        if (!P.compact) rec = py * P.width + px;
+        primary_dir(P.view, P.width, P.height, px, py, dx, dy, dz);
+        ox = P.view.eye[0]; oy = P.view.eye[1]; oz = P.view.eye[2];
+    } else {
+        const float4 *rp = reinterpret_cast<const float4 *>(P.rays + item);
+        const float4 a = rp[0], b = rp[1];
+        ox = a.x; oy = a.y; oz = a.z;
+        dx = b.x; dy = b.y; dz = b.z;
+    }
+    const uint32_t prim = P.hits[rec].prim;
+    float4 r0 = make_float4(1.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0;
+    bool ok = prim < P.n_tris;
+    if (P.inst_xform) {
+        const uint32_t inst = P.inst[rec];
+        ok = ok && inst < P.n_inst;
+        if (ok) {
+            const float4 *m = P.inst_xform + (size_t)inst * 3;
+            r0 = m[0]; r1 = m[1]; r2 = m[2];
+        }
+    }
+    float u = 0.0f, v = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (ok) {
+        const float4 *tp = P.tris + (size_t)prim * 3;
+        const float4 a = tp[0], b = tp[1], c4 = tp[2];
+        const float e1x = b.x, e1y = b.y, e1z = b.z;
+        const float e2x = c4.x, e2y = c4.y, e2z = c4.z;
+        nx = a.w; ny = b.w; nz = c4.w;
+        if (P.inst_xform) {
+            // the object-space ray the BLAS walk tested with
+            const float tox = ((r0.x * ox + r0.y * oy) + r0.z * oz) + r0.w;
+            const float toy = ((r1.x * ox + r1.y * oy) + r1.z * oz) + r1.w;
+            const float toz = ((r2.x * ox + r2.y * oy) + r2.z * oz) + r2.w;
+            const float tdx = (r0.x * dx + r0.y * dy) + r0.z * dz;
+            const float tdy = (r1.x * dx + r1.y * dy) + r1.z * dz;
+            const float tdz = (r2.x * dx + r2.y * dy) + r2.z * dz;
+            ox = tox; oy = toy; oz = toz;
+            dx = tdx; dy = tdy; dz = tdz;
+        }
+        // finish_ray_dir's zero-direction fix (query.hlsl:334)
+        dx = dx == 0.0f ? TRX_F32_EPSILON : dx;
+        dy = dy == 0.0f ? TRX_F32_EPSILON : dy;
+        dz = dz == 0.0f ? TRX_F32_EPSILON : dz;
+        // intersect_tri's u, v
+        const float cx = a.x - ox, cy = a.y - oy, cz = a.z - oz;
+        const float rx = dy * cz - dz * cy;
+        const float ry = dz * cx - dx * cz;
+        const float rz = dx * cy - dy * cx;
+        const float det = dot3(nx, ny, nz, dx, dy, dz);
+        const float un = dot3(rx, ry, rz, e2x, e2y, e2z), vn = dot3(rx, ry, rz, e1x, e1y, e1z);
+        const float inv_det = 1.0f / det;
+        u = un * inv_det;
+        v = vn * inv_det;
+        if (P.inst_xform) {
+            // object-space normal -> world: transpose of world-to-object
+            const float wx = (r0.x * nx + r1.x * ny) + r2.x * nz;
+            const float wy = (r0.y * nx + r1.y * ny) + r2.y * nz;
+            const float wz = (r0.z * nx + r1.z * ny) + r2.z * nz;
+            nx = wx; ny = wy; nz = wz;
+        }
+        const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+        nx *= ninv; ny *= ninv; nz *= ninv;
+    }
+    trx_hit_attr out;
+    out.u = u;
+    out.v = v;
+    out.normal[0] = nx;
+    out.normal[1] = ny;
+    out.normal[2] = nz;
+    out._pad = 0u;
+    P.out[rec] = out;
+}
+
 } // namespace
+
+hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    const dim3 grid((p.n_items + 255u) / 256u), block(256);
+    if (mode == kAttrPrimary) hipLaunchKernelGGL(k_hit_attr<kAttrPrimary>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(k_hit_attr<kAttrRays>, grid, block, 0, stream, p);
+    return hipGetLastError();
+}
 
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count) {
     (void)mode;

@@ -14,6 +14,9 @@ from . import _lib as L
 HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<u4")])
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
 RAYHIT_DTYPE = np.dtype([("primitive_id", "<u4"), ("geometry_id", "<u4"), ("instance_id", "<u4"), ("t", "<f4")])  # obvhs RayHit
+# trx_hit_attr: barycentrics of the committed triangle test (u weights v1, v weights v2) and the world-space unit
+# geometric normal; all zero for a miss
+HIT_ATTR_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("_pad", "<u4")])
 MISS_PRIM = 0xFFFFFFFF
 
 
@@ -417,6 +420,15 @@ class Scene:
         L.check(self._lib.trx_trace_rays_inst(self._h, _ptr(rays), rays.shape[0], sem, _ptr(hits), _ptr(inst), C.byref(ms)))
         return hits, inst, ms.value
 
+    def trace_rays_attr(self, rays, sem=L.SEM_HLSL):
+        """(hits, instance ids, hit attributes): trx_trace_rays_attr, the trace and the attribute pass over its hits."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        n = rays.shape[0]
+        hits, inst, attr = np.empty(n, dtype=HIT_DTYPE), np.empty(n, dtype=np.uint32), np.empty(n, dtype=HIT_ATTR_DTYPE)
+        ms = C.c_float()
+        L.check(self._lib.trx_trace_rays_attr(self._h, _ptr(rays), n, sem, _ptr(hits), _ptr(inst), _ptr(attr), C.byref(ms)))
+        return hits, inst, attr
+
     def trace_rays(self, rays, sem=L.SEM_HLSL):
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
         hits = np.empty(rays.shape[0], dtype=HIT_DTYPE)
@@ -542,6 +554,19 @@ class Scene:
     def trace_occluded_dev(self, d_rays, n, d_flags, sem=L.SEM_HLSL, stream=0):
         L.check(self._lib.trx_trace_occluded_dev(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_flags),
                                                  C.c_void_p(stream)))
+
+    def hit_attributes_rays_dev(self, d_rays, n, d_hits, d_attr, d_inst=0, stream=0):
+        """trx_hit_attributes_rays_dev: n trx_hit_attr records at d_attr for the hits d_hits of the rays d_rays (d_inst: the
+        hits' instance ids, required on scenes with instance transforms)."""
+        L.check(self._lib.trx_hit_attributes_rays_dev(self._h, C.c_void_p(d_rays), n, C.c_void_p(d_hits),
+                                                      C.c_void_p(d_inst), C.c_void_p(d_attr), C.c_void_p(stream)))
+
+    def hit_attributes_primary_dev(self, view, width, height, d_hits, d_attr, d_inst=0, shard=(0, 1), stream=0):
+        """trx_hit_attributes_primary_dev: attributes of a primary frame's records, laid out as the trace wrote them
+        (shard = (index, count) or (index, count, layout))."""
+        L.check(self._lib.trx_hit_attributes_primary_dev(self._h, C.byref(view), width, height, L.Shard(*shard),
+                                                         C.c_void_p(d_hits), C.c_void_p(d_inst), C.c_void_p(d_attr),
+                                                         C.c_void_p(stream)))
 
     def check(self, stream=0):
         L.check(self._lib.trx_scene_check(self._h, C.c_void_p(stream)))
