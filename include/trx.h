@@ -251,6 +251,51 @@ int trx_scene_get_instance_transform(const trx_scene *scene, uint32_t instance_i
 /* The world-to-object rows the kernels use: 3 rows of {m0 m1 m2 t}; x' = ((m0*x + m1*y) + m2*z) + t. */
 int trx_scene_get_instance_world_to_object(const trx_scene *scene, uint32_t instance_id, float out_rows[12]);
 
+/* ---- instance masks (TLAS scenes) ------------------------------------------------------------------------------------
+ * The 8-bit instance mask of DXR / Vulkan instances (the reference's AccelerationStructureInstance packs one beside the
+ * custom index; its software TLAS walk ignores it).  An instance is a TLAS primitive: entry k of instance_offsets, the
+ * index the transforms and the hit records' instance ids use - per TLAS primitive on re-braided scenes too.
+ *  - Every instance has a mask; with no table set every mask is 0xFF.
+ *  - A MASKED call takes a ray_mask in 1..255 (0 or > 255: TRX_ERR_INVALID before anything is enqueued).  Instance k
+ *    is considered only if (mask[k] & ray_mask) != 0.  An instance not considered is never entered: none of its
+ *    triangles can be hit, and it has no effect on t, prim, the instance id, the occlusion flag or the AO pass.  A
+ *    masked trace returns exactly what an unmasked trace returns on the same scene with those instances removed
+ *    (tie-breaking under every semantics word included: the order of the TLAS walk does not change).
+ *  - Only the masked entry points below read the table.  Every other entry point traces every instance whatever table
+ *    is set: the primary, AO, frame, batch, rays, occluded and count calls, trx_frame_loop, trx_traverse1 /
+ *    trx_traverse_batch (and the ray service behind them).
+ *  - On single-level scenes the masked calls trace exactly what their unmasked twins trace (the scene is one instance
+ *    with mask 0xFF), and the setter is refused (TRX_ERR_INVALID).
+ *  - trx_scene_refit*, trx_scene_set_instance_transforms and trx_scene_set_instance_entry_nodes keep the table;
+ *    trx_scene_device_bytes counts it.
+ * n_instances must equal the scene's TLAS primitive count (TRX_ERR_INVALID otherwise).
+ * Ordering: a masked launch enqueued before trx_scene_set_instance_masks uses the old table in full, one enqueued after
+ * it returns the new one (the old table is freed once the scene's launches enqueued before the call have finished). */
+/* masks: n_instances bytes; NULL / 0 removes the table (every instance 0xFF again). */
+int trx_scene_set_instance_masks(trx_scene *scene, const uint8_t *masks, uint32_t n_instances);
+/* The table as set, or 0xFF for every instance when none is (single-level scenes: n_instances 1, mask 0xFF). */
+int trx_scene_get_instance_masks(const trx_scene *scene, uint8_t *out, uint32_t n_instances);
+/* Masked forms of trx_trace_rays_inst_dev, trx_trace_occluded_dev, trx_trace_primary_inst_dev and
+ * trx_trace_ao_inst_dev: the same arguments and rules (d_inst / d_ao_inst may be NULL; the AO call needs d_primary_inst
+ * on scenes with instance transforms) plus ray_mask.  The AO pass takes the records of a primary pass - usually the
+ * masked one - as they are: pixels whose primary record is a miss get a miss record. */
+int trx_trace_rays_masked_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, uint32_t semantics,
+                              uint32_t ray_mask, trx_hit *d_hits, uint32_t *d_inst, void *stream);
+int trx_trace_occluded_masked_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, uint32_t semantics,
+                                  uint32_t ray_mask, uint8_t *d_flags, void *stream);
+int trx_trace_primary_masked_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                 trx_shard shard, uint32_t semantics, uint32_t ray_mask, trx_hit *d_hits,
+                                 uint32_t *d_inst, void *stream);
+int trx_trace_ao_masked_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                            uint32_t semantics, uint32_t frame, float ao_eps, uint32_t ray_mask,
+                            const trx_hit *d_primary, const uint32_t *d_primary_inst, trx_hit *d_ao, uint32_t *d_ao_inst,
+                            void *stream);
+/* Host-buffer forms (synchronous, like trx_trace_rays_inst / trx_trace_occluded; out_* may be NULL). */
+int trx_trace_rays_masked(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, uint32_t semantics, uint32_t ray_mask,
+                          trx_hit *out_hits, uint32_t *out_inst, float *out_ms);
+int trx_trace_occluded_masked(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, uint32_t semantics,
+                              uint32_t ray_mask, uint8_t *out_flags, float *out_ms);
+
 /* ---- refit: geometry moves, topology stays ------------------------------------------------------------------------
  * A refit gives the scene new f32 vertices for every triangle record, in the scene's record order (the layout of
  * trx_flat.tri_verts, TRX_TRI_VERTS_36: 9 floats per record; object-order vertices map through trx_flat.tri_source),

@@ -103,6 +103,14 @@ SIGNATURES = {
     "trx_scene_set_instance_transforms": (_i, [_P, _P, _u32]),
     "trx_scene_get_instance_transform": (_i, [_P, _u32, _P]),
     "trx_scene_get_instance_world_to_object": (_i, [_P, _u32, _P]),
+    "trx_scene_set_instance_masks": (_i, [_P, _P, _u32]),
+    "trx_scene_get_instance_masks": (_i, [_P, _P, _u32]),
+    "trx_trace_rays_masked_dev": (_i, [_P, _P, _u64, _u32, _u32, _P, _P, _P]),
+    "trx_trace_occluded_masked_dev": (_i, [_P, _P, _u64, _u32, _u32, _P, _P]),
+    "trx_trace_primary_masked_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _P, _P, _P]),
+    "trx_trace_ao_masked_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _f, _u32, _P, _P, _P, _P, _P]),
+    "trx_trace_rays_masked": (_i, [_P, _P, _u64, _u32, _u32, _P, _P, C.POINTER(_f)]),
+    "trx_trace_occluded_masked": (_i, [_P, _P, _u64, _u32, _u32, _P, C.POINTER(_f)]),
     "trx_scene_refit": (_i, [_P, _P, _u64]),
     "trx_scene_refit_dev": (_i, [_P, _P, _u64, _P]),
     "trx_scene_read_nodes": (_i, [_P, _P, _u64]),

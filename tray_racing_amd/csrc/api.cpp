@@ -307,6 +307,7 @@ void trx_scene_destroy(trx_scene *s) {
     if (s->d_scratch_attr) (void)hipFree(s->d_scratch_attr);
     if (s->d_wave_times) (void)hipFree(s->d_wave_times);
     if (s->d_inst_xform) (void)hipFree(s->d_inst_xform);
+    if (s->d_inst_mask) (void)hipFree(s->d_inst_mask);
     for (Slot &sl : s->slots) {
         if (sl.ctr) (void)hipFree(sl.ctr);
         if (sl.spill) (void)hipFree(sl.spill);
@@ -341,6 +342,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     uint64_t bytes = s->n_nodes * TRX_NODE_BYTES + s->n_tris * sizeof(TriDev) + (uint64_t)s->n_inst * 4;
     // launch slots claimed so far: stack spill areas and tile-order lists
     std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
+    if (s->d_inst_mask) bytes += s->n_inst; // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
     for (const Slot &sl : s->slots) {
         bytes += (uint64_t)sl.spill_waves * kWaveScratch * sizeof(uint2);
         for (const auto &o : sl.order)
@@ -483,6 +485,60 @@ int trx_scene_set_instance_transforms(trx_scene *s, const float *object_to_world
     if (rc_swap) return rc_swap;
     s->inst_o2w.assign(object_to_world, object_to_world + (size_t)n * 16);
     s->inst_w2o.swap(w2o);
+    return TRX_OK;
+}
+
+// Instance masks (include/trx.h): read by the masked trace calls only (enqueue() hands them the table under s->mu).
+int trx_scene_set_instance_masks(trx_scene *s, const uint8_t *masks, uint32_t n) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    if (!s->tlas) return fail(TRX_ERR_INVALID, "instance masks need a TLAS scene");
+    const bool remove = !masks || n == 0;
+    if (!remove && n != s->n_inst) return fail(TRX_ERR_INVALID, "%u masks for %u instances", n, s->n_inst);
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint8_t> host_copy;
+    uint8_t *fresh = nullptr;
+    if (!remove) {
+        try {
+            host_copy.assign(masks, masks + n);
+        } catch (const std::exception &) {
+            return fail(TRX_ERR_OOM, "host allocation failed");
+        }
+        HIP_TRY(hipMalloc(&fresh, n));
+        const hipError_t e = hipMemcpy(fresh, masks, n, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(TRX_ERR_NO_DEVICE, "upload of the instance masks failed: %s", hipGetErrorString(e));
+        }
+    }
+    // The pointer is swapped under the launch mutex (enqueue() reads it there), and the old table is freed once every
+    // launch slot's last kernel has finished: a masked launch enqueued before this call uses the old table in full.  Slots
+    // are waited for one by one - not the device, on which a resident kernel (a ray service) may be running - and
+    // pinned slots are skipped: the resident kernels never read the table.
+    uint8_t *old = nullptr;
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        old = s->d_inst_mask;
+        s->d_inst_mask = fresh;
+        s->h_inst_mask.swap(host_copy);
+        if (old)
+            for (Slot &sl : s->slots)
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done);
+    }
+    if (e != hipSuccess) // (the old table is kept rather than freed under a kernel that may still read it)
+        return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    if (old) (void)hipFree(old);
+    return TRX_OK;
+}
+
+int trx_scene_get_instance_masks(const trx_scene *s, uint8_t *out, uint32_t n) {
+    if (!s || (!out && n)) return fail(TRX_ERR_INVALID, "null argument");
+    const uint32_t want = s->tlas ? s->n_inst : 1u; // (a single-level scene is one instance with mask 0xFF)
+    if (n != want) return fail(TRX_ERR_INVALID, "%u masks asked for %u instances", n, want);
+    std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
+    if (s->h_inst_mask.empty()) std::memset(out, 0xff, n);
+    else std::memcpy(out, s->h_inst_mask.data(), n);
     return TRX_OK;
 }
 

@@ -264,6 +264,10 @@ struct trx_scene {
     std::vector<uint32_t> h_inst_entry;      // host copy of the entry nodes (empty = node 0 everywhere) ...
     uint64_t inst_entry_version = 0;         // ... bumped whenever they are set: the refit's cached schedule follows them
     trxapi::RefitState *refit = nullptr;     // trx_scene_refit: schedule, node boxes, stream (api_refit.cpp; created on first use)
+    // instance masks (TLAS scenes, trx_scene_set_instance_masks): one byte per TLAS primitive, read by the masked trace
+    // calls only; host copy and device table, empty / null = every instance 0xFF
+    std::vector<uint8_t> h_inst_mask;
+    uint8_t *d_inst_mask = nullptr;
 };
 
 struct trx_bvh {
@@ -289,9 +293,10 @@ void forget_tile_orders(trx_scene *s);
 void refit_state_free(trx_scene *s);
 uint64_t refit_state_bytes(const trx_scene *s);
 // explicit rays (api_trace.cpp; trx_traverse1's batches launch through it)
+// (ray_mask != 0: a masked trace - enqueue() hands the kernel the scene's instance mask table)
 int trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
                     trx::SlotCounters **ctr, bool any_hit = false, uint32_t *d_inst = nullptr, uint32_t *over_host = nullptr,
-                    bool one_queue = false);
+                    bool one_queue = false, uint32_t ray_mask = 0);
 
 } // namespace trxapi
 

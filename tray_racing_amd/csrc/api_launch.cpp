@@ -131,6 +131,11 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     p.inst = s->d_inst;
     p.inst_entry = s->d_inst_entry;
     p.inst_xform = s->d_inst_xform;
+    // instance masks: a masked call (p.ray_mask != 0) gets the table as it is now - trx_scene_set_instance_masks swaps it
+    // under this mutex and frees the old one only after the slots' launches have finished; every other launch, and a masked
+    // one on a single-level scene or a scene without a table, gets null (every instance entered)
+    const uint8_t *inst_mask = p.ray_mask != 0u && s->tlas ? s->d_inst_mask : nullptr;
+    if (!inst_mask) p.ray_mask = 0u;
     p.tlas_start = s->tlas_start;
     p.exp_exact = s->exp_exact;
     p.ctr = slot.ctr;
@@ -320,7 +325,10 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     if (p.tune & 0x10000u) pipe = false;
 #endif
     if (mode == kModeService) pipe = false;
-    HIP_TRY(launch_trace(p, mode, s->tlas, sem, count, pipe, grid, stream));
+    TraceParamsTlas kp;
+    static_cast<TraceParams &>(kp) = p;
+    kp.inst_mask = inst_mask;
+    HIP_TRY(launch_trace(kp, mode, s->tlas, sem, count, pipe, grid, stream));
     HIP_TRY(hipEventRecord(slot.done, stream));
     slot.used = true;
     if (mode == kModeService) slot.pinned = true; // (until the service is stopped: RayService::stop_locked)

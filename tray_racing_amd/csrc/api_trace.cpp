@@ -2,12 +2,11 @@
 // (api_launch.cpp): device-resident forms, host-buffer twins with hipEvent timing (replaces src/timestamp.rs).
 #include "api_internal.h"
 
-extern "C" {
-
 // ---- tracing: device-resident -----------------------------------------------------------
 
-int trx_trace_primary_inst_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard,
-                               uint32_t sem, trx_hit *d_hits, uint32_t *d_inst, void *stream) {
+// The primary and AO passes with a ray mask (0: unmasked, the plain entry points; 1..255: trx_trace_*_masked_dev)
+static int primary_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                        uint32_t ray_mask, trx_hit *d_hits, uint32_t *d_inst, void *stream) {
     if (!s || !d_hits) return fail(TRX_ERR_INVALID, "null argument");
     TraceParams p;
     std::memset(&p, 0, sizeof(p));
@@ -15,8 +14,41 @@ int trx_trace_primary_inst_dev(trx_scene *s, const trx_view *view, uint32_t w, u
     if (rc) return rc;
     p.out = d_hits;
     p.out_inst = d_inst;
+    p.ray_mask = ray_mask;
     if (p.n_items == 0) return TRX_OK;
     return enqueue(s, p, kModePrimary, sem, false, (hipStream_t)stream, nullptr);
+}
+
+static int ao_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                   uint32_t frame, float ao_eps, uint32_t ray_mask, const trx_hit *d_primary, const uint32_t *d_primary_inst,
+                   trx_hit *d_ao, uint32_t *d_ao_inst, void *stream) {
+    if (!s || !d_primary || !d_ao) return fail(TRX_ERR_INVALID, "null argument");
+    TraceParams p;
+    std::memset(&p, 0, sizeof(p));
+    int rc = image_params(p, view, w, h, shard);
+    if (rc) return rc;
+    p.primary = d_primary;
+    p.primary_inst = d_primary_inst;
+    p.out = d_ao;
+    p.out_inst = d_ao_inst;
+    p.frame = frame;
+    p.ao_eps = ao_eps;
+    p.ray_mask = ray_mask;
+    if (p.n_items == 0) return TRX_OK;
+    return enqueue(s, p, kModeAo, sem, false, (hipStream_t)stream, nullptr);
+}
+
+// a masked call's ray mask, checked before anything is enqueued
+static int check_ray_mask(uint32_t ray_mask) {
+    if (ray_mask == 0u || ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 1..255", ray_mask);
+    return TRX_OK;
+}
+
+extern "C" {
+
+int trx_trace_primary_inst_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard,
+                               uint32_t sem, trx_hit *d_hits, uint32_t *d_inst, void *stream) {
+    return primary_impl(s, view, w, h, shard, sem, 0u, d_hits, d_inst, stream);
 }
 
 int trx_trace_primary_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard,
@@ -51,19 +83,7 @@ int trx_trace_primary_batch_dev(trx_scene *s, const trx_view *views, uint32_t n_
 int trx_trace_ao_inst_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
                           uint32_t frame, float ao_eps, const trx_hit *d_primary, const uint32_t *d_primary_inst,
                           trx_hit *d_ao, uint32_t *d_ao_inst, void *stream) {
-    if (!s || !d_primary || !d_ao) return fail(TRX_ERR_INVALID, "null argument");
-    TraceParams p;
-    std::memset(&p, 0, sizeof(p));
-    int rc = image_params(p, view, w, h, shard);
-    if (rc) return rc;
-    p.primary = d_primary;
-    p.primary_inst = d_primary_inst;
-    p.out = d_ao;
-    p.out_inst = d_ao_inst;
-    p.frame = frame;
-    p.ao_eps = ao_eps;
-    if (p.n_items == 0) return TRX_OK;
-    return enqueue(s, p, kModeAo, sem, false, (hipStream_t)stream, nullptr);
+    return ao_impl(s, view, w, h, shard, sem, frame, ao_eps, 0u, d_primary, d_primary_inst, d_ao, d_ao_inst, stream);
 }
 
 int trx_trace_ao_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
@@ -138,7 +158,8 @@ int trx_trace_ao_batch_dev(trx_scene *s, const trx_view *view, uint32_t w, uint3
 } // extern "C"
 
 int trxapi::trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
-                            SlotCounters **ctr, bool any_hit, uint32_t *d_inst, uint32_t *over_host, bool one_queue) {
+                            SlotCounters **ctr, bool any_hit, uint32_t *d_inst, uint32_t *over_host, bool one_queue,
+                            uint32_t ray_mask) {
     // the work queue is 32-bit: split very large batches
     const uint64_t chunk = 1ull << 30;
     for (uint64_t off = 0; off < n; off += chunk) {
@@ -150,6 +171,7 @@ int trxapi::trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uin
         p.out_inst = d_inst ? d_inst + off : nullptr;
         p.over_host = over_host;
         p.single_queue = one_queue ? 1u : 0u;
+        p.ray_mask = ray_mask;
         p.n_items = (uint32_t)std::min(chunk, n - off);
         int rc = enqueue(s, p, kModeRays, sem, count, stream, ctr);
         if (rc) return rc;
@@ -175,6 +197,38 @@ int trx_trace_occluded_dev(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint
     if (n == 0) return TRX_OK;
     return trace_rays_impl(s, d_rays, n, sem, reinterpret_cast<trx_hit *>(d_flags), (hipStream_t)stream, false, nullptr,
                            true);
+}
+
+// ---- instance masks: the masked trace calls (include/trx.h; the table itself is api.cpp's) --------------------------------
+
+int trx_trace_rays_masked_dev(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, uint32_t ray_mask,
+                              trx_hit *d_hits, uint32_t *d_inst, void *stream) {
+    if (!s || (n && (!d_rays || !d_hits))) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_ray_mask(ray_mask)) return rc;
+    if (n == 0) return TRX_OK;
+    return trace_rays_impl(s, d_rays, n, sem, d_hits, (hipStream_t)stream, false, nullptr, false, d_inst, nullptr, false, ray_mask);
+}
+
+int trx_trace_occluded_masked_dev(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, uint32_t ray_mask,
+                                  uint8_t *d_flags, void *stream) {
+    if (!s || (n && (!d_rays || !d_flags))) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_ray_mask(ray_mask)) return rc;
+    if (n == 0) return TRX_OK;
+    return trace_rays_impl(s, d_rays, n, sem, reinterpret_cast<trx_hit *>(d_flags), (hipStream_t)stream, false, nullptr,
+                           true, nullptr, nullptr, false, ray_mask);
+}
+
+int trx_trace_primary_masked_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                                 uint32_t ray_mask, trx_hit *d_hits, uint32_t *d_inst, void *stream) {
+    if (int rc = check_ray_mask(ray_mask)) return rc;
+    return primary_impl(s, view, w, h, shard, sem, ray_mask, d_hits, d_inst, stream);
+}
+
+int trx_trace_ao_masked_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                            uint32_t frame, float ao_eps, uint32_t ray_mask, const trx_hit *d_primary,
+                            const uint32_t *d_primary_inst, trx_hit *d_ao, uint32_t *d_ao_inst, void *stream) {
+    if (int rc = check_ray_mask(ray_mask)) return rc;
+    return ao_impl(s, view, w, h, shard, sem, frame, ao_eps, ray_mask, d_primary, d_primary_inst, d_ao, d_ao_inst, stream);
 }
 
 static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint32_t *hist = nullptr) {
@@ -488,8 +542,11 @@ int trx_trace_rays(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, 
     return trx_trace_rays_inst(s, rays, n, sem, out_hits, nullptr, out_ms);
 }
 
-int trx_trace_rays_inst(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, trx_hit *out_hits, uint32_t *out_inst,
-                        float *out_ms) {
+} // extern "C"
+
+// trx_trace_rays_inst / trx_trace_rays_masked (ray_mask 0: unmasked)
+static int rays_host(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, trx_hit *out_hits,
+                     uint32_t *out_inst, float *out_ms) {
     if (!s || (n && !rays)) return fail(TRX_ERR_INVALID, "null argument");
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     if (n == 0) return TRX_OK;
@@ -498,7 +555,9 @@ int trx_trace_rays_inst(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t 
     if (rc) return rc;
     HIP_TRY(hipMemcpy(s->d_scratch_rays, rays, n * sizeof(trx_ray), hipMemcpyHostToDevice));
     HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    rc = trx_trace_rays_inst_dev(s, s->d_scratch_rays, n, sem, s->d_scratch_a, out_inst ? s->d_scratch_ia : nullptr, nullptr);
+    rc = ray_mask ? trx_trace_rays_masked_dev(s, s->d_scratch_rays, n, sem, ray_mask, s->d_scratch_a,
+                                              out_inst ? s->d_scratch_ia : nullptr, nullptr)
+                  : trx_trace_rays_inst_dev(s, s->d_scratch_rays, n, sem, s->d_scratch_a, out_inst ? s->d_scratch_ia : nullptr, nullptr);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(s->ev1, nullptr));
     HIP_TRY(hipEventSynchronize(s->ev1));
@@ -511,7 +570,9 @@ int trx_trace_rays_inst(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t 
     return trx_scene_check(s, nullptr);
 }
 
-int trx_trace_occluded(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint8_t *out_flags, float *out_ms) {
+// trx_trace_occluded / trx_trace_occluded_masked (ray_mask 0: unmasked)
+static int occluded_host(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, uint8_t *out_flags,
+                         float *out_ms) {
     if (!s || (n && !rays)) return fail(TRX_ERR_INVALID, "null argument");
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
     if (n == 0) return TRX_OK;
@@ -520,13 +581,38 @@ int trx_trace_occluded(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t s
     if (rc) return rc;
     HIP_TRY(hipMemcpy(s->d_scratch_rays, rays, n * sizeof(trx_ray), hipMemcpyHostToDevice));
     HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    rc = trx_trace_occluded_dev(s, s->d_scratch_rays, n, sem, reinterpret_cast<uint8_t *>(s->d_scratch_a), nullptr);
+    uint8_t *d_flags = reinterpret_cast<uint8_t *>(s->d_scratch_a);
+    rc = ray_mask ? trx_trace_occluded_masked_dev(s, s->d_scratch_rays, n, sem, ray_mask, d_flags, nullptr)
+                  : trx_trace_occluded_dev(s, s->d_scratch_rays, n, sem, d_flags, nullptr);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(s->ev1, nullptr));
     HIP_TRY(hipEventSynchronize(s->ev1));
     if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
     if (out_flags) HIP_TRY(hipMemcpy(out_flags, s->d_scratch_a, n, hipMemcpyDeviceToHost));
     return trx_scene_check(s, nullptr);
+}
+
+extern "C" {
+
+int trx_trace_rays_inst(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, trx_hit *out_hits, uint32_t *out_inst,
+                        float *out_ms) {
+    return rays_host(s, rays, n, sem, 0u, out_hits, out_inst, out_ms);
+}
+
+int trx_trace_occluded(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint8_t *out_flags, float *out_ms) {
+    return occluded_host(s, rays, n, sem, 0u, out_flags, out_ms);
+}
+
+int trx_trace_rays_masked(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, trx_hit *out_hits,
+                          uint32_t *out_inst, float *out_ms) {
+    if (int rc = check_ray_mask(ray_mask)) return rc; // (before the upload)
+    return rays_host(s, rays, n, sem, ray_mask, out_hits, out_inst, out_ms);
+}
+
+int trx_trace_occluded_masked(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask,
+                              uint8_t *out_flags, float *out_ms) {
+    if (int rc = check_ray_mask(ray_mask)) return rc; // (before the upload)
+    return occluded_host(s, rays, n, sem, ray_mask, out_flags, out_ms);
 }
 
 

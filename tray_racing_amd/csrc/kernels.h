@@ -177,7 +177,17 @@ struct TraceParams {
     // enqueue(); left to the compiler each division keeps its reciprocal in a VECTOR register for the whole kernel
     uint32_t rcp_tiles_x, rcp_width, rcp_tiles_per_frame, rcp_n_frames;
     ViewDev views[kMaxBatchFrames];
+    uint32_t ray_mask; // instance masks: the masked calls' ray mask (1..255), 0 for every other launch (see TraceParamsTlas)
 };
+// The two-level kernels' parameters: TraceParams, then the instance mask table of the masked trace calls
+// (trx_trace_*_masked*): one byte per TLAS primitive; the two-level walk enters primitive k only if
+// (inst_mask[k] & ray_mask) != 0.  Null: every instance is entered (the unmasked calls, and masked calls on a scene without
+// a table).  The single-level kernels take TraceParams alone: ray_mask sits in what was its tail padding, so TraceParams
+// keeps its 1536 bytes and the single-level kernels' arguments - the hidden ones behind them included - keep their offsets.
+struct TraceParamsTlas : TraceParams {
+    const uint8_t *inst_mask;
+};
+static_assert(sizeof(TraceParams) == 1536, "TraceParams grew: every single-level kernel's hidden arguments would move");
 
 // Hit attributes (k_hit_attr, trx_hit_attributes_*): one lane per hit record, no traversal.
 enum HitAttrMode : int { kAttrRays = 0, kAttrPrimary = 1 };
@@ -199,7 +209,8 @@ hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream)
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count);
 
 // Enqueues one traversal kernel.  sem: trx_semantics bits; pipe: the pipelined walk (BLAS-only scenes; ignored with a TLAS).
-hipError_t launch_trace(const TraceParams &p, int mode, bool tlas, uint32_t sem, bool count, bool pipe, int grid,
+// (single-level kernels receive the TraceParams part of p)
+hipError_t launch_trace(const TraceParamsTlas &p, int mode, bool tlas, uint32_t sem, bool count, bool pipe, int grid,
                         hipStream_t stream);
 
 } // namespace trx

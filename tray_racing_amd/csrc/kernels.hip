@@ -702,8 +702,11 @@ __device__ __forceinline__ u32x4 sys_load128(const void *p) {
 // the triangle phase of the node just tested, so the two memory round trips of a step overlap (the next node does
 // not depend on the triangles' results, only its test does: it reads the shrunken t).  A ray then occupies its lane
 // for one trip more (its last trip has triangle work only), which is why coherent, issue-bound frames do not want it.
+template <bool TLAS>
+using KernelParams = std::conditional_t<TLAS, TraceParamsTlas, TraceParams>; // (kernels.h, TraceParamsTlas)
+
 template <int MODE, bool TLAS, int NODE, bool PIPE, bool COUNT>
-__global__ void __launch_bounds__(kMaxBlock, TRX_MIN_WAVES) k_trace(const TraceParams P) {
+__global__ void __launch_bounds__(kMaxBlock, TRX_MIN_WAVES) k_trace(const KernelParams<TLAS> P) {
     // (P is the kernel's ONLY parameter: refill_params() reads it back from offset 0 of the kernel-argument segment)
     static_assert(!(PIPE && TLAS), "the pipelined walk is BLAS-only");
     // triangles of a lane requested together in a per-lane triangle round (the two-level walk has fewer registers to spare)
@@ -770,16 +773,17 @@ __global__ void __launch_bounds__(kMaxBlock, TRX_MIN_WAVES) k_trace(const TraceP
 #undef wray
 
 template <int MODE, bool TLAS, int NODE, bool PIPE, bool COUNT>
-hipError_t launch_one(const TraceParams &p, int grid, hipStream_t stream) {
+hipError_t launch_one(const TraceParamsTlas &p, int grid, hipStream_t stream) {
     // grid = total waves; p.waves_per_block waves share a workgroup (and nothing else)
     const int wpb = (int)p.waves_per_block;
     const size_t lds = (size_t)wpb * kLdsBytesPerWave;
-    hipLaunchKernelGGL((k_trace<MODE, TLAS, NODE, PIPE, COUNT>), dim3(grid / wpb), dim3(kWave * wpb), lds, stream, p);
+    const KernelParams<TLAS> &kp = p; // (single-level kernels: the TraceParams part)
+    hipLaunchKernelGGL((k_trace<MODE, TLAS, NODE, PIPE, COUNT>), dim3(grid / wpb), dim3(kWave * wpb), lds, stream, kp);
     return hipGetLastError();
 }
 
 template <int MODE, bool TLAS, bool PIPE, bool COUNT>
-hipError_t launch_node(const TraceParams &p, int node, int grid, hipStream_t stream) {
+hipError_t launch_node(const TraceParamsTlas &p, int node, int grid, hipStream_t stream) {
     switch (node) {
     case 0: return launch_one<MODE, TLAS, 0, PIPE, COUNT>(p, grid, stream);
     case 1: return launch_one<MODE, TLAS, 1, PIPE, COUNT>(p, grid, stream);
@@ -789,7 +793,7 @@ hipError_t launch_node(const TraceParams &p, int node, int grid, hipStream_t str
 }
 
 template <int MODE>
-hipError_t launch_mode(const TraceParams &p, bool tlas, int node, bool count, bool pipe, int grid, hipStream_t stream) {
+hipError_t launch_mode(const TraceParamsTlas &p, bool tlas, int node, bool count, bool pipe, int grid, hipStream_t stream) {
     if constexpr (MODE == kModeService) {
         // (the resident kernel is the plain thin walk, single- or two-level: no pipelining, no counting)
         if (count) return hipErrorInvalidValue;
@@ -944,7 +948,7 @@ int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count) {
     return per_cu * prop.multiProcessorCount;
 }
 
-hipError_t launch_trace(const TraceParams &p, int mode, bool tlas, uint32_t sem, bool count, bool pipe, int grid,
+hipError_t launch_trace(const TraceParamsTlas &p, int mode, bool tlas, uint32_t sem, bool count, bool pipe, int grid,
                         hipStream_t stream) {
     const int node = node_variant(sem);
     switch (mode) {

@@ -193,6 +193,28 @@
                         cur = make_uint2(0u, 0u);
                     }
                 }
+                // instance masks (trx_trace_*_masked*): an instance of the TLAS leaf group whose mask misses the call's ray
+                // mask is dropped where the pick below would enter it, and the walk goes on as it would after entering an
+                // EMPTY instance: with the TLAS node group `cur` if it holds children (the rest of the leaf group parked
+                // under it), else with the next instance of the group.  So the TLAS visits everything else in the
+                // unmasked order, and a group whose instances are all invisible enters nothing.  (P.inst_mask is a launch
+                // argument, so the test is wave-uniform; the unmasked launches pass null and never run the loop.)
+                if constexpr (TLAS) {
+                    if (__builtin_expect(P.inst_mask != nullptr, 0) && act && tlas_sp == TRX_INVALID && tri.y != 0u) {
+                        bool park = false;
+                        while (tri.y != 0u) {
+                            const uint32_t local = 31u - (uint32_t)__clz((int)tri.y);
+                            if ((P.inst_mask[tri.x + local] & P.ray_mask) != 0u) break;
+                            tri.y &= ~(1u << local);
+                            if ((cur.y & 0xff000000u) != 0u) {
+                                park = true;
+                                break;
+                            }
+                        }
+                        stack_push(tri, park && tri.y != 0u);
+                        if (park) tri.y = 0u;
+                    }
+                }
                 if (TLAS && act && tlas_sp == TRX_INVALID && tri.y != 0u) { // (after either kind of node step)
                     // a TLAS primitive is an instance (query_tlas.hlsl:410-446): enter its BLAS
                     const uint32_t local = 31u - (uint32_t)__clz((int)tri.y);

@@ -327,6 +327,21 @@ class Scene:
             L.check(self._lib.trx_scene_get_instance_world_to_object(self._h, k, _ptr(out[k])))
         return out
 
+    def set_instance_masks(self, masks):
+        """8-bit mask per TLAS primitive (uint8, n_instances), read by the *_masked calls only; None removes the table
+        (every instance 0xFF).  Refused on single-level scenes."""
+        if masks is None:
+            L.check(self._lib.trx_scene_set_instance_masks(self._h, None, 0))
+            return
+        m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+        L.check(self._lib.trx_scene_set_instance_masks(self._h, _ptr(m), m.size))
+
+    def instance_masks(self):
+        """The mask table as set, 0xFF everywhere when none is (single-level scenes: one instance)."""
+        out = np.empty(max(self.flat.instance_offsets.size, 1), dtype=np.uint8)
+        L.check(self._lib.trx_scene_get_instance_masks(self._h, _ptr(out), out.size))
+        return out
+
     def refit(self, tri_verts):
         """New vertices for every triangle record, in record order ([n_tris, 9] f32; record_order_verts maps object-order
         vertices): trx_scene_refit for a numpy array, trx_scene_refit_dev on torch.cuda.current_stream() for a tensor on
@@ -428,6 +443,25 @@ class Scene:
         ms = C.c_float()
         L.check(self._lib.trx_trace_rays_attr(self._h, _ptr(rays), n, sem, _ptr(hits), _ptr(inst), _ptr(attr), C.byref(ms)))
         return hits, inst, attr
+
+    def trace_rays_masked(self, rays, ray_mask, sem=L.SEM_HLSL):
+        """(hits, instance ids, ms) of a masked trace: instance k is entered only if its mask & ray_mask != 0."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        hits = np.empty(rays.shape[0], dtype=HIT_DTYPE)
+        inst = np.empty(rays.shape[0], dtype=np.uint32)
+        ms = C.c_float()
+        L.check(self._lib.trx_trace_rays_masked(self._h, _ptr(rays), rays.shape[0], sem, ray_mask, _ptr(hits), _ptr(inst),
+                                                C.byref(ms)))
+        return hits, inst, ms.value
+
+    def trace_occluded_masked(self, rays, ray_mask, sem=L.SEM_HLSL):
+        """(uint8 flags, ms): trace_occluded over the instances ray_mask sees."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        flags = np.empty(rays.shape[0], dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_trace_occluded_masked(self._h, _ptr(rays), rays.shape[0], sem, ray_mask, _ptr(flags),
+                                                    C.byref(ms)))
+        return flags, ms.value
 
     def trace_rays(self, rays, sem=L.SEM_HLSL):
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
@@ -554,6 +588,25 @@ class Scene:
     def trace_occluded_dev(self, d_rays, n, d_flags, sem=L.SEM_HLSL, stream=0):
         L.check(self._lib.trx_trace_occluded_dev(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_flags),
                                                  C.c_void_p(stream)))
+
+    def trace_rays_masked_dev(self, d_rays, n, d_hits, ray_mask, sem=L.SEM_HLSL, d_inst=0, stream=0):
+        L.check(self._lib.trx_trace_rays_masked_dev(self._h, C.c_void_p(d_rays), n, sem, ray_mask, C.c_void_p(d_hits),
+                                                    C.c_void_p(d_inst), C.c_void_p(stream)))
+
+    def trace_occluded_masked_dev(self, d_rays, n, d_flags, ray_mask, sem=L.SEM_HLSL, stream=0):
+        L.check(self._lib.trx_trace_occluded_masked_dev(self._h, C.c_void_p(d_rays), n, sem, ray_mask, C.c_void_p(d_flags),
+                                                        C.c_void_p(stream)))
+
+    def trace_primary_masked_dev(self, view, width, height, d_hits, ray_mask, sem=L.SEM_HLSL, d_inst=0, shard=(0, 1),
+                                 stream=0):
+        L.check(self._lib.trx_trace_primary_masked_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask,
+                                                       C.c_void_p(d_hits), C.c_void_p(d_inst), C.c_void_p(stream)))
+
+    def trace_ao_masked_dev(self, view, width, height, d_primary, d_ao, ray_mask, sem=L.SEM_HLSL, frame=0, ao_eps=0.01,
+                            d_primary_inst=0, d_ao_inst=0, shard=(0, 1), stream=0):
+        L.check(self._lib.trx_trace_ao_masked_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, frame, ao_eps,
+                                                  ray_mask, C.c_void_p(d_primary), C.c_void_p(d_primary_inst),
+                                                  C.c_void_p(d_ao), C.c_void_p(d_ao_inst), C.c_void_p(stream)))
 
     def hit_attributes_rays_dev(self, d_rays, n, d_hits, d_attr, d_inst=0, stream=0):
         """trx_hit_attributes_rays_dev: n trx_hit_attr records at d_attr for the hits d_hits of the rays d_rays (d_inst: the
