@@ -10,11 +10,19 @@ on one HIP stream, ONE hipEvent pair on that stream around all of them — after
 the GPU out of its idle clocks and the W warm-up launches.  `value` is rays * K / wall-clock of the timed region;
 `kernel_ms_mean` is that event pair / K (the average launch duration, gaps included); `kernel_ms_min` and
 `kernel_ms_per_step` are per-launch event pairs of the same frames run once more right after the timed region (an event
-pair per launch inside it costs about 5 us of idle GPU per frame).  Beside it, as separate legs that never enter
-`value`: the reference's own protocol (3 passes x [3 discarded + 20 timed frames], min and mean), the first
+pair per launch inside it costs about 5 us of idle GPU per frame).  Beside it, with `--full` only, as separate legs
+that never enter `value`: the reference's own protocol (3 passes x [3 discarded + 20 timed frames], min and mean), the first
 frame of a geometry (tile order not yet learnt: `cold_order_ms`), the literal-HLSL arithmetic
 (`sem_hlsl_ms`), frames overlapped on 4 streams (`pipelined_mrays`), a measured HBM copy ceiling, live
 rocprofv3 counter passes of the same workload (child processes) and the CPU port on the host cores.
+
+A plain run (no `--full`) does only what the headline needs: set-up, the wake frames, the W warm-up steps, the K timed
+steps, `--dump-outputs` / `--dump-frame` if asked, and the JSON line.  `metric`, `value`, `unit`, `ms_per_step`,
+`kernel_ms_mean` and the rest of the headline fields are the same figures either way; what needs runs of its own is null
+or empty there (`roofline`, `roofline_hbm`, `legs`, `kernel_ms_min`, `kernel_ms_per_step` at N = 1,
+`n1_same_protocol_mrays`) or absent (`cpu_baseline`, `parity_vs_oracle_full_frame`), and the line says `"full": false`.
+`--full` adds, after the timed region: the per-launch replay, the timed-region repeats, the N > 1 one-rank run under the
+same protocol, the legs, the counting kernel's roofline, the live counter passes, the CPU baseline and the parity check.
 
 N > 1 (one process per GPU; under `python -m torch.distributed.run` as the driver launches it, or plain
 `python bench.py --gpus N`, which starts those ranks itself before it touches the GPU): the frame's 8x8 tiles are dealt round-robin to the
@@ -162,13 +170,18 @@ def parse():
                          "scene and its clocks take about 20 ms of load to come back up (profiles/r04_clock_ramp.log: the same "
                          "kernel runs 5-7 %% slower for its first ~40 frames after an idle second, whatever the tile order); 0 = "
                          "none, the warm-up steps then run on a GPU at idle clocks")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well (per-launch replay, timed-region repeats, "
+                         "the one-rank same-protocol run at N > 1, the legs, roofline and live counter passes, CPU baseline and "
+                         "parity with the oracle); without it a run does only what `value` and `ms_per_step` need")
     ap.add_argument("--repeats", type=int, default=7,
-                    help="the timed region is run this many times in all; `value` is the FIRST (the contract's K steps), "
-                         "legs.timed_region_repeats carries median / min / max over all of them")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 counter passes (child processes)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (cold order, HLSL, pipelined, HBM copy)")
+                    help="--full: the timed region is run this many times in all; `value` is the FIRST (the contract's K "
+                         "steps), legs.timed_region_repeats carries median / min / max over all of them")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the live rocprofv3 counter passes (child processes)")
+    ap.add_argument("--no-legs", action="store_true",
+                    help="--full without the secondary legs (cold order, HLSL, pipelined, HBM copy, ...)")
     ap.add_argument("--sim-shards", type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument("--gather", default="torch", choices=["torch", "abi"],
                     help="N > 1: the shard gather through torch.distributed (default) or through the C ABI "
@@ -416,9 +429,12 @@ def main():
     frames = [torch.empty(F * n_rays_total, dtype=torch.int64, device="cuda") for _ in range(n_streams)]
     state = {"k": 0, "batch": 0, "last": None}
 
-    # algorithmic bytes of ONE launch on this rank (counting kernel = the reference's PROFILE_RT counters)
-    st = scene.count_primary(view, w, h, sem=args.sem, shard=shard_img)
-    launch_bytes = NODE_BYTES * st.n_node + TRI_BYTES * st.n_tri + HIT_BYTES * st.n_rays
+    # algorithmic bytes of ONE launch on this rank (counting kernel = the reference's PROFILE_RT counters): the roofline's
+    # (--full), and the rays of one rank's shard under --sim-shards
+    st = launch_bytes = None
+    if args.full or args.sim_shards > 1:
+        st = scene.count_primary(view, w, h, sem=args.sem, shard=shard_img)
+        launch_bytes = NODE_BYTES * st.n_node + TRI_BYTES * st.n_tri + HIT_BYTES * st.n_rays
 
     L_launch = args.frames_per_launch if args.frames_per_launch > 0 else (1 if world == 1 else F)
     L_launch = max(1, min(L_launch, 8, F if world > 1 else 8))
@@ -550,14 +566,15 @@ def main():
     region_kernel_ms = None
     if one_pair:
         region_kernel_ms = r0.elapsed_time(r1) / args.steps   # average launch duration over the timed region, gaps included
-        run_frames(min(args.steps, 64), events)               # untimed: the same frames again, an event pair each
-        sync_all()
+        if args.full:
+            run_frames(min(args.steps, 64), events)           # untimed: the same frames again, an event pair each
+            sync_all()
     launch_ms = [a.elapsed_time(b) / n for a, b, n in events]   # per frame of each launch
-    # The timed region again, REPEATS - 1 more times (same K steps, same barriers; never part of `value`): a K = 20 region at
-    # N = 8 is about a millisecond of wall clock, so the line carries the median and the spread of the repetitions next to
-    # the one region the contract defines.
+    # --full: the timed region again, REPEATS - 1 more times (same K steps, same barriers; never part of `value`): a K = 20
+    # region at N = 8 is about a millisecond of wall clock, so the line carries the median and the spread of the repetitions
+    # next to the one region the contract defines.
     repeat_s = [elapsed]
-    for _ in range(max(args.repeats, 1) - 1):
+    for _ in range(max(args.repeats, 1) - 1 if args.full else 0):
         sync_all()
         tr = time.perf_counter()
         run_frames(args.steps, None if one_pair else [])
@@ -574,7 +591,7 @@ def main():
     # this run's streams / frames-per-launch, no gather, while the other ranks wait - the figure a scaling factor has to be
     # quoted against (`scaling_vs_same_protocol`), next to the driver's own N = 1 line.
     n1_same = None
-    if world > 1 and args.sim_shards == 1:
+    if world > 1 and args.sim_shards == 1 and args.full:
         if rank == 0:
             solo = [torch.empty(L_launch * n_rays_total, dtype=torch.int64, device="cuda") for _ in range(n_streams)]
 
@@ -621,7 +638,7 @@ def main():
 
     out = None
     legs = {}
-    if rank == 0 and world == 1 and args.sim_shards == 1 and not args.no_legs:
+    if rank == 0 and world == 1 and args.sim_shards == 1 and args.full and not args.no_legs:
         ctx = {}  # what later legs need of earlier ones (the bench frame's primary hits on the device, ...)
         variant0 = int(args.kernel_variant, 0)
 
@@ -1094,7 +1111,7 @@ def main():
             print("WARNING: bench legs failed: %s" % ", ".join(failed), file=sys.stderr)
 
     pmc, pmc_src, pmc_ms = None, None, None
-    if rank == 0 and world == 1 and args.sim_shards == 1:
+    if rank == 0 and world == 1 and args.sim_shards == 1 and args.full:
         if not args.no_pmc:
             npz = os.path.join(tempfile.gettempdir(), "trx_bench_scene_%d.npz" % os.getpid())
             np.savez(npz, nodes=flat.nodes, tri_verts=flat.tri_verts, instance_offsets=flat.instance_offsets,
@@ -1120,7 +1137,8 @@ def main():
                 except Exception:  # noqa: BLE001
                     pmc = None
 
-    if rank == 0:
+    roof = hbm = None
+    if rank == 0 and args.full:
         req_gbs = launch_bytes / (kernel_ms * 1e-3) / 1e9
         traffic = None
         valu = None
@@ -1231,13 +1249,15 @@ def main():
                     "achieved / frac = MEASURED HBM traffic (FETCH_SIZE doubled + WRITE_SIZE), the requested bytes are "
                     "served by the caches because coherent rays share lines",
         }
-        rep_ms = sorted(x / args.steps * 1e3 for x in repeat_s)
-        legs["timed_region_repeats"] = {
-            "n": len(rep_ms), "steps_each": args.steps, "ms_per_step_median": round(rep_ms[len(rep_ms) // 2], 4),
-            "ms_per_step_min": round(rep_ms[0], 4), "ms_per_step_max": round(rep_ms[-1], 4),
-            "mrays_median": round(rays_per_step / (rep_ms[len(rep_ms) // 2] * 1e-3) / 1e6, 1),
-            "note": "`value` / `ms_per_step` are the FIRST region (the contract's K steps); the others follow it, each behind a barrier",
-        }
+    if rank == 0:
+        if args.full:
+            rep_ms = sorted(x / args.steps * 1e3 for x in repeat_s)
+            legs["timed_region_repeats"] = {
+                "n": len(rep_ms), "steps_each": args.steps, "ms_per_step_median": round(rep_ms[len(rep_ms) // 2], 4),
+                "ms_per_step_min": round(rep_ms[0], 4), "ms_per_step_max": round(rep_ms[-1], 4),
+                "mrays_median": round(rays_per_step / (rep_ms[len(rep_ms) // 2] * 1e-3) / 1e6, 1),
+                "note": "`value` / `ms_per_step` are the FIRST region (the contract's K steps); the others follow it, each behind a barrier",
+            }
         # the collective's world as the communicator itself reports it (ncclCommCount through trx_comm_world_size, or
         # torch.distributed's own count): 1 at N = 1, where no communicator exists
         rccl_world = 1
@@ -1293,6 +1313,7 @@ def main():
             # measured traffic, timed-region repeats, same-protocol N = 1 figure at N > 1, no-wake leg (the round-3 / round-4
             # lines differ from each other by the wake frames: README "Bench protocol")
             "protocol_version": 6,
+            "full": args.full,   # false: the headline alone, nothing that needs runs of its own (see the top of this file)
             "build": stamp,
             "rccl_world": rccl_world,
             # per rank: wall clock from the start of main() to the end of the set-up frames (scene generated / loaded / built
@@ -1304,12 +1325,14 @@ def main():
             "n1_same_protocol_mrays": round(n1_same, 2) if n1_same else None,
             "scaling_vs_same_protocol": round(value / n1_same, 4) if n1_same else None,
             "kernel_ms_mean": round(kernel_ms, 4),
-            "kernel_ms_min": round(min(launch_ms), 4),
-            "kernel_ms_min_source": ("per-launch hipEvent pairs of an untimed REPLAY of the same frames right after the timed "
+            # (null in a plain run with one frame in flight: its per-launch event pairs come from the --full replay)
+            "kernel_ms_min": round(min(launch_ms), 4) if launch_ms else None,
+            "kernel_ms_min_source": (None if not launch_ms else
+                                     "per-launch hipEvent pairs of an untimed REPLAY of the same frames right after the timed "
                                      "region" if region_kernel_ms is not None else "per-launch hipEvent pairs of the timed region"),
             # per-launch event times in order (for one frame in flight: of the untimed pass that follows the timed region;
             # kernel_ms_mean is then the timed region's own event pair / steps): shows a schedule or a clock still settling
-            "kernel_ms_per_step": [round(x, 4) for x in launch_ms] if len(launch_ms) <= 64 else None,
+            "kernel_ms_per_step": [round(x, 4) for x in launch_ms] if launch_ms and len(launch_ms) <= 64 else None,
             "kernel_ms_mean_source": ("one hipEvent pair around the K timed launches / K" if region_kernel_ms is not None else
                                       "mean of the per-launch hipEvent pairs of the timed region"),
             "timed_region_ms": round(elapsed * 1e3, 3),
@@ -1351,7 +1374,7 @@ def main():
         np.save(os.path.join(args.dump_outputs, "prim.npy"), hits["prim"].astype(np.float64))
     # CPU baseline: the oracle (a port, not the reference binary) on the host cores, rank 0 at N=1 only; it is
     # the only place this file touches oracle/ (as the thing timed beside the GPU, and as the frame's checker)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.sim_shards == 1:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.sim_shards == 1:
         from oracle import binding as O
         osc = O.Scene.from_flat(flat)
         ov = O.view_from_bytes(view)

@@ -216,6 +216,7 @@ def test_default_arguments_finish_in_minutes():
     finally:
         sys.argv = argv
     assert a.gpus == 1 and a.steps * 0.5e-3 < 5 and a.warmup < a.steps and a.cpu_seconds <= 30
+    assert a.full is False                                  # a plain run is the headline alone (--full adds the rest)
     assert mod.baseline_metric() == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
 
 

@@ -88,7 +88,7 @@ def test_bench_takes_a_real_scene_file(tmp_path):
     open(scene, "w").write('(\n model_path: "assets/obj/quad.obj",\n camera: (\n eye: (0.0, 0.0, 3.0),\n look_at: (0.0, 0.0, 0.0),\n'
                            ' fov: 60.0,\n exposure: 0.0,\n ),\n sun_direction: (0.5, -0.24, 0.5),\n)')
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--input", scene, "--steps", "5", "--warmup", "2", "--width", "256",
-                          "--height", "144", "--no-legs", "--no-pmc", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--height", "144", "--full", "--no-legs", "--no-pmc", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["data"] == "real" and os.path.basename(scene) in d["config"]["workload"] and d["value"] > 0

@@ -1036,7 +1036,7 @@ def test_bench_two_ranks_share_the_gpu(trx, orc, tmp_path, world, streams, batch
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps",
            str(batch + 2), "--warmup", "2", "--tris", "150000", "--width", "256", "--height", "136", "--dist-backend", "gloo",
-           "--dump-frame", dump, "--streams", str(streams), "--gather-batch", str(batch)] + extra
+           "--dump-frame", dump, "--streams", str(streams), "--gather-batch", str(batch), "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -1094,6 +1094,37 @@ def test_bench_launches_its_own_ranks(trx, orc, tmp_path):
     # a rank that fails makes the parent fail: the launcher's return code is relayed
     bad = subprocess.run(cmd[:-2] + ["--scene", "no_such_scene"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert bad.returncode != 0
+
+
+def test_bench_plain_run_is_the_headline_alone(trx, orc, tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, the outputs and the line, nothing else - no legs,
+    no roofline, no CPU baseline, no per-launch replay - and what --dump-outputs writes is the oracle's frame."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    w, h = 256, 144
+    dump, outs = str(tmp_path / "frame.npy"), str(tmp_path / "outs")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--tris", "150000",
+           "--width", str(w), "--height", str(h), "--dump-frame", dump, "--dump-outputs", outs]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "Mrays/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["value"] > 0 and d["ms_per_step"] > 0 and d["kernel_ms_mean"] > 0
+    assert d["value"] == pytest.approx(w * h / (d["ms_per_step"] * 1e-3) / 1e6, rel=2e-2)
+    assert d["legs"] == {} and d["roofline"] is None and d["roofline_hbm"] is None
+    assert d["kernel_ms_min"] is None and d["kernel_ms_per_step"] is None and d["value_sem_hlsl"] is None
+    assert "cpu_baseline" not in d and "parity_vs_oracle_full_frame" not in d
+    g = np.load(dump + ".scene.npz")
+    osc = orc.Scene(g["nodes"], g["tri_verts"], g["instance_offsets"], int(g["tlas_start"]))
+    want, _ = osc.trace_primary(orc.view_from_bytes(g["view"].tobytes()), w, h, sem=3)
+    hit = want["prim"] != trx.MISS_PRIM
+    assert np.array_equal(np.load(os.path.join(outs, "hit.npy")), hit.astype(np.float32))
+    assert np.array_equal(np.load(os.path.join(outs, "t.npy")), np.where(hit, want["t"], np.float32(0)).astype(np.float32))
+    assert np.array_equal(np.load(os.path.join(outs, "prim.npy")), want["prim"].astype(np.float64))
 
 
 def test_scheduling_variants_and_streams_do_not_change_results(trx, orc):

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_r$(printf %02d "${ROUND:-6}")
 mkdir -p "$out"
 if [ -z "$SKIP_BENCH" ]; then   # (a call is limited to 20 minutes: the seven configs go in three calls, the bench line in the first)
-python3 bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+python3 bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_bench" -- python3 bench.py --steps 200 --warmup 40 --no-cpu-baseline --no-pmc --no-legs > "$out/stats_bench.log" 2>&1
 fi
 for cfg in ${CONFIGS:-primary_bistro primary_bistro_dense primary_hairball ao_bistro ao_hairball ao4_hairball tlas_san_miguel_4k rays_bistro}; do
