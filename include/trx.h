@@ -530,8 +530,7 @@ int trx_trace_occluded(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, u
  * pinned host memory (a caller claims a slot, writes its ray, spins on the slot's answer; single- and two-level scenes,
  * one service per semantics word in use) and that a watchdog thread stops 50 ms after the last call - until then a
  * device-wide synchronisation elsewhere in the process (hipDeviceSynchronize, hipFree) waits for it; trx_scene_destroy
- * stops it at once.  (TRX_TRAVERSE1_COMBINER=1 in the environment sends two-level scenes through round 5's path instead:
- * the callers inside this function at the same moment share one launch.)  A caller blocks for its ray's own walk plus
+ * stops it at once.  A caller blocks for its ray's own walk plus
  * 4 us through host memory, so the rate is (concurrent callers) / (16-45 us): use trx_traverse_batch where the rays can
  * be had together.  primitive_id indexes the PERMUTED triangle
  * list of the hit BLAS (primitive_indices order), exactly like the reference, whose scene structs store their

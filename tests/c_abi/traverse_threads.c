@@ -4,8 +4,7 @@
  * (32-byte trx_ray records, written by the test from the oracle's primary-ray generator), RayHits go to a file
  * (16-byte trx_rayhit records); stdout: "<rays> <seconds> <launches>".
  * usage: traverse_threads <scene> <tris> <threads> <semantics> <rays.bin> <hits.bin> [semantics of the odd threads [tlas]]
- * (an eighth argument builds the scene two-level: the single-ray path of two-level scenes is the launch combiner, that of
- * single-level scenes the resident ray service) */
+ * (an eighth argument builds the scene two-level; either kind of scene is served by the resident ray service) */
 #define _POSIX_C_SOURCE 200809L
 #include <pthread.h>
 #include <stdio.h>
@@ -74,7 +73,7 @@ int main(int argc, char **argv) {
                            flat->n_instances ? flat->instance_offsets : NULL, flat->n_instances, flat->tlas_start, 0, &scene));
     if (flat->instance_entry_nodes && flat->n_instances)
         CHECK(trx_scene_set_instance_entry_nodes(scene, flat->instance_entry_nodes, flat->n_instances));
-    /* one ray ahead of the clock: the first call creates the combiner (pinned buffers, streams) */
+    /* one ray ahead of the clock: the first call starts the ray service */
     if (n) CHECK(trx_traverse1(scene, &rays[0], sem, &hits[0]));
 
     pthread_t *tid = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)threads);

@@ -933,8 +933,8 @@ def test_sixteen_threads_call_traverse_for_their_pixels(trx, orc, tmp_path):
     """The reference's CPU pixel loop over the LITERAL Traversable::traverse (src/rt_cpu/rt_cpu.rs:35-57,
     traversable/src/lib.rs:13-28): tests/c_abi/traverse_threads.c runs 16 host threads, each calling trx_traverse1 for
     its pixels of the 512x1080 demoscene-class frame (configs[0]'s image; 500 000 triangles), one ray per call.  Every
-    RayHit equals the oracle's hit for that ray, and the calls shared launches (the per-scene combiner): far fewer
-    launches than rays."""
+    RayHit equals the oracle's hit for that ray, and the calls launched nothing per ray (the per-scene ray service): far
+    fewer service starts than rays."""
     import subprocess
     from test_abi import build_c_consumer
     exe = build_c_consumer("traverse_threads", tmp_path)
@@ -966,9 +966,8 @@ def test_sixteen_threads_call_traverse_for_their_pixels(trx, orc, tmp_path):
 @pytest.mark.parametrize("tlas", [0, 1])
 def test_callers_of_mixed_semantics_share_the_single_ray_path(trx, orc, tmp_path, tlas):
     """Even threads call trx_traverse1 with the CPU preset, odd threads with the shader's text, all at once: a scene runs
-    one ray service per semantics word (two-level scenes as well since the thin walk learned its two levels; round 5's launch
-    combiner, whose batches are of one semantics each, stays behind TRX_TRAVERSE1_COMBINER=1) - every RayHit equals the
-    oracle's under its caller's semantics."""
+    one ray service per semantics word (two-level scenes as well since the thin walk learned its two levels) - every RayHit
+    equals the oracle's under its caller's semantics."""
     import subprocess
     from test_abi import build_c_consumer
     exe = build_c_consumer("traverse_threads", tmp_path)

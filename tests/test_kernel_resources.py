@@ -86,9 +86,9 @@ def test_scalar_registers_parked_in_lanes_inside_loops():
       * the headline kernel k_trace<primary, BLAS, reciprocal arithmetic> has 14 inside its walk loop, ALL on the path
         that reads or writes a stack entry past the LDS part (the base of the wave's HBM area) or in the decode stage of a
         wave-uniform step (six lane-role masks); the pipelined AO kernel has 4 (triangle rounds);
-      * taking them out was built and measured (TRX_SPILL_BASE_LATE, TRX_DECODE_LANE_AFRESH): 0 in the loop, 76 instead of
-        128 in all - and the frame 0.7-1.2 % slower (another register assignment; profiles/r06_ab_lane_spills.log), so
-        the product keeps them.  The bound below is today's count plus a margin: a change that doubles it should be seen."""
+      * taking them out was built and measured (the HBM base formed on the rare paths, the lane roles taken afresh in the
+        decode stage; both since removed): 0 in the loop, 76 instead of 128 in all - and the frame 0.7-1.2 % slower
+        (another register assignment; profiles/r06_ab_lane_spills.log), so the product keeps them.  The bound below is today's count plus a margin: a change that doubles it should be seen."""
     import collections
     subprocess.run(["make", "-C", CSRC, "build/kernels.s"], check=True, capture_output=True, timeout=600)
     text = open(os.path.join(CSRC, "build", "kernels.s")).read()

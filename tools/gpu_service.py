@@ -1,6 +1,6 @@
-"""Round 6: rays per second of the single-ray trx_traverse1 through the resident ray service (single-level scenes) under
-1 / 4 / 16 / 64 host threads, against trx_traverse_batch on the same rays; and what the service's idle waves cost a
-concurrent primary frame.  usage: python tools/gpu_service.py [scene] [tris] [tlas]   (TRX_TRAVERSE1_COMBINER=1: two-level scenes through round 5's launch combiner)"""
+"""Round 6: rays per second of the single-ray trx_traverse1 through the resident ray service under 1 / 4 / 16 / 64 host
+threads, against trx_traverse_batch on the same rays; and what the service's idle waves cost a concurrent primary frame.
+usage: python tools/gpu_service.py [scene] [tris] [tlas]   (the word tlas: the scene two-level)"""
 import os
 import sys
 import time

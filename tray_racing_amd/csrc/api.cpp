@@ -332,7 +332,6 @@ void trx_scene_destroy(trx_scene *s) {
         if (fl.ao) (void)hipFree(fl.ao);
         if (fl.ao_inst) (void)hipFree(fl.ao_inst);
     }
-    delete s->comb;
     refit_state_free(s);
     delete s;
 }

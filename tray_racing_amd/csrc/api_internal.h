@@ -1,9 +1,9 @@
 // api_internal.h - what the translation units behind include/trx.h share: the scene object, its launch slots, the
-// single-ray combiner, error reporting and the launch path (api_launch.cpp).  Not installed; not part of the ABI.
+// ray service, error reporting and the launch path (api_launch.cpp).  Not installed; not part of the ABI.
 //   api.cpp          errors, devices, scene upload and its setters, the camera
 //   api_launch.cpp   enqueue(): launch slots, kernel parameters, tile-order state, the schedule tuner's host side
 //   api_trace.cpp    the trace / count / bench / diagnostic entry points (device-resident and host-buffer forms)
-//   api_traverse.cpp Traversable::traverse for one ray (concurrent callers share launches) and for batches
+//   api_traverse.cpp Traversable::traverse for one ray (the resident ray service) and for batches
 //   api_build.cpp    builders, flat-buffer assembly (cwbvh_gpu_runner's host half), scene generators and loaders
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
@@ -15,7 +15,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -29,9 +28,6 @@
 #include <thread>
 #include <vector>
 
-#include <climits>
-#include <linux/futex.h>
-#include <sys/syscall.h>
 #include <unistd.h>
 
 #include "../../include/trx.h"
@@ -85,86 +81,6 @@ struct Slot {
 
 } // namespace trxapi
 
-// trx_traverse1 is Traversable::traverse(&self, Ray) -> RayHit (traversable/src/lib.rs:13-28), called per pixel from every
-// worker of a thread pool at once (src/rt_cpu/rt_cpu.rs:35-57).  One launch per ray would be a host-to-device copy, a
-// one-wave launch, a copy back and a stream synchronisation for 32 bytes of work (rounds 1-4: ~25 k rays a second per
-// thread); so the callers that are inside trx_traverse1 at the same time share launches.  A caller drops its ray into the
-// open batch (pinned host memory the kernel reads and writes in place: no copies) and takes a ticket; the first one in
-// is the batch's leader: it waits until arrivals stop for a few microseconds (or kCap rays, or kMaxWait), closes the
-// batch, launches it on the batch's own stream, waits for it and wakes the others, who read their records by ticket.
-// Rays and results are those of the single-ray path; a caller still blocks for one GPU round trip (launch + completion,
-// 15-30 us), so the rate is (callers inside at once) / (round trip): it scales with the thread count, not with the GPU.
-struct RayCombiner {
-    static constexpr uint32_t kCap = 4096, kBatches = 4;
-    static constexpr int64_t kQuietNs = 3000, kMaxWaitNs = 50000;
-    // A wave steps a handful of rays about twice as fast as a few dozen (eight lanes to a ray, kernels.hip "thin waves"),
-    // and a small batch is all latency: its first kSpread rays are dealt eight to a 64-ray chunk - one wave each - the rest
-    // of a chunk being rays that end at the root (tmax < 0).  Ticket i's record sits at slot(i).
-    static constexpr uint32_t kSpread = 512, kSpreadSlots = kSpread / 8 * 64, kSlots = kSpreadSlots + (kCap - kSpread);
-    static uint32_t slot(uint32_t i) { return i < kSpread ? (i >> 3) * 64u + (i & 7u) : kSpreadSlots + (i - kSpread); }
-    static uint32_t slots_used(uint32_t n) { return n <= kSpread ? ((n + 7u) >> 3) * 64u : kSpreadSlots + (n - kSpread); }
-    static trx_ray null_ray() {
-        trx_ray r;
-        std::memset(&r, 0, sizeof(r));
-        r.direction[0] = 1.0f;
-        r.tmax = -1.0f; // nothing lies in [0, -1]: the root's test fails and the ray is finished after one step
-        return r;
-    }
-    struct Batch {
-        trx_ray *rays = nullptr;  // pinned, device-visible
-        trx_hit *hits = nullptr;
-        uint32_t *inst = nullptr;
-        uint32_t *over = nullptr; // pinned word the kernel sets when a ray of the batch overflowed its stack / hit the step cap
-        hipStream_t stream = nullptr;
-        uint32_t n = 0, sem = 0;
-        std::atomic<uint32_t> read{0};       // callers that have taken their record (the last one frees the batch)
-        int rc = 0;
-        std::string err;
-        enum State { kFree, kOpen, kFlying, kDone } state = kFree;
-        // bumped when the batch's results are in: followers spin on it, then sleep on it (a futex: a woken follower reads
-        // its record and leaves without taking any lock - woken through a condition variable they queued up on its mutex,
-        // 5-10 us each, and arrived at the next batch one by one)
-        std::atomic<uint32_t> done_epoch{0};
-    } batch[kBatches];
-    std::mutex mu;
-    std::condition_variable cv;              // the open batch changed, or a batch became free
-    std::atomic<int> inside{0};              // callers inside trx_traverse1 (spinning only pays while they fit the host's cores)
-    int waiting = 0;                         // ... of which wait on cv (another semantics' batch is open, or no batch is free): mu held
-    int cores = 1;
-    int open = -1;
-    int device = 0;
-    bool ok = false;
-    std::string init_err;
-    uint64_t launches = 0, rays = 0; // statistics (trx_debug_traverse1_stats)
-
-    explicit RayCombiner(int dev) : device(dev) {
-        for (Batch &b : batch) {
-            hipError_t e = hipHostMalloc((void **)&b.rays, kSlots * sizeof(trx_ray), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipHostMalloc((void **)&b.hits, kSlots * sizeof(trx_hit), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipHostMalloc((void **)&b.inst, kSlots * sizeof(uint32_t), hipHostMallocDefault);
-            if (e == hipSuccess)
-                for (uint32_t i = 0; i < kSpreadSlots; i++) b.rays[i] = null_ray();
-            if (e == hipSuccess) e = hipHostMalloc((void **)&b.over, 64, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking);
-            if (e != hipSuccess) {
-                init_err = hipGetErrorString(e);
-                return;
-            }
-        }
-        cores = (int)std::max(1u, std::thread::hardware_concurrency());
-        ok = true;
-    }
-    ~RayCombiner() {
-        for (Batch &b : batch) {
-            if (b.stream) (void)hipStreamDestroy(b.stream);
-            if (b.rays) (void)hipHostFree(b.rays);
-            if (b.hits) (void)hipHostFree(b.hits);
-            if (b.inst) (void)hipHostFree(b.inst);
-            if (b.over) (void)hipHostFree(b.over);
-        }
-    }
-};
-
 // trx_frame_loop's streams, events and device buffers (created on first use)
 struct FrameLoop {
     static constexpr int kBuffers = 4; // primary-hit buffers: the primary passes may run this many frames ahead of the AO passes
@@ -175,7 +91,7 @@ struct FrameLoop {
     uint64_t records = 0;
 };
 
-// trx_traverse1 over single-level scenes: a RESIDENT kernel answers the callers' rays out of a ring in pinned host memory
+// trx_traverse1: a RESIDENT kernel answers the callers' rays out of a ring in pinned host memory
 // (kernels.h, kSvcRays; kernel side in trace_service.inc) - no launch, no stream synchronisation per ray.  A caller claims
 // a slot, writes its ray as three 16-byte granules that carry a fresh sequence number, and spins on the slot's answer
 // word.  The kernel is started by the first call and stopped by a watchdog thread after kIdleStopNs without a call (or by
@@ -252,9 +168,7 @@ struct trx_scene {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<uint32_t> blas_tri_start; // geometry_id lookup for trx_traverse1
     FrameLoop loop;                // trx_frame_loop
-    RayCombiner *comb = nullptr;   // trx_traverse1 over two-level scenes: concurrent single-ray callers share launches (created on first use)
-    std::once_flag comb_once;
-    RayService *svc[8] = {};       // trx_traverse1 over single-level scenes: one resident kernel per semantics word in use
+    RayService *svc[8] = {};       // trx_traverse1: one resident kernel per semantics word in use
     std::mutex svc_mu;             // creation of the services
     // instance transforms (TLAS scenes): object-to-world as given (get_instance_transform), world-to-object rows as
     // the kernels use them, and their device copy; empty / null = identity
@@ -292,11 +206,10 @@ void forget_tile_orders(trx_scene *s);
 // trx_scene_refit's per-scene state (api_refit.cpp)
 void refit_state_free(trx_scene *s);
 uint64_t refit_state_bytes(const trx_scene *s);
-// explicit rays (api_trace.cpp; trx_traverse1's batches launch through it)
+// explicit rays (api_trace.cpp)
 // (ray_mask != 0: a masked trace - enqueue() hands the kernel the scene's instance mask table)
 int trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
-                    trx::SlotCounters **ctr, bool any_hit = false, uint32_t *d_inst = nullptr, uint32_t *over_host = nullptr,
-                    bool one_queue = false, uint32_t ray_mask = 0);
+                    trx::SlotCounters **ctr, bool any_hit = false, uint32_t *d_inst = nullptr, uint32_t ray_mask = 0);
 
 } // namespace trxapi
 

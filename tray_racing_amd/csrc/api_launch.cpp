@@ -158,8 +158,8 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     if (p.n_frames > 1 && mode == kModePrimary) p.refill_idle = 64u; // the kernel takes the frame of a wave from its (whole) tile
     p.variant = variant;
 #ifdef TRX_DEV_TUNE
-    {   // development builds only (make KFLAGS=-DTRX_DEV_TUNE): experiment switches of kernels.hip, some of which
-        // produce wrong results on purpose (ablation timing); the product has no such environment variable
+    {   // development builds only (make KFLAGS=-DTRX_DEV_TUNE): 0x100 = the kernels' diagnostic histograms, and the
+        // forcing bits of two heuristics below (pipelined walk, decode-once step); the product has no such environment variable
         const char *tune = getenv("TRX_TUNE");
         p.tune = tune ? (uint32_t)strtoul(tune, nullptr, 0) : 0u;
     }
@@ -175,16 +175,7 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     }
     {   // tuning: variant bits 25..27 = compaction threshold (0 = default, 7 = never); bit 28 = no thin waves (A/B runs)
         const uint32_t c = (variant >> 25) & 0x7u;
-#ifndef TRX_THIN_MAX_DEFAULT
-#define TRX_THIN_MAX_DEFAULT 8u // (tuning builds: 16 with -DTRX_THIN_LEVELS=2, 32 with 3)
-#endif
-        p.thin_max = ((variant >> 28) & 1u) ? 0u : TRX_THIN_MAX_DEFAULT;
-#ifdef TRX_DEV_TUNE
-        {   // (development builds: TRX_THIN_MAX = 0 / 8 / 16 / 32)
-            const char *tm = getenv("TRX_THIN_MAX");
-            if (tm) p.thin_max = (uint32_t)strtoul(tm, nullptr, 0);
-        }
-#endif
+        p.thin_max = ((variant >> 28) & 1u) ? 0u : 8u;
         // a lane's first kTriBatch triangles go in one per-lane round: the scans are only worth computing beyond that
         p.tri_compact_min = c == 0u ? (uint32_t)(s->tlas ? kTriBatchTlas : kTriBatch) + 1u : c == 7u ? 0xffffffffu : c;
         // tuning: variant bits 29..31 = per-lane rounds one cooperative round is worth (0 = default 2; 7 = always cooperative)
@@ -199,7 +190,7 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     }
     p.waves_per_block = wpb;
     p.merge = merge_default ? 1u : 0u;
-    // Decode-once node test on wave-uniform node steps (kernels.hip, node_intersect_dec): every primary pass (two-level
+    // Decode-once node test on wave-uniform node steps (kernels.hip, node_intersect_kept): every primary pass (two-level
     // scenes since round 5: san-miguel-class 4K frame -3.3 %, profiles/r05_ab_5_tlas.log).
     // With the plane-major table of round 3 it paid only where almost every step is uniform (kitchen-class frame -4 %, 90 %
     // of its steps) and was kept to scenes of up to 32 MiB; with the {near, far} pair tables of round 4 the bistro-class
@@ -211,7 +202,7 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     if (p.tune & 0x80000u) p.uni_decode = 0u;
 #endif
     p.wave_times = s->d_wave_times;
-    p.single_queue = ((variant >> 21) & 1u) | (p.single_queue ? 1u : 0u); // (a caller may ask for it: trx_traverse1's small batches)
+    p.single_queue = (variant >> 21) & 1u;
     // tile order feedback (image modes, whole-tile refills only)
     // (an AO batch deals its tiles seed by seed within a queue: it has no tile order to learn)
     // (Round 6 tried an order for one-seed AO passes with mid-tile refills as well - first pass of a view natural, second
@@ -275,9 +266,6 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
         p.fb = (s->dbg_cost || ((variant >> 19) & 1u)) ? nullptr : &slot.ctr->fb[mode == kModeAo ? 1 : 0];
         p.no_order = no_order ? 1u : 0u;
         p.new_view = cut ? 1u : 0u;
-#ifdef TRX_DEV_TUNE
-        if (p.tune & 0x8000000u) p.no_order = cut ? 1u : 0u; // (A/B: the round-3 first version, natural order after a cut)
-#endif
         // A frame whose views are bit for bit those of the previous launch of this kind on the slot replays a complete
         // order as it stands (the kernel decides: it alone knows whether the set it reads is complete) - the order filed
         // by the first frame of a view, frozen, is the fastest one measured and costs no filing (kernels.hip); any other
@@ -307,9 +295,6 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     }
     if (s->dbg_cost) { // diagnostics: cold tile order, costs / iteration counts into the caller's buffers
         p.no_order = 1u;
-#ifdef TRX_DEV_TUNE
-        if (p.tune & 0x2000000u) p.no_order = 0u; // (tools/gpu_tail.py: the costs of a frame in its LEARNT order)
-#endif
         p.cost = s->dbg_cost;
         p.tile_iters = s->dbg_iters;
     }

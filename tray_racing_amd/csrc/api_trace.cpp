@@ -158,8 +158,7 @@ int trx_trace_ao_batch_dev(trx_scene *s, const trx_view *view, uint32_t w, uint3
 } // extern "C"
 
 int trxapi::trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
-                            SlotCounters **ctr, bool any_hit, uint32_t *d_inst, uint32_t *over_host, bool one_queue,
-                            uint32_t ray_mask) {
+                            SlotCounters **ctr, bool any_hit, uint32_t *d_inst, uint32_t ray_mask) {
     // the work queue is 32-bit: split very large batches
     const uint64_t chunk = 1ull << 30;
     for (uint64_t off = 0; off < n; off += chunk) {
@@ -169,8 +168,6 @@ int trxapi::trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uin
         p.out = any_hit ? reinterpret_cast<trx_hit *>(reinterpret_cast<uint8_t *>(d_hits) + off) : d_hits + off;
         p.any_hit = any_hit ? 1u : 0u;
         p.out_inst = d_inst ? d_inst + off : nullptr;
-        p.over_host = over_host;
-        p.single_queue = one_queue ? 1u : 0u;
         p.ray_mask = ray_mask;
         p.n_items = (uint32_t)std::min(chunk, n - off);
         int rc = enqueue(s, p, kModeRays, sem, count, stream, ctr);
@@ -206,7 +203,7 @@ int trx_trace_rays_masked_dev(trx_scene *s, const trx_ray *d_rays, uint64_t n, u
     if (!s || (n && (!d_rays || !d_hits))) return fail(TRX_ERR_INVALID, "null argument");
     if (int rc = check_ray_mask(ray_mask)) return rc;
     if (n == 0) return TRX_OK;
-    return trace_rays_impl(s, d_rays, n, sem, d_hits, (hipStream_t)stream, false, nullptr, false, d_inst, nullptr, false, ray_mask);
+    return trace_rays_impl(s, d_rays, n, sem, d_hits, (hipStream_t)stream, false, nullptr, false, d_inst, ray_mask);
 }
 
 int trx_trace_occluded_masked_dev(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, uint32_t ray_mask,
@@ -215,7 +212,7 @@ int trx_trace_occluded_masked_dev(trx_scene *s, const trx_ray *d_rays, uint64_t 
     if (int rc = check_ray_mask(ray_mask)) return rc;
     if (n == 0) return TRX_OK;
     return trace_rays_impl(s, d_rays, n, sem, reinterpret_cast<trx_hit *>(d_flags), (hipStream_t)stream, false, nullptr,
-                           true, nullptr, nullptr, false, ray_mask);
+                           true, nullptr, ray_mask);
 }
 
 int trx_trace_primary_masked_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
@@ -665,16 +662,10 @@ int trx_debug_tile_profile(trx_scene *s, const trx_view *view, uint32_t w, uint3
     if (e == hipSuccess && !rc) {
         uint32_t *iters = s->dbg_iters;
         s->dbg_iters = nullptr; // second pass: the normal kernel
-#ifdef TRX_DEV_TUNE
-        { const char *tune = getenv("TRX_TUNE"); if (tune && (strtoul(tune, nullptr, 0) & 0x2000000u)) s->dbg_iters = iters; } // (diag builds: trips / rounds per tile)
-#endif
         for (int i = 0; i < 3 && !rc; i++) rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
         s->dbg_iters = iters;
         if (!rc) e = hipDeviceSynchronize();
         if (e == hipSuccess && !rc) e = hipMemcpy(out_cost, s->dbg_cost, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
-#ifdef TRX_DEV_TUNE
-        if (e == hipSuccess && !rc && s->dbg_iters) e = hipMemcpy(out_iters, s->dbg_iters, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
-#endif
     }
     (void)hipDeviceSynchronize();
     (void)hipFree(s->dbg_cost);

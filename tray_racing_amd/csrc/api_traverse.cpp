@@ -1,13 +1,6 @@
 // api_traverse.cpp - Traversable::traverse (traversable/src/lib.rs:13-28) for one ray and for batches.
 #include "api_internal.h"
 
-static void futex_wait(std::atomic<uint32_t> *a, uint32_t while_value) {
-    static_assert(sizeof(std::atomic<uint32_t>) == sizeof(uint32_t), "futex word");
-    (void)syscall(SYS_futex, reinterpret_cast<uint32_t *>(a), FUTEX_WAIT_PRIVATE, while_value, nullptr, nullptr, 0);
-}
-static void futex_wake_all(std::atomic<uint32_t> *a) {
-    (void)syscall(SYS_futex, reinterpret_cast<uint32_t *>(a), FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0);
-}
 static int64_t now_ns() {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -19,7 +12,7 @@ static inline void cpu_relax() {
 #endif
 }
 
-// ---- the ray service (single-level scenes): host side ----------------------------------------------------------------
+// ---- the ray service: host side ------------------------------------------------------------------------------------
 #include <emmintrin.h>
 
 // Every live service, so that a process that exits without destroying its scenes still stops its resident kernels first
@@ -160,135 +153,18 @@ static void to_rayhit(const trx_scene *s, const trx_hit h, uint32_t inst, trx_ra
 int trx_traverse1(trx_scene *s, const trx_ray *ray, uint32_t sem, trx_rayhit *out) {
     if (!s || !ray || !out) return fail(TRX_ERR_INVALID, "null argument");
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
-    // the resident ray service (no launch per ray).  (Two-level scenes went through the launch combiner below until the
-    // thin walk learned its two levels, late in round 6; TRX_TRAVERSE1_COMBINER=1 in the environment still sends them there.)
-    static const bool combiner_for_tlas = [] { const char *e = std::getenv("TRX_TRAVERSE1_COMBINER"); return e && e[0] == '1'; }();
-    if (!s->tlas || !combiner_for_tlas) return traverse1_service(s, ray, sem, out);
-    HIP_TRY(hipSetDevice(s->device));
-    std::call_once(s->comb_once, [s]() { s->comb = new (std::nothrow) RayCombiner(s->device); });
-    RayCombiner *c = s->comb;
-    if (!c || !c->ok) return fail(TRX_ERR_OOM, "single-ray combiner: %s", c ? c->init_err.c_str() : "allocation failed");
-    struct Inside { // (counted while inside: a caller spins for its batch only while the callers fit the host's cores)
-        std::atomic<int> &n;
-        explicit Inside(std::atomic<int> &a) : n(a) { n.fetch_add(1, std::memory_order_relaxed); }
-        ~Inside() { n.fetch_sub(1, std::memory_order_relaxed); }
-    } inside(c->inside);
-    std::unique_lock<std::mutex> lock(c->mu);
-    bool leader = false;
-    int bi = -1;
-    for (;;) {
-        if (c->open >= 0) {
-            if (c->batch[c->open].sem == sem) {
-                bi = c->open;
-                break;
-            }
-            // an open batch of another semantics closes within kMaxWait: wait for it rather than mix.  (Counted: such a caller
-            // is inside trx_traverse1 but will not join the open batch, so its leader must not expect it.)
-            c->waiting++;
-            c->cv.wait(lock);
-            c->waiting--;
-            continue;
-        }
-        for (int i = 0; i < (int)RayCombiner::kBatches && bi < 0; i++)
-            if (c->batch[i].state == RayCombiner::Batch::kFree) bi = i;
-        if (bi >= 0) {
-            RayCombiner::Batch &nb = c->batch[bi];
-            nb.state = RayCombiner::Batch::kOpen;
-            nb.sem = sem;
-            nb.n = 0;
-            nb.read.store(0, std::memory_order_relaxed);
-            nb.rc = 0;
-            c->open = bi;
-            leader = true;
-            break;
-        }
-        c->waiting++;
-        c->cv.wait(lock); // every batch is in flight or being read: one frees up when its last reader leaves
-        c->waiting--;
-    }
-    RayCombiner::Batch &b = c->batch[bi];
-    const uint32_t idx = b.n++;
-    b.rays[RayCombiner::slot(idx)] = *ray;
-    const uint32_t epoch = b.done_epoch.load(std::memory_order_relaxed);
-    if (b.n == RayCombiner::kCap) c->open = -1; // full: closed to later arrivals (its leader notices)
-    if (leader) {
-        // Wait for company.  Everyone who can still join is inside this function and not attached to another batch: once
-        // they are all here (and nobody new has turned up for kQuiet), go; kMaxWait bounds the wait either way.
-        const int64_t t0 = now_ns();
-        int64_t t_last = t0;
-        uint32_t seen = b.n;
-        while (c->open == bi) {
-            lock.unlock();
-            if (c->inside.load(std::memory_order_relaxed) > c->cores) std::this_thread::yield(); // (callers that have no core yet)
-            else for (int k = 0; k < 16; k++) cpu_relax();
-            lock.lock();
-            const int64_t t = now_ns();
-            if (b.n != seen) {
-                seen = b.n;
-                t_last = t;
-            }
-            uint32_t elsewhere = 0;
-            for (int j = 0; j < (int)RayCombiner::kBatches; j++)
-                if (j != bi && c->batch[j].state != RayCombiner::Batch::kFree)
-                    elsewhere += c->batch[j].n - std::min(c->batch[j].n, c->batch[j].read.load(std::memory_order_relaxed));
-            const int expected = c->inside.load(std::memory_order_relaxed) - (int)elsewhere - c->waiting;
-            if (((int)b.n >= expected && t - t_last > RayCombiner::kQuietNs) || t - t0 > RayCombiner::kMaxWaitNs) break;
-        }
-        if (c->open == bi) c->open = -1;
-        const uint32_t n = b.n;
-        b.state = RayCombiner::Batch::kFlying;
-        c->launches++;
-        c->rays += n;
-        lock.unlock();
-        c->cv.notify_all(); // (callers waiting for an open batch of their own semantics)
-        *b.over = 0u;
-        int rc = trace_rays_impl(s, b.rays, RayCombiner::slots_used(n), sem, b.hits, b.stream, false, nullptr, false,
-                                 s->tlas ? b.inst : nullptr, b.over, n <= RayCombiner::kSpread);
-        if (!rc && hipStreamSynchronize(b.stream) != hipSuccess) rc = fail(TRX_ERR_NO_DEVICE, "sync failed");
-        if (!rc && *reinterpret_cast<volatile uint32_t *>(b.over) != 0u)
-            rc = fail(TRX_ERR_STACK_OVERFLOW, "a ray overflowed the %d-entry traversal stack (or the step cap)", kLdsStack + kSpillStack);
-        b.rc = rc;
-        if (rc) b.err = err_string();
-        b.done_epoch.fetch_add(1, std::memory_order_release);
-        if (n > 1) futex_wake_all(&b.done_epoch);
-    } else {
-        // a follower spins on the batch's epoch for about a round trip (when it has a core to spin on), then sleeps on it
-        lock.unlock();
-        if (c->inside.load(std::memory_order_relaxed) <= c->cores) {
-            const int64_t t0 = now_ns();
-            while (b.done_epoch.load(std::memory_order_acquire) == epoch && now_ns() - t0 < 300000)
-                for (int k = 0; k < 16; k++) cpu_relax();
-        }
-        while (b.done_epoch.load(std::memory_order_acquire) == epoch) futex_wait(&b.done_epoch, epoch);
-    }
-    // (no lock: the batch's records stay put until its last reader has left)
-    const int rc = b.rc;
-    if (rc && !leader) err_string() = b.err;
-    const uint32_t at = RayCombiner::slot(idx);
-    const trx_hit h = b.hits[at];
-    const uint32_t inst = s->tlas ? b.inst[at] : 0xFFFFFFFFu;
-    if (idx < RayCombiner::kSpread) b.rays[at] = RayCombiner::null_ray(); // (the slot goes back to being padding)
-    const uint32_t n_final = b.n;
-    if (b.read.fetch_add(1, std::memory_order_acq_rel) + 1 == n_final) { // last reader out: the batch can be opened again
-        lock.lock();
-        b.state = RayCombiner::Batch::kFree;
-        lock.unlock();
-        c->cv.notify_all();
-    }
-    if (rc) return rc;
-    to_rayhit(s, h, inst, out);
-    return TRX_OK;
+    return traverse1_service(s, ray, sem, out); // the resident ray service: no launch per ray
 }
 
 // The reference's CPU pixel loop over the literal Traversable::traverse (src/rt_cpu/rt_cpu.rs:35-57) as a measuring aid:
 // `threads` host threads, thread k calls trx_traverse1 for rays k, k + threads, ...; wall-clock seconds of the loop and the
-// launches its calls shared come back.  (The calls are the public entry point's; only the thread pool lives here, so that a
+// service starts during it come back.  (The calls are the public entry point's; only the thread pool lives here, so that a
 // Python caller is not measuring its interpreter lock.)
 int trx_debug_traverse1_threads(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t threads, uint32_t sem, trx_rayhit *out,
                                 double *out_seconds, uint64_t *out_launches) {
     if (!s || (n && (!rays || !out)) || threads == 0 || threads > 4096) return fail(TRX_ERR_INVALID, "bad argument");
     uint64_t l0 = 0, l1 = 0;
-    if (n) { // the first call creates the combiner: not part of the loop's time
+    if (n) { // the first call starts the service: not part of the loop's time
         const int rc = trx_traverse1(s, &rays[0], sem, &out[0]);
         if (rc) return rc;
     }
@@ -328,17 +204,12 @@ int trx_debug_traverse1_threads(trx_scene *s, const trx_ray *rays, uint64_t n, u
     return TRX_OK;
 }
 
-// Launches and rays the single-ray combiner has served so far (development / tests: rays / launches = callers per launch).
+// Service starts and rays trx_traverse1 has served so far (development / tests; the service launches once per start, not per ray).
 int trx_debug_traverse1_stats(trx_scene *s, uint64_t *out_launches, uint64_t *out_rays) {
     if (!s) return fail(TRX_ERR_INVALID, "null argument");
     uint64_t l = 0, r = 0;
-    if (s->comb) {
-        std::lock_guard<std::mutex> lock(s->comb->mu);
-        l = s->comb->launches;
-        r = s->comb->rays;
-    }
     for (RayService *v : s->svc)
-        if (v) { // (the service launches once per start, not per ray)
+        if (v) {
             l += v->starts.load(std::memory_order_relaxed);
             r += v->sum(&RayService::Caller::rays);
         }

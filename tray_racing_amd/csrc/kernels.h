@@ -167,8 +167,8 @@ struct TraceParams {
     // kModeService: the request / answer ring and the control words (all pinned host memory), see kSvcRays
     uint32_t *svc_ring;
     const uint32_t *svc_ctl;
-    uint32_t *over_host;  // null, or a word in pinned host memory that is set when a ray of THIS launch overflows (trx_traverse1:
-                          // the caller learns it from the word, without a device-to-host copy of the slot's sticky counter)
+    uint32_t *over_host;  // null, or a word in pinned host memory that is set when a ray of THIS launch overflows (no host
+                          // caller sets it since round 5's combiner was removed; it goes with the kernel's check in a measured change)
     // frames per launch: primary passes - frame f = local_tile / tiles_per_frame uses views[f]; AO passes - one view
     // (views[0]) and one primary buffer, frame f uses the noise seed frame + f (a tile's seeds are consecutive tickets of
     // one queue); either way frame f writes its records at out + f * frame_stride

@@ -29,16 +29,6 @@
 
 #pragma clang fp contract(off)
 
-// Lanes-per-ray steps of the thin walk: 1 = eight lanes from 8 rays on (shipped), 2 = also four from 16, 3 = also two from
-// 32.  Measured (profiles/r04_thin_waves.log): 8 / 16 / 32 rays = hairball-class AO pass 0.917 / 0.909 / 0.945 ms against
-// 1.044 without, bistro-class 0.984 / 0.999 / 1.035 against 1.008 - the earlier steps cost what they gain (a re-pack and a
-// drain trip per step, and the waves no longer merge), so the product compiles the last step only.  Measured again over
-// fresh processes once the thin walk's requests had become plain loads (profiles/r04_ab_procs_11_thin_levels.log):
-// 0.810 / 0.817 / 0.857 ms hairball-class, 0.896 / 0.899 / 0.924 bistro-class - the same conclusion.
-#ifndef TRX_THIN_LEVELS
-#define TRX_THIN_LEVELS 1
-#endif
-
 // Diagnostic builds (never the product): TRX_DEV_TUNE = run-time experiment switches (TraceParams::tune), TRX_TAIL_DIAG =
 // what every wave did last and when, TRX_STAMPS = per-wave cycle accounting of the loop's phases (every stamp drains the
 // memory counters first, so a phase owns the latency of what it issued).  They are compile-time flags tested with
@@ -144,19 +134,6 @@ __device__ __forceinline__ float ubyte(uint32_t x, int j) { return (float)((x >>
 // SCENE one (trx_scene_create in api.cpp, exp_exact = 2: every component of every node's p is +0 or 2^-36 <= |p| <= 2^59), and the
 // difference of two such floats is +0 or a multiple of 2^-59 no larger than 2^60.  shortcut = 2: both shortcuts for
 // this step (every lane that takes it), 1: the power-of-two one only, 0: the shader's six divisions.
-// packet culling of wave-uniform node steps (trace_walk_plain.inc): on / off
-#ifndef TRX_PACKET_CULL
-#define TRX_PACKET_CULL 1
-#endif
-#ifndef TRX_PACKET_CULL_LITERAL
-#define TRX_PACKET_CULL_LITERAL 1
-#endif
-#ifndef TRX_PACKET_CULL_TLAS
-#define TRX_PACKET_CULL_TLAS 1
-#endif
-#ifndef TRX_DIV_BY_RCP
-#define TRX_DIV_BY_RCP 1
-#endif
 // RN(a / d) from y = RN(1 / d): see above for when
 __device__ __forceinline__ float div_by_rcp(float a, float d, float y) {
     const float q0 = a * y;
@@ -181,7 +158,7 @@ __device__ __forceinline__ float div_by_rcp(float a, float d, float y) {
         ax = ex * r.ix;                                                                                     \
         ay = ey * r.iy;                                                                                     \
         az = ez * r.iz;                                                                                     \
-        if (TRX_DIV_BY_RCP && pow2 > 1) {                                                                   \
+        if (pow2 > 1) {                                                                                     \
             bx = div_by_rcp(px - r.ox, r.dx, r.ix);                                                         \
             by = div_by_rcp(py - r.oy, r.dy, r.iy);                                                         \
             bz = div_by_rcp(pz - r.oz, r.dz, r.iz);                                                         \
@@ -239,51 +216,14 @@ __device__ __forceinline__ uint32_t node_intersect(const Ray &r, float max_dista
     return hit_mask;
 }
 
-// The same test over child planes that were converted to floats ONCE for the wave (a wave-uniform node step: every
-// lane visits the same node, so the 48 byte-to-float conversions and the 12 near / far selects of the per-lane test are
-// the same work 64 times over).  Two tables in LDS, [3 axes][8 children][2]: dec_pos holds {min, max} of a child's
-// axis, dec_neg {max, min}; a lane picks the table of an axis by ADDRESS (the sign of its direction: the near plane is
-// the max plane when the direction is negative) and reads two children at a time - every lane of a sign class reads
-// the same 16 bytes, which LDS broadcasts - so that each {near, far} pair arrives in the two consecutive registers the
-// packed arithmetic of plane2 wants.  (Until round 4 the table was plane-major and the pairs were put together with
-// two register moves each: 37 moves in a 178-instruction test.)  Same values, same operations, same mask.
-template <int NODE>
-__device__ __forceinline__ uint32_t node_intersect_dec(const Ray &r, float max_distance, const uint4 n0, const uint4 n1,
-                                                       const float *dec_pos, const float *dec_neg, const int pow2) {
-    TRX_NODE_FRAME(r, n0, pow2)
-    const float4 *const qx = reinterpret_cast<const float4 *>(r.dx < 0.0f ? dec_neg : dec_pos);
-    const float4 *const qy = reinterpret_cast<const float4 *>((r.dy < 0.0f ? dec_neg : dec_pos) + 16);
-    const float4 *const qz = reinterpret_cast<const float4 *>((r.dz < 0.0f ? dec_neg : dec_pos) + 32);
-    uint32_t hit_mask = 0;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const uint32_t meta4 = i == 0 ? n1.z : n1.w;
-        const uint32_t is_inner4 = (meta4 & (meta4 << 1)) & 0x10101010u;
-        const uint32_t inner_mask4 = (is_inner4 >> 4) * 0xffu;
-        const uint32_t bit_index4 = (meta4 ^ (r.oct_inv4 & inner_mask4)) & 0x1f1f1f1fu;
-        const uint32_t child_bits4 = (meta4 >> 5) & 0x07070707u;
-#pragma unroll
-        for (int h = 0; h < 2; h++) { // children 4 i + 2 h, 4 i + 2 h + 1
-            const float4 x2 = qx[2 * i + h], y2 = qy[2 * i + h], z2 = qz[2 * i + h]; // {near, far, near, far}
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const int j = 2 * h + k;
-                const f32x2 tx = plane2<NODE>(k == 0 ? f32x2{x2.x, x2.y} : f32x2{x2.z, x2.w}, ax, bx);
-                const f32x2 ty = plane2<NODE>(k == 0 ? f32x2{y2.x, y2.y} : f32x2{y2.z, y2.w}, ay, by);
-                const f32x2 tz = plane2<NODE>(k == 0 ? f32x2{z2.x, z2.y} : f32x2{z2.z, z2.w}, az, bz);
-                const float tmin = fmaxf(fmaxf(fmaxf(tx.x, ty.x), tz.x), 0.0001f);
-                const float tmax = fminf(fminf(fminf(tx.y, ty.y), tz.y), max_distance);
-                if (tmin <= tmax) {
-                    const uint32_t child_bits = (child_bits4 >> (8 * j)) & 0xffu;
-                    const uint32_t bit_index = (bit_index4 >> (8 * j)) & 0xffu;
-                    hit_mask |= child_bits << bit_index;
-                }
-            }
-        }
-    }
-    return hit_mask;
-}
-
+// A wave-uniform node step (every lane visits the same node) converts the child planes to floats ONCE for the wave: the
+// 48 byte-to-float conversions and the 12 near / far selects of the per-lane test are the same work 64 times over.  Two
+// tables in LDS, [3 axes][8 children][2]: dec_pos holds {min, max} of a child's axis, dec_neg {max, min}; a lane picks
+// the table of an axis by ADDRESS (the sign of its direction: the near plane is the max plane when the direction is
+// negative) - every lane of a sign class reads the same bytes, which LDS broadcasts - so that each {near, far} pair
+// arrives in the two consecutive registers the packed arithmetic of plane2 wants.  (Until round 4 the table was
+// plane-major and the pairs were put together with two register moves each: 37 moves in a 178-instruction test.)
+//
 // The decode-once test over the children a PACKET test left (round 5).  In a wave-uniform node step of coherent primary
 // rays most of the eight children are missed by every ray of the wave (bistro-class frame: 1.65 children left on average,
 // none in a fifth of the steps; profiles/r05_cullhist.log).  The packet test (trace_walk_plain.inc): with the rays' common
@@ -293,7 +233,7 @@ __device__ __forceinline__ uint32_t node_intersect_dec(const Ray &r, float max_d
 // multiplication and addition are monotone in each operand, so the values bound what any ray of the wave computes - and
 // a child whose largest lower bound exceeds its smallest upper bound is entered by no ray: it is left out for the whole
 // wave.  This function is the per-ray test of the children that remain (`keep`, wave-uniform, bit c = child c): the
-// operations of node_intersect_dec on the same operands, child by child in a scalar loop; a child left out would have
+// operations of node_intersect on the same operands, child by child in a scalar loop; a child left out would have
 // contributed nothing to the mask.  keep = 0xff: all eight (a wave whose rays do not qualify for the packet test).
 //   The literal-division variants (NODE bit 0 clear) take part where a step's rays all take both division shortcuts
 // (shortcut level 2: a = e RN(1/d) as here, b = RN(c / d) by div_by_rcp).  RN(c / d) is within 3 x 2^-24 (relative) of
@@ -769,7 +709,6 @@ __global__ void __launch_bounds__(kMaxBlock, TRX_MIN_WAVES) k_trace(const Kernel
 
 
 #undef wave_global
-#undef spill
 #undef wray
 
 template <int MODE, bool TLAS, int NODE, bool PIPE, bool COUNT>

@@ -68,34 +68,26 @@
         end_b += (uint32_t)__builtin_amdgcn_readlane((int)end_a, 63);
         ordered = intact && (uint32_t)__builtin_amdgcn_readlane((int)end_b, 63) == n_chunks; // complete lists
     }
-    bool frozen = ordered && P.same_view != 0u;
-    if (kTune && (P.tune & 0x400u)) frozen = false; // (A/B: the order is rewritten by every frame, as until round 3)
+    const bool frozen = ordered && P.same_view != 0u;
     // (through readfirstlane: a wave-uniform flag that lives to the epilogue belongs in a scalar register)
     const bool lpt_write = __builtin_amdgcn_readfirstlane((have_lists && !fb_off && !frozen) ? 1 : 0) != 0;
 
     // Chunks below this index of the heaviest-first order take their successor's ticket LATE (when the wave is idle), the
     // rest a tile ahead (hides the atomic's 1-2 us round trip, which only matters next to a tile of a few us).  Round 2
     // cut the order in half by position (never / always / heaviest 3 % / 12 % / 50 %, profiles/r02_late_binding.log);
-    // round 3 looked at what the last waves out of a frame had been doing (tools/gpu_tail.py): starting a 20-30 us tile
+    // round 3 looked at what the last waves out of a frame had been doing: starting a 20-30 us tile
     // they had reserved a tile earlier, while hundreds of idle waves found the queues dry and left - the position cut
     // sits in the middle of the 20-40 us tiles of the bistro-class frame.  The cut is a class now: tiles of 16 trips or more (class 7 and up, about 35 us mid-frame) bind late (profiles/r03_tile_classes.log:
     // classes 6..9 within 1 % of each other, all ahead of the position cut).
     constexpr uint32_t kLateClass = 7u;
-    uint32_t late_entry = (15u - kLateClass) * kLptShards + (kLptShards - 1u); // last list of that class in the concatenation
+    constexpr uint32_t late_entry = (15u - kLateClass) * kLptShards + (kLptShards - 1u); // last list of that class in the concatenation
     uint32_t late_cut = 0u;
-    const uint32_t late_sel = kTune ? (P.tune >> 4) & 7u : 0u; // 1 always late, 2 / 3 / 4: heaviest 3 / 12 / 50 % by position, 5 never, 6: class = tune bits 20..23
-    if (late_sel == 6u) late_entry = (15u - ((P.tune >> 20) & 15u)) * kLptShards + (kLptShards - 1u);
     if (ordered)
         late_cut = late_entry < 64u ? (uint32_t)__builtin_amdgcn_readlane((int)end_a, (int)late_entry)
                                     : (uint32_t)__builtin_amdgcn_readlane((int)end_b, (int)(late_entry - 64u));
-    if constexpr (kTune) {
-        if (late_sel >= 1u && late_sel <= 5u)
-            late_cut = late_sel == 1u ? 0xffffffffu : late_sel == 5u ? 0u : late_sel == 4u ? (n_chunks >> 1) : P.prio_cut[late_sel - 2u];
-    }
     // ... and so do the last tiles of the order, half as many as there are waves: a ticket reserved a tile ahead there is a
     // tile that an idle wave could have started (profiles/r03_tile_classes.log section 9: 0 / 1024 / 2048 / 4096 / 8192
     // tiles with 4096 waves; kitchen-class -2 %, bistro-class -1 %, the others unchanged up to 2048, slower beyond)
-    uint32_t tail_tiles = (gridDim.x * (blockDim.x / kWave)) >> 1;
-    if (kTune && (P.tune >> 28)) tail_tiles = ((P.tune >> 28) == 15u ? 0u : (P.tune >> 28) * 1024u);
+    const uint32_t tail_tiles = (gridDim.x * (blockDim.x / kWave)) >> 1;
     const uint32_t tail_cut = n_chunks > tail_tiles ? n_chunks - tail_tiles : 0u;
     bool exhausted = false; // wave-uniform

@@ -7,33 +7,22 @@
             // the whole tile is done: record what it cost (feeds the next frame's tile order)
             if (lane == 0) {
                 const uint32_t c = (uint32_t)(wall_clock64() - tile_t0);
-                if (kTailDiag && P.cost && (P.tune & 0x2000000u)) {
-                    P.cost[tile_slot] = ((uint32_t)diag_chunk << 16) | min(c, 65535u); // position in the order | cost
-                    if (P.tile_iters && !COUNT) P.tile_iters[tile_slot] = (min(trip - tile_trip0, 4095u) << 20) | (min(diag_pl, 1023u) << 10) | min(diag_cw, 1023u);
-                } else if (P.cost) P.cost[tile_slot] = c;
+                if (P.cost) P.cost[tile_slot] = c;
                 if (lpt_write) {
                     // The tile's class for the next frame's order = its WORK, in half-octaves of traversal-loop trips (1, 2,
                     // 3, 4, 6, 8 ... 256+), not its duration.  How long a tile takes depends on when it ran - at the start
                     // of the frame with issue priority, mid-frame against four waves a SIMD, in the tail against none - so
                     // a frame ordered by last frame's durations reshuffles itself every frame (static camera: 43 % of the
-                    // tiles moved by two duration classes or more from one frame to the next, tools/gpu_tail.py); trips
+                    // tiles moved by two duration classes or more from one frame to the next); trips
                     // are a property of the tile and the view, the same every frame.  A least-squares fit of mid-frame tile
                     // time on trips, per-lane triangle rounds and cooperative rounds explains no more than trips alone
                     // (residual 28.8 against 29.4 us rms), and classes of weighted work measured slower, so: trips.
                     // profiles/r03_tile_classes.log: hairball-class frame -6 %, dense -1.8 %, bistro-class -1.5 %.
-                    uint32_t b;
-                    if (kTune && (P.tune & 0x4000000u)) { // round-2 classes: 2*log2(duration), 2.56 us .. 0.49 ms
-                        const uint32_t msb = 31u - (uint32_t)__clz((int)(c | 1u));
-                        const uint32_t kk = 2u * msb + (msb ? (c >> (msb - 1u)) & 1u : 0u);
-                        b = kk < 16u ? 0u : min(kk - 16u, 15u);
-                    } else {
-                        const uint32_t wk = max(trip - tile_trip0, 1u);
-                        const uint32_t msb = 31u - (uint32_t)__clz((int)wk);
-                        const uint32_t kk = 2u * msb + (msb ? (wk >> (msb - 1u)) & 1u : 0u);
-                        b = kk == 0u ? 0u : min(kk - 1u, 15u);
-                    }
-                    uint32_t list = b * kLptShards + (wave_global & (kLptShards - 1u)); // (one shard per wave: see flush_pending)
-                    if (kTune && (P.tune & 0x200u)) list = b * kLptShards; // (experiment: one list per class)
+                    const uint32_t wk = max(trip - tile_trip0, 1u);
+                    const uint32_t msb = 31u - (uint32_t)__clz((int)wk);
+                    const uint32_t kk = 2u * msb + (msb ? (wk >> (msb - 1u)) & 1u : 0u);
+                    const uint32_t b = kk == 0u ? 0u : min(kk - 1u, 15u);
+                    const uint32_t list = b * kLptShards + (wave_global & (kLptShards - 1u)); // (one shard per wave: see flush_pending)
                     // park the entry in LDS: the appends (returning atomics) are issued together,
                     // one lane each, when the buffer fills or the wave exits, off every tile's path
                     lds_pend[n_pend] = make_uint2(tile_slot, list);
@@ -135,7 +124,6 @@
                         tile_t0 = wall_clock64();
                         tile_trip0 = trip;
                         if constexpr (kTailDiag) {
-                            diag_pl = diag_cw = 0u;
                             diag_t0 = tile_t0;
                             diag_chunk = chunk;
                             diag_tiles++;

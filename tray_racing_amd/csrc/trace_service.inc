@@ -49,9 +49,6 @@
                              : "s"(ring_base), "s"(P.svc_ctl)
                              : "memory");
                 const bool ctl_look = (look++ & 63u) == 0u;
-#ifdef TRX_SVC_PORTER_SLEEP   // (tuning builds: the porter looks less often)
-                __builtin_amdgcn_s_sleep(TRX_SVC_PORTER_SLEEP);
-#endif
                 bool busy = false;
                 auto take = [&](uint32_t k, const u32x16 &q) { // (q: words 0..3, 4..7, 8..11 = the three granules)
                     if (adm[k] == wr[k] && q.s3 == q.s7 && q.s7 == q.sb && q.s3 != adm[k]) {

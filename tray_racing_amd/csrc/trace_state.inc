@@ -22,38 +22,25 @@
     uint32_t *const lds_head = lds_pref + kWave;                                           // [64] run starts of a window
     uint2 *const lds_pend = reinterpret_cast<uint2 *>(lds_head + kWave);                   // [kLptPend] {tile, list} to append
     float *const lds_dec = reinterpret_cast<float *>(lds_pend + kLptPend);                 // [3][8][2] decoded child planes {min, max} of a wave-uniform node step
-    float *const lds_dec_neg = reinterpret_cast<float *>(lds_head);                        // [3][8][2] the same as {max, min} (node_intersect_dec); shares lds_head
+    float *const lds_dec_neg = reinterpret_cast<float *>(lds_head);                        // [3][8][2] the same as {max, min} (node_intersect_kept); shares lds_head
     float *const lds_cull = reinterpret_cast<float *>(lds_pref);                           // [8][2][4] per child {lower bounds of the near planes x y z -}{upper bounds of the far planes x y z -} of a packet test; shares lds_pref
     float4 *const lds_cull_rays = reinterpret_cast<float4 *>(lds_dec + 48);                // [3] per axis {lo, hi} of the wave's rays' 1/d, their common origin component, -: the packet test's constants
     // The wave's HBM area: stack entries past the LDS part, then the lanes' world-space rays ([6][64] floats, kernels.h).
     // Touched on rare paths only (a stack deeper than kLdsStack; entering and leaving an instance with a transform).  Its
     // base lives in two LANES of a vector register (the kernels hold more wave-uniform values than there are scalar
     // registers) and is read back on those paths - the 14 lane-spill instructions inside the primary kernel's walk loop
-    // are these, none of them on a path a trip normally takes (tests/test_kernel_resources.py).  Forming the base on the
-    // rare paths instead (TRX_SPILL_BASE_LATE=1: from the kernel-argument segment) takes them out of the loop - and the
-    // primary frame runs 1.2 % SLOWER for it, another register assignment (profiles/r06_ab_lane_spills.log).
-#ifndef TRX_SPILL_BASE_LATE
-#define TRX_SPILL_BASE_LATE 0 // (see above: measured, not adopted)
-#endif
-#ifndef TRX_SPILL_BASE_LATE_TLAS
-#define TRX_SPILL_BASE_LATE_TLAS 0 // (the two-level kernels only)
-#endif
-    constexpr bool kSpillLate = (TRX_SPILL_BASE_LATE) != 0 || (TLAS && (TRX_SPILL_BASE_LATE_TLAS) != 0);
-    uint2 *const spill_early = kSpillLate ? nullptr : P.spill + (size_t)wave_global * kWaveScratch;
-    auto spill_base = [&]() -> uint2 * {
-        if constexpr (kSpillLate) return refill_params()->spill + (size_t)wave_global * kWaveScratch;
-        else return spill_early;
-    };
-#define spill (spill_base())
-#define wray (reinterpret_cast<float *>(spill_base() + kSpillStack * kWave))
+    // are these, none of them on a path a trip normally takes (tests/test_kernel_resources.py).  (The base formed on the
+    // rare paths instead, from the kernel-argument segment: measured slower, profiles/r06_ab_lane_spills.log.)
+    uint2 *const spill = P.spill + (size_t)wave_global * kWaveScratch;
+#define wray (reinterpret_cast<float *>(spill + kSpillStack * kWave))
     const bool tie_first = P.tie_first != 0;
     if (P.wave_times && lane == 0) P.wave_times[kWaveTimeStride * wave_global] = wall_clock64();
     // (counting kernels, never timed: what refill_params() reads back IS this launch's parameter block - a second kernel
     // parameter or kernel-argument preloading would move it; a mismatch is reported as a failed launch)
     if (COUNT && lane == 0 && refill_params()->n_items != P.n_items) atomicAdd(&P.ctr->overflow, 1u);
-    // (kTailDiag builds, tools/gpu_tail.py: what was every wave's LAST tile, and when did it start?  kStamps builds: phase cycles)
+    // (kTailDiag builds: what was every wave's LAST tile, and when did it start?  kStamps builds: phase cycles)
     unsigned long long diag_t0 = 0ull, diag_chunk = 0ull, diag_tiles = 0ull;
-    uint32_t diag_pl = 0u, diag_cw = 0u, diag_dry_alive = 0u, diag_dry_age = 0u;
+    uint32_t diag_dry_alive = 0u, diag_dry_age = 0u;
     unsigned long long diag_dry_t = 0ull;
     unsigned long long stamp_prev = kStamps ? __builtin_amdgcn_s_memtime() : 0ull;
     unsigned long long k_refill = 0, k_fetch = 0, k_test = 0, k_tri = 0, k_pop = 0, k_iters = 0;
@@ -73,7 +60,7 @@
     // common origin component, in LDS (lds_cull_rays; registers are what this kernel has least of), refreshed whenever the
     // wave takes new rays (trace_refill.inc).  cull_ok (wave-uniform): the rays share one origin and one direction
     // octant and every bound is finite.
-    constexpr bool kCull = MODE == kModePrimary && !COUNT && ((NODE & 1) != 0 || TRX_PACKET_CULL_LITERAL != 0) && TRX_PACKET_CULL != 0 && (!TLAS || TRX_PACKET_CULL_TLAS != 0);
+    constexpr bool kCull = MODE == kModePrimary && !COUNT;
     bool cull_ok = false;
     uint32_t tlas_sp = TRX_INVALID, bvh_off = 0;
     // instance transforms (TLAS): the instance being walked / the one the current hit was found in, and the
@@ -102,12 +89,8 @@
     // (Single-level walks, and explicit rays over two-level scenes - ten words more per ray, 32 rays at most.  The two-level AO kernel
     // that contains the code is 2.5-3 % slower on the 4K pass than the one that does not, profiles/r03_drain_merge.log,
     // r05_ab_5_tlas.log: compiled out there.)
-    // Thin waves (incoherent single-level passes, queues dry, at most P.thin_max rays left): two, four, eight lanes to a ray, see thin_walk.
-#ifdef TRX_NO_THIN_CODE // (A/B builds: the kernels without the thin walk's code at all)
-    constexpr bool kThin = false;
-#else
+    // Thin waves (incoherent single-level passes, queues dry, at most P.thin_max rays left): eight lanes to a ray, see thin_walk.
     constexpr bool kThin = !TLAS && MODE != kModePrimary && !COUNT;
-#endif
     bool go_thin = false; // wave-uniform
     // (two-level walks: explicit rays only - measured on the 4K two-level scene, profiles/r05_ab_5_tlas.log: rays -4 %, AO pass +2.5 %)
     constexpr bool kMerge = (!TLAS || MODE == kModeRays) && MODE != kModePrimary && MODE != kModeFused && MODE != kModeService && !COUNT;

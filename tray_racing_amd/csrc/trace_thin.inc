@@ -4,8 +4,8 @@
     // drain), and at the end those rays sit one or two to a wave: the wave then issues alone on its SIMD, one
     // instruction every four to five cycles whatever the instruction is, so a ray's trip costs its INSTRUCTION COUNT -
     // 213 vector instructions for the node test of one lane while 63 lanes idle.  So once a dry wave is down to 8 rays
-    // they are moved to lanes 0, 8, 16 ... and every ray gets L = 8 lanes (the code is generic in L = 2, 4, 8; see
-    // TRX_THIN_LEVELS for why only 8 ships): lane j of a group tests children j 8/L ... of the node (their plane bytes,
+    // they are moved to lanes 0, 8, 16 ... and every ray gets L = 8 lanes (the code is generic in L = 2, 4, 8; only 8
+    // ships, see thin_all): lane j of a group tests children j 8/L ... of the node (their plane bytes,
     // loaded by address; the same IEEE operations as the per-lane test: node_children_intersect),
     // the contributions are ORed on the DPP network, and a leaf's triangles are tested L at a time and folded
     // into the ray's 64-bit {t, sequence} key with the same LDS atomic min as the cooperative rounds - node order,
@@ -15,8 +15,8 @@
     // (wave-uniform) may this wave go thin now?  Queues dry, a handful of rays, every stack inside its LDS part, no
     // hand-over with the other wave of the workgroup pending, no lane of a fused frame waiting to become an AO ray.
     auto thin_now = [&](uint32_t alive) -> bool {
-        // (never more rays than the walks compiled in can hold, whatever the launch parameter says: 8 << (TRX_THIN_LEVELS - 1))
-        constexpr uint32_t kHold = kFused ? 8u : 8u << (TRX_THIN_LEVELS - 1);
+        // (never more rays than the walk can hold, whatever the launch parameter says)
+        constexpr uint32_t kHold = 8u;
         return exhausted && alive != 0u && alive <= (P.thin_max < kHold ? P.thin_max : kHold) && !(kMerge && merge_open) &&
                __ballot(has_ray && sp > (uint32_t)kLdsStack) == 0ull && !(kFused && __ballot(pend) != 0ull);
     };
@@ -95,31 +95,12 @@
         uint32_t q0 = 0u, q1 = 0u, q2 = 0u, q3 = 0u, q4 = 0u, q5 = 0u;
         float4 ta = unspecified4(), tb = unspecified4(), tc = unspecified4();
         uint32_t gx = 0u, gy = 0u, cnt = 0u, pre_local = 0u;
-        // Touches (tuning builds): the records of ALL entered children are asked for the moment their parent is tested (see
-        // step (4)).  Built for the ray service, whose rays walk alone through caches nobody has warmed - and worth -6 % per
-        // call there while the porter's reads of host memory stood in front of every request of the walker; with those gone
-        // a service trip is instruction issue, not memory (0.80 us with everything in the caches, 0.83 us without,
-        // tools/svc_phases.py), and the touches' own requests cost 5 %: off everywhere (profiles/r06_ray_service.log).
-#ifndef TRX_THIN_TOUCH
-#define TRX_THIN_TOUCH 0 // (tuning builds: 1 = the thin walks of the incoherent passes touch as well)
-#endif
-#ifndef TRX_SERVICE_TOUCH
-#define TRX_SERVICE_TOUCH 0 // (1 until the porter stopped holding the walker's requests up, trace_service.inc: worth -6 % then, +5 % since)
-#endif
-        constexpr bool kTouch = ((MODE == kModeService && (TRX_SERVICE_TOUCH) != 0) || (TRX_THIN_TOUCH) != 0) && C == 1u;
-        uint32_t touch0 = 0u, touch1 = 0u;
-        const uint32_t *touch_ptr = nullptr;
+        // (the records of all entered children touched the moment their parent is tested: measured slower, profiles/r06_ray_service.log)
         // (the one-launch frame comes back from here into its loop, whose registers stay live meanwhile: it does without
         // the early triangle request, twelve registers carried from trip to trip)
         constexpr bool kPre = !kFused;
-        // (tuning builds of the ray service: the first triangle records requested BEHIND the next node's bytes, in the trip
-        // that tests them, so that one ray's two fetches of a trip are in flight together whatever the compiler's
-        // bookkeeping waits for ahead of the node request; see step (1))
-#ifndef TRX_SERVICE_TRI_LATE
-#define TRX_SERVICE_TRI_LATE 0 // (like the touches: -4 % while the porter's reads held the walker up, +5 % since)
-#endif
-        constexpr bool kPreLate = kPre && MODE == kModeService && (TRX_SERVICE_TRI_LATE) != 0;
-        const float4 *pre_ptr = nullptr;
+        // (the ray service's first triangle records requested behind the next node's bytes instead: measured slower,
+        // profiles/r06_ray_service.log)
         auto request_triangles = [&]() { // (5): the group's pending triangle group, and this lane's record of its first L
             cnt = 0u;
             if (__ballot(ptri.y != 0u) == 0ull) return; // (most trips of a handful of rays find no leaf)
@@ -129,13 +110,9 @@
             if (kPre && sub < cnt) {
                 pre_local = select_from_top(gy, sub); // (kept for (2): the search is thirty-five instructions of a lone wave's trip)
                 const float4 *tp = P.tris + (size_t)(gx + pre_local) * 3;
-                if constexpr (kPreLate) {
-                    pre_ptr = tp;
-                } else {
-                    ta = tp[0];
-                    tb = tp[1];
-                    tc = tp[2];
-                }
+                ta = tp[0];
+                tb = tp[1];
+                tc = tp[2];
             }
         };
         request_triangles(); // (a wave that comes from the pipelined walk brings pending triangle groups)
@@ -231,30 +208,6 @@
                 q0 = load_bytes<(int)C>(nb + 32u + xn); q1 = load_bytes<(int)C>(nb + 32u + (xn ^ 8u));
                 q2 = load_bytes<(int)C>(nb + 48u + yn); q3 = load_bytes<(int)C>(nb + 48u + (yn ^ 8u));
                 q4 = load_bytes<(int)C>(nb + 64u + zn); q5 = load_bytes<(int)C>(nb + 64u + (zn ^ 8u));
-                if constexpr (kTouch) {
-                    // Every inner child the LAST node test entered will be fetched when the walk gets to it - the nearest one
-                    // is the node just requested, the others come off the stack later: the lane that tested such a child asks
-                    // for its record's two ends now (80 bytes: one 128-byte line or two), so that the fetch proper finds it in
-                    // a cache.  BEHIND this trip's node request: a wave's loads return in order, a touch issued ahead of it
-                    // would hold it up by a memory round trip.  And in assembly: a load the compiler knows of is waited for
-                    // at the next join of control flow (its bookkeeping of what may be in flight merges pessimistically) - a
-                    // few instructions further down - which makes a trip as long as its slowest touch.  Nobody ever reads
-                    // what the touches load; their two target registers stay reserved for the whole walk (the empty statement
-                    // reads them) and the walk waits for the last touches on its way out.
-                    asm volatile("" : : "v"(touch0), "v"(touch1));
-                    if (touch_ptr != nullptr)
-                        asm volatile("global_load_dword %0, %2, off\n\tglobal_load_dword %1, %2, off offset:76"
-                                     : "=&v"(touch0), "=&v"(touch1) : "v"(touch_ptr) : "memory");
-                }
-            }
-            if constexpr (kTouch) touch_ptr = nullptr;
-            if constexpr (kPreLate) {
-                if (pre_ptr != nullptr) {
-                    ta = pre_ptr[0];
-                    tb = pre_ptr[1];
-                    tc = pre_ptr[2];
-                }
-                pre_ptr = nullptr;
             }
             SVC_MARK(1);
             // ---- (2) triangles of the node tested in the previous trip, L at a time; the first L are here already
@@ -330,13 +283,6 @@
                 const uint32_t meta = (sub * C < 4u ? n1.z : n1.w) >> (8u * ((sub * C) & 3u));
                 const uint32_t q[6] = {q0, q1, q2, q3, q4, q5};
                 contrib = node_children_intersect<NODE, (int)C>(r, gt, n0, meta, q, pow2);
-                if constexpr (kTouch) {
-                    // (an entered INNER child: its record is touched in the next trip's step (1), see there)
-                    const uint32_t m = meta & 0xffu;
-                    touch_ptr = nullptr;
-                    if (contrib != 0u && (m & 0x18u) == 0x18u)
-                        touch_ptr = reinterpret_cast<const uint32_t *>(P.nodes + (size_t)(n1.x + (uint32_t)__popc((n0.w >> 24) & ((1u << (m & 7u)) - 1u))) * 5);
-                }
             }
             const uint32_t hitmask = group_or_to_first<(int)L>(contrib);
             if (stepping && has_ray) {
@@ -424,7 +370,6 @@
         }
 #endif
 #undef SVC_MARK
-        if constexpr (kTouch) asm volatile("s_waitcnt vmcnt(0)" : "+v"(touch0), "+v"(touch1) : : "memory"); // (the last touches: their registers are free after this)
         __builtin_amdgcn_s_setprio(0);
         if (PIPE) { // (no node was in flight all the while: tell the register allocator so, it cannot see through `fetched`)
             const float4 u0 = unspecified4(), u1 = unspecified4(), u2 = unspecified4(), u3 = unspecified4(), u4 = unspecified4();
@@ -435,20 +380,9 @@
             pn4 = make_uint4(__float_as_uint(u4.x), __float_as_uint(u4.y), __float_as_uint(u4.z), __float_as_uint(u4.w));
         }
     };
-    // The thin walk of a dry wave, with as many lanes to a ray as its rays allow; returns with no ray left or, fused frames,
-    // with a lane waiting to become an AO ray (thin_walk<2 or 4> returns once twice the lanes fit).
+    // The thin walk of a dry wave; returns with no ray left or, fused frames, with a lane waiting to become an AO ray.
+    // (four and two lanes to a ray from 16 and 32 rays on as well: the earlier steps cost what they gain,
+    // profiles/r04_thin_waves.log, r04_ab_procs_11_thin_levels.log)
     auto thin_all = [&]() {
-        // (straight-line, not a loop over the three walks: the lanes to a ray only ever double)
-        auto rays_left = [&]() -> uint32_t {
-            return (kFused && __ballot(pend) != 0ull) ? 0u : (uint32_t)__popcll(__ballot(has_ray));
-        };
-        // (the one-launch frame, whose loop the walk returns into, has the registers for the last step only)
-        if constexpr (!kFused && TRX_THIN_LEVELS >= 3) {
-            if (rays_left() > 16u) thin_walk(std::integral_constant<int, 2>{});
-        }
-        if constexpr (!kFused && TRX_THIN_LEVELS >= 2) {
-            if (rays_left() > 8u) thin_walk(std::integral_constant<int, 4>{});
-        }
-        if (rays_left() != 0u) thin_walk(std::integral_constant<int, 8>{});
+        if (!(kFused && __ballot(pend) != 0ull) && __ballot(has_ray) != 0ull) thin_walk(std::integral_constant<int, 8>{});
     };
-

@@ -36,9 +36,6 @@
                     // per-lane rounds carry kBatch triangles of a lane each, cooperative rounds 64 pairs of the wave
                     coop = (mx + (uint32_t)kBatch - 1u) / (uint32_t)kBatch > P.tri_coop_ratio * ((total + 63u) >> 6);
                 }
-                if constexpr (kTailDiag) { // cooperative windows / per-lane rounds of the tile
-                    if (coop) diag_cw += (total + 63u) >> 6; else diag_pl += mx;
-                }
                 if (!coop) {
                     // Per-lane rounds, up to kBatch triangles of a lane per round: their records are requested
                     // together (one memory round trip per round instead of one per triangle; on incoherent rays the

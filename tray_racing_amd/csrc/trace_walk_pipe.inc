@@ -9,8 +9,7 @@
                 const bool act = has_ray;
                 const int pow2 = (NODE & 1) ? 0 : pow2_exact(P, r, act); // (literal-division variants only)
                 trip++;
-                if ((!kTune || !(P.tune & 0x10000000u)) && // (A/B: no priority by ray age)
-                    !TLAS && MODE != kModePrimary && (trip & 7u) == 0u) old_ray_priority(); // (measured without effect in the two-level kernels)
+                if (!TLAS && MODE != kModePrimary && (trip & 7u) == 0u) old_ray_priority(); // (measured without effect in the two-level kernels)
                 // The fetched node record lives from (1) to (4) of ONE trip and is deliberately left uninitialised here:
                 // carried across trips (a variable of the kernel, as it was) the five loads merge with the previous
                 // trip's values, the register allocator is free to land them in scratch registers and copy them home at

@@ -5,11 +5,10 @@
                 const int pow2 = (NODE & 1) ? 0 : pow2_exact(P, r, act); // (literal-division variants only)
                 uint2 tri = make_uint2(0u, 0u);
                 trip++;
-                if ((!kTune || !(P.tune & 0x10000000u)) && // (A/B: no priority by ray age)
-                    !TLAS && MODE != kModePrimary && (trip & 7u) == 0u) old_ray_priority(); // (measured without effect in the two-level kernels)
+                if (!TLAS && MODE != kModePrimary && (trip & 7u) == 0u) old_ray_priority(); // (measured without effect in the two-level kernels)
                 // Coherent primary rays (BLAS only): when every lane that steps visits the SAME node - 47 % of the wave-level
                 // node steps on the bistro-class frame, 90 % on the kitchen-class one - its 48 quantised plane bytes are
-                // converted once, one byte per lane, parked in LDS as floats and read back by address (node_intersect_dec)
+                // converted once, one byte per lane, parked in LDS as floats and read back by address (node_intersect_kept)
                 // (two-level walks too since round 5 - absolute node indices, lanes with a parked triangle group excluded: in round 4
                 // the two-level primary kernel spilled with it (4K frame +4 %, profiles/r04_ab_procs_16); with the world-space ray
                 // copies out of the registers (kernels.h, kWaveScratch) it has 121 and the 4K frame runs 3.3 % faster,
@@ -17,16 +16,14 @@
                 constexpr bool kUni = MODE == kModePrimary && !COUNT;
                 bool uni_done = false;
                 if constexpr (kUni) {
-#ifndef TRX_UNI_COOL
-#define TRX_UNI_COOL (TLAS ? 1 : 0)
-#endif
                     // (the look itself is some thirty instructions.  Before the packet test a trip whose lanes wanted different
-                    // nodes was followed by TRX_UNI_COOL = 1 trips that did not look - bistro-class frame -0.5 %, hairball-class
+                    // nodes was followed by kUniCool = 1 trips that did not look - bistro-class frame -0.5 %, hairball-class
                     // -0.8 %, kitchen-class -0.2 %, profiles/r05_ab_7_unicool.log; with it a uniform step is worth more than the
                     // look costs: looking every trip -0.8 % / +-0 / -0.9 %, two trips off +0.5 / -0.2 / +0.2 %, r05_ab_22_unicool.log.
                     // The two-level walk keeps its one trip off: 4K frame 2.775 against 2.789 ms, r05_ab_27_cool_tlas.log.
                     // The node's second quarter requested ahead of the packet test: +0.8 %, r05_ab_23_n1early.log.)
-                    if ((TRX_UNI_COOL) != 0 && uni_cool != 0u) {
+                    constexpr uint32_t kUniCool = TLAS ? 1u : 0u;
+                    if (kUniCool != 0u && uni_cool != 0u) {
                         uni_cool--;
                     } else
                     if (P.uni_decode) {
@@ -56,40 +53,18 @@
                             // this were built and measured slower, EXPERIMENTS 5.11: the kept children filed into the first
                             // table slots - one LDS round trip more - and the whole test in registers, DPP and v_readlane.)
                             const bool culling = kCull && cull_ok && ((NODE & 1) != 0 || pow2 == 2); // (literal divisions: where every ray of the step takes both shortcuts)
-                            // (tuning builds, TRX_UNI_SCALAR_NODE: the record's two header quads through the scalar cache - the
-                            // address is the wave's, the data read-only for the launch, and scalar reads do not queue behind
-                            // other waves' vector misses (tools/ubench/tcp_order.hip).  Measured SLOWER: primary frame + 0.6 %
-                            // bistro-class, + 1.6 % kitchen-class, + 0.9 % hairball-class, profiles/r06_ab_uni_scalar.log.)
-#ifndef TRX_UNI_SCALAR_NODE
-#define TRX_UNI_SCALAR_NODE 0
-#endif
-                            typedef const __attribute__((address_space(4))) u32x4 *const_quads;
-                            const const_quads snp = (const_quads)(uintptr_t)np;
+                            // (scalar-cache header reads: measured slower, profiles/r06_ab_uni_scalar.log)
                             uint4 n0 = make_uint4(0u, 0u, 0u, 0u);
-                            if ((TRX_UNI_SCALAR_NODE) != 0) {
-                                const u32x4 q = snp[0];
-                                n0 = make_uint4(q.x, q.y, q.z, q.w);
-                            } else if (culling || act) n0 = np[0];
-                            // (the decode lanes' roles - axis, plane, child - are functions of the lane number, i.e. loop
-                            // invariant: computed ahead of the walk they are scalar masks, six of which come back out of
-                            // vector-register lanes in every uniform step.  Taking the lane number afresh here - behind a
-                            // statement the compiler cannot see through, the roles then three compares in place - removes
-                            // those six instructions and costs the frame 0.8 %: profiles/r06_ab_lane_spills.log.  Off.)
-                            uint32_t dl = lane;
-#ifndef TRX_DECODE_LANE_AFRESH
-#define TRX_DECODE_LANE_AFRESH 0
-#endif
-#ifndef TRX_DECODE_LANE_AFRESH_TLAS
-#define TRX_DECODE_LANE_AFRESH_TLAS 0
-#endif
-                            if ((TRX_DECODE_LANE_AFRESH) != 0 || (TLAS && (TRX_DECODE_LANE_AFRESH_TLAS) != 0)) asm volatile("" : "+v"(dl));
+                            if (culling || act) n0 = np[0];
+                            // (the lane number taken afresh here, not as loop-invariant masks: measured slower, profiles/r06_ab_lane_spills.log)
+                            const uint32_t dl = lane;
                             if (dl < 48u) {
                                 const float v = (float)reinterpret_cast<const uint8_t *>(np)[32u + dl];
                                 const uint32_t a = dl >> 4, slot = a * 16u + (dl & 7u) * 2u, is_max = (dl >> 3) & 1u;
                                 lds_dec[slot + is_max] = v;
                                 lds_dec_neg[slot + (is_max ^ 1u)] = v;
                                 if (culling) {
-                                    const float4 cr = lds_cull_rays[a]; // {lo, hi} of the rays' 1/d on this lane's axis, their origin there
+                                    const float4 cr = lds_cull_rays[a]; // {lo, hi} of the rays' 1/d on this dl's axis, their origin there
                                     const float pa = __uint_as_float(a == 0u ? n0.x : a == 1u ? n0.y : n0.z);
                                     const float ea = __uint_as_float(((n0.w >> (8u * a)) & 0xffu) << 23);
                                     const float c = pa - cr.z;
@@ -123,16 +98,11 @@
                             if (kTune && kCull && (P.tune & 0x100u) && lane == 0u) // (diagnostics, tools/gpu_cullhist.py: children left by the packet test; 9 = no packet test)
                                 atomicAdd(&P.ctr->hist_total[culling ? (uint32_t)__builtin_popcount(keep_children) : 9u], 1u);
                             if (act) {
-                                uint4 n1;
-                                if ((TRX_UNI_SCALAR_NODE) != 0) {
-                                    const u32x4 q = snp[1];
-                                    n1 = make_uint4(q.x, q.y, q.z, q.w);
-                                } else n1 = np[1];
+                                const uint4 n1 = np[1];
                                 cur.y &= ~(1u << child_bit);
                                 stack_push(cur, (cur.y & 0xff000000u) != 0u);
                                 // (the ray's view of the node's frame computed ahead of the barrier, under the bounds' trip through LDS: +0.8 %)
-                                const uint32_t hitmask = kCull ? node_intersect_kept<NODE>(r, t, node_frame<NODE>(r, n0, pow2), n1, lds_dec, lds_dec_neg, keep_children)
-                                                               : node_intersect_dec<NODE>(r, t, n0, n1, lds_dec, lds_dec_neg, pow2);
+                                const uint32_t hitmask = node_intersect_kept<NODE>(r, t, node_frame<NODE>(r, n0, pow2), n1, lds_dec, lds_dec_neg, keep_children);
                                 cur.x = n1.x;
                                 tri.x = n1.y;
                                 cur.y = (hitmask & 0xff000000u) | (n0.w >> 24);
@@ -140,8 +110,8 @@
                             }
                             __builtin_amdgcn_wave_barrier();
                             uni_done = true;
-                        } else if ((TRX_UNI_COOL) != 0) {
-                            uni_cool = (uint32_t)(TRX_UNI_COOL);
+                        } else if (kUniCool != 0u) {
+                            uni_cool = kUniCool;
                         }
                     }
                 }
@@ -187,7 +157,6 @@
                         tri.x = n1.y;
                         cur.y = (hitmask & 0xff000000u) | (n0.w >> 24);
                         tri.y = hitmask & 0x00ffffffu;
-                        if (kTune && (P.tune & 2u)) tri.y = 0u; // ablation (timing only, results wrong): no triangle phase at all
                     } else {
                         tri = cur;
                         cur = make_uint2(0u, 0u);
