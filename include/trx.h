@@ -502,8 +502,8 @@ int trx_trace_primary_ao(trx_scene *scene, const trx_view *view, uint32_t width,
 /* The frame loop of rt_gpu_software::start itself (src/rt_gpu/rt_gpu_software.rs:271-361: per RedrawRequested a
  * primary pass and the AO pass over its hits; --animate advances the noise seed, :285-288), n_frames frames without the
  * host in between.  overlap == 0: both passes of a frame back to back on one stream (what n_frames calls of
- * trx_trace_primary_ao enqueue).  overlap != 0: frame i's AO pass runs on a second stream under frame i + 1's primary
- * pass (two primary-hit buffers; same records).  out_primary / out_ao (host, may be NULL): the LAST frame's records;
+ * trx_trace_primary_ao enqueue).  overlap != 0: the AO passes run on a second stream under later frames' primary passes
+ * (four primary-hit buffers: the primary passes run up to four frames ahead of the AO passes; same records).  out_primary / out_ao (host, may be NULL): the LAST frame's records;
  * out_ms: hipEvent time from the first launch to the end of the last pass (per frame: / n_frames). */
 int trx_frame_loop(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
                    uint32_t frame0, int animate, float ao_eps, uint32_t n_frames, int overlap, trx_hit *out_primary,

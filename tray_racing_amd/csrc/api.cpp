@@ -212,7 +212,8 @@ int trx_scene_create(const void *bvh_bytes, uint64_t n_nodes, const void *tri_by
     if (device < 0 || device >= ndev) return fail(TRX_ERR_INVALID, "device %d of %d", device, ndev);
     HIP_TRY(hipSetDevice(device));
 
-    trx_scene *s = new (std::nothrow) trx_scene();
+    // (a failure below destroys the half-made scene: its members release what was created)
+    std::unique_ptr<trx_scene, void (*)(trx_scene *)> s(new (std::nothrow) trx_scene(), trx_scene_destroy);
     if (!s) return fail(TRX_ERR_OOM, "host allocation failed");
     s->device = device;
     s->n_nodes = n_nodes;
@@ -225,32 +226,21 @@ int trx_scene_create(const void *bvh_bytes, uint64_t n_nodes, const void *tri_by
     std::vector<TriDev> tris(std::max<uint64_t>(n_tris, 1));
     convert_tris(tri_bytes, n_tris, tri_format, tris.data());
 
-    auto cleanup = [&](int code) {
-        trx_scene_destroy(s);
-        return code;
-    };
-#define HIP_TRY_S(expr)                                                                                      \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return cleanup(fail(e_ == hipErrorOutOfMemory ? TRX_ERR_OOM : TRX_ERR_NO_DEVICE, "%s failed: %s", \
-                                #expr, hipGetErrorString(e_)));                                              \
-    } while (0)
-    HIP_TRY_S(hipMalloc(&s->d_nodes, n_nodes * TRX_NODE_BYTES));
-    HIP_TRY_S(hipMemcpy(s->d_nodes, bvh_bytes, n_nodes * TRX_NODE_BYTES, hipMemcpyHostToDevice));
-    HIP_TRY_S(hipMalloc(&s->d_tris, tris.size() * sizeof(TriDev)));
-    HIP_TRY_S(hipMemcpy(s->d_tris, tris.data(), tris.size() * sizeof(TriDev), hipMemcpyHostToDevice));
+    static_assert(TRX_NODE_BYTES % sizeof(uint4) == 0 && sizeof(TriDev) % sizeof(float4) == 0, "records of whole vectors");
+    HIP_TRY(s->nodes.alloc(n_nodes * (TRX_NODE_BYTES / sizeof(uint4))));
+    HIP_TRY(hipMemcpy(s->nodes.get(), bvh_bytes, n_nodes * TRX_NODE_BYTES, hipMemcpyHostToDevice));
+    HIP_TRY(s->tris.alloc(tris.size() * (sizeof(TriDev) / sizeof(float4))));
+    HIP_TRY(hipMemcpy(s->tris.get(), tris.data(), tris.size() * sizeof(TriDev), hipMemcpyHostToDevice));
     uint32_t zero = 0;
     if (n_instances) s->h_inst.assign(instance_offsets, instance_offsets + n_instances);
-    HIP_TRY_S(hipMalloc(&s->d_inst, std::max<uint32_t>(n_instances, 4) * sizeof(uint32_t)));
-    HIP_TRY_S(hipMemcpy(s->d_inst, n_instances ? instance_offsets : &zero, (n_instances ? n_instances : 1) * sizeof(uint32_t),
-                        hipMemcpyHostToDevice));
-    HIP_TRY_S(hipEventCreate(&s->ev0));
-    HIP_TRY_S(hipEventCreate(&s->ev1));
-#undef HIP_TRY_S
+    HIP_TRY(s->inst.alloc(std::max<uint32_t>(n_instances, 4)));
+    HIP_TRY(hipMemcpy(s->inst.get(), n_instances ? instance_offsets : &zero, (n_instances ? n_instances : 1) * sizeof(uint32_t),
+                      hipMemcpyHostToDevice));
+    HIP_TRY(s->ev0.create());
+    HIP_TRY(s->ev1.create());
     {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess) return cleanup(fail(TRX_ERR_NO_DEVICE, "hipGetDeviceProperties failed"));
+        if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
         s->cu_count = prop.multiProcessorCount;
     }
     s->grid = trace_grid_size(device, 0, s->tlas, 0, false);
@@ -282,8 +272,8 @@ int trx_scene_create(const void *bvh_bytes, uint64_t n_nodes, const void *tri_by
             }
         s->exp_exact = ok ? (org ? 2u : 1u) : 0u;
     }
-    if (s->grid <= 0) return cleanup(fail(TRX_ERR_NO_DEVICE, "could not size the persistent grid"));
-    *out = s;
+    if (s->grid <= 0) return fail(TRX_ERR_NO_DEVICE, "could not size the persistent grid");
+    *out = s.release();
     return TRX_OK;
 }
 
@@ -295,45 +285,7 @@ void trx_scene_destroy(trx_scene *s) {
         v = nullptr;
     }
     (void)hipDeviceSynchronize();
-    if (s->d_nodes) (void)hipFree(s->d_nodes);
-    if (s->d_tris) (void)hipFree(s->d_tris);
-    if (s->d_inst) (void)hipFree(s->d_inst);
-    if (s->d_inst_entry) (void)hipFree(s->d_inst_entry);
-    if (s->d_scratch_a) (void)hipFree(s->d_scratch_a);
-    if (s->d_scratch_b) (void)hipFree(s->d_scratch_b);
-    if (s->d_scratch_ia) (void)hipFree(s->d_scratch_ia);
-    if (s->d_scratch_ib) (void)hipFree(s->d_scratch_ib);
-    if (s->d_scratch_rays) (void)hipFree(s->d_scratch_rays);
-    if (s->d_scratch_attr) (void)hipFree(s->d_scratch_attr);
-    if (s->d_wave_times) (void)hipFree(s->d_wave_times);
-    if (s->d_inst_xform) (void)hipFree(s->d_inst_xform);
-    if (s->d_inst_mask) (void)hipFree(s->d_inst_mask);
-    for (Slot &sl : s->slots) {
-        if (sl.ctr) (void)hipFree(sl.ctr);
-        if (sl.spill) (void)hipFree(sl.spill);
-        for (auto &o : sl.order)
-            if (o.lists) (void)hipFree(o.lists);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    {
-        FrameLoop &fl = s->loop;
-        for (int k = 0; k < 2; k++)
-            if (fl.stream[k]) (void)hipStreamDestroy(fl.stream[k]);
-        for (int k = 0; k < FrameLoop::kBuffers; k++) {
-            if (fl.prim_done[k]) (void)hipEventDestroy(fl.prim_done[k]);
-            if (fl.ao_done[k]) (void)hipEventDestroy(fl.ao_done[k]);
-            if (fl.prim[k]) (void)hipFree(fl.prim[k]);
-            if (fl.prim_inst[k]) (void)hipFree(fl.prim_inst[k]);
-        }
-        if (fl.t0) (void)hipEventDestroy(fl.t0);
-        if (fl.t1) (void)hipEventDestroy(fl.t1);
-        if (fl.ao) (void)hipFree(fl.ao);
-        if (fl.ao_inst) (void)hipFree(fl.ao_inst);
-    }
-    refit_state_free(s);
-    delete s;
+    delete s; // (every buffer, event and stream of the scene goes with its members, after the synchronisation above)
 }
 
 uint64_t trx_scene_device_bytes(const trx_scene *s) {
@@ -341,12 +293,10 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     uint64_t bytes = s->n_nodes * TRX_NODE_BYTES + s->n_tris * sizeof(TriDev) + (uint64_t)s->n_inst * 4;
     // launch slots claimed so far: stack spill areas and tile-order lists
     std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
-    if (s->d_inst_mask) bytes += s->n_inst; // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
+    bytes += s->inst_mask.count(); // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
     for (const Slot &sl : s->slots) {
-        bytes += (uint64_t)sl.spill_waves * kWaveScratch * sizeof(uint2);
-        for (const auto &o : sl.order)
-            if (o.lists) bytes += 2ull * (16 * kLptShards + (uint64_t)16 * kLptShards * (o.capacity / 2 + 64)) * sizeof(uint32_t);
-        if (sl.ctr) bytes += sizeof(SlotCounters);
+        bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
+        for (const auto &o : sl.order) bytes += o.lists.count() * sizeof(uint32_t);
     }
     // trx_frame_loop's record buffers (four primary, one AO; instance ids beside them on two-level scenes)
     bytes += s->loop.records * (FrameLoop::kBuffers + 1) * (sizeof(trx_hit) + (s->tlas ? sizeof(uint32_t) : 0));
@@ -372,6 +322,15 @@ void trxapi::forget_tile_orders(trx_scene *s) {
         for (auto &o : sl.order) o.have_views = false;
 }
 
+// A device table swapped out under s->mu is freed once `waited` (the wait for the kernels that may read it) succeeded;
+// after a failed wait it is kept rather than freed under a kernel that may still read it.
+template <typename T>
+static hipError_t retire(DevBuf<T> &old, hipError_t waited) {
+    if (waited == hipSuccess) old.reset();
+    else (void)old.release();
+    return waited;
+}
+
 extern "C" {
 
 // Entry nodes: TLAS primitive k starts its BLAS walk at node entry_nodes[k] of the BLAS at instance_offsets[k] instead
@@ -381,7 +340,7 @@ int trx_scene_set_instance_entry_nodes(trx_scene *s, const uint32_t *entry_nodes
     if (!s) return fail(TRX_ERR_INVALID, "null scene");
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
     HIP_TRY(hipSetDevice(s->device));
-    uint32_t *fresh = nullptr;
+    DevBuf<uint32_t> fresh;
     std::vector<uint32_t> host_copy;
     if (entry_nodes && n) {
         if (!s->tlas) return fail(TRX_ERR_INVALID, "entry nodes need a TLAS scene");
@@ -400,24 +359,20 @@ int trx_scene_set_instance_entry_nodes(trx_scene *s, const uint32_t *entry_nodes
         } catch (const std::exception &) {
             return fail(TRX_ERR_OOM, "host allocation failed");
         }
-        HIP_TRY(hipMalloc(&fresh, (size_t)n * sizeof(uint32_t)));
-        const hipError_t e = hipMemcpy(fresh, entry_nodes, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(TRX_ERR_NO_DEVICE, "upload of the entry nodes failed: %s", hipGetErrorString(e));
-        }
+        HIP_TRY(fresh.alloc(n));
+        const hipError_t e = hipMemcpy(fresh.get(), entry_nodes, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the entry nodes failed: %s", hipGetErrorString(e));
     }
-    uint32_t *old = nullptr;
+    DevBuf<uint32_t> old;
     {   // swapped under the launch mutex, freed after every kernel enqueued before the swap has drained
         std::lock_guard<std::mutex> lock(s->mu);
-        old = s->d_inst_entry;
-        s->d_inst_entry = fresh;
+        old = std::move(s->inst_entry);
+        s->inst_entry = std::move(fresh);
         s->h_inst_entry.swap(host_copy); // (no-throw: device and host copies change together)
         s->inst_entry_version++;
         forget_tile_orders(s);
     }
-    HIP_TRY(hipDeviceSynchronize());
-    if (old) (void)hipFree(old);
+    HIP_TRY(retire(old, hipDeviceSynchronize()));
     return TRX_OK;
 }
 
@@ -430,20 +385,19 @@ int trx_scene_set_instance_transforms(trx_scene *s, const float *object_to_world
     // The new table is built and uploaded first, the pointer is swapped under the launch mutex (enqueue() reads it
     // there, so no launch can pick up a table that is about to be freed), and the old table is freed only after
     // every kernel enqueued before the swap has drained.
-    auto swap_table = [&](float4 *fresh) -> int {
-        float4 *old = nullptr;
+    auto swap_table = [&](DevBuf<float4> fresh) -> int {
+        DevBuf<float4> old;
         {
             std::lock_guard<std::mutex> lock(s->mu);
-            old = s->d_inst_xform;
-            s->d_inst_xform = fresh;
+            old = std::move(s->inst_xform);
+            s->inst_xform = std::move(fresh);
             forget_tile_orders(s);
         }
-        HIP_TRY(hipDeviceSynchronize());
-        if (old) (void)hipFree(old);
+        HIP_TRY(retire(old, hipDeviceSynchronize()));
         return TRX_OK;
     };
     if (!object_to_world || n == 0) { // back to identity
-        const int rc = swap_table(nullptr);
+        const int rc = swap_table(DevBuf<float4>());
         if (rc) return rc;
         s->inst_o2w.clear();
         s->inst_w2o.clear();
@@ -473,14 +427,11 @@ int trx_scene_set_instance_transforms(trx_scene *s, const float *object_to_world
             o[4 * row + 3] = (float)-(inv[3 * row + 0] * tx + inv[3 * row + 1] * ty + inv[3 * row + 2] * tz);
         }
     }
-    float4 *d = nullptr;
-    HIP_TRY(hipMalloc(&d, w2o.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(d, w2o.data(), w2o.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(TRX_ERR_NO_DEVICE, "upload of the instance transforms failed: %s", hipGetErrorString(e));
-    }
-    const int rc_swap = swap_table(d);
+    DevBuf<float4> d;
+    HIP_TRY(d.alloc(w2o.size() / 4));
+    hipError_t e = hipMemcpy(d.get(), w2o.data(), w2o.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the instance transforms failed: %s", hipGetErrorString(e));
+    const int rc_swap = swap_table(std::move(d));
     if (rc_swap) return rc_swap;
     s->inst_o2w.assign(object_to_world, object_to_world + (size_t)n * 16);
     s->inst_w2o.swap(w2o);
@@ -496,38 +447,34 @@ int trx_scene_set_instance_masks(trx_scene *s, const uint8_t *masks, uint32_t n)
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
     HIP_TRY(hipSetDevice(s->device));
     std::vector<uint8_t> host_copy;
-    uint8_t *fresh = nullptr;
+    DevBuf<uint8_t> fresh;
     if (!remove) {
         try {
             host_copy.assign(masks, masks + n);
         } catch (const std::exception &) {
             return fail(TRX_ERR_OOM, "host allocation failed");
         }
-        HIP_TRY(hipMalloc(&fresh, n));
-        const hipError_t e = hipMemcpy(fresh, masks, n, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(TRX_ERR_NO_DEVICE, "upload of the instance masks failed: %s", hipGetErrorString(e));
-        }
+        HIP_TRY(fresh.alloc(n));
+        const hipError_t e = hipMemcpy(fresh.get(), masks, n, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the instance masks failed: %s", hipGetErrorString(e));
     }
     // The pointer is swapped under the launch mutex (enqueue() reads it there), and the old table is freed once every
     // launch slot's last kernel has finished: a masked launch enqueued before this call uses the old table in full.  Slots
     // are waited for one by one - not the device, on which a resident kernel (a ray service) may be running - and
     // pinned slots are skipped: the resident kernels never read the table.
-    uint8_t *old = nullptr;
+    DevBuf<uint8_t> old;
     hipError_t e = hipSuccess;
     {
         std::lock_guard<std::mutex> lock(s->mu);
-        old = s->d_inst_mask;
-        s->d_inst_mask = fresh;
+        old = std::move(s->inst_mask);
+        s->inst_mask = std::move(fresh);
         s->h_inst_mask.swap(host_copy);
         if (old)
             for (Slot &sl : s->slots)
-                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done);
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
     }
-    if (e != hipSuccess) // (the old table is kept rather than freed under a kernel that may still read it)
+    if (retire(old, e) != hipSuccess) // (the old table is kept rather than freed under a kernel that may still read it)
         return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
-    if (old) (void)hipFree(old);
     return TRX_OK;
 }
 

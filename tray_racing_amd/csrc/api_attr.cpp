@@ -9,15 +9,15 @@ namespace {
 int enqueue_attr(trx_scene *s, HitAttrParams &p, int mode, uint64_t n, const uint32_t *d_inst, hipStream_t stream) {
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->mu);
-    const bool xf = s->tlas && s->d_inst_xform;
+    const bool xf = s->tlas && s->inst_xform;
     if (xf && !d_inst)
         return fail(TRX_ERR_INVALID, "this scene has instance transforms: the attribute pass needs the instance id of every "
                                      "hit (the trace's d_inst) to take the ray into object space and the normal to world space");
     if (n == 0) return TRX_OK;
     Slot *slot = nullptr;
     if (int rc = acquire_slot(s, stream, slot)) return rc;
-    p.tris = s->d_tris;
-    p.inst_xform = xf ? s->d_inst_xform : nullptr;
+    p.tris = s->tris.get();
+    p.inst_xform = xf ? s->inst_xform.get() : nullptr;
     p.inst = xf ? d_inst : nullptr;
     p.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull);
     p.n_inst = s->n_inst;
@@ -38,7 +38,7 @@ int enqueue_attr(trx_scene *s, HitAttrParams &p, int mode, uint64_t n, const uin
     } else {
         HIP_TRY(launch_hit_attr(p, mode, stream));
     }
-    HIP_TRY(hipEventRecord(slot->done, stream));
+    HIP_TRY(hipEventRecord(slot->done.get(), stream));
     slot->used = true;
     return TRX_OK;
 }
@@ -62,7 +62,6 @@ int trx_hit_attributes_primary_dev(trx_scene *s, const trx_view *view, uint32_t 
                                    const trx_hit *d_hits, const uint32_t *d_inst, trx_hit_attr *d_attr, void *stream) {
     if (!s || !d_hits || !d_attr) return fail(TRX_ERR_INVALID, "null argument");
     TraceParams t; // (the image geometry exactly as the trace derives it)
-    std::memset(&t, 0, sizeof(t));
     int rc = image_params(t, view, w, h, shard);
     if (rc) return rc;
     HitAttrParams p;
@@ -83,36 +82,22 @@ int trx_hit_attributes_primary_dev(trx_scene *s, const trx_view *view, uint32_t 
 int trx_trace_rays_attr(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, trx_hit *out_hits, uint32_t *out_inst,
                         trx_hit_attr *out_attr, float *out_ms) {
     if (!s || (n && !rays)) return fail(TRX_ERR_INVALID, "null argument");
-    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     if (n == 0) return TRX_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure_scratch(s, n, n);
-    if (rc) return rc;
-    if (n > s->scratch_attr) {
-        if (s->d_scratch_attr) (void)hipFree(s->d_scratch_attr);
-        s->d_scratch_attr = nullptr;
-        s->scratch_attr = 0;
-        HIP_TRY(hipMalloc(&s->d_scratch_attr, n * sizeof(trx_hit_attr)));
-        s->scratch_attr = n;
-    }
     // (two-level scenes always trace the instance ids: the attribute pass needs them under instance transforms)
-    uint32_t *d_inst = s->tlas ? s->d_scratch_ia : nullptr;
-    HIP_TRY(hipMemcpy(s->d_scratch_rays, rays, n * sizeof(trx_ray), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    rc = trx_trace_rays_inst_dev(s, s->d_scratch_rays, n, sem, s->d_scratch_a, d_inst, nullptr);
-    if (rc) return rc;
-    rc = trx_hit_attributes_rays_dev(s, s->d_scratch_rays, n, s->d_scratch_a, d_inst, s->d_scratch_attr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, nullptr));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
-    if (out_hits) HIP_TRY(hipMemcpy(out_hits, s->d_scratch_a, n * sizeof(trx_hit), hipMemcpyDeviceToHost));
-    if (out_inst) {
-        if (d_inst) HIP_TRY(hipMemcpy(out_inst, d_inst, n * 4, hipMemcpyDeviceToHost));
-        else std::memset(out_inst, 0xff, n * 4);
-    }
-    if (out_attr) HIP_TRY(hipMemcpy(out_attr, s->d_scratch_attr, n * sizeof(trx_hit_attr), hipMemcpyDeviceToHost));
-    return trx_scene_check(s, nullptr);
+    auto d_inst = [&] { return s->tlas ? s->scratch_ia.get() : nullptr; };
+    return host_call(
+        s, n, rays, n, n, out_ms,
+        [&] {
+            int rc = trx_trace_rays_inst_dev(s, s->scratch_rays.get(), n, sem, s->scratch_a.get(), d_inst(), nullptr);
+            if (rc) return rc;
+            return trx_hit_attributes_rays_dev(s, s->scratch_rays.get(), n, s->scratch_a.get(), d_inst(), s->scratch_attr.get(), nullptr);
+        },
+        [&]() -> int {
+            if (out_hits) HIP_TRY(hipMemcpy(out_hits, s->scratch_a.get(), n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+            if (int rc = read_inst(out_inst, d_inst(), n)) return rc;
+            if (out_attr) HIP_TRY(hipMemcpy(out_attr, s->scratch_attr.get(), n * sizeof(trx_hit_attr), hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
 }
 
 } // extern "C"

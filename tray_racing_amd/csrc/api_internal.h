@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <queue>
@@ -34,9 +35,13 @@
 #include "../../include/trx_dev.h"
 #include "builder.h"
 #include "cwbvh_format.h"
+#include "hip_owned.h"
 #include "kernels.h"
 #include "scenes.h"
 
+namespace trx {
+struct RefitResult; // refit_gpu.h
+}
 using namespace trx;
 
 namespace trxapi {
@@ -55,14 +60,12 @@ extern std::atomic<uint32_t> g_variant; // tuning aid (trx_set_kernel_variant), 
     } while (0)
 
 constexpr int kSlots = 8;
-struct RefitState; // api_refit.cpp
 constexpr uint32_t kDefaultWavesPerBlock = 1;
 
 struct Slot {
-    SlotCounters *ctr = nullptr;
-    uint2 *spill = nullptr;
-    uint32_t spill_waves = 0;  // waves the spill area is sized for
-    hipEvent_t done = nullptr; // everything enqueued for this slot has finished
+    DevBuf<SlotCounters> ctr;
+    DevBuf<uint2> spill; // stack spill area: kWaveScratch entries per wave
+    Event done;          // everything enqueued for this slot has finished
     bool used = false;
     bool pinned = false;               // a resident kernel (the ray service) runs on this slot: never recycled for another stream
     hipStream_t last_stream = nullptr; // stream of the last launch on this slot
@@ -71,12 +74,24 @@ struct Slot {
     // next one of that kind with the same image geometry starts its heaviest tiles first.  One state per kind: the
     // reference's frame loop runs both passes on one queue, and each has its own order.
     struct Order {
-        uint32_t *lists = nullptr; // two sets of {16 counts, 16 lists}
-        uint32_t capacity = 0;
+        DevBuf<uint32_t> lists; // two sets of {16 counts, 16 lists}
+        uint32_t capacity = 0;  // tiles the lists are sized for
         bool have_views = false; // view[] holds the views of a previous launch
         uint64_t key = 0;    // (width, height, shard, mode) the lists were measured for; 0 = none
         ViewDev view[kMaxBatchFrames]{}; // views of the last launch that read or wrote the lists (camera-cut detection)
     } order[2];
+};
+
+// trx_scene_refit's per-scene state (api_refit.cpp; the stream and result word are created on first use)
+struct RefitState {
+    Stream stream;                    // read-backs and the host-memory refit
+    bool have_topology = false;
+    uint64_t entry_version = 0;       // s->inst_entry_version the schedule was derived for
+    std::vector<uint32_t> level_start;
+    DevBuf<uint32_t> order, seg_base;
+    DevBuf<float> boxes;
+    DevBuf<float> o2w;                // the instances' object-to-world matrices (16 floats each)
+    DevBuf<RefitResult> result;
 };
 
 } // namespace trxapi
@@ -84,11 +99,11 @@ struct Slot {
 // trx_frame_loop's streams, events and device buffers (created on first use)
 struct FrameLoop {
     static constexpr int kBuffers = 4; // primary-hit buffers: the primary passes may run this many frames ahead of the AO passes
-    hipStream_t stream[2] = {nullptr, nullptr};
-    hipEvent_t prim_done[kBuffers] = {}, ao_done[kBuffers] = {}, t0 = nullptr, t1 = nullptr;
-    trx_hit *prim[kBuffers] = {}, *ao = nullptr;
-    uint32_t *prim_inst[kBuffers] = {}, *ao_inst = nullptr;
-    uint64_t records = 0;
+    trxapi::Stream stream[2];
+    trxapi::Event prim_done[kBuffers], ao_done[kBuffers], t0, t1;
+    trxapi::DevBuf<trx_hit> prim[kBuffers], ao;
+    trxapi::DevBuf<uint32_t> prim_inst[kBuffers], ao_inst;
+    uint64_t records = 0; // every buffer holds this many records
 };
 
 // trx_traverse1: a RESIDENT kernel answers the callers' rays out of a ring in pinned host memory
@@ -102,8 +117,8 @@ struct RayService {
     static constexpr int64_t kIdleStopNs = 50 * 1000 * 1000, kBeatNs = 2 * 1000 * 1000, kGiveUpNs = 5LL * 1000 * 1000 * 1000;
     trx_scene *scene = nullptr;
     uint32_t sem = 0;
-    uint32_t *ring = nullptr, *ctl = nullptr; // pinned, device-visible
-    hipStream_t stream = nullptr;
+    trxapi::HostBuf<uint32_t> ring, ctl; // pinned, device-visible
+    trxapi::Stream stream;
     std::mutex mu;                    // start / stop
     std::atomic<bool> running{false};
     // Per slot, on cache lines of its own: everything a call writes on the host side.  (Until late in round 6 every call
@@ -140,10 +155,10 @@ struct RayService {
 
 struct trx_scene {
     int device = 0;
-    uint4 *d_nodes = nullptr;
-    float4 *d_tris = nullptr;
-    uint32_t *d_inst = nullptr;
-    uint32_t *d_inst_entry = nullptr;        // entry node per TLAS primitive (re-braided scenes), or null
+    trxapi::DevBuf<uint4> nodes;
+    trxapi::DevBuf<float4> tris;
+    trxapi::DevBuf<uint32_t> inst;
+    trxapi::DevBuf<uint32_t> inst_entry;     // entry node per TLAS primitive (re-braided scenes), or empty
     std::vector<uint32_t> h_inst;            // host copy of the instance offsets (entry-node validation)
     uint64_t n_nodes = 0, n_tris = 0;
     uint32_t n_inst = 0, tlas_start = 0;
@@ -152,20 +167,18 @@ struct trx_scene {
     uint32_t exp_exact = 0u; // 1: every node exponent byte is 0 or >= 21; 2: and every node origin admits div_by_rcp (TraceParams::exp_exact)
     int grid = 0;      // default number of persistent waves
     int cu_count = 0;
-    unsigned long long *d_wave_times = nullptr; // diagnostics only (trx_debug_wave_timeline)
-    uint32_t *dbg_cost = nullptr, *dbg_iters = nullptr; // diagnostics only (trx_debug_tile_profile)
+    trxapi::DevBuf<unsigned long long> wave_times; // diagnostics only (trx_debug_wave_timeline)
+    uint32_t *dbg_cost = nullptr, *dbg_iters = nullptr; // diagnostics only: trx_debug_tile_profile's buffers while it runs
     trxapi::Slot slots[trxapi::kSlots];
     uint64_t launches = 0;
     std::mutex mu;      // launch slots (every enqueue)
     std::recursive_mutex host_mu; // scratch buffers and event pair of the synchronous entry points
     // scratch for the host-buffer convenience entry points
-    trx_hit *d_scratch_a = nullptr, *d_scratch_b = nullptr;
-    uint32_t *d_scratch_ia = nullptr, *d_scratch_ib = nullptr; // instance ids beside scratch_a / scratch_b
-    trx_ray *d_scratch_rays = nullptr;
-    uint64_t scratch_hits = 0, scratch_rays = 0;
-    trx_hit_attr *d_scratch_attr = nullptr; // trx_trace_rays_attr's attribute records (api_attr.cpp)
-    uint64_t scratch_attr = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    trxapi::DevBuf<trx_hit> scratch_a, scratch_b;
+    trxapi::DevBuf<uint32_t> scratch_ia, scratch_ib; // instance ids beside scratch_a / scratch_b (two-level scenes)
+    trxapi::DevBuf<trx_ray> scratch_rays;
+    trxapi::DevBuf<trx_hit_attr> scratch_attr; // trx_trace_rays_attr's attribute records (api_attr.cpp)
+    trxapi::Event ev0, ev1;
     std::vector<uint32_t> blas_tri_start; // geometry_id lookup for trx_traverse1
     FrameLoop loop;                // trx_frame_loop
     RayService *svc[8] = {};       // trx_traverse1: one resident kernel per semantics word in use
@@ -173,15 +186,15 @@ struct trx_scene {
     // instance transforms (TLAS scenes): object-to-world as given (get_instance_transform), world-to-object rows as
     // the kernels use them, and their device copy; empty / null = identity
     std::vector<float> inst_o2w, inst_w2o;
-    float4 *d_inst_xform = nullptr;
+    trxapi::DevBuf<float4> inst_xform;
     uint32_t tri_format = 0;                 // trx_tri_format the scene was created from (trx_scene_refit takes the f32 ones)
     std::vector<uint32_t> h_inst_entry;      // host copy of the entry nodes (empty = node 0 everywhere) ...
     uint64_t inst_entry_version = 0;         // ... bumped whenever they are set: the refit's cached schedule follows them
-    trxapi::RefitState *refit = nullptr;     // trx_scene_refit: schedule, node boxes, stream (api_refit.cpp; created on first use)
+    trxapi::RefitState refit;                // trx_scene_refit: schedule, node boxes, stream (api_refit.cpp)
     // instance masks (TLAS scenes, trx_scene_set_instance_masks): one byte per TLAS primitive, read by the masked trace
-    // calls only; host copy and device table, empty / null = every instance 0xFF
+    // calls only; host copy and device table, empty = every instance 0xFF
     std::vector<uint8_t> h_inst_mask;
-    uint8_t *d_inst_mask = nullptr;
+    trxapi::DevBuf<uint8_t> inst_mask;
 };
 
 struct trx_bvh {
@@ -190,12 +203,15 @@ struct trx_bvh {
 
 namespace trxapi {
 
-int ensure_scratch(trx_scene *s, uint64_t hits, uint64_t rays);
+// the host-buffer entry points' scratch: at least `hits` records (and instance ids on two-level scenes), `rays` rays and
+// `attrs` attribute records
+int ensure_scratch(trx_scene *s, uint64_t hits, uint64_t rays, uint64_t attrs = 0);
 void fill_view(const trx_view *v, trx::ViewDev &out);
 // The launch slot a kernel enqueued on `stream` runs on, set up and waited for (api_launch.cpp; s->mu held)
 int acquire_slot(trx_scene *s, hipStream_t stream, Slot *&out);
 // Enqueues one traversal kernel on a launch slot of the scene (api_launch.cpp)
 int enqueue(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream, trx::SlotCounters **ctr_out);
+// an image pass's kernel parameters: p zeroed, then the geometry of `view` / w x h / shard
 int image_params(trx::TraceParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard);
 int read_overflow(trx_scene *s, trx::SlotCounters *ctr);
 // structural validation of an untrusted node buffer (api.cpp): every index a walk can form is in range
@@ -203,13 +219,39 @@ int validate_nodes(const CwbvhNode *nodes, uint64_t n_nodes, uint64_t n_tris, co
                    uint32_t tlas_start);
 // the scene under the launch slots' learnt tile orders changed: the next frame of every slot files a new order (s->mu held)
 void forget_tile_orders(trx_scene *s);
-// trx_scene_refit's per-scene state (api_refit.cpp)
-void refit_state_free(trx_scene *s);
+// device bytes of trx_scene_refit's per-scene state (api_refit.cpp)
 uint64_t refit_state_bytes(const trx_scene *s);
 // explicit rays (api_trace.cpp)
 // (ray_mask != 0: a masked trace - enqueue() hands the kernel the scene's instance mask table)
 int trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
                     trx::SlotCounters **ctr, bool any_hit = false, uint32_t *d_inst = nullptr, uint32_t ray_mask = 0);
+
+// ---- the synchronous host-buffer entry points (api_trace.cpp, api_attr.cpp) ----
+// ev0, what `run` enqueues on the null stream, ev1; waits for ev1 and puts the elapsed time into *ms (may be null)
+template <typename Run>
+int timed(trx_scene *s, float *ms, Run run) {
+    HIP_TRY(hipEventRecord(s->ev0.get(), nullptr));
+    if (int rc = run()) return rc;
+    HIP_TRY(hipEventRecord(s->ev1.get(), nullptr));
+    HIP_TRY(hipEventSynchronize(s->ev1.get()));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0.get(), s->ev1.get()));
+    return TRX_OK;
+}
+// One host-buffer call: under host_mu (the scratch and the event pair are shared) on the scene's device, scratch for
+// `hits` records and `attrs` attribute records, the n_rays `rays` uploaded when given, `run` timed, then `read` copies
+// the results back and trx_scene_check reports an overflow.
+template <typename Run, typename Read>
+int host_call(trx_scene *s, uint64_t hits, const trx_ray *rays, uint64_t n_rays, uint64_t attrs, float *out_ms, Run run, Read read) {
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = ensure_scratch(s, hits, rays ? n_rays : 0, attrs)) return rc;
+    if (rays) HIP_TRY(hipMemcpy(s->scratch_rays.get(), rays, n_rays * sizeof(trx_ray), hipMemcpyHostToDevice));
+    if (int rc = timed(s, out_ms, run)) return rc;
+    if (int rc = read()) return rc;
+    return trx_scene_check(s, nullptr);
+}
+// n instance ids back into dst (may be null): the device's, or 0xFFFFFFFF everywhere on a scene without a TLAS (src null)
+int read_inst(uint32_t *dst, const uint32_t *src, uint64_t n);
 
 } // namespace trxapi
 

@@ -5,30 +5,15 @@
 
 namespace trxapi {
 
-int ensure_scratch(trx_scene *s, uint64_t hits, uint64_t rays) {
-    if (hits > s->scratch_hits) {
-        if (s->d_scratch_a) (void)hipFree(s->d_scratch_a);
-        if (s->d_scratch_b) (void)hipFree(s->d_scratch_b);
-        if (s->d_scratch_ia) (void)hipFree(s->d_scratch_ia);
-        if (s->d_scratch_ib) (void)hipFree(s->d_scratch_ib);
-        s->d_scratch_a = s->d_scratch_b = nullptr;
-        s->d_scratch_ia = s->d_scratch_ib = nullptr;
-        s->scratch_hits = 0;
-        HIP_TRY(hipMalloc(&s->d_scratch_a, hits * sizeof(trx_hit)));
-        HIP_TRY(hipMalloc(&s->d_scratch_b, hits * sizeof(trx_hit)));
-        if (s->tlas) {
-            HIP_TRY(hipMalloc(&s->d_scratch_ia, hits * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&s->d_scratch_ib, hits * sizeof(uint32_t)));
-        }
-        s->scratch_hits = hits;
+int ensure_scratch(trx_scene *s, uint64_t hits, uint64_t rays, uint64_t attrs) {
+    HIP_TRY(s->scratch_a.grow(hits));
+    HIP_TRY(s->scratch_b.grow(hits));
+    if (s->tlas) {
+        HIP_TRY(s->scratch_ia.grow(hits));
+        HIP_TRY(s->scratch_ib.grow(hits));
     }
-    if (rays > s->scratch_rays) {
-        if (s->d_scratch_rays) (void)hipFree(s->d_scratch_rays);
-        s->d_scratch_rays = nullptr;
-        s->scratch_rays = 0;
-        HIP_TRY(hipMalloc(&s->d_scratch_rays, rays * sizeof(trx_ray)));
-        s->scratch_rays = rays;
-    }
+    HIP_TRY(s->scratch_rays.grow(rays));
+    HIP_TRY(s->scratch_attr.grow(attrs));
     return TRX_OK;
 }
 
@@ -60,25 +45,22 @@ int acquire_slot(trx_scene *s, hipStream_t stream, Slot *&out) {
     const bool same_stream = slot.used && slot.last_stream == stream;
     if (!slot.ctr) {
         // all or nothing: a slot is either fully usable or untouched
-        SlotCounters *ctr = nullptr;
-        hipEvent_t done = nullptr;
-        HIP_TRY(hipMalloc(&ctr, sizeof(SlotCounters)));
+        DevBuf<SlotCounters> ctr;
+        Event done;
+        HIP_TRY(ctr.alloc(1));
         // On the LAUNCH stream: hipMemset returns before a device-side fill has run and orders it on the null stream only,
         // which a non-blocking user stream does not wait for - the first kernel of a slot could start, take tickets and
         // count exiting waves, and THEN have its queue heads and exit ticket zeroed under it (chunks dealt twice, the exit
         // ticket never reaching the grid size, the heads never re-armed: the next launch on the slot finds every queue dry
         // and writes nothing).  Seen once four processes time-shared the GPU; found by the sentinel check of bench.py's
         // test mode (profiles/r03_slot_init_race.log).
-        hipError_t e = hipMemsetAsync(ctr, 0, sizeof(SlotCounters), stream);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            (void)hipFree(ctr);
-            return fail(TRX_ERR_NO_DEVICE, "launch slot set-up failed: %s", hipGetErrorString(e));
-        }
-        slot.ctr = ctr;
-        slot.done = done;
+        hipError_t e = hipMemsetAsync(ctr.get(), 0, sizeof(SlotCounters), stream);
+        if (e == hipSuccess) e = done.create(hipEventDisableTiming);
+        if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "launch slot set-up failed: %s", hipGetErrorString(e));
+        slot.ctr = std::move(ctr);
+        slot.done = std::move(done);
     }
-    if (slot.used && !same_stream) HIP_TRY(hipStreamWaitEvent(stream, slot.done, 0));
+    if (slot.used && !same_stream) HIP_TRY(hipStreamWaitEvent(stream, slot.done.get(), 0));
     out = &slot;
     return TRX_OK;
 }
@@ -91,7 +73,7 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->mu);
-    if (s->d_inst_xform && mode == kModeAo && !p.primary_inst)
+    if (s->inst_xform && mode == kModeAo && !p.primary_inst)
         return fail(TRX_ERR_INVALID, "this scene has instance transforms: the AO pass needs the primary pass's instance ids "
                                      "(trx_trace_ao_inst_dev) to take the hit normal into world space");
     Slot *slot_p = nullptr;
@@ -114,32 +96,28 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     const uint64_t n_chunks = ((uint64_t)p.n_items + 63u) >> 6;
     if ((uint64_t)grid > n_chunks) grid = (int)std::max<uint64_t>(n_chunks, 1);
     grid = std::max((int)wpb, (grid + (int)wpb - 1) / (int)wpb * (int)wpb);
-    if (slot.spill_waves < (uint32_t)grid) {
+    if (slot.spill.count() < (uint64_t)grid * kWaveScratch) {
         // stack spill area (entries kLdsStack.. of every lane), sized for the grid actually launched; growing it
         // waits for the slot's previous kernel, which may still be writing the old one
-        if (slot.used) HIP_TRY(hipEventSynchronize(slot.done));
-        if (slot.spill) (void)hipFree(slot.spill);
-        slot.spill = nullptr;
-        slot.spill_waves = 0;
-        HIP_TRY(hipMalloc(&slot.spill, (size_t)grid * kWaveScratch * sizeof(uint2)));
-        slot.spill_waves = (uint32_t)grid;
+        if (slot.used) HIP_TRY(hipEventSynchronize(slot.done.get()));
+        HIP_TRY(slot.spill.alloc((uint64_t)grid * kWaveScratch));
     }
     slot.last_stream = stream;
     slot.last_use = ++s->launches;
-    p.nodes = s->d_nodes;
-    p.tris = s->d_tris;
-    p.inst = s->d_inst;
-    p.inst_entry = s->d_inst_entry;
-    p.inst_xform = s->d_inst_xform;
+    p.nodes = s->nodes.get();
+    p.tris = s->tris.get();
+    p.inst = s->inst.get();
+    p.inst_entry = s->inst_entry.get();
+    p.inst_xform = s->inst_xform.get();
     // instance masks: a masked call (p.ray_mask != 0) gets the table as it is now - trx_scene_set_instance_masks swaps it
     // under this mutex and frees the old one only after the slots' launches have finished; every other launch, and a masked
     // one on a single-level scene or a scene without a table, gets null (every instance entered)
-    const uint8_t *inst_mask = p.ray_mask != 0u && s->tlas ? s->d_inst_mask : nullptr;
+    const uint8_t *inst_mask = p.ray_mask != 0u && s->tlas ? s->inst_mask.get() : nullptr;
     if (!inst_mask) p.ray_mask = 0u;
     p.tlas_start = s->tlas_start;
     p.exp_exact = s->exp_exact;
-    p.ctr = slot.ctr;
-    p.spill = slot.spill;
+    p.ctr = slot.ctr.get();
+    p.spill = slot.spill.get();
     p.tie_first = (sem & TRX_SEM_TIE_FIRST) ? 1u : 0u;
     uint32_t refill = variant & 0x7fu;
     // coherent primary rays: refill a wave only when its whole tile is done (mixing tiles costs more
@@ -201,7 +179,7 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     if (p.tune & 0x40000u) p.uni_decode = 1u;
     if (p.tune & 0x80000u) p.uni_decode = 0u;
 #endif
-    p.wave_times = s->d_wave_times;
+    p.wave_times = s->wave_times.get();
     p.single_queue = (variant >> 21) & 1u;
     // tile order feedback (image modes, whole-tile refills only)
     // (an AO batch deals its tiles seed by seed within a queue: it has no tile order to learn)
@@ -226,18 +204,16 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
         bool fresh = false;
         if (ord.capacity != n_tiles) {
             // (the slot's previous kernel may still be appending to the old lists: wait for it before they go)
-            if (ord.lists && slot.used) HIP_TRY(hipEventSynchronize(slot.done));
-            if (ord.lists) (void)hipFree(ord.lists);
-            ord.lists = nullptr;
+            if (ord.lists && slot.used) HIP_TRY(hipEventSynchronize(slot.done.get()));
             ord.capacity = 0;
             ord.key = 0;
-            HIP_TRY(hipMalloc(&ord.lists, 2 * set_words * sizeof(uint32_t)));
+            HIP_TRY(ord.lists.alloc(2 * set_words));
             ord.capacity = n_tiles;
             fresh = true;
         }
         key = ((uint64_t)p.width << 40) ^ ((uint64_t)p.height << 20) ^ ((uint64_t)p.shard_count << 8) ^ p.shard_index ^
               ((uint64_t)(mode + 1) << 60) ^ ((uint64_t)p.n_frames << 56);
-        uint32_t *set[2] = {ord.lists, ord.lists + set_words};
+        uint32_t *set[2] = {ord.lists.get(), ord.lists.get() + set_words};
         // The order was learnt for an image geometry (the key); it is replayed whatever the camera did since.  Round 3
         // first emptied the lists at a camera cut - natural order while the new view is measured - and then measured
         // that choice once the classes were trips instead of durations (profiles/r03_camera_cut.log): a camera turning
@@ -263,7 +239,7 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
         }
         ord.key = key;
         // (variant bit 19: feedback always on, for A/B runs)
-        p.fb = (s->dbg_cost || ((variant >> 19) & 1u)) ? nullptr : &slot.ctr->fb[mode == kModeAo ? 1 : 0];
+        p.fb = (s->dbg_cost || ((variant >> 19) & 1u)) ? nullptr : &slot.ctr.get()->fb[mode == kModeAo ? 1 : 0];
         p.no_order = no_order ? 1u : 0u;
         p.new_view = cut ? 1u : 0u;
         // A frame whose views are bit for bit those of the previous launch of this kind on the slot replays a complete
@@ -275,13 +251,13 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
             same_view = std::memcmp(&ord.view[f], &p.views[f], sizeof(ViewDev)) == 0;
         for (uint32_t f = 0; f < std::max(p.n_frames, 1u); f++) ord.view[f] = p.views[f];
         ord.have_views = true;
-        unsigned int *sel = &slot.ctr->lpt_sel[mode == kModeAo ? 1 : 0];
+        unsigned int *sel = &slot.ctr.get()->lpt_sel[mode == kModeAo ? 1 : 0];
         if (fresh) { // new lists start empty; from then on a frame that files an order empties the set it read
             HIP_TRY(hipMemsetAsync(set[0], 0, n_lists * sizeof(uint32_t), stream));
             HIP_TRY(hipMemsetAsync(set[1], 0, n_lists * sizeof(uint32_t), stream));
             HIP_TRY(hipMemsetAsync(sel, 0, sizeof(unsigned int), stream));
         }
-        p.lpt_sets = ord.lists;
+        p.lpt_sets = ord.lists.get();
         p.lpt_sel = sel;
         p.lpt_set_words = (uint32_t)set_words;
         p.lpt_cap = list_cap;
@@ -314,14 +290,15 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     static_cast<TraceParams &>(kp) = p;
     kp.inst_mask = inst_mask;
     HIP_TRY(launch_trace(kp, mode, s->tlas, sem, count, pipe, grid, stream));
-    HIP_TRY(hipEventRecord(slot.done, stream));
+    HIP_TRY(hipEventRecord(slot.done.get(), stream));
     slot.used = true;
     if (mode == kModeService) slot.pinned = true; // (until the service is stopped: RayService::stop_locked)
-    if (ctr_out) *ctr_out = slot.ctr;
+    if (ctr_out) *ctr_out = slot.ctr.get();
     return TRX_OK;
 }
 
 int image_params(TraceParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard) {
+    std::memset(&p, 0, sizeof(p));
     if (!view) return fail(TRX_ERR_INVALID, "view is null");
     if (w == 0 || h == 0) return fail(TRX_ERR_INVALID, "empty image %ux%u", w, h);
     if ((uint64_t)w * h > 0x7fffffffull) return fail(TRX_ERR_INVALID, "image %ux%u too large", w, h);

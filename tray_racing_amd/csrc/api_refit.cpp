@@ -98,37 +98,11 @@ int refit_topology(const CwbvhNode *nodes, uint64_t n_nodes, const uint32_t *ins
 
 namespace trxapi {
 
-struct RefitState {
-    hipStream_t stream = nullptr;     // read-backs and the host-memory refit
-    bool have_topology = false;
-    uint64_t entry_version = 0;       // s->inst_entry_version the schedule was derived for
-    std::vector<uint32_t> level_start;
-    uint32_t *d_order = nullptr, *d_seg_base = nullptr;
-    float *d_boxes = nullptr;
-    float *d_o2w = nullptr;
-    uint32_t o2w_count = 0;
-    RefitResult *d_result = nullptr;
-};
-
-void refit_state_free(trx_scene *s) {
-    RefitState *r = s->refit;
-    if (!r) return;
-    if (r->d_order) (void)hipFree(r->d_order);
-    if (r->d_seg_base) (void)hipFree(r->d_seg_base);
-    if (r->d_boxes) (void)hipFree(r->d_boxes);
-    if (r->d_o2w) (void)hipFree(r->d_o2w);
-    if (r->d_result) (void)hipFree(r->d_result);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;
-    s->refit = nullptr;
-}
-
 uint64_t refit_state_bytes(const trx_scene *s) {
-    const RefitState *r = s->refit;
-    if (!r) return 0;
-    uint64_t b = r->d_result ? sizeof(RefitResult) : 0;
-    if (r->have_topology) b += s->n_nodes * (2 * sizeof(uint32_t) + 6 * sizeof(float));
-    return b + (uint64_t)r->o2w_count * 16 * sizeof(float);
+    const RefitState &r = s->refit;
+    uint64_t b = r.result.count() * sizeof(RefitResult);
+    if (r.have_topology) b += s->n_nodes * (2 * sizeof(uint32_t) + 6 * sizeof(float));
+    return b + r.o2w.count() * sizeof(float);
 }
 
 } // namespace trxapi
@@ -171,20 +145,15 @@ struct ServicesHeld {
 };
 
 int ensure_state(trx_scene *s) {
-    if (!s->refit) {
-        RefitState *r = new (std::nothrow) RefitState();
-        if (!r) return fail(TRX_ERR_OOM, "host allocation failed");
-        s->refit = r;
-    }
-    RefitState &r = *s->refit;
-    if (!r.stream) HIP_TRY(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
-    if (!r.d_result) HIP_TRY(hipMalloc(&r.d_result, sizeof(RefitResult)));
+    RefitState &r = s->refit;
+    if (!r.stream) HIP_TRY(r.stream.create(hipStreamNonBlocking));
+    if (!r.result) HIP_TRY(r.result.alloc(1));
     return TRX_OK;
 }
 
 // The schedule of the scene's node buffer: derived from one download of the nodes, kept until the entry nodes change.
 int ensure_topology(trx_scene *s) {
-    RefitState &r = *s->refit;
+    RefitState &r = s->refit;
     if (r.have_topology && r.entry_version == s->inst_entry_version) return TRX_OK;
     r.have_topology = false;
     std::vector<CwbvhNode> nodes;
@@ -193,8 +162,8 @@ int ensure_topology(trx_scene *s) {
     } catch (const std::exception &) {
         return fail(TRX_ERR_OOM, "host allocation failed");
     }
-    HIP_TRY(hipMemcpyAsync(nodes.data(), s->d_nodes, s->n_nodes * TRX_NODE_BYTES, hipMemcpyDeviceToHost, r.stream));
-    HIP_TRY(hipStreamSynchronize(r.stream));
+    HIP_TRY(hipMemcpyAsync(nodes.data(), s->nodes.get(), s->n_nodes * TRX_NODE_BYTES, hipMemcpyDeviceToHost, r.stream.get()));
+    HIP_TRY(hipStreamSynchronize(r.stream.get()));
     RefitTopology topo;
     const char *why = "";
     const uint32_t *entry = s->h_inst_entry.empty() ? nullptr : s->h_inst_entry.data();
@@ -205,12 +174,12 @@ int ensure_topology(trx_scene *s) {
     } catch (const std::exception &) {
         return fail(TRX_ERR_OOM, "host allocation failed");
     }
-    if (!r.d_order) HIP_TRY(hipMalloc(&r.d_order, s->n_nodes * sizeof(uint32_t)));
-    if (!r.d_seg_base) HIP_TRY(hipMalloc(&r.d_seg_base, s->n_nodes * sizeof(uint32_t)));
-    if (!r.d_boxes) HIP_TRY(hipMalloc(&r.d_boxes, s->n_nodes * 6 * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(r.d_order, topo.order.data(), s->n_nodes * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream));
-    HIP_TRY(hipMemcpyAsync(r.d_seg_base, topo.seg_base.data(), s->n_nodes * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream));
-    HIP_TRY(hipStreamSynchronize(r.stream));
+    if (!r.order) HIP_TRY(r.order.alloc(s->n_nodes));
+    if (!r.seg_base) HIP_TRY(r.seg_base.alloc(s->n_nodes));
+    if (!r.boxes) HIP_TRY(r.boxes.alloc(s->n_nodes * 6));
+    HIP_TRY(hipMemcpyAsync(r.order.get(), topo.order.data(), s->n_nodes * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream.get()));
+    HIP_TRY(hipMemcpyAsync(r.seg_base.get(), topo.seg_base.data(), s->n_nodes * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream.get()));
+    HIP_TRY(hipStreamSynchronize(r.stream.get()));
     r.level_start.swap(topo.level_start);
     r.entry_version = s->inst_entry_version;
     r.have_topology = true;
@@ -243,69 +212,59 @@ int scene_refit(trx_scene *s, const float *d_verts, const float *h_verts, uint64
     }
     int rc = ensure_state(s);
     if (rc) return rc;
-    RefitState &r = *s->refit;
-    if (own_stream) stream = r.stream;
+    RefitState &r = s->refit;
+    if (own_stream) stream = r.stream.get();
     ServicesHeld services(s);
     rc = ensure_topology(s);
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     // launches enqueued before this call (any stream) finish on the old geometry before anything is overwritten
     for (Slot &sl : s->slots)
-        if (sl.used && sl.done) HIP_TRY(hipStreamWaitEvent(stream, sl.done, 0));
-    float *staged = nullptr;
+        if (sl.used && sl.done) HIP_TRY(hipStreamWaitEvent(stream, sl.done.get(), 0));
+    StreamBuf<float> staged;
     auto release = [&](int code) {
-        if (staged) (void)hipFreeAsync(staged, stream);
+        (void)staged.reset();
         (void)hipStreamSynchronize(stream);
         return code;
     };
     if (h_verts) {
-        HIP_TRY(hipMallocAsync((void **)&staged, std::max<uint64_t>(n_tris, 1) * 36, stream));
-        if (n_tris && hipMemcpyAsync(staged, h_verts, n_tris * 36, hipMemcpyHostToDevice, stream) != hipSuccess)
+        HIP_TRY(staged.alloc(std::max<uint64_t>(n_tris, 1) * 9, stream));
+        if (n_tris && hipMemcpyAsync(staged.get(), h_verts, n_tris * 36, hipMemcpyHostToDevice, stream) != hipSuccess)
             return release(fail(TRX_ERR_NO_DEVICE, "upload of the vertices failed"));
-        d_verts = staged;
+        d_verts = staged.get();
     }
     RefitResult res = {0u, 1u, 1u, 0u};
-    if (hipMemcpyAsync(r.d_result, &res, sizeof(res), hipMemcpyHostToDevice, stream) != hipSuccess)
+    if (hipMemcpyAsync(r.result.get(), &res, sizeof(res), hipMemcpyHostToDevice, stream) != hipSuccess)
         return release(fail(TRX_ERR_NO_DEVICE, "refit: upload failed"));
     if (!h_verts) { // (host input was checked above) nothing is written before the check has answered
-        if (!refit_launch_check(d_verts, n_tris, r.d_result, stream) ||
-            hipMemcpyAsync(&res, r.d_result, sizeof(res), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        if (!refit_launch_check(d_verts, n_tris, r.result.get(), stream) ||
+            hipMemcpyAsync(&res, r.result.get(), sizeof(res), hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess)
             return release(fail(TRX_ERR_NO_DEVICE, "refit: the finiteness check failed to run"));
         if (res.bad_input) return release(fail(TRX_ERR_INVALID, "a vertex coordinate is not finite"));
     }
     const bool xf = s->tlas && !s->inst_o2w.empty();
     if (xf) {
-        if (r.o2w_count < s->n_inst) {
-            if (r.d_o2w) (void)hipFreeAsync(r.d_o2w, stream);
-            r.d_o2w = nullptr;
-            r.o2w_count = 0;
-            if (hipMallocAsync((void **)&r.d_o2w, (size_t)s->n_inst * 64, stream) != hipSuccess)
-                return release(fail(TRX_ERR_OOM, "refit: allocation failed"));
-            r.o2w_count = s->n_inst;
-        }
-        if (hipMemcpyAsync(r.d_o2w, s->inst_o2w.data(), (size_t)s->n_inst * 64, hipMemcpyHostToDevice, stream) != hipSuccess)
+        if (r.o2w.grow((uint64_t)s->n_inst * 16) != hipSuccess) return release(fail(TRX_ERR_OOM, "refit: allocation failed"));
+        if (hipMemcpyAsync(r.o2w.get(), s->inst_o2w.data(), (size_t)s->n_inst * 64, hipMemcpyHostToDevice, stream) != hipSuccess)
             return release(fail(TRX_ERR_NO_DEVICE, "refit: upload failed"));
     }
-    bool ok = refit_launch_tris(d_verts, n_tris, s->d_tris, stream);
+    bool ok = refit_launch_tris(d_verts, n_tris, s->tris.get(), stream);
     RefitCtx ctx;
-    ctx.nodes = s->d_nodes;
-    ctx.boxes = r.d_boxes;
+    ctx.nodes = s->nodes.get();
+    ctx.boxes = r.boxes.get();
     ctx.verts = d_verts;
-    ctx.seg_base = r.d_seg_base;
-    ctx.inst = s->tlas ? s->d_inst : nullptr;
-    ctx.entry = s->tlas ? s->d_inst_entry : nullptr;
-    ctx.o2w = xf ? r.d_o2w : nullptr;
+    ctx.seg_base = r.seg_base.get();
+    ctx.inst = s->tlas ? s->inst.get() : nullptr;
+    ctx.entry = s->tlas ? s->inst_entry.get() : nullptr;
+    ctx.o2w = xf ? r.o2w.get() : nullptr;
     ctx.n_inst = s->n_inst;
     ctx.tlas_start = s->tlas_start;
     for (size_t l = 0; ok && l + 1 < r.level_start.size(); l++)
-        ok = refit_launch_level(ctx, r.d_order, r.level_start[l], r.level_start[l + 1] - r.level_start[l], stream);
-    ok = ok && refit_launch_stats(s->d_nodes, s->n_nodes, s->tlas ? s->tlas_start : 0u, r.d_result, stream);
-    ok = ok && hipMemcpyAsync(&res, r.d_result, sizeof(res), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    if (staged) {
-        ok = ok && hipFreeAsync(staged, stream) == hipSuccess;
-        staged = nullptr;
-    }
+        ok = refit_launch_level(ctx, r.order.get(), r.level_start[l], r.level_start[l + 1] - r.level_start[l], stream);
+    ok = ok && refit_launch_stats(s->nodes.get(), s->n_nodes, s->tlas ? s->tlas_start : 0u, r.result.get(), stream);
+    ok = ok && hipMemcpyAsync(&res, r.result.get(), sizeof(res), hipMemcpyDeviceToHost, stream) == hipSuccess;
+    ok = ok && staged.reset() == hipSuccess;
     ok = ok && hipStreamSynchronize(stream) == hipSuccess;
     if (!ok) return release(fail(TRX_ERR_NO_DEVICE, "refit: a launch failed: %s", hipGetErrorString(hipGetLastError())));
     // the traversal's shortcut flags and the scene scale, derived from the new nodes as trx_scene_create derives them
@@ -341,11 +300,10 @@ int trx_scene_read_nodes(trx_scene *s, void *out_nodes, uint64_t n_nodes) {
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (a refit writes the nodes under it)
     HIP_TRY(hipSetDevice(s->device));
     // a stream of its own for the read-back: the null stream would wait for the scene's resident ray services
-    hipStream_t stream = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    hipError_t e = hipMemcpyAsync(out_nodes, s->d_nodes, n_nodes * TRX_NODE_BYTES, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipStreamDestroy(stream);
+    Stream stream;
+    HIP_TRY(stream.create(hipStreamNonBlocking));
+    hipError_t e = hipMemcpyAsync(out_nodes, s->nodes.get(), n_nodes * TRX_NODE_BYTES, hipMemcpyDeviceToHost, stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(stream.get());
     if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "read-back of the nodes failed: %s", hipGetErrorString(e));
     return TRX_OK;
 }
@@ -356,7 +314,7 @@ int trx_debug_scene_info(trx_scene *s, uint32_t *out_exp_exact, float *out_scene
     if (out_exp_exact) *out_exp_exact = s->exp_exact;
     if (out_scene_diag) *out_scene_diag = s->scene_diag;
     if (out_refit_levels)
-        *out_refit_levels = s->refit && s->refit->have_topology ? (uint32_t)s->refit->level_start.size() - 1u : 0u;
+        *out_refit_levels = s->refit.have_topology ? (uint32_t)s->refit.level_start.size() - 1u : 0u;
     return TRX_OK;
 }
 

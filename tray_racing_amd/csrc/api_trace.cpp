@@ -9,7 +9,6 @@ static int primary_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
                         uint32_t ray_mask, trx_hit *d_hits, uint32_t *d_inst, void *stream) {
     if (!s || !d_hits) return fail(TRX_ERR_INVALID, "null argument");
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, shard);
     if (rc) return rc;
     p.out = d_hits;
@@ -24,7 +23,6 @@ static int ao_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, t
                    trx_hit *d_ao, uint32_t *d_ao_inst, void *stream) {
     if (!s || !d_primary || !d_ao) return fail(TRX_ERR_INVALID, "null argument");
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, shard);
     if (rc) return rc;
     p.primary = d_primary;
@@ -62,7 +60,6 @@ int trx_trace_primary_batch_dev(trx_scene *s, const trx_view *views, uint32_t n_
     if (n_frames == 0 || n_frames > (uint32_t)kMaxBatchFrames)
         return fail(TRX_ERR_INVALID, "n_frames %u outside 1..%d", n_frames, kMaxBatchFrames);
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, views, w, h, shard);
     if (rc) return rc;
     const uint64_t frame_records = p.compact ? (uint64_t)p.tiles_per_frame * 64 : (uint64_t)w * h;
@@ -99,7 +96,7 @@ int trx_trace_frame_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
         // two-level scenes: the two-level walk has no registers to spare for the in-place hand-over (the kernel that
         // contains it spills), so their frame stays two launches on the caller's stream - same records.  (Variant bit 13:
         // every frame this way, for A/B runs.)
-        if (s->d_inst_xform && !d_primary_inst)
+        if (s->inst_xform && !d_primary_inst)
             return fail(TRX_ERR_INVALID, "this scene has instance transforms: the frame needs d_primary_inst (the AO pass takes "
                                          "the hit normal into world space with the primary pass's instance ids)");
         int rc2 = trx_trace_primary_inst_dev(s, view, w, h, shard, sem, d_primary, d_primary_inst, stream);
@@ -107,7 +104,6 @@ int trx_trace_frame_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
         return trx_trace_ao_inst_dev(s, view, w, h, shard, sem, frame, ao_eps, d_primary, d_primary_inst, d_ao, d_ao_inst, stream);
     }
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, shard);
     if (rc) return rc;
     p.out = d_primary;
@@ -130,7 +126,6 @@ int trx_trace_ao_batch_dev(trx_scene *s, const trx_view *view, uint32_t w, uint3
     if (n_frames == 1)
         return trx_trace_ao_inst_dev(s, view, w, h, shard, sem, frame0, ao_eps, d_primary, d_primary_inst, d_ao, d_ao_inst, stream);
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, shard);
     if (rc) return rc;
     const uint64_t frame_records = p.compact ? (uint64_t)p.tiles_per_frame * 64 : (uint64_t)w * h;
@@ -228,9 +223,9 @@ int trx_trace_ao_masked_dev(trx_scene *s, const trx_view *view, uint32_t w, uint
     return ao_impl(s, view, w, h, shard, sem, frame, ao_eps, ray_mask, d_primary, d_primary_inst, d_ao, d_ao_inst, stream);
 }
 
-static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint32_t *hist = nullptr) {
-    HIP_TRY(hipEventRecord(s->ev1, nullptr));
-    HIP_TRY(hipEventSynchronize(s->ev1));
+static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint32_t *hist) {
+    HIP_TRY(hipEventRecord(s->ev1.get(), nullptr));
+    HIP_TRY(hipEventSynchronize(s->ev1.get()));
     SlotCounters c;
     HIP_TRY(hipMemcpy(&c, ctr, sizeof(c), hipMemcpyDeviceToHost));
     SlotCounters z = c;
@@ -246,7 +241,7 @@ static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint3
     }
     HIP_TRY(hipMemcpy(ctr, &z, sizeof(z), hipMemcpyHostToDevice));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()));
     if (stats) {
         stats->n_rays = c.n_rays;
         stats->n_node = c.n_node;
@@ -263,28 +258,34 @@ static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint3
     return TRX_OK;
 }
 
+// A counted pass on the null stream, timed from an idle device: the kernel counts into its slot's counters, which
+// finish_count reads into stats / hist and zeroes.  (count = false: the normal kernel, whose diagnostic histograms a
+// development build may file.)
+static int count_pass(trx_scene *s, TraceParams &p, int mode, uint32_t sem, trx_stats *stats, uint32_t *hist = nullptr,
+                      bool count = true) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipEventRecord(s->ev0.get(), nullptr));
+    SlotCounters *ctr = nullptr;
+    if (int rc = enqueue(s, p, mode, sem, count, nullptr, &ctr)) return rc;
+    return finish_count(s, ctr, stats, hist);
+}
+
 int trx_count_primary(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
                       trx_hit *d_hits, trx_stats *stats) {
     if (!s) return fail(TRX_ERR_INVALID, "null scene");
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     HIP_TRY(hipSetDevice(s->device));
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, shard);
     if (rc) return rc;
     if (!d_hits) {
         // the shard layout addresses local_tile * 64 + k: whole tiles, also where the image ends mid-tile
         rc = ensure_scratch(s, std::max<uint64_t>((uint64_t)w * h, (uint64_t)p.n_items), 0);
         if (rc) return rc;
-        d_hits = s->d_scratch_a;
+        d_hits = s->scratch_a.get();
     }
     p.out = d_hits;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    SlotCounters *ctr = nullptr;
-    rc = enqueue(s, p, kModePrimary, sem, true, nullptr, &ctr);
-    if (rc) return rc;
-    return finish_count(s, ctr, stats);
+    return count_pass(s, p, kModePrimary, sem, stats);
 }
 
 // Compulsory footprint of one primary frame: distinct nodes fetched and distinct triangles tested.
@@ -294,27 +295,22 @@ int trx_debug_footprint(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
     HIP_TRY(hipSetDevice(s->device));
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, trx_shard{0, 1, 0, 0});
     if (rc) return rc;
     rc = ensure_scratch(s, (uint64_t)w * h, 0);
     if (rc) return rc;
-    p.out = s->d_scratch_a;
+    p.out = s->scratch_a.get();
     const size_t nb = s->n_nodes, tb = std::max<uint64_t>(s->n_tris, 1);
-    uint8_t *d_marks = nullptr;
-    HIP_TRY(hipMalloc(&d_marks, nb + tb));
-    hipError_t e = hipMemset(d_marks, 0, nb + tb);
-    p.touch_nodes = d_marks;
-    p.touch_tris = d_marks + nb;
-    SlotCounters *ctr = nullptr;
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipEventRecord(s->ev0, nullptr);
-    if (e == hipSuccess) rc = enqueue(s, p, kModePrimary, sem, true, nullptr, &ctr);
-    if (e == hipSuccess && !rc) rc = finish_count(s, ctr, nullptr);
-    std::vector<uint8_t> host(nb + tb);
-    if (e == hipSuccess && !rc) e = hipMemcpy(host.data(), d_marks, nb + tb, hipMemcpyDeviceToHost);
-    (void)hipFree(d_marks);
+    DevBuf<uint8_t> marks;
+    HIP_TRY(marks.alloc(nb + tb));
+    hipError_t e = hipMemset(marks.get(), 0, nb + tb);
+    if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "footprint pass failed: %s", hipGetErrorString(e));
+    p.touch_nodes = marks.get();
+    p.touch_tris = marks.get() + nb;
+    rc = count_pass(s, p, kModePrimary, sem, nullptr);
     if (rc) return rc;
+    std::vector<uint8_t> host(nb + tb);
+    e = hipMemcpy(host.data(), marks.get(), nb + tb, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "footprint pass failed: %s", hipGetErrorString(e));
     uint64_t n = 0, t = 0;
     for (size_t i = 0; i < nb; i++) n += host[i] != 0;
@@ -329,22 +325,16 @@ int trx_debug_tri_histogram(trx_scene *s, const trx_view *view, uint32_t w, uint
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
     HIP_TRY(hipSetDevice(s->device));
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, trx_shard{0, 1, 0, 0});
     if (rc) return rc;
     rc = ensure_scratch(s, (uint64_t)w * h, 0);
     if (rc) return rc;
-    p.out = s->d_scratch_a;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    SlotCounters *ctr = nullptr;
+    p.out = s->scratch_a.get();
     bool count = true;
 #ifdef TRX_DEV_TUNE
     if (getenv("TRX_HIST_NORMAL")) count = false; // (development builds: the histograms a NORMAL frame files under a tune word)
 #endif
-    rc = enqueue(s, p, kModePrimary, sem, count, nullptr, &ctr);
-    if (rc) return rc;
-    return finish_count(s, ctr, nullptr, out_hist);
+    return count_pass(s, p, kModePrimary, sem, nullptr, out_hist, count);
 }
 
 int trx_count_ao(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
@@ -353,19 +343,13 @@ int trx_count_ao(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     HIP_TRY(hipSetDevice(s->device));
     TraceParams p;
-    std::memset(&p, 0, sizeof(p));
     int rc = image_params(p, view, w, h, shard);
     if (rc) return rc;
     p.primary = d_primary;
     p.out = d_ao;
     p.frame = frame;
     p.ao_eps = ao_eps;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    SlotCounters *ctr = nullptr;
-    rc = enqueue(s, p, kModeAo, sem, true, nullptr, &ctr);
-    if (rc) return rc;
-    return finish_count(s, ctr, stats);
+    return count_pass(s, p, kModeAo, sem, stats);
 }
 
 int trx_count_rays(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, trx_stats *stats) {
@@ -375,14 +359,14 @@ int trx_count_rays(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem
     if (!d_hits) {
         int rc = ensure_scratch(s, n, 0);
         if (rc) return rc;
-        d_hits = s->d_scratch_a;
+        d_hits = s->scratch_a.get();
     }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    SlotCounters *ctr = nullptr;
-    int rc = trace_rays_impl(s, d_rays, n, sem, d_hits, nullptr, true, &ctr);
-    if (rc) return rc;
-    return finish_count(s, ctr, stats);
+    TraceParams p; // (one launch: a batch of at most 2^30 rays is one chunk of trace_rays_impl)
+    std::memset(&p, 0, sizeof(p));
+    p.rays = d_rays;
+    p.out = d_hits;
+    p.n_items = (uint32_t)n;
+    return count_pass(s, p, kModeRays, sem, stats);
 }
 
 int trx_scene_check(trx_scene *s, void *stream) {
@@ -391,29 +375,36 @@ int trx_scene_check(trx_scene *s, void *stream) {
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     for (Slot &sl : s->slots) {
         if (!sl.ctr) continue;
-        int rc = read_overflow(s, sl.ctr);
+        int rc = read_overflow(s, sl.ctr.get());
         if (rc) return rc;
     }
     return TRX_OK;
 }
 
+} // extern "C"
+
 // ---- tracing: host buffers ------------------------------------------------------------------
+
+int trxapi::read_inst(uint32_t *dst, const uint32_t *src, uint64_t n) {
+    if (!dst) return TRX_OK;
+    if (src) HIP_TRY(hipMemcpy(dst, src, n * 4, hipMemcpyDeviceToHost));
+    else std::memset(dst, 0xff, n * 4); // no TLAS: no instances
+    return TRX_OK;
+}
+
+extern "C" {
 
 int trx_trace_primary(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, trx_hit *out_hits,
                       float *out_ms) {
     if (!s) return fail(TRX_ERR_INVALID, "null scene");
-    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
-    HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure_scratch(s, (uint64_t)w * h, 0);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, nullptr));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
-    if (out_hits) HIP_TRY(hipMemcpy(out_hits, s->d_scratch_a, (uint64_t)w * h * sizeof(trx_hit), hipMemcpyDeviceToHost));
-    return trx_scene_check(s, nullptr);
+    const uint64_t n = (uint64_t)w * h;
+    return host_call(
+        s, n, nullptr, 0, 0, out_ms,
+        [&] { return trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->scratch_a.get(), nullptr); },
+        [&]() -> int {
+            if (out_hits) HIP_TRY(hipMemcpy(out_hits, s->scratch_a.get(), n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
 }
 
 int trx_trace_primary_ao(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame,
@@ -425,31 +416,23 @@ int trx_trace_primary_ao_inst(trx_scene *s, const trx_view *view, uint32_t w, ui
                               float ao_eps, trx_hit *out_primary, uint32_t *out_primary_inst, trx_hit *out_ao,
                               uint32_t *out_ao_inst, float *out_ms) {
     if (!s) return fail(TRX_ERR_INVALID, "null scene");
-    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
-    HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure_scratch(s, (uint64_t)w * h, 0);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    // instance ids travel with the hits whenever the scene has a TLAS (the AO pass needs them once transforms are set)
-    rc = trx_trace_primary_inst_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, s->d_scratch_ia, nullptr);
-    if (rc) return rc;
-    rc = trx_trace_ao_inst_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, frame, ao_eps, s->d_scratch_a, s->d_scratch_ia,
-                               s->d_scratch_b, s->d_scratch_ib, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, nullptr));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
-    const uint64_t bytes = (uint64_t)w * h * sizeof(trx_hit);
-    if (out_primary) HIP_TRY(hipMemcpy(out_primary, s->d_scratch_a, bytes, hipMemcpyDeviceToHost));
-    if (out_ao) HIP_TRY(hipMemcpy(out_ao, s->d_scratch_b, bytes, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 2; k++) {
-        uint32_t *dst = k ? out_ao_inst : out_primary_inst;
-        const uint32_t *src = k ? s->d_scratch_ib : s->d_scratch_ia;
-        if (!dst) continue;
-        if (src) HIP_TRY(hipMemcpy(dst, src, (uint64_t)w * h * 4, hipMemcpyDeviceToHost));
-        else std::memset(dst, 0xff, (uint64_t)w * h * 4); // no TLAS: no instances
-    }
-    return trx_scene_check(s, nullptr);
+    const uint64_t n = (uint64_t)w * h;
+    const trx_shard whole{0, 1, 0, 0};
+    return host_call(
+        s, n, nullptr, 0, 0, out_ms,
+        [&] {
+            // instance ids travel with the hits whenever the scene has a TLAS (the AO pass needs them once transforms are set)
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, s->scratch_a.get(), s->scratch_ia.get(), nullptr);
+            if (rc) return rc;
+            return trx_trace_ao_inst_dev(s, view, w, h, whole, sem, frame, ao_eps, s->scratch_a.get(), s->scratch_ia.get(),
+                                         s->scratch_b.get(), s->scratch_ib.get(), nullptr);
+        },
+        [&]() -> int {
+            if (out_primary) HIP_TRY(hipMemcpy(out_primary, s->scratch_a.get(), n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+            if (out_ao) HIP_TRY(hipMemcpy(out_ao, s->scratch_b.get(), n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+            if (int rc = read_inst(out_primary_inst, s->scratch_ia.get(), n)) return rc;
+            return read_inst(out_ao_inst, s->scratch_ib.get(), n);
+        });
 }
 
 // The reference's frame loop, device-resident (src/rt_gpu/rt_gpu_software.rs:271-361: every frame a primary pass and the AO
@@ -468,68 +451,61 @@ int trx_frame_loop(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, u
     const uint64_t n = (uint64_t)w * h;
     if (n == 0 || n > 0x7fffffffull) return fail(TRX_ERR_INVALID, "image %ux%u", w, h);
     FrameLoop &fl = s->loop;
-    if (!fl.stream[0]) {
-        for (int k = 0; k < 2; k++) HIP_TRY(hipStreamCreateWithFlags(&fl.stream[k], hipStreamNonBlocking));
+    if (!fl.t1) { // (t1 is created last: a set-up that failed half-way is made again)
+        for (int k = 0; k < 2; k++) HIP_TRY(fl.stream[k].create(hipStreamNonBlocking));
         for (int k = 0; k < FrameLoop::kBuffers; k++) {
-            HIP_TRY(hipEventCreateWithFlags(&fl.prim_done[k], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&fl.ao_done[k], hipEventDisableTiming));
+            HIP_TRY(fl.prim_done[k].create(hipEventDisableTiming));
+            HIP_TRY(fl.ao_done[k].create(hipEventDisableTiming));
         }
-        HIP_TRY(hipEventCreate(&fl.t0));
-        HIP_TRY(hipEventCreate(&fl.t1));
+        HIP_TRY(fl.t0.create());
+        HIP_TRY(fl.t1.create());
     }
     if (fl.records < n) {
-        for (int k = 0; k < 2; k++) HIP_TRY(hipStreamSynchronize(fl.stream[k]));
-        for (int k = 0; k < FrameLoop::kBuffers; k++) {
-            if (fl.prim[k]) (void)hipFree(fl.prim[k]);
-            if (fl.prim_inst[k]) (void)hipFree(fl.prim_inst[k]);
-            fl.prim[k] = nullptr;
-            fl.prim_inst[k] = nullptr;
-        }
-        if (fl.ao) (void)hipFree(fl.ao);
-        if (fl.ao_inst) (void)hipFree(fl.ao_inst);
-        fl.ao = nullptr;
-        fl.ao_inst = nullptr;
+        for (int k = 0; k < 2; k++) HIP_TRY(hipStreamSynchronize(fl.stream[k].get()));
         fl.records = 0;
         for (int k = 0; k < FrameLoop::kBuffers; k++) {
-            HIP_TRY(hipMalloc(&fl.prim[k], n * sizeof(trx_hit)));
-            if (s->tlas) HIP_TRY(hipMalloc(&fl.prim_inst[k], n * sizeof(uint32_t)));
+            HIP_TRY(fl.prim[k].grow(n));
+            if (s->tlas) HIP_TRY(fl.prim_inst[k].grow(n));
         }
-        HIP_TRY(hipMalloc(&fl.ao, n * sizeof(trx_hit)));
-        if (s->tlas) HIP_TRY(hipMalloc(&fl.ao_inst, n * sizeof(uint32_t)));
+        HIP_TRY(fl.ao.grow(n));
+        if (s->tlas) HIP_TRY(fl.ao_inst.grow(n));
         fl.records = n;
     }
-    hipStream_t sa = fl.stream[0], sb = overlap ? fl.stream[1] : fl.stream[0];
+    hipStream_t sa = fl.stream[0].get(), sb = overlap ? fl.stream[1].get() : sa;
     const trx_shard whole{0, 1, 0, 0};
-    HIP_TRY(hipEventRecord(fl.t0, sa));
-    int rc = TRX_OK;
-    for (uint32_t i = 0; i < n_frames && rc == TRX_OK; i++) {
-        const int b = (int)(i % (uint32_t)FrameLoop::kBuffers);
-        if (i >= (uint32_t)FrameLoop::kBuffers && overlap) HIP_TRY(hipStreamWaitEvent(sa, fl.ao_done[b], 0)); // AO(i - 4) has read this buffer
-        rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, fl.prim[b], fl.prim_inst[b], sa);
-        if (rc) break;
-        if (overlap) {
-            HIP_TRY(hipEventRecord(fl.prim_done[b], sa));
-            HIP_TRY(hipStreamWaitEvent(sb, fl.prim_done[b], 0));
+    auto enqueue_frames = [&]() -> int {
+        HIP_TRY(hipEventRecord(fl.t0.get(), sa));
+        for (uint32_t i = 0; i < n_frames; i++) {
+            const int b = (int)(i % (uint32_t)FrameLoop::kBuffers);
+            if (i >= (uint32_t)FrameLoop::kBuffers && overlap) HIP_TRY(hipStreamWaitEvent(sa, fl.ao_done[b].get(), 0)); // AO(i - 4) has read this buffer
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, fl.prim[b].get(), fl.prim_inst[b].get(), sa);
+            if (rc) return rc;
+            if (overlap) {
+                HIP_TRY(hipEventRecord(fl.prim_done[b].get(), sa));
+                HIP_TRY(hipStreamWaitEvent(sb, fl.prim_done[b].get(), 0));
+            }
+            rc = trx_trace_ao_inst_dev(s, view, w, h, whole, sem, frame0 + (animate ? i : 0u), ao_eps, fl.prim[b].get(),
+                                       fl.prim_inst[b].get(), fl.ao.get(), fl.ao_inst.get(), sb);
+            if (rc) return rc;
+            if (overlap) HIP_TRY(hipEventRecord(fl.ao_done[b].get(), sb));
         }
-        rc = trx_trace_ao_inst_dev(s, view, w, h, whole, sem, frame0 + (animate ? i : 0u), ao_eps, fl.prim[b], fl.prim_inst[b], fl.ao,
-                                   fl.ao_inst, sb);
-        if (rc) break;
-        if (overlap) HIP_TRY(hipEventRecord(fl.ao_done[b], sb));
-    }
-    if (rc == TRX_OK && overlap) HIP_TRY(hipStreamWaitEvent(sa, fl.ao_done[(n_frames - 1u) % (uint32_t)FrameLoop::kBuffers], 0));
-    if (rc == TRX_OK) HIP_TRY(hipEventRecord(fl.t1, sa));
+        if (overlap) HIP_TRY(hipStreamWaitEvent(sa, fl.ao_done[(n_frames - 1u) % (uint32_t)FrameLoop::kBuffers].get(), 0));
+        HIP_TRY(hipEventRecord(fl.t1.get(), sa));
+        return TRX_OK;
+    };
+    int rc = enqueue_frames();
     // (whatever happened, nothing of this call is left in flight when it returns)
-    const hipError_t e0 = hipStreamSynchronize(fl.stream[0]), e1 = hipStreamSynchronize(fl.stream[1]);
+    const hipError_t e0 = hipStreamSynchronize(fl.stream[0].get()), e1 = hipStreamSynchronize(fl.stream[1].get());
     if (rc) return rc;
     HIP_TRY(e0);
     HIP_TRY(e1);
-    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, fl.t0, fl.t1));
+    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, fl.t0.get(), fl.t1.get()));
     const int last = (int)((n_frames - 1u) % (uint32_t)FrameLoop::kBuffers);
-    if (out_primary) HIP_TRY(hipMemcpy(out_primary, fl.prim[last], n * sizeof(trx_hit), hipMemcpyDeviceToHost));
-    if (out_ao) HIP_TRY(hipMemcpy(out_ao, fl.ao, n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+    if (out_primary) HIP_TRY(hipMemcpy(out_primary, fl.prim[last].get(), n * sizeof(trx_hit), hipMemcpyDeviceToHost));
+    if (out_ao) HIP_TRY(hipMemcpy(out_ao, fl.ao.get(), n * sizeof(trx_hit), hipMemcpyDeviceToHost));
     for (Slot &sl : s->slots) {
         if (!sl.ctr) continue;
-        rc = read_overflow(s, sl.ctr);
+        rc = read_overflow(s, sl.ctr.get());
         if (rc) return rc;
     }
     return TRX_OK;
@@ -541,75 +517,45 @@ int trx_trace_rays(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, 
 
 } // extern "C"
 
-// trx_trace_rays_inst / trx_trace_rays_masked (ray_mask 0: unmasked)
-static int rays_host(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, trx_hit *out_hits,
+// trx_trace_rays_inst / trx_trace_rays_masked, and with any_hit trx_trace_occluded / trx_trace_occluded_masked (ray_mask 0:
+// unmasked): `out` takes n hit records, or n occlusion flags
+static int rays_host(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, bool any_hit, void *out,
                      uint32_t *out_inst, float *out_ms) {
     if (!s || (n && !rays)) return fail(TRX_ERR_INVALID, "null argument");
-    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     if (n == 0) return TRX_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure_scratch(s, n, n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(s->d_scratch_rays, rays, n * sizeof(trx_ray), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    rc = ray_mask ? trx_trace_rays_masked_dev(s, s->d_scratch_rays, n, sem, ray_mask, s->d_scratch_a,
-                                              out_inst ? s->d_scratch_ia : nullptr, nullptr)
-                  : trx_trace_rays_inst_dev(s, s->d_scratch_rays, n, sem, s->d_scratch_a, out_inst ? s->d_scratch_ia : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, nullptr));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
-    if (out_hits) HIP_TRY(hipMemcpy(out_hits, s->d_scratch_a, n * sizeof(trx_hit), hipMemcpyDeviceToHost));
-    if (out_inst) {
-        if (s->d_scratch_ia) HIP_TRY(hipMemcpy(out_inst, s->d_scratch_ia, n * 4, hipMemcpyDeviceToHost));
-        else std::memset(out_inst, 0xff, n * 4);
-    }
-    return trx_scene_check(s, nullptr);
-}
-
-// trx_trace_occluded / trx_trace_occluded_masked (ray_mask 0: unmasked)
-static int occluded_host(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, uint8_t *out_flags,
-                         float *out_ms) {
-    if (!s || (n && !rays)) return fail(TRX_ERR_INVALID, "null argument");
-    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
-    if (n == 0) return TRX_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure_scratch(s, n, n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(s->d_scratch_rays, rays, n * sizeof(trx_ray), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(s->ev0, nullptr));
-    uint8_t *d_flags = reinterpret_cast<uint8_t *>(s->d_scratch_a);
-    rc = ray_mask ? trx_trace_occluded_masked_dev(s, s->d_scratch_rays, n, sem, ray_mask, d_flags, nullptr)
-                  : trx_trace_occluded_dev(s, s->d_scratch_rays, n, sem, d_flags, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, nullptr));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    if (out_ms) HIP_TRY(hipEventElapsedTime(out_ms, s->ev0, s->ev1));
-    if (out_flags) HIP_TRY(hipMemcpy(out_flags, s->d_scratch_a, n, hipMemcpyDeviceToHost));
-    return trx_scene_check(s, nullptr);
+    return host_call(
+        s, n, rays, n, 0, out_ms,
+        [&] {
+            return trace_rays_impl(s, s->scratch_rays.get(), n, sem, s->scratch_a.get(), nullptr, false, nullptr, any_hit,
+                                   out_inst ? s->scratch_ia.get() : nullptr, ray_mask);
+        },
+        [&]() -> int {
+            if (out) HIP_TRY(hipMemcpy(out, s->scratch_a.get(), n * (any_hit ? 1u : sizeof(trx_hit)), hipMemcpyDeviceToHost));
+            return read_inst(out_inst, s->scratch_ia.get(), n);
+        });
 }
 
 extern "C" {
 
 int trx_trace_rays_inst(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, trx_hit *out_hits, uint32_t *out_inst,
                         float *out_ms) {
-    return rays_host(s, rays, n, sem, 0u, out_hits, out_inst, out_ms);
+    return rays_host(s, rays, n, sem, 0u, false, out_hits, out_inst, out_ms);
 }
 
 int trx_trace_occluded(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint8_t *out_flags, float *out_ms) {
-    return occluded_host(s, rays, n, sem, 0u, out_flags, out_ms);
+    return rays_host(s, rays, n, sem, 0u, true, out_flags, nullptr, out_ms);
 }
 
 int trx_trace_rays_masked(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask, trx_hit *out_hits,
                           uint32_t *out_inst, float *out_ms) {
     if (int rc = check_ray_mask(ray_mask)) return rc; // (before the upload)
-    return rays_host(s, rays, n, sem, ray_mask, out_hits, out_inst, out_ms);
+    return rays_host(s, rays, n, sem, ray_mask, false, out_hits, out_inst, out_ms);
 }
 
 int trx_trace_occluded_masked(trx_scene *s, const trx_ray *rays, uint64_t n, uint32_t sem, uint32_t ray_mask,
                               uint8_t *out_flags, float *out_ms) {
     if (int rc = check_ray_mask(ray_mask)) return rc; // (before the upload)
-    return occluded_host(s, rays, n, sem, ray_mask, out_flags, out_ms);
+    return rays_host(s, rays, n, sem, ray_mask, true, out_flags, nullptr, out_ms);
 }
 
 
@@ -620,20 +566,17 @@ int trx_bench_primary(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
     HIP_TRY(hipSetDevice(s->device));
     int rc = ensure_scratch(s, (uint64_t)w * h, 0);
     if (rc) return rc;
+    auto frame = [&] { return trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->scratch_a.get(), nullptr); };
     for (uint32_t i = 0; i < warmup; i++) {
-        rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
+        rc = frame();
         if (rc) return rc;
     }
     float mn = 1e30f;
     double sum = 0.0;
     for (uint32_t i = 0; i < frames; i++) {
-        HIP_TRY(hipEventRecord(s->ev0, nullptr));
-        rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(s->ev1, nullptr));
-        HIP_TRY(hipEventSynchronize(s->ev1));
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        rc = timed(s, &ms, frame);
+        if (rc) return rc;
         mn = std::min(mn, ms);
         sum += ms;
     }
@@ -653,24 +596,23 @@ int trx_debug_tile_profile(trx_scene *s, const trx_view *view, uint32_t w, uint3
     int rc = ensure_scratch(s, (uint64_t)w * h, 0);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMalloc(&s->dbg_cost, (size_t)n_tiles * 4));
-    hipError_t e = hipMalloc(&s->dbg_iters, (size_t)n_tiles * 4);
-    if (e == hipSuccess) e = hipMemset(s->dbg_iters, 0, (size_t)n_tiles * 4);
+    DevBuf<uint32_t> cost, iters;
+    HIP_TRY(cost.alloc(n_tiles));
+    hipError_t e = iters.alloc(n_tiles);
+    if (e == hipSuccess) e = hipMemset(iters.get(), 0, (size_t)n_tiles * 4);
+    s->dbg_cost = cost.get();
+    s->dbg_iters = iters.get();
     trx_stats st;
-    if (e == hipSuccess) rc = trx_count_primary(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, &st);
-    if (e == hipSuccess && !rc) e = hipMemcpy(out_iters, s->dbg_iters, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) rc = trx_count_primary(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->scratch_a.get(), &st);
+    if (e == hipSuccess && !rc) e = hipMemcpy(out_iters, iters.get(), (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && !rc) {
-        uint32_t *iters = s->dbg_iters;
         s->dbg_iters = nullptr; // second pass: the normal kernel
-        for (int i = 0; i < 3 && !rc; i++) rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
-        s->dbg_iters = iters;
+        for (int i = 0; i < 3 && !rc; i++) rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->scratch_a.get(), nullptr);
         if (!rc) e = hipDeviceSynchronize();
-        if (e == hipSuccess && !rc) e = hipMemcpy(out_cost, s->dbg_cost, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && !rc) e = hipMemcpy(out_cost, cost.get(), (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
     }
     (void)hipDeviceSynchronize();
-    (void)hipFree(s->dbg_cost);
-    if (s->dbg_iters) (void)hipFree(s->dbg_iters);
-    s->dbg_cost = s->dbg_iters = nullptr;
+    s->dbg_cost = s->dbg_iters = nullptr; // (the buffers go at the return)
     if (rc) return rc;
     if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "tile profile failed: %s", hipGetErrorString(e));
     return TRX_OK;
@@ -688,21 +630,20 @@ static int wave_records(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
     const size_t n = (size_t)s->cu_count * 32;
     const size_t words = n * kWaveTimeStride;
     if (ao) { // the AO pass is the one recorded: its input first, without records
-        rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
+        rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->scratch_a.get(), nullptr);
         if (rc) return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
-    if (!s->d_wave_times) HIP_TRY(hipMalloc(&s->d_wave_times, words * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->d_wave_times, 0, words * sizeof(unsigned long long)));
+    HIP_TRY(s->wave_times.grow(words));
+    HIP_TRY(hipMemset(s->wave_times.get(), 0, words * sizeof(unsigned long long)));
     if (ao)
-        rc = trx_trace_ao_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, 0u, 0.01f, s->d_scratch_a, s->d_scratch_b, nullptr);
+        rc = trx_trace_ao_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, 0u, 0.01f, s->scratch_a.get(), s->scratch_b.get(), nullptr);
     else
-        rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->d_scratch_a, nullptr);
+        rc = trx_trace_primary_dev(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, s->scratch_a.get(), nullptr);
     hipError_t e = hipDeviceSynchronize();
     std::vector<unsigned long long> host(words);
-    if (e == hipSuccess) e = hipMemcpy(host.data(), s->d_wave_times, words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(s->d_wave_times);
-    s->d_wave_times = nullptr;
+    if (e == hipSuccess) e = hipMemcpy(host.data(), s->wave_times.get(), words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    s->wave_times.reset();
     if (rc) return rc;
     if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "timeline read-back failed: %s", hipGetErrorString(e));
     uint32_t k = 0;

@@ -31,15 +31,15 @@ static void stop_services_at_exit() {
 }
 
 RayService::RayService(trx_scene *s, uint32_t semantics) : scene(s), sem(semantics) {
-    hipError_t e = hipHostMalloc((void **)&ring, (size_t)kSlots * kSvcSlotWords * 4, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&ctl, 64, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    hipError_t e = ring.alloc((size_t)kSlots * kSvcSlotWords, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) e = ctl.alloc(16, hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) e = stream.create(hipStreamNonBlocking);
     if (e != hipSuccess) {
         init_err = hipGetErrorString(e);
         return;
     }
-    std::memset(ring, 0, (size_t)kSlots * kSvcSlotWords * 4);
-    std::memset(ctl, 0, 64);
+    std::memset(ring.get(), 0, (size_t)kSlots * kSvcSlotWords * 4);
+    std::memset(ctl.get(), 0, 64);
     caller[0].last_use_ns.store(now_ns(), std::memory_order_relaxed);
     try {
         watchdog = std::thread([this]() {
@@ -47,7 +47,7 @@ RayService::RayService(trx_scene *s, uint32_t semantics) : scene(s), sem(semanti
             int64_t beat = 0;
             while (!quit.load(std::memory_order_acquire)) {
                 std::this_thread::sleep_for(std::chrono::nanoseconds(kBeatNs));
-                reinterpret_cast<volatile uint32_t *>(ctl)[1] = (uint32_t)++beat;
+                reinterpret_cast<volatile uint32_t *>(ctl.get())[1] = (uint32_t)++beat;
                 // (a caller that claims a slot at this very moment finds the service stopped and starts it again - its request
                 // is still in the ring: traverse1_service looks every 1024 spins)
                 if (running.load(std::memory_order_acquire) && idle_since(now_ns() - kIdleStopNs)) {
@@ -79,25 +79,20 @@ RayService::~RayService() {
     }
     quit.store(true, std::memory_order_release);
     if (watchdog.joinable()) watchdog.join();
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        stop_locked();
-    }
-    if (stream) (void)hipStreamDestroy(stream);
-    if (ring) (void)hipHostFree(ring);
-    if (ctl) (void)hipHostFree(ctl);
+    std::lock_guard<std::mutex> lock(mu);
+    stop_locked(); // (the ring, the control words and the stream go with the members)
 }
 
 int RayService::start_locked() {
     if (running.load(std::memory_order_acquire)) return TRX_OK;
-    reinterpret_cast<volatile uint32_t *>(ctl)[0] = 0u;
+    reinterpret_cast<volatile uint32_t *>(ctl.get())[0] = 0u;
     TraceParams p;
     std::memset(&p, 0, sizeof(p));
     p.n_items = 2u * kGroups * 64u; // (a chunk per wave: enqueue() sizes the grid from it - kGroups workgroups of two waves)
     p.n_frames = 1;
-    p.svc_ring = ring;
-    p.svc_ctl = ctl;
-    const int rc = enqueue(scene, p, kModeService, sem, false, stream, nullptr);
+    p.svc_ring = ring.get();
+    p.svc_ctl = ctl.get();
+    const int rc = enqueue(scene, p, kModeService, sem, false, stream.get(), nullptr);
     if (rc) return rc;
     running.store(true, std::memory_order_release);
     starts.fetch_add(1, std::memory_order_relaxed);
@@ -107,11 +102,11 @@ int RayService::start_locked() {
 void RayService::stop_locked() {
     if (!running.load(std::memory_order_acquire)) return;
     (void)hipSetDevice(scene->device);
-    reinterpret_cast<volatile uint32_t *>(ctl)[0] = 1u;
-    (void)hipStreamSynchronize(stream);
+    reinterpret_cast<volatile uint32_t *>(ctl.get())[0] = 1u;
+    (void)hipStreamSynchronize(stream.get());
 #ifdef TRX_SVC_PHASES   // (tuning builds, trace_thin.inc: cycles per step of the walkers' trips)
     for (uint32_t g = 0; g < kGroups; g++) {
-        const volatile uint32_t *w = ring + (size_t)g * trx::kSvcRays * trx::kSvcSlotWords + 24;
+        const volatile uint32_t *w = ring.get() + (size_t)g * trx::kSvcRays * trx::kSvcSlotWords + 24;
         if (w[7] != 0u)
             fprintf(stderr, "SVC_PHASES group %u: %u trips; cycles per trip: (0) %.0f (1) %.0f (2) %.0f (3) %.0f (4) %.0f (5) %.0f back-edge %.0f\n", g, w[7],
                     (double)w[0] / w[7], (double)w[1] / w[7], (double)w[2] / w[7], (double)w[3] / w[7], (double)w[4] / w[7], (double)w[5] / w[7], (double)w[6] / w[7]);
@@ -120,7 +115,7 @@ void RayService::stop_locked() {
     {
         std::lock_guard<std::mutex> lock(scene->mu);
         for (Slot &sl : scene->slots)
-            if (sl.used && sl.last_stream == stream) sl.pinned = false;
+            if (sl.used && sl.last_stream == stream.get()) sl.pinned = false;
     }
     running.store(false, std::memory_order_release);
 }
@@ -304,7 +299,7 @@ static int traverse1_service(trx_scene *s, const trx_ray *ray, uint32_t sem, trx
     uint32_t seq = me.seq + 1u;
     if (seq == 0u) seq = 1u;
     me.seq = seq;
-    uint32_t *slot = v->ring + (size_t)k * kSvcSlotWords;
+    uint32_t *slot = v->ring.get() + (size_t)k * kSvcSlotWords;
     const float tmax = ray->tmax;
     // three 16-byte stores, each whole on its own (the kernel takes the request once all three carry `seq`)
     auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return i; };

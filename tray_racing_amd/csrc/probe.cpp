@@ -77,14 +77,14 @@ extern "C" int trx_debug_copy_rate(int device, uint64_t bytes, uint32_t reps, do
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return fail(TRX_ERR_NO_DEVICE, "no HIP device %d", device);
     HIP_TRY(hipSetDevice(device));
-    float4 *src = nullptr, *dst = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&src, bytes);
-    if (e == hipSuccess) e = hipMalloc(&dst, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(src, 1, bytes, nullptr);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
     const size_t n = bytes / sizeof(float4);
+    DevBuf<float4> src, dst;
+    Event e0, e1;
+    hipError_t e = src.alloc(n);
+    if (e == hipSuccess) e = dst.alloc(n);
+    if (e == hipSuccess) e = hipMemsetAsync(src.get(), 1, bytes, nullptr);
+    if (e == hipSuccess) e = e0.create();
+    if (e == hipSuccess) e = e1.create();
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
     float best = 0.0f;
@@ -96,24 +96,20 @@ extern "C" int trx_debug_copy_rate(int device, uint64_t bytes, uint32_t reps, do
             for (int per_cu = 8; per_cu <= 32 && e == hipSuccess; per_cu *= 2) { // (2 048 .. 8 192 lanes per CU in flight)
                 const int blocks = prop.multiProcessorCount * per_cu;
                 for (uint32_t rep = 0; rep < reps + 1u && e == hipSuccess; rep++) { // (one warm-up pass per shape)
-                    e = hipEventRecord(e0, nullptr);
+                    e = hipEventRecord(e0.get(), nullptr);
                     if (e == hipSuccess) {
-                        hipLaunchKernelGGL(shapes[shape], dim3(blocks), dim3(256), 0, nullptr, src, dst, n);
+                        hipLaunchKernelGGL(shapes[shape], dim3(blocks), dim3(256), 0, nullptr, src.get(), dst.get(), n);
                         e = hipGetLastError();
                     }
-                    if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-                    if (e == hipSuccess) e = hipEventSynchronize(e1);
+                    if (e == hipSuccess) e = hipEventRecord(e1.get(), nullptr);
+                    if (e == hipSuccess) e = hipEventSynchronize(e1.get());
                     float ms = 0.0f;
-                    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+                    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0.get(), e1.get());
                     if (e == hipSuccess && rep >= 1u && (best == 0.0f || ms < best)) best = ms;
                 }
             }
         }
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (src) (void)hipFree(src);
-    if (dst) (void)hipFree(dst);
     if (e != hipSuccess || best <= 0.0f) return fail(e == hipErrorOutOfMemory ? TRX_ERR_OOM : TRX_ERR_NO_DEVICE, "copy probe failed: %s", hipGetErrorString(e));
     *out_bytes_per_s = 2.0 * (double)bytes / (best * 1e-3); // read + written
     return TRX_OK;
@@ -127,24 +123,23 @@ extern "C" int trx_debug_fetch_rate(trx_scene *s, uint32_t steps, uint32_t tris_
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the scene's event pair
     HIP_TRY(hipSetDevice(s->device));
     const int waves = s->grid > 0 ? s->grid : 4096, blocks = (waves + 1) / 2;
-    uint32_t *sink = nullptr;
-    HIP_TRY(hipMalloc(&sink, (size_t)blocks * 2 * kWave * sizeof(uint32_t)));
+    DevBuf<uint32_t> sink;
+    HIP_TRY(sink.alloc((size_t)blocks * 2 * kWave));
     float best = 0.0f;
     hipError_t e = hipSuccess;
     for (int rep = 0; rep < 3 && e == hipSuccess; rep++) { // (the first repetition warms clocks and caches)
-        e = hipEventRecord(s->ev0, nullptr);
+        e = hipEventRecord(s->ev0.get(), nullptr);
         if (e == hipSuccess) {
-            k_fetch_probe<<<blocks, 2 * kWave, 2 * kLdsBytesPerWave, nullptr>>>(s->d_nodes, (uint32_t)s->n_nodes, s->d_tris, (uint32_t)s->n_tris,
-                                                                                 steps, tris_per_node_x256, sink);
+            k_fetch_probe<<<blocks, 2 * kWave, 2 * kLdsBytesPerWave, nullptr>>>(s->nodes.get(), (uint32_t)s->n_nodes, s->tris.get(),
+                                                                                 (uint32_t)s->n_tris, steps, tris_per_node_x256, sink.get());
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipEventRecord(s->ev1, nullptr);
-        if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
+        if (e == hipSuccess) e = hipEventRecord(s->ev1.get(), nullptr);
+        if (e == hipSuccess) e = hipEventSynchronize(s->ev1.get());
         float ms = 0.0f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0, s->ev1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get());
         if (e == hipSuccess && rep > 0 && (best == 0.0f || ms < best)) best = ms;
     }
-    (void)hipFree(sink);
     if (e != hipSuccess || best <= 0.0f) return fail(TRX_ERR_NO_DEVICE, "fetch probe failed: %s", hipGetErrorString(e));
     const double lanes = (double)blocks * 2 * kWave, secs = best * 1e-3;
     *out_nodes_per_s = lanes * steps / secs;
