@@ -89,6 +89,7 @@ def load():
         "orc_brute_primary": (None, [P, u64, VP, u32, u32, u32, i, P]),
         "orc_validate": (i, [SP, P, P, C.c_char_p, i]),
         "orc_count_primary_per_ray": (None, [SP, VP, u32, u32, u32, i, P, P]),
+        "orc_footprint_primary": (None, [SP, VP, u32, u32, u32, i, P, P]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -219,6 +220,18 @@ class Scene:
         nt = np.zeros(w * h, dtype=np.uint16)
         load().orc_count_primary_per_ray(C.byref(self.c), C.byref(view), w, h, sem, threads, _ptr(nn), _ptr(nt))
         return nn, nt
+
+    def footprint_marks(self, view, w, h, sem=SEM_HLSL, threads=0):
+        """(node marks, triangle marks) of a primary frame: a byte per node / triangle, 1 where a walk visited / tested it."""
+        nm = np.zeros(self.nodes.shape[0], dtype=np.uint8)
+        tm = np.zeros(max(self.tris.shape[0], 1), dtype=np.uint8)
+        load().orc_footprint_primary(C.byref(self.c), C.byref(view), w, h, sem, threads, _ptr(nm), _ptr(tm))
+        return nm, tm[: self.tris.shape[0]]
+
+    def footprint(self, view, w, h, sem=SEM_HLSL, threads=0):
+        """(n_nodes_touched, n_tris_touched): distinct nodes visited and distinct triangles tested by a primary frame."""
+        nm, tm = self.footprint_marks(view, w, h, sem, threads)
+        return int(np.count_nonzero(nm)), int(np.count_nonzero(tm))
 
     def render_frame(self, view, w, h, sem=SEM_HLSL, frame=0, ao_eps=0.01, threads=0):
         return load().orc_render_frame(C.byref(self.c), C.byref(view), w, h, sem, frame, ao_eps, threads, None)

@@ -569,7 +569,8 @@ orc_hit orc_traverse(const orc_scene *s, const float o[3], const float d_in[3], 
  * inlined into the loop (orc_set_simd).  Everything but the node test is the same scalar code in both. */
 static inline __attribute__((always_inline)) orc_hit traverse_body(const orc_scene *s, const float o_in[3], const float d_in[3],
                                                                    float tmin, float tmax, uint32_t sem, orc_stats *st,
-                                                                   uint32_t *inst_out, const int simd) {
+                                                                   uint32_t *inst_out, uint8_t *node_marks, uint8_t *tri_marks,
+                                                                   const int simd) {
     float o[3] = {o_in[0], o_in[1], o_in[2]}, d[3], inv_d[3];
     for (int k = 0; k < 3; k++) { /* :334 zero-direction fix, seen by node AND triangle tests */
         d[k] = d_in[k] == 0.0f ? F32_EPSILON : d_in[k];
@@ -610,6 +611,7 @@ static inline __attribute__((always_inline)) orc_hit traverse_body(const orc_sce
             const uint32_t *node = s->nodes + 20 * (uint64_t)(bvh_offset + child_node_index);
             n_node++;
             n_tlas_node += tlas && tlas_stack_size == INVALID;
+            if (node_marks) node_marks[bvh_offset + child_node_index] = 1; /* (orc_footprint_primary) */
 #ifdef ORC_HAVE_AVX2
             uint32_t hitmask = simd ? node_intersect_avx2(o, d, inv_d, oct_inv4, t, node, sem)
                                     : node_intersect_scalar(o, d, inv_d, oct_inv4, t, node, sem);
@@ -657,6 +659,7 @@ static inline __attribute__((always_inline)) orc_hit traverse_body(const orc_sce
                 break;
             }
             n_tri++;
+            if (tri_marks) tri_marks[global] = 1;
             if (orc_intersect_tri(o, d, s->tris + 9 * (uint64_t)global, tmin, &t, sem)) {
                 prim = global;
                 hit_inst = cur_inst;
@@ -706,23 +709,30 @@ static inline __attribute__((always_inline)) orc_hit traverse_body(const orc_sce
 }
 
 static orc_hit traverse_scalar(const orc_scene *s, const float o[3], const float d[3], float tmin, float tmax, uint32_t sem,
-                               orc_stats *st, uint32_t *inst_out) {
-    return traverse_body(s, o, d, tmin, tmax, sem, st, inst_out, 0);
+                               orc_stats *st, uint32_t *inst_out, uint8_t *node_marks, uint8_t *tri_marks) {
+    return traverse_body(s, o, d, tmin, tmax, sem, st, inst_out, node_marks, tri_marks, 0);
 }
 #ifdef ORC_HAVE_AVX2
 __attribute__((target("avx2,fma"))) static orc_hit traverse_avx2(const orc_scene *s, const float o[3], const float d[3],
                                                                  float tmin, float tmax, uint32_t sem, orc_stats *st,
-                                                                 uint32_t *inst_out) {
-    return traverse_body(s, o, d, tmin, tmax, sem, st, inst_out, 1);
+                                                                 uint32_t *inst_out, uint8_t *node_marks, uint8_t *tri_marks) {
+    return traverse_body(s, o, d, tmin, tmax, sem, st, inst_out, node_marks, tri_marks, 1);
 }
 #endif
 
+/* the walk with all its optional outputs: statistics, the hit's instance, and (orc_footprint_primary) a byte set per
+ * node where a node visit is counted and per triangle where a triangle test is counted */
+static orc_hit traverse_marked(const orc_scene *s, const float o[3], const float d[3], float tmin, float tmax, uint32_t sem,
+                               orc_stats *st, uint32_t *inst_out, uint8_t *node_marks, uint8_t *tri_marks) {
+#ifdef ORC_HAVE_AVX2
+    if (g_simd) return traverse_avx2(s, o, d, tmin, tmax, sem, st, inst_out, node_marks, tri_marks);
+#endif
+    return traverse_scalar(s, o, d, tmin, tmax, sem, st, inst_out, node_marks, tri_marks);
+}
+
 orc_hit orc_traverse_inst(const orc_scene *s, const float o[3], const float d[3], float tmin, float tmax, uint32_t sem,
                           orc_stats *st, uint32_t *inst_out) {
-#ifdef ORC_HAVE_AVX2
-    if (g_simd) return traverse_avx2(s, o, d, tmin, tmax, sem, st, inst_out);
-#endif
-    return traverse_scalar(s, o, d, tmin, tmax, sem, st, inst_out);
+    return traverse_marked(s, o, d, tmin, tmax, sem, st, inst_out, NULL, NULL);
 }
 
 /* ---- frames ----------------------------------------------------------------------- */
@@ -1104,5 +1114,21 @@ void orc_count_primary_per_ray(const orc_scene *s, const orc_view *view, uint32_
         orc_traverse(s, o, d, 0.0f, F32_MAX, sem, &st);
         n_node[i] = (uint16_t)(st.n_node > 65535 ? 65535 : st.n_node);
         n_tri[i] = (uint16_t)(st.n_tri > 65535 ? 65535 : st.n_tri);
+    }
+}
+
+/* the compulsory footprint of a primary frame: node_marks[i] = 1 for every node the frame's walks visit (n_nodes bytes,
+ * absolute node indices: both levels of a two-level scene), tri_marks[i] = 1 for every triangle they test (n_tris
+ * bytes).  The walk is orc_trace_primary's, and a mark is set exactly where it counts n_node / n_tri.  The caller
+ * clears the arrays; every thread stores the same value 1, so stores that race are harmless. */
+void orc_footprint_primary(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t sem, int threads,
+                           uint8_t *node_marks, uint8_t *tri_marks) {
+    threads = pick_threads(threads);
+    const int64_t n = (int64_t)w * h;
+#pragma omp parallel for schedule(dynamic, 256) num_threads(threads)
+    for (int64_t i = 0; i < n; i++) {
+        float o[3], d[3];
+        orc_primary_ray(view, w, h, (uint32_t)(i % w), (uint32_t)(i / w), o, d);
+        traverse_marked(s, o, d, 0.0f, F32_MAX, sem, NULL, NULL, node_marks, tri_marks);
     }
 }

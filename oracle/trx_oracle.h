@@ -157,6 +157,11 @@ double orc_render_frame(const orc_scene *s, const orc_view *view, uint32_t w, ui
 void orc_count_primary_per_ray(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t sem,
                                int threads, uint16_t *n_node, uint16_t *n_tri);
 
+/* distinct nodes visited / triangles tested by a primary frame: a byte of node_marks (n_nodes) / tri_marks (n_tris) is
+ * set to 1 where orc_trace_primary's walk counts a node visit / a triangle test; the caller clears the arrays */
+void orc_footprint_primary(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t sem, int threads,
+                           uint8_t *node_marks, uint8_t *tri_marks);
+
 /* BVH-independent ground truth: every ray against every triangle in index
  * order with the same triangle test and tie rule. */
 void orc_brute_rays(const float *tris9, uint64_t n_tris, const orc_ray *rays, uint64_t n, uint32_t sem,

@@ -1,0 +1,584 @@
+"""The counting kernels (k_trace<..., COUNT = true>: trx_count_primary / trx_count_ao / trx_count_rays, trx_debug_footprint,
+trx_debug_tri_histogram) against the oracle's counters.
+
+They are code objects of their own - no packet cull, no wave-uniform walk, no thin waves, no ray merge, counters and
+touch marks added - and their numbers are published (bench.py --full: nodes_per_ray, tris_per_ray, fetch_vs_random,
+roofline.compulsory_bytes; tools/gpu_cullhist.py).  Bar: exact integer equality for counters, bit equality for the hit
+records a counting pass writes.  No tolerance anywhere.  Run with `-m gpu` on an MI355X.
+
+Every case asserts, in the oracle's own output, that its input is not degenerate (enough primary hits, AO passes with
+hits and misses, ray batches that hit and miss, re-braided or not as the case says, frames that do not touch the whole tree).
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from helpers import ALL_SEMS, F32_MAX, aimed_rays, assert_hits_equal, deep_chain_scene, golden_inputs, instanced_scene, random_rays
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MISS = 0xFFFFFFFF
+REBRAID_DEFAULT = 1.0 / 4096.0
+SLACK = 37   # records past the end of an output buffer: must stay as they were
+# the incoherent single-level passes take the pipelined walk (trace_walk_pipe.inc) only over scenes larger than this
+# (api_launch.cpp, TRX_PIPE_MIN_BYTES; 80-byte nodes, 48-byte device triangles): the hairball-class cases are built past
+# it, so both walks' counting kernels are under test
+PIPE_MIN_BYTES = 32 << 20
+HAIRBALL_TRIS = 700000
+
+
+@pytest.fixture(scope="module", autouse=True)
+def need_gpu(trx):
+    lib = trx.load()  # raises if libtrx.so is missing: the HIP extension is mandatory here
+    assert lib.trx_device_count() > 0, "no HIP device visible to libtrx.so"
+    buf = C.create_string_buffer(64)
+    lib.trx_device_name(0, buf, 64)
+    assert buf.value.startswith(b"gfx950"), buf.value
+
+
+def six(st):
+    """The fields trx_stats and orc_stats share."""
+    return (int(st.n_rays), int(st.n_node), int(st.n_tri), int(st.n_hits), int(st.max_stack), int(st.overflow))
+
+
+def check_wave(st, what, one_ray=False):
+    """trx_stats.n_wave_node / n_wave_tri: bounds that hold by construction (no oracle value exists: both depend on which
+    rays share a wave).
+
+    * ceil(n_node / 64) <= n_wave_node <= n_node.  Both walks (trace_walk_plain.inc, trace_walk_pipe.inc) count a node
+      step as `c_node++; if (lane_rank(__ballot(1)) == 0) c_wnode++;` inside the branch the stepping lanes take: every
+      execution of that branch adds one to n_wave_node (its first active lane) and between 1 and 64 to n_node.
+    * ceil(n_tri / 64) <= n_wave_tri <= n_tri, hence n_wave_tri > 0 exactly when n_tri > 0.  Per-lane rounds
+      (trace_triangles.inc) count `c_tri++; if (lane_rank(__ballot(1)) == 0) c_wtri++;` under `have[k]`: one wave-level
+      test for 1..64 lane-level ones.  Cooperative rounds add `cnt` to every owner's c_tri (the wave's `total` pairs) and
+      one to lane 0's c_wtri per window of 64 pairs: ceil(total / 64) windows, at least one (total >= 1 in a phase that
+      runs), at most total.
+    * one ray: n_wave_node == n_node (the only active lane leads every step).  For n_wave_tri the code fixes a range, not
+      a value: a per-lane phase adds 1 per test, but a single lane's triangle group can also go cooperative (cnt >=
+      tri_compact_min and ceil(cnt / kBatch) > tri_coop_ratio x 1 window), which adds 1 for the whole group; a group is
+      at most 24 triangles (the 24-bit triangle mask of a node), so ceil(n_tri / 24) <= n_wave_tri <= n_tri."""
+    n_node, n_tri, wn, wt = int(st.n_node), int(st.n_tri), int(st.n_wave_node), int(st.n_wave_tri)
+    assert (n_node + 63) // 64 <= wn <= n_node, "%s: n_wave_node %d, n_node %d" % (what, wn, n_node)
+    assert (n_tri + 63) // 64 <= wt <= n_tri, "%s: n_wave_tri %d, n_tri %d" % (what, wt, n_tri)
+    assert (wt > 0) == (n_tri > 0), what
+    if one_ray:
+        assert wn == n_node, "%s: one ray, n_wave_node %d != n_node %d" % (what, wn, n_node)
+        assert (n_tri + 23) // 24 <= wt <= n_tri, "%s: one ray, n_wave_tri %d, n_tri %d" % (what, wt, n_tri)
+
+
+def scene_verts(trx, name, n):
+    """(vertices, object counts, camera name).  `kitchen_open` is the kitchen-class stand-in without its ceiling: the room
+    is closed, so from the inside every AO ray of the plain scene hits something and an AO counter test would never see a
+    miss; with the ceiling off the camera still sees walls, floor and furniture in every pixel."""
+    if name != "kitchen_open":
+        verts, counts = trx.gen_scene(name, n, 1)
+        return verts, counts, name
+    verts, counts = trx.gen_scene("kitchen", n, 1)
+    y = verts.reshape(-1, 3, 3)[:, :, 1]
+    ceiling = y.min(1) >= y.max() - 1e-4
+    assert 0 < ceiling.sum() < 0.1 * verts.shape[0]
+    owner = np.repeat(np.arange(len(counts)), [int(c) for c in counts])
+    kept = np.bincount(owner[~ceiling], minlength=len(counts))
+    return verts[~ceiling], [int(c) for c in kept], "kitchen"
+
+
+def build_case(trx, orc, name, n, w, h, tlas=False, rebraid=None):
+    """(flat, view, oracle scene, oracle view).  rebraid: None = single-level; True = two-level, re-braided (the
+    default build); False = two-level, built with trx_set_build_rebraid(0)."""
+    lib = trx.load()
+    verts, counts, cam = scene_verts(trx, name, n)
+    try:
+        if tlas:
+            assert lib.trx_set_build_rebraid(REBRAID_DEFAULT if rebraid else 0.0) == 0
+        flat = trx.flat_build(verts, counts, use_tlas=tlas)
+    finally:
+        lib.trx_set_build_rebraid(REBRAID_DEFAULT)
+    if tlas:
+        assert flat.instance_offsets.size > 0
+        braided = flat.instance_entry is not None and bool((flat.instance_entry != 0).any())
+        assert braided == bool(rebraid), "%s: re-braided %s, wanted %s" % (name, braided, rebraid)
+    eye, look, fov = trx.scene_camera(cam)
+    view = trx.view_from_camera(eye, look, fov, w, h)
+    return flat, view, orc.Scene.from_flat(flat), orc.view_from_bytes(view)
+
+
+def assert_past_pipe_threshold(flat):
+    assert flat.n_nodes * 80 + flat.n_tris * 48 > PIPE_MIN_BYTES, "the hairball-class scene no longer reaches the pipelined walk"
+
+
+def mixed_rays(trx, flat, n, seed, tri_verts=None):
+    """n rays: a third aimed at random triangles (they hit), the rest random_rays(zero_dirs=True) - ranged rays, zero
+    direction components, axis-parallel rays.  A one-ray batch is an aimed ray."""
+    tv = flat.tri_verts if tri_verts is None else tri_verts
+    n_aimed = (n + 2) // 3
+    parts = [aimed_rays(trx, tv, n_aimed, seed + 1)]
+    if n - n_aimed:
+        parts.append(random_rays(trx, type("W", (), {"tri_verts": tv}), n - n_aimed, seed, zero_dirs=True))
+    rays = np.concatenate(parts)
+    assert rays.shape[0] == n
+    return rays
+
+
+def to_device(rays):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(rays).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def filled(n, value=-1):
+    import torch
+    return torch.full((n,), value, dtype=torch.int64, device="cuda")
+
+
+def miss_record():
+    return int(np.array([0x7F800000 | (MISS << 32)], dtype=np.uint64).view(np.int64)[0])
+
+
+# ---- (a) the AO counting pass ------------------------------------------------------------------------------------
+
+AO_CASES = [("cornell", 0, 33, 47, False, None),            # 30 tiles (not a multiple of eight), ends mid-tile both ways
+            ("cornell", 0, 9, 9, False, None),              # 4 tiles for 81 pixels
+            ("kitchen_open", 20000, 72, 48, False, None),
+            ("hairball", HAIRBALL_TRIS, 64, 64, False, None),
+            ("san_miguel", 120000, 72, 48, True, True),
+            ("san_miguel", 60000, 64, 40, True, False)]
+
+
+@pytest.mark.parametrize("name,n,w,h,tlas,rebraid", AO_CASES)
+def test_ao_counting_pass_equals_the_oracle(trx, orc, name, n, w, h, tlas, rebraid):
+    """trx_count_ao over the device primary buffer trx_trace_primary_dev wrote, all eight semantics words, both AO
+    epsilons, two frame seeds: the six counters are the oracle's trace_ao stats, n_rays is the number of primary hits
+    (what bench.py divides by), the records are the oracle's and - element for element, slack included - what
+    trx_trace_ao_dev writes for the same arguments."""
+    import torch
+    from tray_racing_amd import dist as D
+    flat, view, osc, ov = build_case(trx, orc, name, n, w, h, tlas, rebraid)
+    if name == "hairball":
+        assert_past_pipe_threshold(flat)
+    sc = trx.Scene(flat)
+    npx = w * h
+    try:
+        d_prim, d_ao, d_ref = filled(npx), filled(npx + SLACK), filled(npx + SLACK)
+        for sem in ALL_SEMS:
+            op, pst = osc.trace_primary(ov, w, h, sem=sem)
+            assert pst.n_hits >= 0.25 * npx, "%s sem %d: %d primary hits of %d pixels" % (name, sem, pst.n_hits, npx)
+            d_prim.fill_(-1)
+            sc.trace_primary_dev(view, w, h, d_prim.data_ptr(), sem=sem)
+            torch.cuda.synchronize()
+            gp = D.int64_to_hits(d_prim)
+            assert_hits_equal(gp, op, "%s sem %d primary" % (name, sem))
+            n_primary_hits = int((gp["prim"] != MISS).sum())
+            for eps in (0.01, 0.0001):
+                for frame in (0, 5):
+                    what = "%s %dx%d sem %d eps %g frame %d" % (name, w, h, sem, eps, frame)
+                    want, ost = osc.trace_ao(ov, w, h, op, sem=sem, frame=frame, ao_eps=eps)
+                    assert 0 < ost.n_hits < ost.n_rays, "%s: AO pass without both hits and misses" % what
+                    d_ao.fill_(-1)
+                    st = sc.count_ao(view, w, h, d_prim.data_ptr(), d_ao.data_ptr(), sem=sem, frame=frame, ao_eps=eps)
+                    print(what, "gpu", six(st), "oracle", six(ost), "wave", st.n_wave_node, st.n_wave_tri)
+                    assert six(st) == six(ost), what
+                    assert st.n_rays == n_primary_hits, what
+                    assert_hits_equal(D.int64_to_hits(d_ao[:npx]), want, what)
+                    assert bool((d_ao[npx:] == -1).all()), what
+                    d_ref.fill_(-1)
+                    sc.trace_ao_dev(view, w, h, d_prim.data_ptr(), d_ref.data_ptr(), sem=sem, frame=frame, ao_eps=eps)
+                    torch.cuda.synchronize()
+                    assert torch.equal(d_ao, d_ref), what
+                    check_wave(st, what)
+        sc.check()
+    finally:
+        sc.close()
+
+
+# ---- (b) AO counting over tile shards, and over a frame of misses ----------------------------------------------
+
+def test_ao_counting_over_tile_shards(trx, orc):
+    """1, 2, 3 and 8 tile shards in both layouts: every rank's counters are the oracle's for that shard, their sums (the
+    maximum for max_stack) the whole image's, the records the oracle's where the rank owns the pixel and untouched
+    everywhere else (other ranks' pixels in image layout, padding records in shard layout, slack); the shard-layout
+    records, de-interleaved by FrameGather.assemble, are the oracle's frame.  An AO pass over a primary buffer of
+    misses counts nothing and writes a miss for every record it owns."""
+    import torch
+    from tray_racing_amd import dist as D
+    w, h, sem, frame, eps = 100, 52, 3, 2, 0.01             # 13 x 7 = 91 tiles, the last tile column ends mid-tile
+    flat, view, osc, ov = build_case(trx, orc, "kitchen_open", 20000, w, h)
+    npx = w * h
+    op, pst = osc.trace_primary(ov, w, h, sem=sem)
+    want, ost = osc.trace_ao(ov, w, h, op, sem=sem, frame=frame, ao_eps=eps)
+    assert pst.n_hits >= 0.25 * npx and 0 < ost.n_hits < ost.n_rays
+    sc = trx.Scene(flat)
+    try:
+        d_prim = filled(npx)
+        sc.trace_primary_dev(view, w, h, d_prim.data_ptr(), sem=sem)
+        torch.cuda.synchronize()
+        assert_hits_equal(D.int64_to_hits(d_prim), op, "primary")
+        for world in (1, 2, 3, 8):
+            pix = D.pixel_index_of_records(w, h, world).numpy()           # [world, records]: pixel of every record, -1 = padding
+            for layout in (0, 1):
+                total, deepest, gathered = np.zeros(4, dtype=np.int64), 0, []
+                for r in range(world):
+                    what = "%d shards, layout %d, rank %d" % (world, layout, r)
+                    _, ost_r = osc.trace_ao(ov, w, h, op, sem=sem, frame=frame, ao_eps=eps, shard=(r, world))
+                    owned = pix[r][pix[r] >= 0]
+                    if layout == 0:
+                        out = filled(npx + SLACK)
+                        st = sc.count_ao(view, w, h, d_prim.data_ptr(), out.data_ptr(), sem=sem, frame=frame, ao_eps=eps,
+                                         shard=(r, world, 0))
+                        raw = out.cpu().numpy()
+                        mine = np.zeros(npx + SLACK, dtype=bool)
+                        mine[owned] = True
+                        assert_hits_equal(D.int64_to_hits(out[:npx])[owned], want[owned], what)
+                        assert (raw[~mine] == -1).all(), what + ": wrote a record of another rank or past the buffer"
+                    else:
+                        fg = D.FrameGather(w, h, r, world, "cuda")
+                        lp = fg.new_local()
+                        sc.trace_primary_dev(view, w, h, lp.data_ptr(), sem=sem, shard=(r, world, 1))
+                        out = filled(fg.records + SLACK)
+                        st = sc.count_ao(view, w, h, lp.data_ptr(), out.data_ptr(), sem=sem, frame=frame, ao_eps=eps,
+                                         shard=(r, world, 1))
+                        raw = out.cpu().numpy()
+                        assert pix[r].size == fg.records
+                        assert (raw[:fg.records][pix[r] < 0] == -1).all() and (raw[fg.records:] == -1).all(), what
+                        assert_hits_equal(D.int64_to_hits(out[:fg.records])[pix[r] >= 0], want[owned], what)
+                        gathered.append(out[:fg.records])
+                    print(what, "gpu", six(st), "oracle", six(ost_r))
+                    assert six(st) == six(ost_r), what
+                    check_wave(st, what)
+                    total += np.array(six(st)[:4], dtype=np.int64)
+                    deepest = max(deepest, int(st.max_stack))
+                assert tuple(total) == six(ost)[:4] and deepest == ost.max_stack, "%d shards, layout %d" % (world, layout)
+                if layout == 1:
+                    fg.gathered.copy_(torch.stack(gathered))
+                    assert_hits_equal(D.int64_to_hits(fg.assemble()), want, "%d shards assembled" % world)
+        # all-miss primary buffer: nothing is traced, every owned record becomes a miss
+        no_hits = np.zeros(npx, dtype=orc.HIT_DTYPE)
+        no_hits["t"], no_hits["prim"] = np.inf, MISS
+        _, ost0 = osc.trace_ao(ov, w, h, no_hits, sem=sem, frame=frame, ao_eps=eps)
+        assert six(ost0) == (0, 0, 0, 0, 0, 0)
+        d_miss, out = filled(npx, miss_record()), filled(npx + SLACK)
+        st = sc.count_ao(view, w, h, d_miss.data_ptr(), out.data_ptr(), sem=sem, frame=frame, ao_eps=eps)
+        assert six(st) == (0, 0, 0, 0, 0, 0) and (st.n_wave_node, st.n_wave_tri) == (0, 0)
+        assert bool((out[:npx] == miss_record()).all()) and bool((out[npx:] == -1).all())
+        world, r = 3, 1
+        pix = D.pixel_index_of_records(w, h, world).numpy()[r]
+        out = filled(pix.size + SLACK)
+        st = sc.count_ao(view, w, h, d_miss.data_ptr(), out.data_ptr(), sem=sem, frame=frame, ao_eps=eps, shard=(r, world, 1))
+        raw = out.cpu().numpy()
+        assert six(st) == (0, 0, 0, 0, 0, 0)
+        assert (raw[:pix.size][pix >= 0] == miss_record()).all() and (raw[:pix.size][pix < 0] == -1).all() and (raw[pix.size:] == -1).all()
+        # and the counters of the pass after it are that pass's own
+        out = filled(npx + SLACK)
+        st = sc.count_ao(view, w, h, d_prim.data_ptr(), out.data_ptr(), sem=sem, frame=frame, ao_eps=eps)
+        assert six(st) == six(ost)
+        sc.check()
+    finally:
+        sc.close()
+
+
+# ---- (c) the explicit-ray counting pass ------------------------------------------------------------------------------
+
+RAY_SIZES = (1, 2, 7, 8, 9, 63, 64, 65, 100, 5000, 300000)
+RAY_CASES = [("cornell", 0, False), ("kitchen", 20000, False), ("hairball", HAIRBALL_TRIS, False), ("san_miguel", 120000, True),
+             ("instanced", 0, True)]
+
+
+@pytest.mark.parametrize("name,n_tris,tlas", RAY_CASES)
+def test_ray_counting_pass_equals_the_oracle(trx, orc, name, n_tris, tlas):
+    """trx_count_rays, all eight semantics words, batches of 1 ... 300 000 rays (ranged rays, zero direction components,
+    axis-parallel rays, aimed rays) over single-level scenes (one past the pipelined walk's size threshold), a
+    re-braided two-level scene and transformed instances: the six counters and the records are the oracle's, and the
+    counters are the same when the records go to the scene's scratch buffer (d_hits == NULL)."""
+    if name == "instanced":
+        flat, _o2w, world, _first, _blas = instanced_scene(trx)
+        sc = trx.Scene(flat)
+        osc = orc.Scene(flat.nodes, flat.tri_verts, flat.instance_offsets, flat.tlas_start,
+                        instance_w2o=sc.instance_world_to_object())
+        tri_verts = world
+
+        def oracle(rays, sem):
+            hits, _inst, st = osc.trace_rays_inst(rays, sem=sem)
+            return hits, st
+    else:
+        flat, _view, osc, _ov = build_case(trx, orc, name, n_tris, 32, 32, tlas, True if tlas else None)
+        sc = trx.Scene(flat)
+        tri_verts = None
+
+        def oracle(rays, sem):
+            return osc.trace_rays(rays, sem=sem)
+    if name == "hairball":
+        assert_past_pipe_threshold(flat)
+    from tray_racing_amd import dist as D
+    try:
+        for n in RAY_SIZES:
+            rays = mixed_rays(trx, flat, n, 4000 + n, tri_verts)
+            d_rays, d_hits = to_device(rays), filled(n + SLACK)
+            for sem in ALL_SEMS:
+                what = "%s %d rays sem %d" % (name, n, sem)
+                want, ost = oracle(rays, sem)
+                if n >= 5000:
+                    assert 0.02 < ost.n_hits / n < 0.99 and ost.n_tri > 0, "%s: hit fraction %.3f" % (what, ost.n_hits / n)
+                if n == 1:
+                    assert ost.n_node > 1 and ost.n_tri > 0, what + ": the one ray walks nothing"
+                d_hits.fill_(-1)
+                st = sc.count_rays(d_rays.data_ptr(), n, d_hits.data_ptr(), sem=sem)
+                if n >= 5000 or n == 1:
+                    print(what, "gpu", six(st), "oracle", six(ost), "wave", st.n_wave_node, st.n_wave_tri)
+                assert six(st) == six(ost), what
+                assert_hits_equal(D.int64_to_hits(d_hits[:n]), want, what)
+                assert bool((d_hits[n:] == -1).all()), what
+                check_wave(st, what, one_ray=n == 1)
+                st0 = sc.count_rays(d_rays.data_ptr(), n, 0, sem=sem)
+                assert six(st0) == six(ost), what + ", records into the scratch buffer"
+                check_wave(st0, what + " (scratch)", one_ray=n == 1)
+        sc.check()
+    finally:
+        sc.close()
+
+
+def test_ray_counting_pass_on_exact_ties(trx, orc):
+    """tests/golden/ties_rays.npz (exact ties, zero direction components) under semantics 0 and 3: the counting pass
+    writes the golden records and counts what the oracle counts over the golden's own nodes and triangles - the two tie
+    rules walk the tree differently, and their counters differ."""
+    from tray_racing_amd import dist as D
+    g = np.load(os.path.join(GOLDEN, "ties_rays.npz"))
+    nodes, tri_verts, inst, tlas_start = golden_inputs(trx, g)
+    flat = trx.FlatScene(nodes, tri_verts, inst, tlas_start, np.arange(tri_verts.shape[0]), [0, tri_verts.shape[0]])
+    osc = orc.Scene(nodes, tri_verts, inst, tlas_start)
+    rays = np.ascontiguousarray(g["rays"])
+    n = rays.shape[0]
+    sc = trx.Scene(flat)
+    try:
+        d_rays, d_hits = to_device(rays), filled(n + SLACK)
+        for sem in (0, 3):
+            want, ost = osc.trace_rays(rays, sem=sem)
+            assert_hits_equal(want, g["orc_rays_sem%d" % sem], "the oracle against its golden, sem %d" % sem)
+            assert ost.n_tri > 0 and 0 < ost.n_hits
+            d_hits.fill_(-1)
+            st = sc.count_rays(d_rays.data_ptr(), n, d_hits.data_ptr(), sem=sem)
+            print("ties sem %d" % sem, "gpu", six(st), "oracle", six(ost))
+            assert six(st) == six(ost), "ties sem %d" % sem
+            assert_hits_equal(D.int64_to_hits(d_hits[:n]), g["orc_rays_sem%d" % sem], "ties sem %d" % sem)
+            assert bool((d_hits[n:] == -1).all())
+            check_wave(st, "ties sem %d" % sem)
+        sc.check()
+    finally:
+        sc.close()
+
+
+# ---- (d) stack depth and overflow ---------------------------------------------------------------------------------------
+
+def test_stack_depth_and_overflow_through_the_counting_path(trx, orc):
+    """deep_chain_scene with the 70 mixed-direction rays of test_stack_spill_to_hbm_and_overflow_detection: max_stack is the
+    oracle's (depth - 1) across the 12-entry LDS part into the HBM spill.  At depth 70 the counting call returns
+    TRX_ERR_STACK_OVERFLOW with trx_stats.overflow = the oracle's number of overflowed rays; finish_count has zeroed the
+    slot's counters before it returns the error, so the next counting call - one ray that does not overflow - succeeds
+    with that ray's counters alone, and trx_scene_check is clean."""
+    from tray_racing_amd import _lib as L
+    from tray_racing_amd import dist as D
+    lib = trx.load()
+    rays = np.zeros(70, dtype=trx.RAY_DTYPE)
+    rays["origin"] = (0.3, 0.3, 1)
+    rays["direction"] = (0, 0, -1)
+    rays["origin"][1::2] = (0.3, 0.3, -100)   # half the wave looks the other way: mixed stack depths
+    rays["direction"][1::2] = (0, 0, 1)
+    rays["tmax"] = F32_MAX
+    d_rays = to_device(rays)
+    for depth in (10, 13, 40, 64):
+        nodes, tris = deep_chain_scene(depth)
+        osc = orc.Scene(nodes, tris)
+        want, ost = osc.trace_rays(rays, sem=0)
+        assert ost.overflow == 0 and ost.max_stack == depth - 1
+        sc = trx.Scene(trx.FlatScene(nodes, tris, [], 0, np.arange(depth), [0, depth]))
+        try:
+            d_hits = filled(70 + SLACK)
+            st = sc.count_rays(d_rays.data_ptr(), 70, d_hits.data_ptr(), sem=0)
+            print("depth %d" % depth, "gpu", six(st), "oracle", six(ost))
+            assert st.max_stack == ost.max_stack
+            assert six(st) == six(ost), "depth %d" % depth
+            assert_hits_equal(D.int64_to_hits(d_hits[:70]), want, "depth %d" % depth)
+            check_wave(st, "depth %d" % depth)
+            sc.check()
+        finally:
+            sc.close()
+    nodes, tris = deep_chain_scene(70)
+    osc = orc.Scene(nodes, tris)
+    _, ost = osc.trace_rays(rays, sem=0)
+    assert ost.overflow > 0
+    _, one = osc.trace_rays(rays[1:2], sem=0)
+    assert one.overflow == 0 and one.n_node > 1 and one.n_tri > 0
+    sc = trx.Scene(trx.FlatScene(nodes, tris, [], 0, np.arange(70), [0, 70]))
+    try:
+        d_hits = filled(70 + SLACK)
+        st = L.Stats()
+        rc = lib.trx_count_rays(sc.handle, C.c_void_p(d_rays.data_ptr()), 70, 0, C.c_void_p(d_hits.data_ptr()), C.byref(st))
+        print("depth 70: rc", rc, "gpu overflow", st.overflow, "oracle overflow", ost.overflow)
+        assert rc == L.TRX_ERR_STACK_OVERFLOW and b"overflowed" in lib.trx_last_error()
+        assert st.overflow == ost.overflow
+        assert bool((d_hits[70:] == -1).all())
+        d_one = to_device(rays[1:2])
+        st = sc.count_rays(d_one.data_ptr(), 1, d_hits.data_ptr(), sem=0)
+        assert six(st) == six(one)
+        check_wave(st, "the ray after the overflow", one_ray=True)
+        sc.check()
+    finally:
+        sc.close()
+
+
+# ---- (e) counters do not leak between calls ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,n,tlas", [("kitchen_open", 20000, False), ("san_miguel", 60000, True)])
+def test_counters_do_not_leak_between_calls(trx, orc, name, n, tlas):
+    """count_primary, count_ao, count_rays, a plain trace_rays, count_rays again, then the three counting calls in another
+    order with other arguments: every result is the oracle's for that call alone."""
+    import torch
+    w, h, sem = 64, 40, 3
+    flat, view, osc, ov = build_case(trx, orc, name, n, w, h, tlas, True if tlas else None)
+    npx = w * h
+    op, pst = osc.trace_primary(ov, w, h, sem=sem)
+    assert pst.n_hits >= 0.25 * npx
+    ao_stats = {}
+    for frame in (1, 6):
+        _, ao_stats[frame] = osc.trace_ao(ov, w, h, op, sem=sem, frame=frame, ao_eps=0.01)
+        assert 0 < ao_stats[frame].n_hits < ao_stats[frame].n_rays
+    batches = [mixed_rays(trx, flat, k, 90 + k) for k in (5000, 777, 64)]
+    ray_stats = [osc.trace_rays(b, sem=sem)[1] for b in batches]
+    assert 0.02 < ray_stats[0].n_hits / 5000 < 0.99 and ray_stats[0].n_tri > 0
+    assert len({six(s) for s in ray_stats} | {six(s) for s in ao_stats.values()} | {six(pst)}) == 6   # no two calls alike
+    sc = trx.Scene(flat)
+    try:
+        d_prim, d_ao = filled(npx), filled(npx)
+        sc.trace_primary_dev(view, w, h, d_prim.data_ptr(), sem=sem)
+        torch.cuda.synchronize()
+        d_batches = [to_device(b) for b in batches]
+        d_hits = filled(5000)
+
+        def primary():
+            st = sc.count_primary(view, w, h, sem=sem)
+            assert six(st) == six(pst), "count_primary"
+            check_wave(st, "count_primary")
+
+        def ao(frame):
+            st = sc.count_ao(view, w, h, d_prim.data_ptr(), d_ao.data_ptr(), sem=sem, frame=frame, ao_eps=0.01)
+            assert six(st) == six(ao_stats[frame]), "count_ao frame %d" % frame
+            check_wave(st, "count_ao")
+
+        def rays(k):
+            st = sc.count_rays(d_batches[k].data_ptr(), batches[k].shape[0], d_hits.data_ptr(), sem=sem)
+            assert six(st) == six(ray_stats[k]), "count_rays batch %d" % k
+            check_wave(st, "count_rays")
+
+        primary()
+        ao(1)
+        rays(0)
+        got, _ = sc.trace_rays(batches[1], sem=sem)
+        assert_hits_equal(got, osc.trace_rays(batches[1], sem=sem)[0], "plain trace between counting calls")
+        rays(2)
+        rays(1)
+        ao(6)
+        primary()
+        rays(0)
+        sc.check()
+    finally:
+        sc.close()
+
+
+# ---- (g) the footprint ------------------------------------------------------------------------------------------------
+
+FOOTPRINT_CASES = [("cornell", 0, False, ((64, 64), (33, 47))), ("kitchen", 20000, False, ((120, 72), (33, 47))),
+                   ("bistro", 150000, False, ((160, 90), (33, 47))), ("kitchen", 20000, True, ((72, 48), (9, 9)))]
+
+
+@pytest.mark.parametrize("name,n,tlas,sizes", FOOTPRINT_CASES)
+def test_footprint_equals_the_oracle(trx, orc, name, n, tlas, sizes):
+    """trx_debug_footprint (roofline.compulsory_bytes of bench.py --full) against orc_footprint_primary: the counting
+    kernel and the oracle visit the same nodes and test the same triangles, so the distinct sets have the same sizes.
+    Two-level scenes are accepted (absolute node indices, both levels)."""
+    for w, h in sizes:
+        flat, view, osc, ov = build_case(trx, orc, name, n, w, h, tlas, True if tlas else None)
+        sc = trx.Scene(flat)
+        try:
+            for sem in (0, 3):
+                what = "%s %dx%d sem %d" % (name, w, h, sem)
+                want = osc.footprint(ov, w, h, sem=sem)
+                _, ost = osc.trace_primary(ov, w, h, sem=sem)
+                assert 0 < want[0] <= ost.n_node and 0 < want[1] <= ost.n_tri
+                if name in ("kitchen", "bistro"):
+                    assert want[0] < flat.n_nodes, what + ": the frame touches the whole tree"
+                got = sc.footprint(view, w, h, sem=sem)
+                st = sc.count_primary(view, w, h, sem=sem)
+                print(what, "gpu", got, "oracle", want, "of", flat.n_nodes, flat.n_tris)
+                assert got == want, what
+                assert got[0] <= flat.n_nodes and got[1] <= flat.n_tris and got[0] <= st.n_node and got[1] <= st.n_tri
+                assert six(st) == six(ost), what + ": count_primary after the footprint pass"
+            sc.check()
+        finally:
+            sc.close()
+
+
+# ---- (h) the triangle histogram -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,n,tlas,w,h", [("cornell", 0, False, 96, 64), ("bistro", 60000, False, 160, 90),
+                                             ("san_miguel", 60000, True, 64, 40)])
+def test_triangle_histogram_is_consistent(trx, orc, name, n, tlas, w, h):
+    """trx_debug_tri_histogram: words 0..15 (largest per-lane count of a triangle phase) and 16..31 (its pairs, in units of
+    eight, rounded up) are both filed once per non-empty phase, so their sums are equal; a filed phase has a largest
+    count of at least one and at least one pair, so words 0 and 16 stay zero.  (No oracle value: the histogram depends on
+    which rays share a wave.)  The counting call after it returns its own counters."""
+    from tray_racing_amd import _lib as L
+    lib = trx.load()
+    flat, view, osc, ov = build_case(trx, orc, name, n, w, h, tlas, True if tlas else None)
+    sc = trx.Scene(flat)
+    try:
+        for sem in (0, 3):
+            _, ost = osc.trace_primary(ov, w, h, sem=sem)
+            assert ost.n_tri > 0
+            hist = np.full(32, 0xDEADBEEF, dtype=np.uint32)
+            L.check(lib.trx_debug_tri_histogram(sc.handle, C.byref(view), w, h, sem, hist.ctypes.data_as(C.c_void_p)))
+            print(name, "sem", sem, "hist", hist.tolist())
+            assert int(hist[:16].sum()) == int(hist[16:].sum()) > 0
+            assert hist[0] == 0 and hist[16] == 0
+            assert int(hist[:16].sum()) <= ost.n_tri               # a phase holds at least one test
+            st = sc.count_primary(view, w, h, sem=sem)
+            assert six(st) == six(ost), "%s sem %d: count_primary after the histogram pass" % (name, sem)
+            check_wave(st, "count_primary after the histogram pass")
+        sc.check()
+    finally:
+        sc.close()
+
+
+# ---- (i) refusals ---------------------------------------------------------------------------------------------------
+
+def test_refusals_leave_the_counters_alone(trx, orc):
+    """trx_count_ao has no d_primary_inst parameter, so a scene with instance transforms refuses it (TRX_ERR_INVALID, as
+    the AO pass itself does); trx_count_rays refuses an empty batch.  Both before anything is enqueued: the counting
+    call that follows is correct."""
+    from tray_racing_amd import _lib as L
+    flat, _o2w, world, _first, _blas = instanced_scene(trx)
+    sc = trx.Scene(flat)
+    osc = orc.Scene(flat.nodes, flat.tri_verts, flat.instance_offsets, flat.tlas_start, instance_w2o=sc.instance_world_to_object())
+    w, h = 40, 24
+    lo, hi = world.reshape(-1, 3).min(0), world.reshape(-1, 3).max(0)
+    view = trx.view_from_camera((hi + 0.1 * (hi - lo)).tolist(), (0.5 * (lo + hi)).tolist(), 80.0, w, h)
+    rays = mixed_rays(trx, flat, 5000, 31, world)
+    _, _, ost = osc.trace_rays_inst(rays, sem=3)
+    assert 0.02 < ost.n_hits / 5000 < 0.99 and ost.n_tri > 0
+    try:
+        d_prim, d_ao, d_rays, d_hits = filled(w * h), filled(w * h), to_device(rays), filled(5000)
+        sc.trace_primary_dev(view, w, h, d_prim.data_ptr(), sem=3)
+        with pytest.raises(trx.TrxError) as e:
+            sc.count_ao(view, w, h, d_prim.data_ptr(), d_ao.data_ptr(), sem=3)
+        assert e.value.code == L.TRX_ERR_INVALID and "instance" in str(e.value)
+        assert bool((d_ao == -1).all())
+        st = sc.count_rays(d_rays.data_ptr(), 5000, d_hits.data_ptr(), sem=3)
+        assert six(st) == six(ost)
+        with pytest.raises(trx.TrxError) as e:
+            sc.count_rays(d_rays.data_ptr(), 0, d_hits.data_ptr(), sem=3)
+        assert e.value.code == L.TRX_ERR_INVALID
+        st = sc.count_rays(d_rays.data_ptr(), 5000, 0, sem=3)
+        assert six(st) == six(ost)
+        check_wave(st, "count_rays after the refusals")
+        sc.check()
+    finally:
+        sc.close()

@@ -459,3 +459,40 @@ def test_simd_node_test_is_bit_identical_to_the_scalar_one(trx, orc):
         assert (gst.n_node, gst.n_tri, gst.n_hits) == (wst.n_node, wst.n_tri, wst.n_hits)
     finally:
         orc.set_simd(False)
+
+
+def test_footprint_of_a_primary_frame(trx, orc):
+    """orc_footprint_primary marks a node where the primary walk counts a node visit and a triangle where it counts a
+    triangle test (the reference for trx_debug_footprint, tests/test_gpu_counters.py).  So on the same frame: no more
+    distinct nodes / triangles than visits / tests, the walk's root marked, every triangle a hit record names marked
+    (it was tested), marks that are 0 or 1, the same marks whatever the thread count, and ordinary traces - which go
+    through the same function with null mark pointers - unchanged.  A golden fixture of each kind and one seeded scene."""
+    cases = []
+    for name in ("cornell_64", "cornell_tlas_48"):
+        g, osc = load_golden(orc, name)
+        cases.append((name, osc, orc.view_from_bytes(g["view"].tobytes()), int(g["width"]), int(g["height"]), g))
+    _flat, _view, osc, ov = make_scene(trx, orc, "kitchen", 6000, 64, 40)
+    cases.append(("kitchen", osc, ov, 64, 40, None))
+    for name, osc, view, w, h, g in cases:
+        for sem in (0, 3):
+            prim, st = osc.trace_primary(view, w, h, sem=sem)
+            nm, tm = osc.footprint_marks(view, w, h, sem=sem)
+            nodes, tris = osc.footprint(view, w, h, sem=sem)
+            assert (nodes, tris) == (int(nm.sum()), int(tm.sum())) and set(np.unique(nm)) <= {0, 1} and set(np.unique(tm)) <= {0, 1}
+            assert nm.size == osc.nodes.shape[0] and tm.size == osc.tris.shape[0]
+            assert 0 < nodes <= min(st.n_node, nm.size) and 0 < tris <= min(st.n_tri, tm.size), (name, sem, nodes, tris)
+            assert nm[osc.c.tlas_start if osc.inst.size else 0] == 1                 # every ray starts at the root
+            hit = prim["prim"] != 0xFFFFFFFF
+            assert hit.any() and tm[prim["prim"][hit]].all(), "%s sem %d: a hit triangle that was never tested" % (name, sem)
+            for threads in (1, 3, 16):
+                nm2, tm2 = osc.footprint_marks(view, w, h, sem=sem, threads=threads)
+                assert np.array_equal(nm, nm2) and np.array_equal(tm, tm2), (name, sem, threads)
+            again, st2 = osc.trace_primary(view, w, h, sem=sem)
+            assert_hits_equal(again, prim, "%s sem %d after the footprint pass" % (name, sem))
+            assert (st2.n_node, st2.n_tri, st2.n_hits, st2.max_stack) == (st.n_node, st.n_tri, st.n_hits, st.max_stack)
+            if g is not None:
+                assert_hits_equal(prim, g["orc_primary_sem%d" % sem], "%s sem %d primary" % (name, sem))
+                assert [st.n_node, st.n_tri, st.n_hits, st.max_stack] == list(g["orc_counts_sem%d" % sem])
+    # a frame does not touch the whole tree of a room seen from inside
+    nodes, _ = cases[2][1].footprint(cases[2][2], 64, 40, sem=3)
+    assert nodes < cases[2][1].nodes.shape[0]
