@@ -464,6 +464,45 @@ int trx_hit_attributes_primary_dev(trx_scene *scene, const trx_view *view, uint3
                                    trx_shard shard, const trx_hit *d_hits, const uint32_t *d_inst, trx_hit_attr *d_attr,
                                    void *stream);
 
+/* ---- AO visibility: any-hit AO rays with a radius, N samples per pixel -----------------------------------------------
+ * The reference traces its AO ray with a closest-hit query "to create a bit more work for the benchmark" and notes that
+ * "actual AO could use a faster anyhit query" (rt_gpu_software.hlsl:126-127, src/rt_cpu/rt_cpu.rs:78-79); the calls above
+ * are that benchmark work.  These are what a renderer wants from the pass: per pixel, how many of n_samples AO rays of
+ * bounded length reach nothing, without the records ever leaving the device.
+ *
+ * trx_ao_rays_dev writes the AO pass's rays as explicit rays: one trx_ray per record, records laid out exactly like the hit
+ * buffers of trx_trace_ao_inst_dev for `shard` (image layout or TRX_LAYOUT_SHARD); records of pixels outside the shard or the
+ * image are left untouched.  A pixel whose primary record is a hit gets, bit for bit, the ray trx_trace_ao_inst_dev builds
+ * for it under seed `frame` (origin (eye + d*t) - d*ao_eps, cosine-hemisphere direction around the hit triangle's normal -
+ * taken to world space through the instance's world-to-object rows when the scene has transforms - flipped toward the
+ * viewer) with tmin = 0 and tmax = ao_radius.  ao_radius must be > 0; +inf is allowed and stored as FLT_MAX, which is what
+ * the AO pass walks to; anything else (0, negative, NaN) is TRX_ERR_INVALID.  A pixel whose primary record is a miss
+ * (!(t < FLT_MAX) or prim == 0xFFFFFFFF) gets the INERT ray: every word 0 except tmax = -1.0f - no walk can commit a hit on
+ * it (closest-hit and any-hit kernels alike start from min(tmax, FLT_MAX)).  d_primary_inst is REQUIRED on scenes with
+ * instance transforms, as for trx_trace_ao_inst_dev: without it the call returns TRX_ERR_INVALID before anything is enqueued. */
+int trx_ao_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                    uint32_t frame, float ao_eps, float ao_radius, const trx_hit *d_primary,
+                    const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream);
+/* The visibility pass.  d_unoccluded holds one byte per record, laid out like the hit buffers: a pixel whose primary record
+ * is a hit gets the number of samples f in 0..n_samples-1 whose AO ray - trx_ao_rays_dev's under seed frame0 + f - is NOT
+ * occluded, "occluded" meaning that trx_trace_occluded_dev over that ray answers 1; a pixel whose primary record is a miss
+ * gets TRX_AO_NO_SURFACE; records outside the shard or the image are untouched.  A renderer's AO term is count / n_samples.
+ * n_samples outside 1..TRX_MAX_AO_SAMPLES, a bad radius and a missing d_primary_inst are refused (TRX_ERR_INVALID) before
+ * anything is enqueued: the output is left as it was.
+ * Everything runs on `stream` without host synchronisation: the rays of a chunk of tiles and samples are written into a
+ * scratch the stream's launch slot of the scene owns ([tile][sample][64 pixels]: the samples of a tile lie together, at
+ * most 288 MiB per slot, counted by trx_scene_device_bytes, released by trx_scene_destroy; growing it waits for the slot's
+ * previous launch), the any-hit rays launch of trx_trace_occluded_dev walks them, a reduce kernel adds the flags into the
+ * counts; chunk after chunk until every tile and sample is done.
+ * Ordering: as for the other trace launches - a trx_scene_refit* called after this call has returned waits for the pass,
+ * which sees the old geometry in full.  A stack overflow latches as for every rays launch (trx_scene_check). */
+#define TRX_MAX_AO_SAMPLES 64
+#define TRX_AO_NO_SURFACE 0xFFu
+int trx_trace_ao_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                trx_shard shard, uint32_t semantics, uint32_t frame0, uint32_t n_samples,
+                                float ao_eps, float ao_radius, const trx_hit *d_primary,
+                                const uint32_t *d_primary_inst, uint8_t *d_unoccluded, void *stream);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,
@@ -524,6 +563,12 @@ int trx_trace_rays_attr(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, 
 /* Host-buffer form of trx_trace_occluded_dev. */
 int trx_trace_occluded(trx_scene *scene, const trx_ray *rays, uint64_t n_rays, uint32_t semantics,
                        uint8_t *out_flags, float *out_ms);
+/* Host-buffer form of trx_trace_ao_visibility_dev for a whole image: the primary pass and the visibility pass over its
+ * records, synchronous (serialised by the per-scene lock like its siblings); out_unoccluded: width * height bytes (may be
+ * NULL), out_ms the hipEvent time of both passes. */
+int trx_trace_ao_visibility(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                            uint32_t semantics, uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius,
+                            uint8_t *out_unoccluded, float *out_ms);
 /* Single-ray Traversable::traverse (traversable/src/lib.rs:13-28).  Thread-safe and meant to be called the way the
  * reference calls it - from every worker of a thread pool at once (src/rt_cpu/rt_cpu.rs:35-57).  No call launches
  * anything: the first call starts the scene's RAY SERVICE, a resident kernel that answers out of a ring of 64 slots in

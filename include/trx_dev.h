@@ -78,6 +78,17 @@ int trx_debug_fetch_rate(trx_scene *scene, uint32_t steps, uint32_t tris_per_nod
  * second, best of `reps` passes after two warm-up passes): bench.py's `roofline_hbm.peak_measured`. */
 int trx_debug_copy_rate(int device, uint64_t bytes, uint32_t reps, double *out_bytes_per_s);
 
+/* AO visibility (trx_trace_ao_visibility_dev, include/trx.h): the cap, in bytes, on the ray scratch of a launch slot for
+ * passes that start after the call (process-wide; 0 restores the default of 288 MiB).  Returns the previous cap.  Counts
+ * are identical under every cap: a small one makes small images run the chunk loops (the test suite does that). */
+uint64_t trx_debug_ao_scratch_cap(uint64_t bytes);
+/* Measuring aid: one whole-image trx_trace_ao_visibility_dev pass on the null stream with hipEvents around the three
+ * phases of every chunk; out_ms = {ray generation, any-hit walk, reduce} summed over the chunks.  Synchronous. */
+int trx_debug_ao_visibility_phases(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                   uint32_t semantics, uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius,
+                                   const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_unoccluded,
+                                   float out_ms[3]);
+
 /* Kernel variant selection (tuning aid; 0 = default).  Returns the previous
  * value.  Variants compute identical results. */
 uint32_t trx_set_kernel_variant(uint32_t variant);

@@ -28,6 +28,9 @@ SEM_TIE_FIRST = 2
 SEM_NODE_FMA = 4
 SEM_CPU = 3
 
+MAX_AO_SAMPLES = 64
+AO_NO_SURFACE = 0xFF
+
 
 class TrxError(RuntimeError):
     def __init__(self, code, message):
@@ -129,6 +132,12 @@ SIGNATURES = {
     "trx_hit_attributes_rays_dev": (_i, [_P, _P, _u64, _P, _P, _P, _P]),
     "trx_hit_attributes_primary_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _P, _P, _P, _P]),
     "trx_trace_occluded": (_i, [_P, _P, _u64, _u32, _P, C.POINTER(_f)]),
+    "trx_ao_rays_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _f, _f, _P, _P, _P, _P]),
+    "trx_trace_ao_visibility_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _u32, _f, _f, _P, _P, _P, _P]),
+    "trx_trace_ao_visibility": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, C.POINTER(_f)]),
+    "trx_debug_ao_scratch_cap": (_u64, [_u64]),
+    "trx_debug_ao_visibility_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, _P, _P,
+                                            C.POINTER(_f)]),
     "trx_count_primary": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _P, C.POINTER(Stats)]),
     "trx_count_ao": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _f, _P, _P, C.POINTER(Stats)]),
     "trx_count_rays": (_i, [_P, _P, _u64, _u32, _P, C.POINTER(Stats)]),

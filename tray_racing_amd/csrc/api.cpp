@@ -296,6 +296,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     bytes += s->inst_mask.count(); // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
     for (const Slot &sl : s->slots) {
         bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
+        bytes += sl.ao_rays.count() * sizeof(trx_ray) + sl.ao_flags.count(); // the AO visibility pass's scratch (api_ao.cpp)
         for (const auto &o : sl.order) bytes += o.lists.count() * sizeof(uint32_t);
     }
     // trx_frame_loop's record buffers (four primary, one AO; instance ids beside them on two-level scenes)

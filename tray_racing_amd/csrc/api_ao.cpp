@@ -1,0 +1,226 @@
+// api_ao.cpp - AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility*): the AO pass's rays written out as
+// explicit rays (k_ao_rays, kernels.hip), walked by the any-hit rays launch every trx_trace_occluded*_dev call uses, and
+// their flags added into one count per pixel (k_ao_reduce).  A composition around the shipped walk: no traversal kernel
+// knows about it.  Everything of one call runs on the caller's stream, on that stream's launch slot of the scene - the slot
+// owns the ray scratch, so concurrent calls on other streams have their own - and trx_scene_refit waits for it like for any
+// other launch of the slot.
+#include "api_internal.h"
+
+#include <cfloat>
+
+namespace {
+
+// The scratch of one launch slot holds at most this many bytes of rays and flags (kAoUnitBytes per tile and sample): the
+// four-sample 1080p pass (32 400 tiles x 4 x 2 112 B = 261 MiB) is one chunk, anything larger runs in several.
+constexpr uint64_t kAoScratchCapDefault = 288ull << 20;
+std::atomic<uint64_t> g_ao_scratch_cap{kAoScratchCapDefault};
+
+// ao_radius -> the rays' tmax: > 0, +inf stored as FLT_MAX (what the AO pass walks to)
+int radius_tmax(float ao_radius, float &tmax) {
+    if (!(ao_radius > 0.0f)) return fail(TRX_ERR_INVALID, "ao_radius %g: must be > 0 (+inf allowed)", (double)ao_radius);
+    tmax = ao_radius > FLT_MAX ? FLT_MAX : ao_radius;
+    return TRX_OK;
+}
+
+// the image geometry exactly as the trace derives it, and what both kernels need of the scene (s->mu held for the scene part)
+int ao_geometry(AoRaysParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t &tiles) {
+    TraceParams t;
+    if (int rc = image_params(t, view, w, h, shard)) return rc;
+    std::memset(&p, 0, sizeof(p));
+    p.width = t.width;
+    p.height = t.height;
+    p.tiles_x = t.tiles_x;
+    p.shard_index = t.shard_index;
+    p.shard_count = t.shard_count;
+    p.compact = t.compact;
+    p.view = t.views[0];
+    tiles = t.tiles_per_frame;
+    return TRX_OK;
+}
+
+int need_inst(const trx_scene *s, const uint32_t *d_primary_inst) {
+    if (s->tlas && s->inst_xform && !d_primary_inst)
+        return fail(TRX_ERR_INVALID, "this scene has instance transforms: the AO rays need the primary pass's instance ids "
+                                     "(d_primary_inst) to take the hit normal into world space");
+    return TRX_OK;
+}
+
+// hipEvents around the three phases of every chunk (trx_debug_ao_visibility_phases)
+struct Phases {
+    std::vector<Event> ev; // 4 per chunk: before the rays, after them, after the walk, after the reduce
+    int mark(hipStream_t stream) {
+        ev.emplace_back();
+        HIP_TRY(ev.back().create());
+        HIP_TRY(hipEventRecord(ev.back().get(), stream));
+        return TRX_OK;
+    }
+};
+
+int visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t frame0,
+                    uint32_t n_samples, float ao_eps, float ao_radius, const trx_hit *d_primary,
+                    const uint32_t *d_primary_inst, uint8_t *d_unoccluded, hipStream_t stream, Phases *phases) {
+    if (!s || !d_primary || !d_unoccluded) return fail(TRX_ERR_INVALID, "null argument");
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    AoRaysParams g;
+    uint32_t tiles = 0;
+    float tmax = 0.f;
+    if (int rc = radius_tmax(ao_radius, tmax)) return rc;
+    if (int rc = ao_geometry(g, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    if (tiles == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, stream, slot)) return rc;
+    // chunks: as many tiles as the scratch holds, and for them as many samples as it holds
+    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / kAoUnitBytes, 1), 1ull << 24);
+    const uint32_t tile_chunk = (uint32_t)std::min<uint64_t>(tiles, units);
+    const uint32_t sample_chunk = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(units / tile_chunk, 1));
+    const uint64_t rays = (uint64_t)tile_chunk * sample_chunk * 64;
+    if (slot->ao_rays.count() < rays) {
+        // (the slot's previous kernel may still be walking the old scratch)
+        if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
+        slot->ao_flags.reset();
+        HIP_TRY(slot->ao_rays.alloc(rays));
+        HIP_TRY(slot->ao_flags.alloc(rays));
+    }
+    g.tris = s->tris.get();
+    g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
+    g.primary = d_primary;
+    g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.rays = slot->ao_rays.get();
+    g.flags = slot->ao_flags.get();
+    g.counts = d_unoccluded;
+    g.scratch = 1u;
+    g.ao_eps = ao_eps;
+    g.tmax = tmax;
+    for (uint32_t tile0 = 0; tile0 < tiles; tile0 += tile_chunk) {
+        for (uint32_t s0 = 0; s0 < n_samples; s0 += sample_chunk) {
+            g.tile0 = tile0;
+            g.n_tiles = std::min(tile_chunk, tiles - tile0);
+            g.n_samples = std::min(sample_chunk, n_samples - s0);
+            g.frame = frame0 + s0;
+            g.first = s0 == 0 ? 1u : 0u;
+            if (phases) if (int rc = phases->mark(stream)) return rc;
+            HIP_TRY(launch_ao_rays(g, stream));
+            // (from here on the slot is this stream's: the rays launch below finds it by its stream)
+            slot->last_stream = stream;
+            slot->last_use = ++s->launches;
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+            slot->used = true;
+            if (phases) if (int rc = phases->mark(stream)) return rc;
+            TraceParams p;
+            std::memset(&p, 0, sizeof(p));
+            p.rays = g.rays;
+            p.out = reinterpret_cast<trx_hit *>(slot->ao_flags.get());
+            p.any_hit = 1u;
+            p.n_items = g.n_tiles * g.n_samples * 64u;
+            SlotCounters *ctr = nullptr;
+            if (int rc = enqueue_locked(s, p, kModeRays, sem, false, stream, &ctr)) return rc;
+            if (ctr != slot->ctr.get()) return fail(TRX_ERR_INVALID, "internal: the rays launch left the pass's launch slot");
+            if (phases) if (int rc = phases->mark(stream)) return rc;
+            HIP_TRY(launch_ao_reduce(g, stream));
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+            if (phases) if (int rc = phases->mark(stream)) return rc;
+        }
+    }
+    return TRX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int trx_ao_rays_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t frame, float ao_eps,
+                    float ao_radius, const trx_hit *d_primary, const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream) {
+    if (!s || !d_primary || !d_rays) return fail(TRX_ERR_INVALID, "null argument");
+    AoRaysParams g;
+    uint32_t tiles = 0;
+    float tmax = 0.f;
+    if (int rc = radius_tmax(ao_radius, tmax)) return rc;
+    if (int rc = ao_geometry(g, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    if (tiles == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, (hipStream_t)stream, slot)) return rc;
+    g.tris = s->tris.get();
+    g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
+    g.primary = d_primary;
+    g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.rays = d_rays;
+    g.n_tiles = tiles;
+    g.n_samples = 1u;
+    g.frame = frame;
+    g.ao_eps = ao_eps;
+    g.tmax = tmax;
+    slot->last_stream = (hipStream_t)stream;
+    slot->last_use = ++s->launches;
+    HIP_TRY(launch_ao_rays(g, (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(slot->done.get(), (hipStream_t)stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
+int trx_trace_ao_visibility_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                                uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius, const trx_hit *d_primary,
+                                const uint32_t *d_primary_inst, uint8_t *d_unoccluded, void *stream) {
+    return visibility_impl(s, view, w, h, shard, sem, frame0, n_samples, ao_eps, ao_radius, d_primary, d_primary_inst,
+                           d_unoccluded, (hipStream_t)stream, nullptr);
+}
+
+int trx_trace_ao_visibility(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame0,
+                            uint32_t n_samples, float ao_eps, float ao_radius, uint8_t *out_unoccluded, float *out_ms) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    float tmax = 0.f;
+    if (int rc = radius_tmax(ao_radius, tmax)) return rc; // (before the primary pass)
+    const uint64_t n = (uint64_t)w * h;
+    const trx_shard whole{0, 1, 0, 0};
+    // (the counts go where the AO records of trx_trace_primary_ao go: n bytes of the second record buffer)
+    auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
+    return host_call(
+        s, n, nullptr, 0, 0, out_ms,
+        [&] {
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, s->scratch_a.get(), s->scratch_ia.get(), nullptr);
+            if (rc) return rc;
+            return trx_trace_ao_visibility_dev(s, view, w, h, whole, sem, frame0, n_samples, ao_eps, ao_radius,
+                                               s->scratch_a.get(), s->scratch_ia.get(), d_counts(), nullptr);
+        },
+        [&]() -> int {
+            if (out_unoccluded) HIP_TRY(hipMemcpy(out_unoccluded, d_counts(), n, hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
+}
+
+// ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------
+
+uint64_t trx_debug_ao_scratch_cap(uint64_t bytes) {
+    return g_ao_scratch_cap.exchange(bytes ? bytes : kAoScratchCapDefault, std::memory_order_relaxed);
+}
+
+int trx_debug_ao_visibility_phases(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame0,
+                                   uint32_t n_samples, float ao_eps, float ao_radius, const trx_hit *d_primary,
+                                   const uint32_t *d_primary_inst, uint8_t *d_unoccluded, float out_ms[3]) {
+    if (!s || !out_ms) return fail(TRX_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    Phases ph;
+    if (int rc = visibility_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, frame0, n_samples, ao_eps, ao_radius, d_primary,
+                                 d_primary_inst, d_unoccluded, nullptr, &ph))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    out_ms[0] = out_ms[1] = out_ms[2] = 0.f;
+    for (size_t c = 0; c + 3 < ph.ev.size(); c += 4)
+        for (int k = 0; k < 3; k++) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ph.ev[c + k].get(), ph.ev[c + k + 1].get()));
+            out_ms[k] += ms;
+        }
+    return trx_scene_check(s, nullptr);
+}
+
+} // extern "C"

@@ -7,6 +7,7 @@
 //   api_build.cpp    builders, flat-buffer assembly (cwbvh_gpu_runner's host half), scene generators and loaders
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
+//   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -66,6 +67,8 @@ struct Slot {
     DevBuf<SlotCounters> ctr;
     DevBuf<uint2> spill; // stack spill area: kWaveScratch entries per wave
     Event done;          // everything enqueued for this slot has finished
+    DevBuf<trx_ray> ao_rays;   // trx_trace_ao_visibility_dev on this slot's stream: the rays of one chunk of tiles and samples ...
+    DevBuf<uint8_t> ao_flags;  // ... and their occlusion flags (api_ao.cpp)
     bool used = false;
     bool pinned = false;               // a resident kernel (the ray service) runs on this slot: never recycled for another stream
     hipStream_t last_stream = nullptr; // stream of the last launch on this slot
@@ -211,6 +214,8 @@ void fill_view(const trx_view *v, trx::ViewDev &out);
 int acquire_slot(trx_scene *s, hipStream_t stream, Slot *&out);
 // Enqueues one traversal kernel on a launch slot of the scene (api_launch.cpp)
 int enqueue(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream, trx::SlotCounters **ctr_out);
+// ... the same for a caller that holds s->mu and has set the device and checked `sem` (a pass of several launches on one slot)
+int enqueue_locked(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream, trx::SlotCounters **ctr_out);
 // an image pass's kernel parameters: p zeroed, then the geometry of `view` / w x h / shard
 int image_params(trx::TraceParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard);
 int read_overflow(trx_scene *s, trx::SlotCounters *ctr);

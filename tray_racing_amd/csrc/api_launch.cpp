@@ -73,6 +73,11 @@ int enqueue(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hi
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->mu);
+    return enqueue_locked(s, p, mode, sem, count, stream, ctr_out);
+}
+
+int enqueue_locked(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream,
+                   SlotCounters **ctr_out) {
     if (s->inst_xform && mode == kModeAo && !p.primary_inst)
         return fail(TRX_ERR_INVALID, "this scene has instance transforms: the AO pass needs the primary pass's instance ids "
                                      "(trx_trace_ao_inst_dev) to take the hit normal into world space");

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -39,6 +40,10 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     bool gpu_build = false; // --gpu-build: Morton sort + PLOC rounds of the build on the device (trx_set_build_device)
     bool split = false;   // --split: pre-splitting of large triangles
     bool overlap = false; // --overlap: frame i's AO pass under frame i + 1's primary pass (trx_frame_loop, two streams)
+    // --ao-samples N / --ao-radius R: with --png, the image's AO term is count / N of the AO visibility pass
+    // (trx_trace_ao_visibility) instead of t / (1 + t); either flag switches it on (N defaults to 1, R to +inf)
+    unsigned ao_samples = 0;
+    float ao_radius = 0.0f;
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -68,6 +73,7 @@ void usage() {
               "  [--png] [--cpu-semantics] [--dry-run (load + build only, needs no GPU)] [-r reinsertion_batch_ratio]\n"
               "  [--search-distance d] [--search-depth-threshold n] [--sort-precision 64|128] [--split] [--gpu-build]\n"
               "  [--overlap (frames stay on the device, frame i's AO pass under frame i+1's primary pass; reports the average)]\n"
+              "  [--ao-samples 1..64] [--ao-radius r] (with --png: AO term = unoccluded samples / N of the any-hit visibility pass)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -101,6 +107,13 @@ Options parse_args(int argc, char **argv) {
         else if (a == "--dry-run") o.dry_run = true;
         else if (a == "--gpu-build") o.gpu_build = true;
         else if (a == "--overlap") o.overlap = true;
+        else if (a == "--ao-samples") {
+            o.ao_samples = (unsigned)std::atoi(need(i));
+            if (o.ao_samples == 0 || o.ao_samples > TRX_MAX_AO_SAMPLES) die("--ao-samples takes 1.." + std::to_string(TRX_MAX_AO_SAMPLES));
+        } else if (a == "--ao-radius") {
+            o.ao_radius = (float)std::atof(need(i));
+            if (!(o.ao_radius > 0.0f)) die("--ao-radius must be > 0");
+        }
         else if (a == "-h" || a == "--help") {
             usage();
             std::exit(0);
@@ -179,11 +192,30 @@ bool write_png(const std::string &path, const std::vector<unsigned char> &rgba, 
 // (src/rt_cpu/rt_cpu.rs:57-85,102-112; the same shading ends the GPU shader, rt_gpu_software.hlsl:47-144).
 void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned frame_count, const std::string &name) {
     const size_t n = (size_t)o.width * o.height;
-    std::vector<trx_hit> primary(n), ao(n);
+    std::vector<unsigned char> rgba(n * 4);
+    const std::string path = name + "_rend.png";
     float ms = 0;
+    if (o.ao_samples != 0 || o.ao_radius > 0.0f) {
+        // the AO term a renderer would use: the share of N bounded any-hit AO rays that reach nothing
+        const unsigned samples = o.ao_samples ? o.ao_samples : 1u;
+        const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
+        std::vector<uint8_t> counts(n);
+        check(trx_trace_ao_visibility(scene, &view, o.width, o.height, o.semantics, frame_count, samples, 0.0001f, radius,
+                                      counts.data(), &ms), "png frame");
+        for (size_t i = 0; i < n; i++) {
+            // (no surface: the reference's 1 / t of a miss, 0)
+            const float col = counts[i] == TRX_AO_NO_SURFACE ? 0.0f : (float)counts[i] / (float)samples;
+            const float g = std::pow(col, 2.2f) * 255.0f;
+            rgba[4 * i + 0] = rgba[4 * i + 1] = rgba[4 * i + 2] = (unsigned char)(uint32_t)g;
+            rgba[4 * i + 3] = 255;
+        }
+        if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
+        if (o.verbose) std::printf("saved %s\n", path.c_str());
+        return;
+    }
+    std::vector<trx_hit> primary(n), ao(n);
     check(trx_trace_primary_ao(scene, &view, o.width, o.height, o.semantics, frame_count, 0.0001f, primary.data(),
                                ao.data(), &ms), "png frame");
-    std::vector<unsigned char> rgba(n * 4);
     for (size_t i = 0; i < n; i++) {
         float col = 1.0f / primary[i].t;
         if (primary[i].t < 3.4028234663852886e38f) col = ao[i].t < 3.4028234663852886e38f ? ao[i].t / (1.0f + ao[i].t) : 1.0f;
@@ -192,7 +224,6 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         rgba[4 * i + 0] = rgba[4 * i + 1] = rgba[4 * i + 2] = c;
         rgba[4 * i + 3] = 255;
     }
-    const std::string path = name + "_rend.png";
     if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
     if (o.verbose) std::printf("saved %s\n", path.c_str());
 }

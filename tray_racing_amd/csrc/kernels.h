@@ -205,6 +205,33 @@ struct HitAttrParams {
 };
 hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream);
 
+// AO visibility (trx_ao_rays_dev / trx_trace_ao_visibility_dev): k_ao_rays writes the AO pass's rays as explicit rays, the
+// any-hit rays launch walks them, k_ao_reduce adds the flags into per-pixel counts.  One lane per (tile, sample, pixel).
+//   record layout (scratch == 0, one sample): rays[record], records laid out by the shard like the hit buffers; pixels
+// outside the image are left alone.
+//   scratch layout (scratch == 1): rays[((tile - tile0) * n_samples + sample) * 64 + pixel-in-tile] for the shard's local
+// tiles tile0 .. tile0 + n_tiles - 1 and the seeds frame .. frame + n_samples - 1; EVERY entry is written (pixels outside the
+// image and primary misses get the inert ray), because the rays launch walks all of them.
+constexpr uint32_t kAoNoSurface = 0xffu;        // TRX_AO_NO_SURFACE
+constexpr uint32_t kAoUnitBytes = 64u * 32u + 64u; // scratch per (tile, sample): 64 rays and their 64 flags
+struct AoRaysParams {
+    const float4 *tris;
+    const float4 *inst_xform;     // world-to-object rows per instance, or null (no instance transforms)
+    const trx_hit *primary;
+    const uint32_t *primary_inst; // read only with inst_xform
+    trx_ray *rays;
+    const uint8_t *flags;         // k_ao_reduce: the occlusion flags of the scratch rays
+    uint8_t *counts;              // k_ao_reduce: one byte per record, laid out by the shard
+    uint32_t tile0, n_tiles, n_samples, scratch;
+    uint32_t first;               // k_ao_reduce: the first samples of these tiles (counts are set, not added to)
+    uint32_t width, height, tiles_x, shard_index, shard_count, compact; // as in TraceParams
+    uint32_t frame;
+    float ao_eps, tmax;
+    ViewDev view;
+};
+hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream);
+hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream);
+
 // Resident waves the persistent kernel should be launched with on `device`.
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count);
 

@@ -862,7 +862,116 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
     P.out[rec] = out;
 }
 
+// AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility_dev; kernels.h, AoRaysParams).  The pixel of a
+// lane: false where the tile's 8x8 block leaves the image.  rec = the pixel's record, laid out by the shard like the hit buffers.
+__device__ __forceinline__ bool ao_pixel(const AoRaysParams &P, uint32_t local_tile, uint32_t k, uint32_t &px, uint32_t &py, uint32_t &rec) {
+    const uint32_t tile = local_tile * P.shard_count + P.shard_index;
+    const uint32_t ty = tile / P.tiles_x;
+    px = (tile - ty * P.tiles_x) * 8u + (k & 7u);
+    py = ty * 8u + (k >> 3);
+    rec = P.compact ? local_tile * 64u + k : py * P.width + px;
+    return px < P.width && py < P.height;
+}
+
+// The AO ray of every (tile, sample, pixel) as an explicit ray: what the refill of k_trace<kModeAo> builds for that pixel
+// and seed (trace_refill.inc), operation for operation with the same device functions - primary_dir, the normal through the
+// instance's rows and flipped toward the viewer, the origin pulled back by ao_eps, hash_noise, sincos_det, the basis, the
+// final normalise - with tmin = 0 and tmax = the AO radius.  A pixel whose primary record is a miss gets the inert ray (all
+// words 0 but tmax = -1: no walk commits a hit on it, every walk starts from min(tmax, FLT_MAX)).  A streaming kernel: 8 B of
+// primary record, 48 B of triangle (and 48 B of rows) read per ray, 32 B written.
+__global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * P.n_samples * 64u) return;
+    const uint32_t unit = item >> 6, k = item & 63u;
+    const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
+    uint32_t px, py, rec;
+    const bool inside = ao_pixel(P, P.tile0 + lt, k, px, py, rec);
+    if (!inside && !P.scratch) return; // (the trace writes no record for it either)
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    trx_hit ph;
+    ph.t = __builtin_inff();
+    ph.prim = TRX_INVALID;
+    if (inside) ph = P.primary[rec];
+    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
+        float dx, dy, dz;
+        primary_dir(P.view, P.width, P.height, px, py, dx, dy, dz);
+        const float4 *tp = P.tris + (size_t)ph.prim * 3;
+        float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
+        if (P.inst_xform) {
+            const uint32_t pi = P.primary_inst[rec];
+            if (pi != TRX_INVALID) {
+                const float4 *m = P.inst_xform + (size_t)pi * 3;
+                const float4 r0 = m[0], r1 = m[1], r2 = m[2];
+                const float ax = (r0.x * nx + r1.x * ny) + r2.x * nz;
+                const float ay = (r0.y * nx + r1.y * ny) + r2.y * nz;
+                const float az = (r0.z * nx + r1.z * ny) + r2.z * nz;
+                nx = ax; ny = ay; nz = az;
+            }
+        }
+        const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+        nx *= ninv; ny *= ninv; nz *= ninv;
+        const float nd = (nx * -dx + ny * -dy) + nz * -dz;
+        const float sg = copysignf(1.0f, nd);
+        nx *= sg; ny *= sg; nz *= sg;
+        a.x = (P.view.eye[0] + dx * ph.t) - dx * P.ao_eps;
+        a.y = (P.view.eye[1] + dy * ph.t) - dy * P.ao_eps;
+        a.z = (P.view.eye[2] + dz * ph.t) - dz * P.ao_eps;
+        const uint32_t seed = P.frame + sample;
+        const float u1 = hash_noise(px, py, seed);
+        const float u2 = hash_noise(px, py, seed + 1024u);
+        const float rr = sqrtf(u1);
+        const float theta = u2 * 6.28318530717958647692f;
+        float sn, cs;
+        sincos_det(theta, sn, cs);
+        const float lx = rr * cs, ly = rr * sn, lz = sqrtf(fmaxf(0.0f, 1.0f - u1));
+        const float sign = nz >= 0.0f ? 1.0f : -1.0f;
+        const float aa = -1.0f / (sign + nz);
+        const float bb = nx * ny * aa;
+        const float b1x = 1.0f + sign * nx * nx * aa, b1y = sign * bb, b1z = -sign * nx;
+        const float b2x = bb, b2y = sign + ny * ny * aa, b2z = -ny;
+        dx = (b1x * lx + b2x * ly) + nx * lz;
+        dy = (b1y * lx + b2y * ly) + ny * lz;
+        dz = (b1z * lx + b2z * ly) + nz * lz;
+        const float dinv = 1.0f / sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+        b.x = dx * dinv; b.y = dy * dinv; b.z = dz * dinv;
+        b.w = P.tmax;
+    }
+    float4 *out = reinterpret_cast<float4 *>(P.rays + (P.scratch ? item : rec));
+    out[0] = a;
+    out[1] = b;
+}
+
+// One lane per pixel of the chunk's tiles: the samples of the chunk whose ray was NOT occluded, set (first samples of the
+// tile: TRX_AO_NO_SURFACE where the primary record is a miss - the inert ray names it) or added to the pixel's count.
+__global__ void __launch_bounds__(256) k_ao_reduce(const AoRaysParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * 64u) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    uint32_t px, py, rec;
+    if (!ao_pixel(P, P.tile0 + lt, k, px, py, rec)) return;
+    const uint32_t base = lt * P.n_samples * 64u + k;
+    const bool surface = !(P.rays[base].tmax < 0.0f);
+    uint32_t n = 0u;
+    for (uint32_t s = 0; s < P.n_samples; s++) n += P.flags[base + s * 64u] == 0u ? 1u : 0u;
+    if (P.first) P.counts[rec] = (uint8_t)(surface ? n : kAoNoSurface);
+    else if (surface) P.counts[rec] = (uint8_t)(P.counts[rec] + n);
+}
+
 } // namespace
+
+hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream) {
+    const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
+    if (n == 0) return hipSuccess;
+    if (n > 0xffffff00ull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ao_rays, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream) {
+    if (p.n_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ao_reduce, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream) {
     if (p.n_items == 0) return hipSuccess;

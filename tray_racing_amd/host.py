@@ -478,6 +478,16 @@ class Scene:
         L.check(self._lib.trx_trace_occluded(self._h, _ptr(rays), rays.shape[0], sem, _ptr(flags), C.byref(ms)))
         return flags, ms.value
 
+    def trace_ao_visibility(self, view, width, height, n_samples, ao_radius, sem=L.SEM_HLSL, frame0=0, ao_eps=0.01):
+        """(uint8 counts [width * height], ms): the primary pass and the AO visibility pass over it (trx_trace_ao_visibility) -
+        per surface pixel how many of n_samples AO rays of length ao_radius (float('inf') allowed) reach nothing,
+        L.AO_NO_SURFACE where the primary ray missed."""
+        counts = np.empty(width * height, dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_trace_ao_visibility(self._h, C.byref(view), width, height, sem, frame0, n_samples, ao_eps,
+                                                  ao_radius, _ptr(counts), C.byref(ms)))
+        return counts, ms.value
+
     def traverse(self, origin, direction, tmin=0.0, tmax=3.4028234663852886e38, sem=L.SEM_HLSL):
         """Traversable::traverse (traversable/src/lib.rs:17-21) for one ray."""
         ray = L.Ray((C.c_float * 3)(*origin), tmin, (C.c_float * 3)(*direction), tmax)
@@ -607,6 +617,23 @@ class Scene:
         L.check(self._lib.trx_trace_ao_masked_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, frame, ao_eps,
                                                   ray_mask, C.c_void_p(d_primary), C.c_void_p(d_primary_inst),
                                                   C.c_void_p(d_ao), C.c_void_p(d_ao_inst), C.c_void_p(stream)))
+
+    def ao_rays_dev(self, view, width, height, d_primary, d_rays, ao_radius, frame=0, ao_eps=0.01, d_primary_inst=0,
+                    shard=(0, 1), stream=0):
+        """trx_ao_rays_dev: the AO pass's rays for seed `frame` as explicit rays at d_rays, one per record laid out like the
+        hit buffers of `shard`; the inert ray (tmax = -1) where the primary record is a miss."""
+        L.check(self._lib.trx_ao_rays_dev(self._h, C.byref(view), width, height, L.Shard(*shard), frame, ao_eps, ao_radius,
+                                          C.c_void_p(d_primary), C.c_void_p(d_primary_inst), C.c_void_p(d_rays),
+                                          C.c_void_p(stream)))
+
+    def trace_ao_visibility_dev(self, view, width, height, d_primary, d_unoccluded, n_samples, ao_radius, sem=L.SEM_HLSL,
+                                frame0=0, ao_eps=0.01, d_primary_inst=0, shard=(0, 1), stream=0):
+        """trx_trace_ao_visibility_dev: one byte per record at d_unoccluded - the number of the n_samples AO rays (seeds
+        frame0 ..) that are not occluded within ao_radius, L.AO_NO_SURFACE where the primary record is a miss."""
+        L.check(self._lib.trx_trace_ao_visibility_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, frame0,
+                                                      n_samples, ao_eps, ao_radius, C.c_void_p(d_primary),
+                                                      C.c_void_p(d_primary_inst), C.c_void_p(d_unoccluded),
+                                                      C.c_void_p(stream)))
 
     def hit_attributes_rays_dev(self, d_rays, n, d_hits, d_attr, d_inst=0, stream=0):
         """trx_hit_attributes_rays_dev: n trx_hit_attr records at d_attr for the hits d_hits of the rays d_rays (d_inst: the
