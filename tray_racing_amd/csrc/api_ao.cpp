@@ -27,12 +27,7 @@ int ao_geometry(AoRaysParams &p, const trx_view *view, uint32_t w, uint32_t h, t
     TraceParams t;
     if (int rc = image_params(t, view, w, h, shard)) return rc;
     std::memset(&p, 0, sizeof(p));
-    p.width = t.width;
-    p.height = t.height;
-    p.tiles_x = t.tiles_x;
-    p.shard_index = t.shard_index;
-    p.shard_count = t.shard_count;
-    p.compact = t.compact;
+    p.geom = tile_geom(t);
     p.view = t.views[0];
     tiles = t.tiles_per_frame;
     return TRX_OK;

@@ -69,12 +69,7 @@ int trx_hit_attributes_primary_dev(trx_scene *s, const trx_view *view, uint32_t 
     p.hits = d_hits;
     p.out = d_attr;
     p.n_items = t.n_items;
-    p.width = t.width;
-    p.height = t.height;
-    p.tiles_x = t.tiles_x;
-    p.shard_index = t.shard_index;
-    p.shard_count = t.shard_count;
-    p.compact = t.compact;
+    p.geom = tile_geom(t);
     p.view = t.views[0];
     return enqueue_attr(s, p, kAttrPrimary, t.n_items, d_inst, (hipStream_t)stream);
 }

@@ -189,6 +189,12 @@ struct TraceParamsTlas : TraceParams {
 };
 static_assert(sizeof(TraceParams) == 1536, "TraceParams grew: every single-level kernel's hidden arguments would move");
 
+// The image geometry of a tile-ordered pass as the small kernels take it: the fields of TraceParams of the same names.
+struct TileGeom {
+    uint32_t width, height, tiles_x, shard_index, shard_count, compact;
+};
+inline TileGeom tile_geom(const TraceParams &t) { return TileGeom{t.width, t.height, t.tiles_x, t.shard_index, t.shard_count, t.compact}; }
+
 // Hit attributes (k_hit_attr, trx_hit_attributes_*): one lane per hit record, no traversal.
 enum HitAttrMode : int { kAttrRays = 0, kAttrPrimary = 1 };
 struct HitAttrParams {
@@ -200,7 +206,7 @@ struct HitAttrParams {
     trx_hit_attr *out;
     uint32_t n_items;         // kAttrRays: records; kAttrPrimary: the shard's tiles * 64, in tile order
     uint32_t n_tris, n_inst;
-    uint32_t width, height, tiles_x, shard_index, shard_count, compact; // kAttrPrimary, as in TraceParams
+    TileGeom geom;            // kAttrPrimary
     ViewDev view;
 };
 hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream);
@@ -224,7 +230,7 @@ struct AoRaysParams {
     uint8_t *counts;              // k_ao_reduce: one byte per record, laid out by the shard
     uint32_t tile0, n_tiles, n_samples, scratch;
     uint32_t first;               // k_ao_reduce: the first samples of these tiles (counts are set, not added to)
-    uint32_t width, height, tiles_x, shard_index, shard_count, compact; // as in TraceParams
+    TileGeom geom;
     uint32_t frame;
     float ao_eps, tmax;
     ViewDev view;

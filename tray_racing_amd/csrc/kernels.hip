@@ -18,6 +18,11 @@
 //   AO ray           src/rt_gpu/rt_gpu_software.hlsl:105-121, src/rt_cpu/rt_cpu.rs:61-76,
 //                    src/rt_gpu/sampling.hlsl:5-51
 //
+// What k_trace shares with the small kernels at the end of this file (k_hit_attr, k_ao_rays, k_ao_reduce) is stated once:
+// TRX_AO_RAY (the AO ray of a primary hit), normal_to_world and TRX_RAY_TO_OBJECT (an instance's rows), and inside k_trace
+// TRX_PUBLISH_RAY (a lane's ray into LDS).  Where such a statement is a macro, the function form was built and changed the
+// register assignment of some k_trace instantiation; the comment at the macro says which.
+//
 // Arithmetic contract (DESIGN.md "Numerics"): binary32, no contraction
 // (-ffp-contract=off; the only fused op is the explicit fmaf of
 // TRX_SEM_NODE_FMA), IEEE divide and sqrt, dot = (ax*bx + ay*by) + az*bz.
@@ -58,6 +63,13 @@
             stamp_prev = now_;                                          \
         }                                                               \
     } while (0)
+
+// k_trace: a lane's ray where the cooperative triangle rounds read it - {o, tmin}, {d, 0} in the wave's table in LDS.  Text:
+// as a lambda beside finish_lane the walks that call it from inside other lambdas (thin walk, drain) come out in other
+// registers; one expression, not a do { } while (0): a loop statement renumbers the kernel's jump destinations.
+#define TRX_PUBLISH_RAY()                                                      \
+    ((void)(lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin)),       \
+     (void)(lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f)))
 
 namespace trx {
 namespace {
@@ -281,11 +293,13 @@ __device__ __forceinline__ uint32_t node_intersect_kept(const Ray &r, float max_
     return hit_mask;
 }
 
-// C consecutive CHILDREN of a node (thin waves: L = 8 / C lanes share a ray).  The same IEEE operations on the same
-// operands as the per-child body of node_intersect: this lane's contribution to the hit mask, child_bits << bit_index
-// for every child of its share whose box the ray enters.  q = the six plane words of the share, C bytes each, in the
-// order {x near, x far, y near, y far, z near, z far} (near = the max plane where the direction is negative); meta = its
-// C child_meta bytes.
+// C consecutive CHILDREN of a node.  The thin walk calls it with C = 1: the eight lanes that share a ray take a child each
+// (two and four children to a lane were built and declined with the four- and two-lane walks, trace_thin.inc).  The loop over
+// one child stays as written: without it the same operations reach the scheduler in another order and every kernel with a
+// thin walk comes out in other registers.  The same IEEE operations on the same operands as the per-child body of
+// node_intersect: this lane's contribution to the hit mask, child_bits << bit_index for every child of its share whose box
+// the ray enters.  q = the six plane words of the share, C bytes each, in the order {x near, x far, y near, y far, z near,
+// z far} (near = the max plane where the direction is negative); meta = its C child_meta bytes.
 template <int NODE, int C>
 __device__ __forceinline__ uint32_t node_children_intersect(const Ray &r, float max_distance, const uint4 n0, uint32_t meta,
                                                             const uint32_t q[6], const int pow2) {
@@ -307,29 +321,17 @@ __device__ __forceinline__ uint32_t node_children_intersect(const Ray &r, float 
     return hit_mask;
 }
 
-// C bytes (1, 2 or 4) of a node at a byte address aligned to C: one load instruction.
-template <int C>
-__device__ __forceinline__ uint32_t load_bytes(const uint8_t *p) {
-    if (C == 1) return *p;
-    if (C == 2) return *reinterpret_cast<const uint16_t *>(p);
-    return *reinterpret_cast<const uint32_t *>(p);
-}
-
-// Groups of L = 2, 4 or 8 lanes (thin waves): the value of a group's first lane in all of them, and the OR of all of
-// them in the first - both on the DPP network (VALU only).  Every lane of the wave must be active.
-template <int L>
+// Groups of eight lanes (thin waves): the value of a group's first lane in all of them, and the OR of all of them in the
+// first - both on the DPP network (VALU only).  Every lane of the wave must be active.
 __device__ __forceinline__ uint32_t group_first(uint32_t v) {
-    if (L == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xa0, 0xf, 0xf, false); // quad_perm [0,0,2,2]
     const uint32_t q = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x00, 0xf, 0xf, false);  // quad_perm [0,0,0,0]
-    if (L == 4) return q;
     const uint32_t h = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0x114, 0xf, 0xf, false); // row_shr:4
     return (__lane_id() & 4u) ? h : q;
 }
-template <int L>
 __device__ __forceinline__ uint32_t group_or_to_first(uint32_t v) {
     v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true); // row_shl:1 (0 past the row's end)
-    if (L >= 4) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x102, 0xf, 0xf, true); // row_shl:2
-    if (L >= 8) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xf, 0xf, true); // row_shl:4
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x102, 0xf, 0xf, true); // row_shl:2
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xf, 0xf, true); // row_shl:4
     return v; // (complete in the first lane of every group; the others hold partial ORs)
 }
 
@@ -491,6 +493,55 @@ __device__ __forceinline__ void sincos_det(float theta, float &s, float &c) {
     default: s = -cp; c = sp; break;
     }
 }
+
+// An instance's world-to-object rows r0, r1, r2 ({m0 m1 m2 t} each), stated once for the two walks, the refill and the small
+// kernels below.  The world ray (wo, wd) in the instance's object space: three rows on the origin, assigned to ox, oy, oz, and
+// their 3x3 part on the direction, DECLARED here as dx, dy, dz - not renormalised, so t keeps its world-space meaning (the TODO
+// at query_tlas.hlsl:433).  Text: as a function the two-level service walk comes out in other registers.
+#define TRX_RAY_TO_OBJECT(r0, r1, r2, wox, woy, woz, wdx, wdy, wdz, ox, oy, oz, dx, dy, dz) \
+    ox = ((r0.x * wox + r0.y * woy) + r0.z * woz) + r0.w;                                   \
+    oy = ((r1.x * wox + r1.y * woy) + r1.z * woz) + r1.w;                                   \
+    oz = ((r2.x * wox + r2.y * woy) + r2.z * woz) + r2.w;                                   \
+    const float dx = (r0.x * wdx + r0.y * wdy) + r0.z * wdz;                                \
+    const float dy = (r1.x * wdx + r1.y * wdy) + r1.z * wdz;                                \
+    const float dz = (r2.x * wdx + r2.y * wdy) + r2.z * wdz;
+// An object-space normal in world space: the transpose of the rows' 3x3 part (not normalised).
+__device__ __forceinline__ float3 normal_to_world(const float4 r0, const float4 r1, const float4 r2, float nx, float ny, float nz) {
+    return make_float3((r0.x * nx + r1.x * ny) + r2.x * nz, (r0.y * nx + r1.y * ny) + r2.y * nz, (r0.z * nx + r1.z * ny) + r2.z * nz);
+}
+
+// The AO ray of a primary hit (rt_gpu_software.hlsl:105-121), stated once for the refill of k_trace<kModeAo / kModeFused>
+// (trace_refill.inc) and for k_ao_rays.  In: the hit triangle's normal n (world space, any length), the primary ray's unit
+// direction d, the hit's t, the eye, ao_eps, the pixel and the noise seed.  Out: the origin o - the hit point pulled back by
+// ao_eps - and, in d, the unit direction - cosine-weighted around n flipped toward the viewer.  n comes out normalised and
+// flipped.  Text, not a function, for the reason TRX_NODE_FRAME is: as a function the refill's registers and loads come out
+// in another order in every AO kernel; the arguments are evaluated where the text names them.
+#define TRX_AO_RAY(nx, ny, nz, dx, dy, dz, t, eye, ao_eps, px, py, seed, ox, oy, oz)                        \
+    const float ninv_ = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));                                         \
+    nx *= ninv_; ny *= ninv_; nz *= ninv_;                                                                  \
+    const float nd_ = (nx * -dx + ny * -dy) + nz * -dz;                                                     \
+    const float sg_ = copysignf(1.0f, nd_);                                                                 \
+    nx *= sg_; ny *= sg_; nz *= sg_;                                                                        \
+    ox = (eye[0] + dx * t) - dx * ao_eps;                                                                   \
+    oy = (eye[1] + dy * t) - dy * ao_eps;                                                                   \
+    oz = (eye[2] + dz * t) - dz * ao_eps;                                                                   \
+    const float u1_ = hash_noise(px, py, seed);                                                             \
+    const float u2_ = hash_noise(px, py, seed + 1024u);                                                     \
+    const float rr_ = sqrtf(u1_);                                                                           \
+    const float theta_ = u2_ * 6.28318530717958647692f;                                                     \
+    float sn_, cs_;                                                                                         \
+    sincos_det(theta_, sn_, cs_);                                                                           \
+    const float lx_ = rr_ * cs_, ly_ = rr_ * sn_, lz_ = sqrtf(fmaxf(0.0f, 1.0f - u1_));                     \
+    const float sign_ = nz >= 0.0f ? 1.0f : -1.0f;                                                          \
+    const float aa_ = -1.0f / (sign_ + nz);                                                                 \
+    const float bb_ = nx * ny * aa_;                                                                        \
+    const float b1x_ = 1.0f + sign_ * nx * nx * aa_, b1y_ = sign_ * bb_, b1z_ = -sign_ * nx;                \
+    const float b2x_ = bb_, b2y_ = sign_ + ny * ny * aa_, b2z_ = -ny;                                       \
+    dx = (b1x_ * lx_ + b2x_ * ly_) + nx * lz_;                                                              \
+    dy = (b1y_ * lx_ + b2y_ * ly_) + ny * lz_;                                                              \
+    dz = (b1z_ * lx_ + b2z_ * ly_) + nz * lz_;                                                              \
+    const float dinv_ = 1.0f / sqrtf(dot3(dx, dy, dz, dx, dy, dz));                                         \
+    dx *= dinv_; dy *= dinv_; dz *= dinv_;
 
 __device__ __forceinline__ uint32_t read_xcc_id() {
     uint32_t x;
@@ -772,10 +823,22 @@ int node_variant(uint32_t sem) {
     return ((sem & TRX_SEM_NODE_RCP) ? 1 : 0) | ((sem & TRX_SEM_NODE_FMA) ? 2 : 0);
 }
 
+// The pixel of lane k of a shard's local tile, for the small kernels below (the refill of k_trace states it with div_uniform,
+// trace_refill.inc): false where the tile's 8x8 block leaves the image.  rec = the pixel's record, laid out by the shard like
+// the hit buffers.
+__device__ __forceinline__ bool tile_pixel(const TileGeom &G, uint32_t local_tile, uint32_t k, uint32_t &px, uint32_t &py, uint32_t &rec) {
+    const uint32_t tile = local_tile * G.shard_count + G.shard_index;
+    const uint32_t ty = tile / G.tiles_x;
+    px = (tile - ty * G.tiles_x) * 8u + (k & 7u);
+    py = ty * 8u + (k >> 3);
+    rec = G.compact ? local_tile * 64u + k : py * G.width + px;
+    return px < G.width && py < G.height;
+}
+
 // Hit attributes (include/trx.h, trx_hit_attr): one lane per hit record.  The ray the committing triangle test saw is
 // rebuilt - the explicit ray, or the primary ray of the record's pixel; with instance transforms the world ray as given
-// through the instance's world-to-object rows (trace_walk_plain.inc) - and the test's u, v are recomputed with
-// intersect_tri's operations; the normal is the AO pass's before its flip (trace_refill.inc).  A gather: 8 B of hit,
+// through the instance's world-to-object rows (TRX_RAY_TO_OBJECT, as the walks do) - and the test's u, v are recomputed with
+// intersect_tri's operations, restated here; the normal is the AO pass's before its flip (normal_to_world, as the refill does).  A gather: 8 B of hit,
 // 4 B of instance id, 48 B of triangle (and 48 B of rows) per record, 24 B written.  Primary frames are walked in the
 // tile order of the trace (64 lanes = one 8x8 tile), so a wave's hits are the same tile's.
 template <int MODE>
@@ -785,13 +848,9 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
     uint32_t rec = item;
     float ox, oy, oz, dx, dy, dz;
     if constexpr (MODE == kAttrPrimary) {
-        const uint32_t local_tile = item >> 6, k = item & 63u;
-        const uint32_t tile = local_tile * P.shard_count + P.shard_index;
-        const uint32_t ty = tile / P.tiles_x;
-        const uint32_t px = (tile - ty * P.tiles_x) * 8u + (k & 7u), py = ty * 8u + (k >> 3);
-        if (px >= P.width || py >= P.height) return; // (the trace writes no record for it either)
-        if (!P.compact) rec = py * P.width + px;
-        primary_dir(P.view, P.width, P.height, px, py, dx, dy, dz);
+        uint32_t px, py;
+        if (!tile_pixel(P.geom, item >> 6, item & 63u, px, py, rec)) return; // (the trace writes no record for it either)
+        primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
         ox = P.view.eye[0]; oy = P.view.eye[1]; oz = P.view.eye[2];
     } else {
         const float4 *rp = reinterpret_cast<const float4 *>(P.rays + item);
@@ -819,12 +878,8 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
         nx = a.w; ny = b.w; nz = c4.w;
         if (P.inst_xform) {
             // the object-space ray the BLAS walk tested with
-            const float tox = ((r0.x * ox + r0.y * oy) + r0.z * oz) + r0.w;
-            const float toy = ((r1.x * ox + r1.y * oy) + r1.z * oz) + r1.w;
-            const float toz = ((r2.x * ox + r2.y * oy) + r2.z * oz) + r2.w;
-            const float tdx = (r0.x * dx + r0.y * dy) + r0.z * dz;
-            const float tdy = (r1.x * dx + r1.y * dy) + r1.z * dz;
-            const float tdz = (r2.x * dx + r2.y * dy) + r2.z * dz;
+            float tox, toy, toz;
+            TRX_RAY_TO_OBJECT(r0, r1, r2, ox, oy, oz, dx, dy, dz, tox, toy, toz, tdx, tdy, tdz)
             ox = tox; oy = toy; oz = toz;
             dx = tdx; dy = tdy; dz = tdz;
         }
@@ -843,11 +898,8 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
         u = un * inv_det;
         v = vn * inv_det;
         if (P.inst_xform) {
-            // object-space normal -> world: transpose of world-to-object
-            const float wx = (r0.x * nx + r1.x * ny) + r2.x * nz;
-            const float wy = (r0.y * nx + r1.y * ny) + r2.y * nz;
-            const float wz = (r0.z * nx + r1.z * ny) + r2.z * nz;
-            nx = wx; ny = wy; nz = wz;
+            const float3 w = normal_to_world(r0, r1, r2, nx, ny, nz);
+            nx = w.x; ny = w.y; nz = w.z;
         }
         const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
         nx *= ninv; ny *= ninv; nz *= ninv;
@@ -862,21 +914,10 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
     P.out[rec] = out;
 }
 
-// AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility_dev; kernels.h, AoRaysParams).  The pixel of a
-// lane: false where the tile's 8x8 block leaves the image.  rec = the pixel's record, laid out by the shard like the hit buffers.
-__device__ __forceinline__ bool ao_pixel(const AoRaysParams &P, uint32_t local_tile, uint32_t k, uint32_t &px, uint32_t &py, uint32_t &rec) {
-    const uint32_t tile = local_tile * P.shard_count + P.shard_index;
-    const uint32_t ty = tile / P.tiles_x;
-    px = (tile - ty * P.tiles_x) * 8u + (k & 7u);
-    py = ty * 8u + (k >> 3);
-    rec = P.compact ? local_tile * 64u + k : py * P.width + px;
-    return px < P.width && py < P.height;
-}
-
+// AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility_dev; kernels.h, AoRaysParams).
 // The AO ray of every (tile, sample, pixel) as an explicit ray: what the refill of k_trace<kModeAo> builds for that pixel
-// and seed (trace_refill.inc), operation for operation with the same device functions - primary_dir, the normal through the
-// instance's rows and flipped toward the viewer, the origin pulled back by ao_eps, hash_noise, sincos_det, the basis, the
-// final normalise - with tmin = 0 and tmax = the AO radius.  A pixel whose primary record is a miss gets the inert ray (all
+// and seed (trace_refill.inc) through the same statements - primary_dir, normal_to_world, TRX_AO_RAY - with tmin = 0 and
+// tmax = the AO radius.  Its own: the addressing and the inert ray - a pixel whose primary record is a miss gets it (all
 // words 0 but tmax = -1: no walk commits a hit on it, every walk starts from min(tmax, FLT_MAX)).  A streaming kernel: 8 B of
 // primary record, 48 B of triangle (and 48 B of rows) read per ray, 32 B written.
 __global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
@@ -885,7 +926,7 @@ __global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
     const uint32_t unit = item >> 6, k = item & 63u;
     const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
     uint32_t px, py, rec;
-    const bool inside = ao_pixel(P, P.tile0 + lt, k, px, py, rec);
+    const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
     if (!inside && !P.scratch) return; // (the trace writes no record for it either)
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
     trx_hit ph;
@@ -894,46 +935,20 @@ __global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
     if (inside) ph = P.primary[rec];
     if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
         float dx, dy, dz;
-        primary_dir(P.view, P.width, P.height, px, py, dx, dy, dz);
+        primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
         const float4 *tp = P.tris + (size_t)ph.prim * 3;
         float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
         if (P.inst_xform) {
             const uint32_t pi = P.primary_inst[rec];
             if (pi != TRX_INVALID) {
                 const float4 *m = P.inst_xform + (size_t)pi * 3;
-                const float4 r0 = m[0], r1 = m[1], r2 = m[2];
-                const float ax = (r0.x * nx + r1.x * ny) + r2.x * nz;
-                const float ay = (r0.y * nx + r1.y * ny) + r2.y * nz;
-                const float az = (r0.z * nx + r1.z * ny) + r2.z * nz;
-                nx = ax; ny = ay; nz = az;
+                const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
+                nx = w.x; ny = w.y; nz = w.z;
             }
         }
-        const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
-        nx *= ninv; ny *= ninv; nz *= ninv;
-        const float nd = (nx * -dx + ny * -dy) + nz * -dz;
-        const float sg = copysignf(1.0f, nd);
-        nx *= sg; ny *= sg; nz *= sg;
-        a.x = (P.view.eye[0] + dx * ph.t) - dx * P.ao_eps;
-        a.y = (P.view.eye[1] + dy * ph.t) - dy * P.ao_eps;
-        a.z = (P.view.eye[2] + dz * ph.t) - dz * P.ao_eps;
         const uint32_t seed = P.frame + sample;
-        const float u1 = hash_noise(px, py, seed);
-        const float u2 = hash_noise(px, py, seed + 1024u);
-        const float rr = sqrtf(u1);
-        const float theta = u2 * 6.28318530717958647692f;
-        float sn, cs;
-        sincos_det(theta, sn, cs);
-        const float lx = rr * cs, ly = rr * sn, lz = sqrtf(fmaxf(0.0f, 1.0f - u1));
-        const float sign = nz >= 0.0f ? 1.0f : -1.0f;
-        const float aa = -1.0f / (sign + nz);
-        const float bb = nx * ny * aa;
-        const float b1x = 1.0f + sign * nx * nx * aa, b1y = sign * bb, b1z = -sign * nx;
-        const float b2x = bb, b2y = sign + ny * ny * aa, b2z = -ny;
-        dx = (b1x * lx + b2x * ly) + nx * lz;
-        dy = (b1y * lx + b2y * ly) + ny * lz;
-        dz = (b1z * lx + b2z * ly) + nz * lz;
-        const float dinv = 1.0f / sqrtf(dot3(dx, dy, dz, dx, dy, dz));
-        b.x = dx * dinv; b.y = dy * dinv; b.z = dz * dinv;
+        TRX_AO_RAY(nx, ny, nz, dx, dy, dz, ph.t, P.view.eye, P.ao_eps, px, py, seed, a.x, a.y, a.z)
+        b.x = dx; b.y = dy; b.z = dz;
         b.w = P.tmax;
     }
     float4 *out = reinterpret_cast<float4 *>(P.rays + (P.scratch ? item : rec));
@@ -948,7 +963,7 @@ __global__ void __launch_bounds__(256) k_ao_reduce(const AoRaysParams P) {
     if (item >= P.n_tiles * 64u) return;
     const uint32_t lt = item >> 6, k = item & 63u;
     uint32_t px, py, rec;
-    if (!ao_pixel(P, P.tile0 + lt, k, px, py, rec)) return;
+    if (!tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec)) return;
     const uint32_t base = lt * P.n_samples * 64u + k;
     const bool surface = !(P.rays[base].tmax < 0.0f);
     uint32_t n = 0u;

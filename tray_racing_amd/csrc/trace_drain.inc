@@ -25,8 +25,7 @@
             merge_open = false; // one offer per wave
             if (old != 0u) { // the first wave has left: finish them here (the parking area covered this wave's ray copies)
                 if (has_ray) {
-                    lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-                    lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f);
+                    TRX_PUBLISH_RAY();
                 }
                 return false;
             }
@@ -51,8 +50,7 @@
                 }
                 const uint32_t from = m[20];
                 for (uint32_t k = 0; k < sp; k++) lds_st(&lds_stack[k * kWave + lane], merge_stack1[k * kWave + from]);
-                lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-                lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f);
+                TRX_PUBLISH_RAY();
                 fetched = false;
                 overflow = 0u;
                 has_ray = true;

@@ -224,38 +224,11 @@
                                     const uint32_t pi = kFused ? hit_inst : R.primary_inst[out_index - frame_base];
                                     if (pi != TRX_INVALID) {
                                         const float4 *m = R.inst_xform + (size_t)pi * 3;
-                                        const float4 r0 = m[0], r1 = m[1], r2 = m[2];
-                                        const float ax = (r0.x * nx + r1.x * ny) + r2.x * nz;
-                                        const float ay = (r0.y * nx + r1.y * ny) + r2.y * nz;
-                                        const float az = (r0.z * nx + r1.z * ny) + r2.z * nz;
-                                        nx = ax; ny = ay; nz = az;
+                                        const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
+                                        nx = w.x; ny = w.y; nz = w.z;
                                     }
                                 }
-                                const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
-                                nx *= ninv; ny *= ninv; nz *= ninv;
-                                const float nd = (nx * -dx + ny * -dy) + nz * -dz;
-                                const float sg = copysignf(1.0f, nd);
-                                nx *= sg; ny *= sg; nz *= sg;
-                                r.ox = (view.eye[0] + dx * ph.t) - dx * R.ao_eps;
-                                r.oy = (view.eye[1] + dy * ph.t) - dy * R.ao_eps;
-                                r.oz = (view.eye[2] + dz * ph.t) - dz * R.ao_eps;
-                                const float u1 = hash_noise(px, py, seed);
-                                const float u2 = hash_noise(px, py, seed + 1024u);
-                                const float rr = sqrtf(u1);
-                                const float theta = u2 * 6.28318530717958647692f;
-                                float sn, cs;
-                                sincos_det(theta, sn, cs);
-                                const float lx = rr * cs, ly = rr * sn, lz = sqrtf(fmaxf(0.0f, 1.0f - u1));
-                                const float sign = nz >= 0.0f ? 1.0f : -1.0f;
-                                const float a = -1.0f / (sign + nz);
-                                const float bb = nx * ny * a;
-                                const float b1x = 1.0f + sign * nx * nx * a, b1y = sign * bb, b1z = -sign * nx;
-                                const float b2x = bb, b2y = sign + ny * ny * a, b2z = -ny;
-                                dx = (b1x * lx + b2x * ly) + nx * lz;
-                                dy = (b1y * lx + b2y * ly) + ny * lz;
-                                dz = (b1z * lx + b2z * ly) + nz * lz;
-                                const float dinv = 1.0f / sqrtf(dot3(dx, dy, dz, dx, dy, dz));
-                                dx *= dinv; dy *= dinv; dz *= dinv;
+                                TRX_AO_RAY(nx, ny, nz, dx, dy, dz, ph.t, view.eye, R.ao_eps, px, py, seed, r.ox, r.oy, r.oz)
                                 ok = true;
                             } else if (!kFused) { // (a fused frame writes its AO misses where the primary ray ends)
                                 trx_hit miss;
@@ -274,8 +247,7 @@
                 if (kFused) pend = false;
                 if (ok) {
                     finish_ray_dir<(NODE & 1) == 0>(r, dx, dy, dz);
-                    lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-                    lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f);
+                    TRX_PUBLISH_RAY();
                     prim = TRX_INVALID;
                     sp = 0;
                     steps = trip; // the wave trip this ray starts at

@@ -92,5 +92,5 @@
         } else {
             __syncthreads(); // (the porter has set the mailboxes' numbers)
             svc_seq = (lane >> 3) < kSvcRays ? svc_box[16u * (lane >> 3) + 12u] : 0u;
-            thin_walk(std::integral_constant<int, 8>{});
+            thin_walk();
         }

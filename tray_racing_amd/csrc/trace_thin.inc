@@ -4,8 +4,9 @@
     // drain), and at the end those rays sit one or two to a wave: the wave then issues alone on its SIMD, one
     // instruction every four to five cycles whatever the instruction is, so a ray's trip costs its INSTRUCTION COUNT -
     // 213 vector instructions for the node test of one lane while 63 lanes idle.  So once a dry wave is down to 8 rays
-    // they are moved to lanes 0, 8, 16 ... and every ray gets L = 8 lanes (the code is generic in L = 2, 4, 8; only 8
-    // ships, see thin_all): lane j of a group tests children j 8/L ... of the node (their plane bytes,
+    // they are moved to lanes 0, 8, 16 ... and every ray gets L = 8 lanes (four and two lanes to a ray from 16 and 32 rays
+    // on were built and measured as well: the earlier steps cost what they gain, profiles/r04_thin_waves.log,
+    // r04_ab_procs_11_thin_levels.log): lane j of a group tests child j of the node (its plane bytes,
     // loaded by address; the same IEEE operations as the per-lane test: node_children_intersect),
     // the contributions are ORed on the DPP network, and a leaf's triangles are tested L at a time and folded
     // into the ray's 64-bit {t, sequence} key with the same LDS atomic min as the cooperative rounds - node order,
@@ -20,10 +21,8 @@
         return exhausted && alive != 0u && alive <= (P.thin_max < kHold ? P.thin_max : kHold) && !(kMerge && merge_open) &&
                __ballot(has_ray && sp > (uint32_t)kLdsStack) == 0ull && !(kFused && __ballot(pend) != 0ull);
     };
-    auto thin_walk = [&](auto lanes_per_ray) {
-        constexpr uint32_t L = (uint32_t)decltype(lanes_per_ray)::value; // lanes to a ray: 2, 4 or 8
-        constexpr uint32_t C = 8u / L;                                   // children of a node to a lane
-        constexpr uint32_t kCap = (uint32_t)kWave / L;                   // rays the wave holds this way
+    auto thin_walk = [&]() {
+        constexpr uint32_t L = 8u; // lanes to a ray: one to a child of a node
         const uint32_t sub = lane & (L - 1u), first = lane & ~(L - 1u);
         {   // ---- move ray k (in lane order) to lane L k, stack column and all; give its L - 1 helpers the ray
             const unsigned long long act = __ballot(has_ray);
@@ -74,12 +73,9 @@
                 cur = make_uint2(0u, 0u);
                 if (!filled) r.oct_inv4 &= 0x3fffffffu; // (a group without a ray must not veto the literal-division shortcuts)
             }
-            if (owner) {
-                lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-                lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f);
-            }
+            if (owner) TRX_PUBLISH_RAY();
             fetched = false;
-            __builtin_amdgcn_s_setprio(L == 8u ? 3 : 2);
+            __builtin_amdgcn_s_setprio(3);
         }
         unsigned long long *const lds_key = reinterpret_cast<unsigned long long *>(lds_res);
         // The trip is rotated like the pipelined walk's, and one step further: (1) the ray's next node is chosen and its
@@ -104,8 +100,8 @@
         auto request_triangles = [&]() { // (5): the group's pending triangle group, and this lane's record of its first L
             cnt = 0u;
             if (__ballot(ptri.y != 0u) == 0ull) return; // (most trips of a handful of rays find no leaf)
-            gx = group_first<(int)L>(ptri.x);
-            gy = group_first<(int)L>(ptri.y);
+            gx = group_first(ptri.x);
+            gy = group_first(ptri.y);
             cnt = (uint32_t)__popc(gy);
             if (kPre && sub < cnt) {
                 pre_local = select_from_top(gy, sub); // (kept for (2): the search is thirty-five instructions of a lone wave's trip)
@@ -116,8 +112,7 @@
             }
         };
         request_triangles(); // (a wave that comes from the pipelined walk brings pending triangle groups)
-        // wave-uniform: what is in flight is finished, then out - a fused frame's primary ray has hit, or the rays have
-        // become few enough for twice the lanes each
+        // wave-uniform: what is in flight is finished, then out - a fused frame's primary ray has hit
         bool leaving = false;
         // Two-level scenes (the ray service only): the group's world-space ray, to come back to when a BLAS is left and to
         // transform into the next instance's space (trace_walk_plain.inc keeps it in the wave's HBM area; here the eight
@@ -137,7 +132,6 @@
             trip++;
             if constexpr (MODE == kModeService) {
                 // ---- (0) the ray service: a group without a ray looks into its mailbox (kernels.h, kSvcRays)
-                static_assert(L == 8u, "the ray service walks eight lanes to a ray");
                 const uint32_t g = lane >> 3;
                 const bool gfree = g < kSvcRays && ((__ballot(has_ray) >> first) & 1ull) == 0ull; // (the upper groups have no slots)
                 uint32_t in_seq = svc_seq;
@@ -198,16 +192,17 @@
             }
             const bool gstep = ((__ballot(stepping) >> first) & 1ull) != 0ull;
             if (gstep) {
-                const uint4 *np = P.nodes + (size_t)group_first<(int)L>(node_index) * 5;
-                const uint8_t *nb = reinterpret_cast<const uint8_t *>(np) + sub * C;
+                const uint4 *np = P.nodes + (size_t)group_first(node_index) * 5;
+                const uint8_t *nb = reinterpret_cast<const uint8_t *>(np) + sub;
                 n0 = np[0];
                 n1 = np[1];
-                // the plane bytes of this lane's C children by address: min planes at +32 / +48 / +64, max planes eight bytes
+                // the plane bytes of this lane's child by address: min planes at +32 / +48 / +64, max planes eight bytes
                 // on; near = max where d < 0
                 const uint32_t xn = r.dx < 0.0f ? 8u : 0u, yn = r.dy < 0.0f ? 8u : 0u, zn = r.dz < 0.0f ? 8u : 0u;
-                q0 = load_bytes<(int)C>(nb + 32u + xn); q1 = load_bytes<(int)C>(nb + 32u + (xn ^ 8u));
-                q2 = load_bytes<(int)C>(nb + 48u + yn); q3 = load_bytes<(int)C>(nb + 48u + (yn ^ 8u));
-                q4 = load_bytes<(int)C>(nb + 64u + zn); q5 = load_bytes<(int)C>(nb + 64u + (zn ^ 8u));
+                const uint8_t *const bx = nb + 32u, *const by = nb + 48u, *const bz = nb + 64u;
+                q0 = bx[xn]; q1 = bx[xn ^ 8u];
+                q2 = by[yn]; q3 = by[yn ^ 8u];
+                q4 = bz[zn]; q5 = bz[zn ^ 8u];
             }
             SVC_MARK(1);
             // ---- (2) triangles of the node tested in the previous trip, L at a time; the first L are here already
@@ -273,18 +268,18 @@
             // that every ray left holds a node group and nothing pending: the state the other walks expect.)
             if (leaving) break;
             const unsigned long long alive_mask = __ballot(has_ray);
-            if ((kFused && __ballot(pend) != 0ull) || (L < 8u && (uint32_t)__popcll(alive_mask) <= kCap / 2u)) leaving = true;
-            // ---- (4) node test, C children per lane, for the rays still there
+            if (kFused && __ballot(pend) != 0ull) leaving = true;
+            // ---- (4) node test, a child per lane, for the rays still there
             const bool galive = ((alive_mask >> first) & 1ull) != 0ull;
-            const float gt = __uint_as_float(group_first<(int)L>(__float_as_uint(t)));
+            const float gt = __uint_as_float(group_first(__float_as_uint(t)));
             const int pow2 = (NODE & 1) ? 0 : pow2_exact(P, r, gstep && galive);
             uint32_t contrib = 0u;
             if (gstep && galive) {
-                const uint32_t meta = (sub * C < 4u ? n1.z : n1.w) >> (8u * ((sub * C) & 3u));
+                const uint32_t meta = (sub < 4u ? n1.z : n1.w) >> (8u * (sub & 3u));
                 const uint32_t q[6] = {q0, q1, q2, q3, q4, q5};
-                contrib = node_children_intersect<NODE, (int)C>(r, gt, n0, meta, q, pow2);
+                contrib = node_children_intersect<NODE, 1>(r, gt, n0, meta, q, pow2);
             }
-            const uint32_t hitmask = group_or_to_first<(int)L>(contrib);
+            const uint32_t hitmask = group_or_to_first(contrib);
             if (stepping && has_ray) {
                 cur.x = n1.x;
                 ptri.x = n1.y;
@@ -340,18 +335,12 @@
                     }
                 }
                 if (P.inst_xform) {
-                    word = group_first<(int)L>(word);
+                    word = group_first(word);
                     if (word & 2u) {
-                        // the ray in the instance's object space; the direction is not renormalised, so t keeps its
-                        // world-space meaning (the TODO at query_tlas.hlsl:433) - trace_walk_plain.inc's operations
+                        // the ray in the instance's object space
                         const float4 *m = P.inst_xform + (size_t)(word >> 2) * 3;
                         const float4 r0 = m[0], r1 = m[1], r2 = m[2];
-                        r.ox = ((r0.x * wox + r0.y * woy) + r0.z * woz) + r0.w;
-                        r.oy = ((r1.x * wox + r1.y * woy) + r1.z * woz) + r1.w;
-                        r.oz = ((r2.x * wox + r2.y * woy) + r2.z * woz) + r2.w;
-                        const float odx = (r0.x * wdx + r0.y * wdy) + r0.z * wdz;
-                        const float ody = (r1.x * wdx + r1.y * wdy) + r1.z * wdz;
-                        const float odz = (r2.x * wdx + r2.y * wdy) + r2.z * wdz;
+                        TRX_RAY_TO_OBJECT(r0, r1, r2, wox, woy, woz, wdx, wdy, wdz, r.ox, r.oy, r.oz, odx, ody, odz)
                         finish_ray_dir<(NODE & 1) == 0>(r, odx, ody, odz);
                     } else if (word & 1u) { // "Reset Ray to untransformed version" (query_tlas.hlsl:484)
                         r.ox = wox; r.oy = woy; r.oz = woz;
@@ -381,8 +370,6 @@
         }
     };
     // The thin walk of a dry wave; returns with no ray left or, fused frames, with a lane waiting to become an AO ray.
-    // (four and two lanes to a ray from 16 and 32 rays on as well: the earlier steps cost what they gain,
-    // profiles/r04_thin_waves.log, r04_ab_procs_11_thin_levels.log)
     auto thin_all = [&]() {
-        if (!(kFused && __ballot(pend) != 0ull) && __ballot(has_ray) != 0ull) thin_walk(std::integral_constant<int, 8>{});
+        if (!(kFused && __ballot(pend) != 0ull) && __ballot(has_ray) != 0ull) thin_walk();
     };

@@ -195,21 +195,14 @@
                     bvh_off = P.inst[gidx];
                     cur_inst = gidx;
                     if (P.inst_xform) {
-                        // the ray in the instance's object space; the direction is not renormalised, so t keeps
-                        // its world-space meaning (the TODO at query_tlas.hlsl:433)
+                        // the ray in the instance's object space
                         const float4 *m = P.inst_xform + (size_t)gidx * 3;
                         const float4 r0 = m[0], r1 = m[1], r2 = m[2];
                         const float wox = wray[0 * kWave + lane], woy = wray[1 * kWave + lane], woz = wray[2 * kWave + lane];
                         const float wdx = wray[3 * kWave + lane], wdy = wray[4 * kWave + lane], wdz = wray[5 * kWave + lane];
-                        r.ox = ((r0.x * wox + r0.y * woy) + r0.z * woz) + r0.w;
-                        r.oy = ((r1.x * wox + r1.y * woy) + r1.z * woz) + r1.w;
-                        r.oz = ((r2.x * wox + r2.y * woy) + r2.z * woz) + r2.w;
-                        const float odx = (r0.x * wdx + r0.y * wdy) + r0.z * wdz;
-                        const float ody = (r1.x * wdx + r1.y * wdy) + r1.z * wdz;
-                        const float odz = (r2.x * wdx + r2.y * wdy) + r2.z * wdz;
+                        TRX_RAY_TO_OBJECT(r0, r1, r2, wox, woy, woz, wdx, wdy, wdz, r.ox, r.oy, r.oz, odx, ody, odz)
                         finish_ray_dir<(NODE & 1) == 0>(r, odx, ody, odz);
-                        lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-                        lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f);
+                        TRX_PUBLISH_RAY();
                     }
                     // the walk of the BLAS starts at its node 0 (query_tlas.hlsl:443) - or, for a TLAS primitive that
                     // stands for a SUBTREE of its BLAS (re-braided scenes, trx_scene_set_instance_entry_nodes), at
@@ -234,8 +227,7 @@
                             if (P.inst_xform) { // "Reset Ray to untransformed version" (query_tlas.hlsl:484)
                                 r.ox = wray[0 * kWave + lane]; r.oy = wray[1 * kWave + lane]; r.oz = wray[2 * kWave + lane];
                                 finish_ray_dir<(NODE & 1) == 0>(r, wray[3 * kWave + lane], wray[4 * kWave + lane], wray[5 * kWave + lane]);
-                                lds_ray[2u * lane] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-                                lds_ray[2u * lane + 1u] = make_float4(r.dx, r.dy, r.dz, 0.0f);
+                                TRX_PUBLISH_RAY();
                             }
                         }
                         cur = stack_pop();
