@@ -503,6 +503,69 @@ int trx_trace_ao_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t
                                 float ao_eps, float ao_radius, const trx_hit *d_primary,
                                 const uint32_t *d_primary_inst, uint8_t *d_unoccluded, void *stream);
 
+/* ---- the frame's image: the AO term filtered, the frame shaded to RGBA8 on the device ------------------------------------
+ * The reference's pixel program ends by storing a colour into an rgba8 output_texture in the same dispatch
+ * (rt_gpu_software.hlsl:91,130-142).  These are the image passes after the walk: with them a frame leaves the device as
+ * 4 bytes per pixel of finished image instead of 16 bytes per pixel of records.  None of them reads scene data; they take
+ * the scene for its device and its launch order.
+ * Ordering: as for the attribute pass - every launch takes a launch slot of the scene, so a trx_scene_refit* called after
+ * one of these calls has returned waits for it.
+ *
+ * The edge-aware AO filter.  All buffers hold WHOLE-IMAGE records in image layout (y * width + x): what
+ * trx_trace_primary*_dev, trx_hit_attributes_primary_dev and trx_trace_ao_visibility_dev write with shard {0, 1,
+ * TRX_LAYOUT_IMAGE}.  There is no shard argument and no sharded form: a pixel's neighbours belong to other shards, and a
+ * rank would need its neighbours' halo - a multi-GPU host filters after trx_assemble_frames.
+ *  - A pixel p is a SURFACE pixel iff t_p < FLT_MAX and prim_p != 0xFFFFFFFF.  Any other pixel gets {0, 0}.
+ *  - A surface pixel p gets the sums over the ACCEPTED pixels q of its (2 * radius + 1)^2 window clipped to the image:
+ *    unoccluded = sum of d_unoccluded[q], samples = n_samples * (number of accepted q).  q is accepted iff it is a surface
+ *    pixel, fabsf(t_q - t_p) <= depth_tol * t_p (every operation rounded once in binary32) and - with d_attr -
+ *    (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z >= normal_cos (no contraction); p itself is accepted unconditionally.
+ *  - radius 0 gives {d_unoccluded[p], n_samples}.  The largest sum is 81 * 255: uint16_t cannot overflow.
+ * Only the comparisons are done in float; the sums are integers.  A renderer's AO term is unoccluded / samples.
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): radius > TRX_MAX_AO_FILTER_RADIUS,
+ * n_samples outside 1..TRX_MAX_AO_SAMPLES, depth_tol negative or NaN (+inf allowed), normal_cos NaN, width * height == 0 or
+ * beyond 2^31 - 1, a null scene, d_primary, d_unoccluded or d_term (d_attr may be NULL: no normal test). */
+typedef struct trx_ao_term {
+    uint16_t unoccluded;
+    uint16_t samples;
+} trx_ao_term;
+#define TRX_MAX_AO_FILTER_RADIUS 4
+int trx_ao_filter_dev(trx_scene *scene, uint32_t width, uint32_t height, const trx_hit *d_primary,
+                      const trx_hit_attr *d_attr, const uint8_t *d_unoccluded, uint32_t n_samples, uint32_t radius,
+                      float depth_tol, float normal_cos, trx_ao_term *d_term, void *stream);
+/* Shading to RGBA8: elementwise over n_records records in ANY layout (image or TRX_LAYOUT_SHARD; the output is laid out
+ * like the input), 4 bytes {c, c, c, 255} per record at d_rgba (n_records * 4 bytes, 4-byte aligned; nothing beyond them is
+ * written).  The colour per record, every division a single IEEE division:
+ *   reference  the reference's shading (src/rt_cpu/rt_cpu.rs:57-85, the end of rt_gpu_software.hlsl): col = 1.0f / t where
+ *              the primary record is a miss (!(t < FLT_MAX); 0 for t = +inf); on a hit col = ao.t / (1.0f + ao.t) where
+ *              ao.t < FLT_MAX, 1 where the AO ray reached nothing.
+ *   counts     TRX_AO_NO_SURFACE gives 0, otherwise col = (float)count / (float)n_samples (n_samples 1..TRX_MAX_AO_SAMPLES).
+ *   term       samples == 0 gives 0, otherwise col = (float)unoccluded / (float)samples.
+ * The code c is what the reference's host computes, on THIS host: (uint8_t)(uint32_t)(powf(col, 2.2f) * 255.0f), 0 for
+ * col < 0 or NaN, 255 for col >= 1.  The device's powf is not the C library's, so the device evaluates no pow: at first
+ * use the library derives thr[1..255], thr[k] the smallest binary32 in [0, 1] whose host code is >= k (bisection over the
+ * bit pattern; thr[0] = 0), and on the device c is the number of k >= 1 with col >= thr[k].  trx_image_code_table hands the
+ * table out (host only, no device needed).
+ * Refused with TRX_ERR_INVALID before anything is enqueued: a null scene or - with n_records != 0 - a null buffer, a
+ * misaligned d_rgba, n_samples outside its range.  n_records == 0 does nothing. */
+int trx_image_code_table(float out_thresholds[256]);
+int trx_shade_reference_dev(trx_scene *scene, const trx_hit *d_primary, const trx_hit *d_ao, uint64_t n_records,
+                            uint8_t *d_rgba, void *stream);
+int trx_shade_ao_counts_dev(trx_scene *scene, const uint8_t *d_unoccluded, uint32_t n_samples, uint64_t n_records,
+                            uint8_t *d_rgba, void *stream);
+int trx_shade_ao_term_dev(trx_scene *scene, const trx_ao_term *d_term, uint64_t n_records, uint8_t *d_rgba, void *stream);
+/* Host-buffer form for a whole image (synchronous, serialised by the per-scene lock like its siblings): only the
+ * width * height * 4 bytes of out_rgba (may be NULL) cross the bus; out_ms is the hipEvent time of all passes.
+ *   n_samples == 0  the primary pass, the closest-hit AO pass under seed frame0, the reference shade (ao_radius,
+ *                   filter_radius, depth_tol and normal_cos are not looked at): the image of trx_trace_primary_ao's records.
+ *   n_samples >= 1  the primary pass and the AO visibility pass (seeds frame0 .., ao_radius as for
+ *                   trx_trace_ao_visibility_dev); then with filter_radius == 0 the counts shade, with filter_radius >= 1
+ *                   the attribute pass, the filter (with normals) and the term shade.
+ * Every argument is validated before the first pass is enqueued. */
+int trx_render_image(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                     uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius, uint32_t filter_radius,
+                     float depth_tol, float normal_cos, uint8_t *out_rgba, float *out_ms);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,

@@ -30,6 +30,7 @@ SEM_CPU = 3
 
 MAX_AO_SAMPLES = 64
 AO_NO_SURFACE = 0xFF
+MAX_AO_FILTER_RADIUS = 4
 
 
 class TrxError(RuntimeError):
@@ -54,6 +55,11 @@ class Hit(C.Structure):
 class HitAttr(C.Structure):
     """trx_hit_attr: barycentrics (u weights v1, v weights v2) and world-space unit geometric normal of a hit."""
     _fields_ = [("u", C.c_float), ("v", C.c_float), ("normal", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class AoTerm(C.Structure):
+    """trx_ao_term: the filtered AO term of a pixel - unoccluded samples over samples of the accepted window pixels."""
+    _fields_ = [("unoccluded", C.c_uint16), ("samples", C.c_uint16)]
 
 
 class RayHit(C.Structure):
@@ -135,6 +141,12 @@ SIGNATURES = {
     "trx_ao_rays_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _f, _f, _P, _P, _P, _P]),
     "trx_trace_ao_visibility_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _u32, _f, _f, _P, _P, _P, _P]),
     "trx_trace_ao_visibility": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, C.POINTER(_f)]),
+    "trx_ao_filter_dev": (_i, [_P, _u32, _u32, _P, _P, _P, _u32, _u32, _f, _f, _P, _P]),
+    "trx_image_code_table": (_i, [_P]),
+    "trx_shade_reference_dev": (_i, [_P, _P, _P, _u64, _P, _P]),
+    "trx_shade_ao_counts_dev": (_i, [_P, _P, _u32, _u64, _P, _P]),
+    "trx_shade_ao_term_dev": (_i, [_P, _P, _u64, _P, _P]),
+    "trx_render_image": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _P, C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),
     "trx_debug_ao_visibility_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, _P, _P,
                                             C.POINTER(_f)]),

@@ -294,6 +294,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     // launch slots claimed so far: stack spill areas and tile-order lists
     std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
     bytes += s->inst_mask.count(); // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
+    bytes += s->image_thr.count() * sizeof(float); // the shade's code thresholds (api_image.cpp)
     for (const Slot &sl : s->slots) {
         bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
         bytes += sl.ao_rays.count() * sizeof(trx_ray) + sl.ao_flags.count(); // the AO visibility pass's scratch (api_ao.cpp)

@@ -1,0 +1,222 @@
+// api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_shade_*_dev / trx_render_image): the edge-aware
+// filter over the AO visibility pass's counts and the shading to RGBA8 (k_ao_filter, k_shade, image.hip), and the table of
+// code thresholds the shade searches instead of evaluating pow.  Image passes after the walk: none reads scene data, but
+// each takes a launch slot of the scene like the attribute pass, so trx_scene_refit waits for them.
+#include "api_internal.h"
+
+#include <cfloat>
+#include <limits>
+
+namespace {
+
+// The reference's colour code on this host (src/rt_cpu/rt_cpu.rs:102-112, cli.cpp save_png), for col in [0, 1].
+uint32_t host_code(float col) { return (uint32_t)(uint8_t)(uint32_t)(::powf(col, 2.2f) * 255.0f); }
+
+// thr[k], k = 1..255: the smallest binary32 in [0, 1] whose host code is >= k, by bisection over the bit pattern (the
+// patterns of the non-negative floats are ordered like their values); thr[0] = 0.
+const float *code_table() {
+    static float thr[256];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const float one = 1.0f;
+        uint32_t one_bits;
+        std::memcpy(&one_bits, &one, 4);
+        thr[0] = 0.0f;
+        for (uint32_t k = 1; k < 256; k++) {
+            if (host_code(one) < k) { // (no colour reaches the code: never the case with a powf that returns 1 for 1)
+                thr[k] = std::numeric_limits<float>::infinity();
+                continue;
+            }
+            uint32_t lo = 0u, hi = one_bits; // code(lo) < k <= code(hi)
+            while (hi - lo > 1u) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                float x;
+                std::memcpy(&x, &mid, 4);
+                if (host_code(x) >= k) hi = mid;
+                else lo = mid;
+            }
+            std::memcpy(&thr[k], &hi, 4);
+        }
+    });
+    return thr;
+}
+
+int check_samples(uint32_t n_samples) {
+    if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    return TRX_OK;
+}
+
+int check_filter(uint32_t radius, float depth_tol, float normal_cos) {
+    if (radius > TRX_MAX_AO_FILTER_RADIUS) return fail(TRX_ERR_INVALID, "filter radius %u beyond %d", radius, TRX_MAX_AO_FILTER_RADIUS);
+    if (!(depth_tol >= 0.0f)) return fail(TRX_ERR_INVALID, "depth_tol %g: must be >= 0 (+inf allowed)", (double)depth_tol);
+    if (normal_cos != normal_cos) return fail(TRX_ERR_INVALID, "normal_cos is NaN");
+    return TRX_OK;
+}
+
+int check_image(uint32_t w, uint32_t h) {
+    const uint64_t n = (uint64_t)w * h;
+    if (n == 0 || n > 0x7fffffffull) return fail(TRX_ERR_INVALID, "image %ux%u", w, h);
+    return TRX_OK;
+}
+
+// A launch slot of the scene for `stream`, then `launch`, then the slot's event: what orders the pass with trx_scene_refit.
+template <typename Launch>
+int enqueue_image(trx_scene *s, hipStream_t stream, bool need_table, Launch launch) {
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (need_table && !s->image_thr) { // first shade on this scene: the code thresholds beside it on its device
+        HIP_TRY(s->image_thr.alloc(256));
+        if (hipError_t e = hipMemcpy(s->image_thr.get(), code_table(), 256 * sizeof(float), hipMemcpyHostToDevice); e != hipSuccess) {
+            s->image_thr.reset();
+            return fail(TRX_ERR_NO_DEVICE, "uploading the code table failed: %s", hipGetErrorString(e));
+        }
+    }
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, stream, slot)) return rc;
+    slot->last_stream = stream;
+    slot->last_use = ++s->launches;
+    if (int rc = launch()) return rc;
+    HIP_TRY(hipEventRecord(slot->done.get(), stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
+// One k_shade pass over n records (launches of at most 2^30), on a launch slot.
+int enqueue_shade(trx_scene *s, ShadeParams base, int mode, uint64_t n, hipStream_t stream) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    if (n == 0) return TRX_OK;
+    if (!base.rgba || (mode == kShadeReference && (!base.primary || !base.ao)) || (mode == kShadeCounts && !base.counts) ||
+        (mode == kShadeTerm && !base.term))
+        return fail(TRX_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(base.rgba) & 3u) return fail(TRX_ERR_INVALID, "d_rgba is not 4-byte aligned");
+    return enqueue_image(s, stream, true, [&]() -> int {
+        const uint64_t chunk = 1ull << 30;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            ShadeParams p = base;
+            p.thr = s->image_thr.get();
+            if (p.primary) p.primary += off;
+            if (p.ao) p.ao += off;
+            if (p.counts) p.counts += off;
+            if (p.term) p.term += off;
+            p.rgba += off * 4;
+            p.n_items = (uint32_t)std::min(chunk, n - off);
+            HIP_TRY(launch_shade(p, mode, stream));
+        }
+        return TRX_OK;
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int trx_image_code_table(float out[256]) {
+    if (!out) return fail(TRX_ERR_INVALID, "null argument");
+    std::memcpy(out, code_table(), 256 * sizeof(float));
+    return TRX_OK;
+}
+
+int trx_ao_filter_dev(trx_scene *s, uint32_t w, uint32_t h, const trx_hit *d_primary, const trx_hit_attr *d_attr,
+                      const uint8_t *d_unoccluded, uint32_t n_samples, uint32_t radius, float depth_tol, float normal_cos,
+                      trx_ao_term *d_term, void *stream) {
+    if (int rc = check_filter(radius, depth_tol, normal_cos)) return rc;
+    if (int rc = check_samples(n_samples)) return rc;
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !d_primary || !d_unoccluded || !d_term) return fail(TRX_ERR_INVALID, "null argument");
+    AoFilterParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.primary = d_primary;
+    p.attr = d_attr;
+    p.counts = d_unoccluded;
+    p.out = d_term;
+    p.width = w;
+    p.height = h;
+    p.n_samples = n_samples;
+    p.radius = radius;
+    p.depth_tol = depth_tol;
+    p.normal_cos = normal_cos;
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        HIP_TRY(launch_ao_filter(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
+int trx_shade_reference_dev(trx_scene *s, const trx_hit *d_primary, const trx_hit *d_ao, uint64_t n, uint8_t *d_rgba, void *stream) {
+    ShadeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.primary = d_primary;
+    p.ao = d_ao;
+    p.rgba = d_rgba;
+    return enqueue_shade(s, p, kShadeReference, n, (hipStream_t)stream);
+}
+
+int trx_shade_ao_counts_dev(trx_scene *s, const uint8_t *d_unoccluded, uint32_t n_samples, uint64_t n, uint8_t *d_rgba, void *stream) {
+    if (int rc = check_samples(n_samples)) return rc;
+    ShadeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.counts = d_unoccluded;
+    p.n_samples = n_samples;
+    p.rgba = d_rgba;
+    return enqueue_shade(s, p, kShadeCounts, n, (hipStream_t)stream);
+}
+
+int trx_shade_ao_term_dev(trx_scene *s, const trx_ao_term *d_term, uint64_t n, uint8_t *d_rgba, void *stream) {
+    ShadeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.term = d_term;
+    p.rgba = d_rgba;
+    return enqueue_shade(s, p, kShadeTerm, n, (hipStream_t)stream);
+}
+
+int trx_render_image(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame0, uint32_t n_samples,
+                     float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos, uint8_t *out_rgba,
+                     float *out_ms) {
+    if (n_samples > TRX_MAX_AO_SAMPLES) return fail(TRX_ERR_INVALID, "n_samples %u outside 0..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    if (n_samples != 0) {
+        if (!(ao_radius > 0.0f)) return fail(TRX_ERR_INVALID, "ao_radius %g: must be > 0 (+inf allowed)", (double)ao_radius);
+        if (filter_radius != 0)
+            if (int rc = check_filter(filter_radius, depth_tol, normal_cos)) return rc;
+    }
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !view) return fail(TRX_ERR_INVALID, "null argument");
+    const uint64_t n = (uint64_t)w * h;
+    const trx_shard whole{0, 1, 0, 0};
+    const bool filter = n_samples != 0 && filter_radius != 0;
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
+    HIP_TRY(hipSetDevice(s->device));
+    // the image scratch: the filter's terms, then the image
+    HIP_TRY(s->scratch_img.grow(n * 8));
+    auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
+    auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
+    // (the counts go where trx_trace_ao_visibility puts them: n bytes of the second record buffer)
+    auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
+    return host_call(
+        s, n, nullptr, 0, filter ? n : 0, out_ms,
+        [&] {
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, s->scratch_a.get(), s->scratch_ia.get(), nullptr);
+            if (rc) return rc;
+            if (n_samples == 0) {
+                rc = trx_trace_ao_inst_dev(s, view, w, h, whole, sem, frame0, ao_eps, s->scratch_a.get(), s->scratch_ia.get(),
+                                           s->scratch_b.get(), s->scratch_ib.get(), nullptr);
+                if (rc) return rc;
+                return trx_shade_reference_dev(s, s->scratch_a.get(), s->scratch_b.get(), n, d_rgba(), nullptr);
+            }
+            rc = trx_trace_ao_visibility_dev(s, view, w, h, whole, sem, frame0, n_samples, ao_eps, ao_radius, s->scratch_a.get(),
+                                             s->scratch_ia.get(), d_counts(), nullptr);
+            if (rc) return rc;
+            if (!filter) return trx_shade_ao_counts_dev(s, d_counts(), n_samples, n, d_rgba(), nullptr);
+            rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_ao_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), d_counts(), n_samples, filter_radius, depth_tol,
+                                   normal_cos, d_term(), nullptr);
+            if (rc) return rc;
+            return trx_shade_ao_term_dev(s, d_term(), n, d_rgba(), nullptr);
+        },
+        [&]() -> int {
+            if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
+}
+
+} // extern "C"

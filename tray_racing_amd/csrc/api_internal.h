@@ -8,6 +8,7 @@
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
 //   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts
+//   api_image.cpp    trx_ao_filter_dev / trx_shade_*_dev / trx_render_image: the image passes after the walk (image.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -37,6 +38,7 @@
 #include "builder.h"
 #include "cwbvh_format.h"
 #include "hip_owned.h"
+#include "image.h"
 #include "kernels.h"
 #include "scenes.h"
 
@@ -198,6 +200,10 @@ struct trx_scene {
     // calls only; host copy and device table, empty = every instance 0xFF
     std::vector<uint8_t> h_inst_mask;
     trxapi::DevBuf<uint8_t> inst_mask;
+    // the frame's image (api_image.cpp): the shade's 256 code thresholds on the scene's device (first shade; under mu), and
+    // trx_render_image's scratch - the filter's terms, then the RGBA8 image (under host_mu)
+    trxapi::DevBuf<float> image_thr;
+    trxapi::DevBuf<uint8_t> scratch_img;
 };
 
 struct trx_bvh {

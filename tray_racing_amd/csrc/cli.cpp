@@ -44,6 +44,10 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // (trx_trace_ao_visibility) instead of t / (1 + t); either flag switches it on (N defaults to 1, R to +inf)
     unsigned ao_samples = 0;
     float ao_radius = 0.0f;
+    // --ao-filter R [--ao-depth-tol x] [--ao-normal-cos c]: with --png --ao-samples N the image is made on the device
+    // (trx_render_image): the counts through the edge-aware filter of radius R (0: unfiltered), shaded to RGBA8 there
+    int ao_filter = -1; // -1: not given, save_png's host loop stays as it is
+    float ao_depth_tol = 0.02f, ao_normal_cos = 0.9f;
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -74,6 +78,8 @@ void usage() {
               "  [--search-distance d] [--search-depth-threshold n] [--sort-precision 64|128] [--split] [--gpu-build]\n"
               "  [--overlap (frames stay on the device, frame i's AO pass under frame i+1's primary pass; reports the average)]\n"
               "  [--ao-samples 1..64] [--ao-radius r] (with --png: AO term = unoccluded samples / N of the any-hit visibility pass)\n"
+              "  [--ao-filter 0..4] [--ao-depth-tol x] [--ao-normal-cos c] (with --png --ao-samples: edge-aware filter of that radius\n"
+              "   over the AO counts, image shaded on the device; only the RGBA8 bytes are copied back)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -114,6 +120,16 @@ Options parse_args(int argc, char **argv) {
             o.ao_radius = (float)std::atof(need(i));
             if (!(o.ao_radius > 0.0f)) die("--ao-radius must be > 0");
         }
+        else if (a == "--ao-filter") {
+            o.ao_filter = std::atoi(need(i));
+            if (o.ao_filter < 0 || o.ao_filter > TRX_MAX_AO_FILTER_RADIUS) die("--ao-filter takes 0.." + std::to_string(TRX_MAX_AO_FILTER_RADIUS));
+        } else if (a == "--ao-depth-tol") {
+            o.ao_depth_tol = (float)std::atof(need(i));
+            if (!(o.ao_depth_tol >= 0.0f)) die("--ao-depth-tol must be >= 0");
+        } else if (a == "--ao-normal-cos") {
+            o.ao_normal_cos = (float)std::atof(need(i));
+            if (o.ao_normal_cos != o.ao_normal_cos) die("--ao-normal-cos must be a number");
+        }
         else if (a == "-h" || a == "--help") {
             usage();
             std::exit(0);
@@ -144,6 +160,7 @@ Options parse_args(int argc, char **argv) {
     if (o.build != "ploc_cwbvh") die("NO BVH BUILDER SPECIFIED (this backend serves --build ploc_cwbvh)"); // src/cwbvh.rs:99
     if (o.cpu) die("--cpu is the reference's own rt_cpu path; the HIP backend has no CPU traversal");
     if (o.hardware) die("--hardware needs ray-tracing hardware; MI355X (CDNA4) has none");
+    if (o.ao_filter >= 0 && o.ao_samples == 0) die("--ao-filter filters the counts of --ao-samples N");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -199,6 +216,14 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         // the AO term a renderer would use: the share of N bounded any-hit AO rays that reach nothing
         const unsigned samples = o.ao_samples ? o.ao_samples : 1u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
+        if (o.ao_filter >= 0) {
+            // the image made on the device: filter and shade there, 4 bytes per pixel back
+            check(trx_render_image(scene, &view, o.width, o.height, o.semantics, frame_count, samples, 0.0001f, radius,
+                                   (uint32_t)o.ao_filter, o.ao_depth_tol, o.ao_normal_cos, rgba.data(), &ms), "png frame");
+            if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
+            if (o.verbose) std::printf("saved %s (device image, filter radius %d, %.3f ms)\n", path.c_str(), o.ao_filter, ms);
+            return;
+        }
         std::vector<uint8_t> counts(n);
         check(trx_trace_ao_visibility(scene, &view, o.width, o.height, o.semantics, frame_count, samples, 0.0001f, radius,
                                       counts.data(), &ms), "png frame");

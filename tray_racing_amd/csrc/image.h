@@ -1,0 +1,42 @@
+// image.h - launch interface between api_image.cpp and the image passes after the walk (image.hip): the edge-aware AO
+// filter and the shading to RGBA8 (include/trx.h, "the frame's image").  No traversal kernel knows about them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/trx.h"
+
+namespace trx {
+
+// k_ao_filter: one workgroup of 256 lanes per kFilterTileW x kFilterTileH pixel tile (a wave = two rows of 32 pixels).
+// The tile and its halo of `radius` pixels on every side are loaded once into LDS, then every lane sums its window.
+constexpr uint32_t kFilterTileW = 32, kFilterTileH = 8;
+constexpr uint32_t kFilterMaxRadius = TRX_MAX_AO_FILTER_RADIUS;
+constexpr uint32_t kFilterMaxCells = (kFilterTileW + 2 * kFilterMaxRadius) * (kFilterTileH + 2 * kFilterMaxRadius); // 640
+struct AoFilterParams {
+    const trx_hit *primary;   // whole image, y * width + x
+    const trx_hit_attr *attr; // or null: no normal test
+    const uint8_t *counts;
+    trx_ao_term *out;
+    uint32_t width, height, n_samples, radius;
+    float depth_tol, normal_cos;
+};
+hipError_t launch_ao_filter(const AoFilterParams &p, hipStream_t stream);
+
+// k_shade: one lane per record, 4 bytes {c, c, c, 255} written per record; c by an 8-step search of the 256 thresholds
+// (trx_image_code_table) each workgroup first copies into LDS.
+enum ShadeMode : int { kShadeReference = 0, kShadeCounts = 1, kShadeTerm = 2 };
+struct ShadeParams {
+    const float *thr;        // 256 floats, device memory
+    const trx_hit *primary;  // kShadeReference
+    const trx_hit *ao;       // kShadeReference
+    const uint8_t *counts;   // kShadeCounts
+    const trx_ao_term *term; // kShadeTerm
+    uint8_t *rgba;
+    uint32_t n_items;
+    uint32_t n_samples;      // kShadeCounts
+};
+hipError_t launch_shade(const ShadeParams &p, int mode, hipStream_t stream);
+
+} // namespace trx

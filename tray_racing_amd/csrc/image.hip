@@ -1,0 +1,156 @@
+// image.hip - gfx950 (MI355X, wave64) image passes after the walk (include/trx.h, "the frame's image"): the edge-aware
+// filter over the AO visibility pass's counts and the shading of a frame's records to RGBA8.  A translation unit of its
+// own: nothing here is seen by kernels.hip, whose instructions stay what they were.
+//
+// Arithmetic contract (DESIGN.md "Numerics"): binary32, no contraction, IEEE divide, dot = (ax*bx + ay*by) + az*bz.  The
+// filter compares in float and sums in integers, the shade divides once and then only compares, so a host twin
+// (tests/image_twin.py) gives the same bits.
+#include "image.h"
+
+#pragma clang fp contract(off)
+
+namespace trx {
+namespace {
+
+#define TRX_F32_MAX 3.402823466e+38f
+#define TRX_INVALID 0xFFFFFFFFu
+
+constexpr uint32_t kNotSurface = 0xFFFFFFFFu; // a cell's count word in LDS: outside the image, or no surface there
+
+// The edge-aware AO filter (trx_ao_filter_dev).  One workgroup per 32 x 8 pixel tile; lane l of the workgroup is pixel
+// (l & 31, l >> 5) of the tile, so a wave is two rows of 32 pixels: its global loads and its store are two runs of
+// consecutive records, and its LDS reads are - per 32-lane half, the unit ds_read_b32 banks over - 32 consecutive
+// dwords of one row, conflict-free whatever the row pitch (32 + 2 * radius dwords).
+//   phase 1: the (32 + 2r) x (8 + 2r) cells of the tile and its halo into LDS as separate arrays (depth, count word and,
+// with normals, three components): every input pixel is read from memory once per workgroup.  A cell outside the image
+// or without a surface gets kNotSurface and no further loads - its count and normal are never looked at.
+//   phase 2: every lane walks its (2r + 1)^2 window out of LDS.  At r = 4 with normals that is 81 x 5 LDS reads per
+// pixel against 33 B from memory; the pass is bound by the LDS there and by memory at small radii.
+// 12.8 KB of LDS per workgroup with normals, 5.1 KB without.
+template <bool NORMALS>
+__global__ void __launch_bounds__(256) k_ao_filter(const AoFilterParams P) {
+    __shared__ float s_t[kFilterMaxCells];
+    __shared__ uint32_t s_cnt[kFilterMaxCells];
+    __shared__ float s_n[NORMALS ? 3 * kFilterMaxCells : 1];
+    const uint32_t r = P.radius;
+    const uint32_t hw = kFilterTileW + 2u * r, hh = kFilterTileH + 2u * r, cells = hw * hh;
+    const uint32_t tiles_x = (P.width + kFilterTileW - 1u) / kFilterTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int x0 = (int)(tx * kFilterTileW) - (int)r, y0 = (int)(ty * kFilterTileH) - (int)r;
+    for (uint32_t c = threadIdx.x; c < cells; c += 256u) {
+        const uint32_t cy = c / hw, cx = c - cy * hw;
+        const int gx = x0 + (int)cx, gy = y0 + (int)cy;
+        float t = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        uint32_t cnt = kNotSurface;
+        if (gx >= 0 && gy >= 0 && (uint32_t)gx < P.width && (uint32_t)gy < P.height) {
+            const size_t i = (size_t)gy * P.width + (uint32_t)gx;
+            const trx_hit h = P.primary[i];
+            if (h.t < TRX_F32_MAX && h.prim != TRX_INVALID) {
+                t = h.t;
+                cnt = P.counts[i];
+                if constexpr (NORMALS) {
+                    const float *n = P.attr[i].normal;
+                    nx = n[0]; ny = n[1]; nz = n[2];
+                }
+            }
+        }
+        s_t[c] = t;
+        s_cnt[c] = cnt;
+        if constexpr (NORMALS) {
+            s_n[c] = nx;
+            s_n[kFilterMaxCells + c] = ny;
+            s_n[2u * kFilterMaxCells + c] = nz;
+        }
+    }
+    __syncthreads();
+    const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
+    const uint32_t px = tx * kFilterTileW + lx, py = ty * kFilterTileH + ly;
+    if (px >= P.width || py >= P.height) return;
+    const uint32_t c0 = (ly + r) * hw + lx + r;
+    trx_ao_term out;
+    out.unoccluded = 0;
+    out.samples = 0;
+    if (s_cnt[c0] != kNotSurface) {
+        const float tp = s_t[c0], tol = P.depth_tol * tp;
+        float npx = 0.0f, npy = 0.0f, npz = 0.0f;
+        if constexpr (NORMALS) {
+            npx = s_n[c0]; npy = s_n[kFilterMaxCells + c0]; npz = s_n[2u * kFilterMaxCells + c0];
+        }
+        uint32_t sum = 0u, accepted = 0u;
+        for (uint32_t dy = 0; dy <= 2u * r; dy++) {
+            const uint32_t row = (ly + dy) * hw + lx;
+            for (uint32_t dx = 0; dx <= 2u * r; dx++) {
+                const uint32_t c = row + dx;
+                const uint32_t cq = s_cnt[c];
+                bool ok = cq != kNotSurface && __builtin_fabsf(s_t[c] - tp) <= tol;
+                if constexpr (NORMALS)
+                    ok = ok && (npx * s_n[c] + npy * s_n[kFilterMaxCells + c]) + npz * s_n[2u * kFilterMaxCells + c] >= P.normal_cos;
+                ok = ok || c == c0;
+                sum += ok ? cq : 0u;
+                accepted += ok ? 1u : 0u;
+            }
+        }
+        out.unoccluded = (uint16_t)sum;
+        out.samples = (uint16_t)(P.n_samples * accepted);
+    }
+    P.out[(size_t)py * P.width + px] = out;
+}
+
+// Shading to RGBA8 (trx_shade_*_dev): one lane per record.  The colour is one IEEE division at most; its 8-bit code is the
+// number of thresholds thr[1..255] it reaches (trx_image_code_table: the host's powf(col, 2.2f) * 255 truncated, turned
+// into the smallest binary32 of every code), found in 8 steps in the workgroup's copy of the table in LDS - the device
+// evaluates no pow.  NaN and negative colours reach no threshold (code 0), everything from 1 upward reaches all (255).
+template <int MODE>
+__global__ void __launch_bounds__(256) k_shade(const ShadeParams P) {
+    __shared__ float s_thr[256];
+    s_thr[threadIdx.x] = P.thr[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    float col = 0.0f;
+    if constexpr (MODE == kShadeReference) {
+        // rt_gpu_software.hlsl:130-142 / src/rt_cpu/rt_cpu.rs:57-85: 1 / t where the primary ray missed, else the AO term
+        const float t = P.primary[i].t;
+        if (t < TRX_F32_MAX) {
+            const float at = P.ao[i].t;
+            col = at < TRX_F32_MAX ? __fdiv_rn(at, 1.0f + at) : 1.0f;
+        } else {
+            col = __fdiv_rn(1.0f, t);
+        }
+    } else if constexpr (MODE == kShadeCounts) {
+        const uint32_t n = P.counts[i];
+        col = n == TRX_AO_NO_SURFACE ? 0.0f : __fdiv_rn((float)n, (float)P.n_samples);
+    } else {
+        const trx_ao_term a = P.term[i];
+        col = a.samples == 0 ? 0.0f : __fdiv_rn((float)a.unoccluded, (float)a.samples);
+    }
+    uint32_t c = 0u;
+#pragma unroll
+    for (uint32_t step = 128u; step != 0u; step >>= 1) c += col >= s_thr[c + step] ? step : 0u;
+    reinterpret_cast<uint32_t *>(P.rgba)[i] = c * 0x00010101u | 0xFF000000u; // {c, c, c, 255}
+}
+
+} // namespace
+
+hipError_t launch_ao_filter(const AoFilterParams &p, hipStream_t stream) {
+    const uint64_t tiles = (uint64_t)((p.width + kFilterTileW - 1u) / kFilterTileW) * ((p.height + kFilterTileH - 1u) / kFilterTileH);
+    if (tiles == 0) return hipSuccess;
+    if (tiles > 0x7fffffffull || p.radius > kFilterMaxRadius) return hipErrorInvalidValue;
+    if (p.attr) hipLaunchKernelGGL(k_ao_filter<true>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(k_ao_filter<false>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade(const ShadeParams &p, int mode, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    const dim3 grid((p.n_items + 255u) / 256u), block(256);
+    switch (mode) {
+    case kShadeReference: hipLaunchKernelGGL(k_shade<kShadeReference>, grid, block, 0, stream, p); break;
+    case kShadeCounts: hipLaunchKernelGGL(k_shade<kShadeCounts>, grid, block, 0, stream, p); break;
+    case kShadeTerm: hipLaunchKernelGGL(k_shade<kShadeTerm>, grid, block, 0, stream, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+} // namespace trx

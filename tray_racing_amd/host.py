@@ -17,6 +17,8 @@ RAYHIT_DTYPE = np.dtype([("primitive_id", "<u4"), ("geometry_id", "<u4"), ("inst
 # trx_hit_attr: barycentrics of the committed triangle test (u weights v1, v weights v2) and the world-space unit
 # geometric normal; all zero for a miss
 HIT_ATTR_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("_pad", "<u4")])
+# trx_ao_term: the edge-aware AO filter's output per pixel
+AO_TERM_DTYPE = np.dtype([("unoccluded", "<u2"), ("samples", "<u2")])
 MISS_PRIM = 0xFFFFFFFF
 
 
@@ -63,6 +65,14 @@ def load_scene(path):
     L.check(lib.trx_load_scene(str(path).encode(), C.byref(vp), C.byref(n), C.byref(cp), C.byref(nobj), eye, look, C.byref(fov)))
     verts, counts = _take_mesh(vp, n, cp, nobj)
     return verts, counts, list(eye), list(look), fov.value
+
+
+def image_code_table():
+    """[256] f32 (trx_image_code_table, no device needed): thr[k] is the smallest colour in [0, 1] whose 8-bit code on this
+    host, uint8(powf(col, 2.2f) * 255), is >= k; the device's code of a colour is the number of k >= 1 with col >= thr[k]."""
+    out = np.empty(256, dtype=np.float32)
+    L.check(L.load().trx_image_code_table(_ptr(out)))
+    return out
 
 
 def copy_rate(device=0, nbytes=1 << 30, reps=5):
@@ -488,6 +498,18 @@ class Scene:
                                                   ao_radius, _ptr(counts), C.byref(ms)))
         return counts, ms.value
 
+    def render_image(self, view, width, height, sem=L.SEM_HLSL, frame0=0, n_samples=0, ao_eps=0.01, ao_radius=float("inf"),
+                     filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image - the frame traced, its AO term optionally filtered, and
+        shaded to RGBA8 on the device; only the image crosses the bus.  n_samples == 0: the reference's image (closest-hit AO
+        pass under seed frame0); n_samples >= 1: the AO visibility pass's counts / n_samples, through the edge-aware
+        filter (with normals) when filter_radius >= 1."""
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image(self._h, C.byref(view), width, height, sem, frame0, n_samples, ao_eps, ao_radius,
+                                           filter_radius, depth_tol, normal_cos, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
     def traverse(self, origin, direction, tmin=0.0, tmax=3.4028234663852886e38, sem=L.SEM_HLSL):
         """Traversable::traverse (traversable/src/lib.rs:17-21) for one ray."""
         ray = L.Ray((C.c_float * 3)(*origin), tmin, (C.c_float * 3)(*direction), tmax)
@@ -647,6 +669,29 @@ class Scene:
         L.check(self._lib.trx_hit_attributes_primary_dev(self._h, C.byref(view), width, height, L.Shard(*shard),
                                                          C.c_void_p(d_hits), C.c_void_p(d_inst), C.c_void_p(d_attr),
                                                          C.c_void_p(stream)))
+
+    def ao_filter_dev(self, width, height, d_primary, d_unoccluded, d_term, n_samples, radius, depth_tol=0.02, normal_cos=0.9,
+                      d_attr=0, stream=0):
+        """trx_ao_filter_dev: one trx_ao_term per pixel at d_term from whole-image, image-layout records - the counts of
+        the accepted pixels of the (2 * radius + 1)^2 window summed (accepted: a surface, depth within depth_tol * t_p and,
+        with d_attr, normals within normal_cos; the pixel itself always)."""
+        L.check(self._lib.trx_ao_filter_dev(self._h, width, height, C.c_void_p(d_primary), C.c_void_p(d_attr),
+                                            C.c_void_p(d_unoccluded), n_samples, radius, depth_tol, normal_cos,
+                                            C.c_void_p(d_term), C.c_void_p(stream)))
+
+    def shade_reference_dev(self, d_primary, d_ao, n, d_rgba, stream=0):
+        """trx_shade_reference_dev: the reference's grey image of n primary / AO record pairs, 4 bytes per record."""
+        L.check(self._lib.trx_shade_reference_dev(self._h, C.c_void_p(d_primary), C.c_void_p(d_ao), n, C.c_void_p(d_rgba),
+                                                  C.c_void_p(stream)))
+
+    def shade_ao_counts_dev(self, d_unoccluded, n_samples, n, d_rgba, stream=0):
+        """trx_shade_ao_counts_dev: count / n_samples of n visibility counts (0 where there is no surface) as RGBA8."""
+        L.check(self._lib.trx_shade_ao_counts_dev(self._h, C.c_void_p(d_unoccluded), n_samples, n, C.c_void_p(d_rgba),
+                                                  C.c_void_p(stream)))
+
+    def shade_ao_term_dev(self, d_term, n, d_rgba, stream=0):
+        """trx_shade_ao_term_dev: unoccluded / samples of n filtered terms (0 where samples == 0) as RGBA8."""
+        L.check(self._lib.trx_shade_ao_term_dev(self._h, C.c_void_p(d_term), n, C.c_void_p(d_rgba), C.c_void_p(stream)))
 
     def check(self, stream=0):
         L.check(self._lib.trx_scene_check(self._h, C.c_void_p(stream)))
