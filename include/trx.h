@@ -776,6 +776,12 @@ typedef struct trx_flat {
                                      * which TLAS primitive k starts (re-braided TLAS, trx_set_build_rebraid); NULL when
                                      * every primitive is a whole BLAS (the reference's layout) */
 } trx_flat;
+/* Every flat builder below (trx_flat_build, trx_flat_build_instanced, trx_flat_build_params,
+ * trx_flat_build_preset_device), like trx_bvh_build_tris, refuses a non-finite vertex coordinate (NaN, +-inf) with TRX_ERR_INVALID, as
+ * trx_scene_refit does: nothing is built and *out is left as it was.  Finite degenerate geometry - duplicates, points,
+ * segments, boxes without extent, coordinates whose box areas underflow to 0 or overflow to +inf, signed zeros - is
+ * built.  A collapsed tree deeper than 512 levels (the depth the validators and the traversal stacks are sized for) is
+ * refused with TRX_ERR_INVALID as well, not returned. */
 int trx_flat_build(const float *verts, const uint64_t *object_tri_counts, uint32_t n_objects,
                    int use_tlas, uint32_t max_prims_per_leaf, int threads, trx_flat **out);
 void trx_flat_destroy(trx_flat *flat);

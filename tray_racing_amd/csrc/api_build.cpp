@@ -47,6 +47,18 @@ BuildParams to_build_params(const BuildSettings &b, uint32_t max_prims, int thre
     return bp;
 }
 
+// Index of the first NaN or infinity among `count` floats, or `count`.  Every builder entry point refuses such input
+// (the rule trx_scene_refit states): one such box poisons every box above it, the Morton order of its object and the
+// collapse costs, whose decisions then index past their table.
+uint64_t first_non_finite(const float *v, uint64_t count) {
+    for (uint64_t i = 0; i < count; i++) {
+        uint32_t bits;
+        std::memcpy(&bits, v + i, 4);
+        if ((bits & 0x7f800000u) == 0x7f800000u) return i;
+    }
+    return count;
+}
+
 } // namespace
 
 extern "C" {
@@ -58,11 +70,16 @@ int trx_bvh_build_tris(const float *verts, uint64_t n, uint32_t max_prims, int t
     if (max_prims < 1 || max_prims > 3)
         return fail(TRX_ERR_INVALID, "CWBVH only supports a maximum of 3 primitives per leaf."); // src/main.rs:176-178
     if (n >= 0x7fffffffull) return fail(TRX_ERR_INVALID, "too many primitives");
+    if (const uint64_t bad = first_non_finite(verts, n * 9); bad != n * 9)
+        return fail(TRX_ERR_INVALID, "vertex %llu of triangle %llu is not finite", (unsigned long long)(bad % 9 / 3), (unsigned long long)(bad / 9));
     trx_bvh *b = new (std::nothrow) trx_bvh();
     if (!b) return fail(TRX_ERR_OOM, "host allocation failed");
     const BuildParams bp = to_build_params(build_settings(), max_prims, threads);
     try {
         build_cwbvh_from_tris(verts, n, bp, b->bvh);
+    } catch (const TreeTooDeep &e) {
+        delete b;
+        return fail(TRX_ERR_INVALID, "%s", e.what());
     } catch (const std::runtime_error &e) { // the GPU build stage reports its own failures
         delete b;
         return fail(TRX_ERR_NO_DEVICE, "%s", e.what());
@@ -84,6 +101,9 @@ int trx_bvh_build_aabbs(const float *aabbs, uint64_t n, uint32_t max_prims, int 
     bp.reinsertion_batch_ratio = 0.f; // boxes of instances: see trx_flat_build
     try {
         build_cwbvh_from_aabbs((const Aabb *)aabbs, n, bp, b->bvh);
+    } catch (const TreeTooDeep &e) {
+        delete b;
+        return fail(TRX_ERR_INVALID, "%s", e.what());
     } catch (const std::runtime_error &e) { // the GPU build stage reports its own failures
         delete b;
         return fail(TRX_ERR_NO_DEVICE, "%s", e.what());
@@ -288,6 +308,8 @@ static int flat_build_impl(const float *verts, const uint64_t *object_tri_counts
     for (uint32_t i = 0; i < n_objects; i++) total += object_tri_counts[i];
     if (total && !verts) return fail(TRX_ERR_INVALID, "verts is null");
     if (total >= 0x7fffffffull) return fail(TRX_ERR_INVALID, "too many triangles");
+    if (const uint64_t bad = first_non_finite(verts, total * 9); bad != total * 9)
+        return fail(TRX_ERR_INVALID, "vertex %llu of triangle %llu is not finite", (unsigned long long)(bad % 9 / 3), (unsigned long long)(bad / 9));
     const BuildParams bp = to_build_params(settings, max_prims, threads);
     try {
         // without --tlas everything is flattened into the first object (src/main.rs:300-308)
@@ -571,6 +593,8 @@ static int flat_build_impl(const float *verts, const uint64_t *object_tri_counts
             return fail(TRX_ERR_OOM, "host allocation failed");
         }
         *out = f;
+    } catch (const TreeTooDeep &e) {
+        return fail(TRX_ERR_INVALID, "%s", e.what());
     } catch (const std::runtime_error &e) { // the GPU build stage reports its own failures
         return fail(TRX_ERR_NO_DEVICE, "%s", e.what());
     } catch (const std::exception &) {

@@ -266,7 +266,15 @@ struct Bvh2Builder {
                 }
             }
         }
-        (void)bounds;
+        if (best_axis < 0) {
+            // no split has a cost below +inf (the half-areas overflowed): the median along the widest axis of the box, as
+            // split() falls back to - order[-1] was read here
+            best_axis = 0;
+            const float ext[3] = {bounds.mx[0] - bounds.mn[0], bounds.mx[1] - bounds.mn[1], bounds.mx[2] - bounds.mn[2]};
+            if (ext[1] > ext[best_axis]) best_axis = 1;
+            if (ext[2] > ext[best_axis]) best_axis = 2;
+            best_k = n / 2;
+        }
         for (uint32_t i = 0; i < n; i++) idx[begin + i] = order[best_axis][i];
         return begin + best_k;
     }
@@ -774,18 +782,26 @@ struct PlocBuilder {
                 for (uint32_t i = begin; i < end; i++) {
                     const Aabb &bi = nodes[cur[i]].box;
                     const uint32_t j0 = i > r ? i - r : 0u, j1 = std::min(m - 1u, i + r);
-                    float best = kInf;
+                    float best = kInf, pair_area = -1.f;
                     uint32_t best_j = i == 0 ? 1u : i - 1u;
+                    const uint32_t pair = i ^ 1u; // (always within the window: r >= 1; past the end for the last of an odd m)
                     for (uint32_t j = j0; j <= j1; j++) {
                         if (j == i) continue;
                         Aabb u = bi;
                         grow(u, nodes[cur[j]].box);
                         const float a = half_area(u);
-                        if (a < best) { // first of equals: the lowest index
+                        if (j == pair) pair_area = a;
+                        if (a < best) { // first of equals: the lowest index ...
                             best = a;
                             best_j = j;
                         }
                     }
+                    // ... unless the pair partner i ^ 1 is one of the equals: then i and i ^ 1 choose each other whenever
+                    // neither has a strictly better neighbour, so a run of tied clusters (duplicates, boxes without
+                    // area, areas that are all 0 or all +inf) halves every round.  With the lowest index alone every
+                    // cluster of such a run points at i - r, only the first two are mutual, and the tree becomes a chain
+                    // built in O(n) rounds.  A cluster whose candidate areas are all different chooses as before.
+                    if (pair_area == best) best_j = pair;
                     nn[i] = best_j;
                 }
             };
@@ -868,7 +884,9 @@ struct Reinserter {
         while (!stack.empty()) {
             auto [g, id] = stack.back();
             stack.pop_back();
-            if (g - area <= best_gain) continue; // even a zero-growth insertion cannot win
+            // even a zero-growth insertion cannot win.  (Written so that a NaN is dropped as well: below a box whose half-area
+            // overflowed to +inf the gains are inf - inf, and `g - area <= best_gain` let such an entry walk its whole subtree.)
+            if (!(g - area > best_gain)) continue;
             const Node2 &dst = nodes[id];
             Aabb merged = dst.box;
             grow(merged, box);
@@ -893,6 +911,13 @@ struct Reinserter {
         float gain = half_area(nodes[p].box); // p disappears
         float best_gain = 0.f;
         uint32_t best_to = kNone;
+        // Where the half-areas have overflowed to +inf no two places can be compared any more (every gain is +inf or
+        // NaN, nothing is pruned and each search walked the whole tree): such a node stays where it is, and the way up
+        // ends where the gain stops being finite.
+        if (!(gain < kInf)) {
+            to = kNone;
+            return false;
+        }
         uint32_t sib = sibling(from);
         search(stack, sib, gain, box, area, best_to, best_gain);
         Aabb shrunk = nodes[sib].box; // what the path node looks like without `from`
@@ -901,6 +926,7 @@ struct Reinserter {
             search(stack, sib, gain, box, area, best_to, best_gain);
             grow(shrunk, nodes[sib].box);
             gain += half_area(nodes[parent[cur]].box) - half_area(shrunk);
+            if (!(gain < kInf)) break;
         }
         to = best_to;
         return best_to != kNone;
@@ -984,6 +1010,18 @@ struct Reinserter {
         const size_t n = nodes.size();
         uint32_t moved = 0;
         if (n < 8 || batch_ratio <= 0.f) return 0;
+        // Every inner box as its left child's grown by its right child's, bit for bit.  The device pass recomputes all of
+        // them that way after an iteration (k_refit), while refit_up here stops where a box's bytes do not change and so
+        // keeps what the BVH2 builder wrote - for the binned-SAH builder a union in primitive order.  The values are the
+        // same; the SIGN OF A ZERO is the first operand's, and a node's origin is its box minimum: a mesh with +0.0 and
+        // -0.0 coordinates came out with different bytes on the host and on the device.  (Pre-order layout on entry:
+        // children follow their parent.  PLOC's boxes are already such unions.)
+        for (size_t i = n; i-- > 0;) {
+            Node2 &nd = nodes[i];
+            if (nd.count == 1 || nd.left <= i || nd.right <= i) continue;
+            nd.box = nodes[nd.left].box;
+            grow(nd.box, nodes[nd.right].box);
+        }
         threads = std::max(1, std::min(threads, std::min(usable_threads(), 64)));
         BigVec<Cand> cand, cand_tmp;
         std::vector<uint32_t> ids, found;
@@ -1401,7 +1439,9 @@ struct Collapser {
                                   ? area * (float)nd.count * params.prim_cost
                                   : kInf;
             float cost_dist = kInf;
-            uint8_t bl = 0xff, br = 0xff;
+            // (1 + 7 slots unless a split costs less: where the children's costs have overflowed to +inf none does, and the
+            // 0xff these started as sent get_children to decision 255 of the children - another node's entries)
+            uint8_t bl = 0, br = 6;
             for (int k = 0; k < 7; k++) {
                 float c = dl[k].cost + dr[6 - k].cost;
                 if (c < cost_dist) {
@@ -1530,9 +1570,15 @@ struct Collapser {
     struct Task {
         std::vector<CwbvhNode> nodes; // [0] the subtree's root, then its descendants in emission order
         std::vector<uint32_t> prims;
+        uint32_t levels_below = 0; // depth of the deepest node under the subtree's root
     };
     const std::vector<uint32_t> *task_roots = nullptr; // sorted BVH2 indices of the subtrees emitted as tasks
     std::vector<Task> *tasks = nullptr;
+    // emit() recurses once per level of the collapsed tree.  A BVH2 that is one long chain (nested boxes: PLOC merges one
+    // pair per round) collapses into a chain of tens of thousands of levels, and the recursion ran off the thread's stack
+    // on it.  Nothing downstream takes such a tree either - validators and traversal stacks are sized for
+    // kMaxCwbvhDepth levels - so the emission stops descending there and the build is refused (TreeTooDeep).
+    std::atomic<bool> too_deep{false};
 
     // The inner (CWBVH-node) children of the node that BVH2 node `ni` becomes, in slot order.
     void inner_children(uint32_t ni, uint32_t *inner, int &n_inner) const {
@@ -1559,7 +1605,8 @@ struct Collapser {
         Sink global{&out.nodes, &out.primitive_indices};
         const uint32_t grain = std::max<uint32_t>(4096u, n2[0].count / (uint32_t)(std::max(threads, 1) * 16));
         if (threads <= 1 || n2[0].count <= grain || n2.size() < ((size_t)1 << 16)) {
-            emit(global, 0, 0);
+            emit(global, 0, 0, 0, nullptr);
+            if (too_deep.load()) throw TreeTooDeep();
             return;
         }
         std::vector<uint32_t> roots;
@@ -1584,7 +1631,7 @@ struct Collapser {
                 Task &t = done[k];
                 t.nodes.resize(1);
                 Sink local{&t.nodes, &t.prims};
-                emit(local, 0, roots[k]);
+                emit(local, 0, roots[k], 0, &t.levels_below);
             }
         };
         std::vector<std::thread> pool;
@@ -1593,9 +1640,10 @@ struct Collapser {
         for (auto &th : pool) th.join();
         task_roots = &roots;
         tasks = &done;
-        emit(global, 0, 0);
+        emit(global, 0, 0, 0, nullptr);
         task_roots = nullptr;
         tasks = nullptr;
+        if (too_deep.load()) throw TreeTooDeep();
     }
 
     // Puts a finished subtree where the sequential emission would have written it: root at out_idx, descendants and
@@ -1614,11 +1662,19 @@ struct Collapser {
         sink.prims->insert(sink.prims->end(), t.prims.begin(), t.prims.end());
     }
 
-    void emit(Sink sink, uint32_t out_idx, uint32_t ni) {
+    // depth: levels between this node and the node the emission started at; deepest: where a task keeps its largest
+    void emit(Sink sink, uint32_t out_idx, uint32_t ni, uint32_t depth, uint32_t *deepest) {
+        if (deepest && depth > *deepest) *deepest = depth;
+        if (depth > kMaxCwbvhDepth) {
+            too_deep.store(true);
+            return;
+        }
         if (task_roots && sink.nodes == &out.nodes) {
             auto it = std::lower_bound(task_roots->begin(), task_roots->end(), ni);
             if (it != task_roots->end() && *it == ni) {
-                splice(sink, out_idx, (*tasks)[(size_t)(it - task_roots->begin())]);
+                const Task &t = (*tasks)[(size_t)(it - task_roots->begin())];
+                if (depth + t.levels_below > kMaxCwbvhDepth) too_deep.store(true);
+                splice(sink, out_idx, t);
                 return;
             }
         }
@@ -1690,7 +1746,7 @@ struct Collapser {
         uint32_t k = 0;
         for (int s = 0; s < 8; s++) {
             if (slots[s].used && slots[s].inner) {
-                emit(sink, child_base + k, slots[s].n2);
+                emit(sink, child_base + k, slots[s].n2, depth + 1, deepest);
                 k++;
             }
         }
@@ -1772,9 +1828,11 @@ void build_from_boxes(const Aabb *boxes, const float *centroids, uint64_t n, con
         std::string err;
         double dev_s = 0.0;
         float root_cost = 0.f;
+        uint32_t levels = 0;
         if (!collapse_encode_device(params.ploc_device, b2.nodes.data(), b2.nodes.size(), params.max_prims_per_leaf, params.traversal_cost,
-                                    params.prim_cost, out.nodes, out.primitive_indices, &root_cost, &dev_s, err))
+                                    params.prim_cost, out.nodes, out.primitive_indices, &root_cost, &dev_s, err, &levels))
             throw std::runtime_error("GPU build stage: " + err);
+        if (levels > kMaxCwbvhDepth + 1) throw TreeTooDeep(); // as Collapser::emit_all refuses it
         out.sah_cost = root_cost / std::max(half_area(b2.nodes[0].box), 1e-30f);
         if (verbose) fprintf(stderr, "[trx build] collapse + encode on device %d: %.4f s of kernels, sah8=%.3f\n", params.ploc_device, dev_s, out.sah_cost);
         lap("collapse (device)");

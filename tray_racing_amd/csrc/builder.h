@@ -8,6 +8,7 @@
 // encoding (embree/src/bvh_embree_to_cwbvh.rs:85-186).
 #pragma once
 #include <cstdint>
+#include <exception>
 #include <vector>
 
 #include "cwbvh_format.h"
@@ -57,6 +58,13 @@ struct BuildParams {
 };
 
 constexpr uint64_t kDevicePlocMinPrims = 32768;
+
+// A collapsed tree may have nodes this many levels below its root, no more: the depth the validators accept and the
+// traversal stacks are sized for.  A build that would exceed it throws TreeTooDeep instead of returning the tree.
+constexpr uint32_t kMaxCwbvhDepth = 512;
+struct TreeTooDeep : std::exception {
+    const char *what() const noexcept override { return "the tree would be deeper than 512 levels"; }
+};
 
 // Host cores this process may really use: hardware threads, capped by the CPU affinity mask and the cgroup CPU quota
 // (a container that sees 256 hardware threads but owns 16 must not start 256 workers).

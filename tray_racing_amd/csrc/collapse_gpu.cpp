@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k2_cost(DevNode *nodes, uint2 *dec, co
     const float inf = __builtin_inff();
     const float cost_leaf = nd.count <= max_prims ? area * (float)nd.count * prim_cost : inf;
     float cost_dist = inf;
-    uint32_t bl = 0xff, br = 0xff;
+    uint32_t bl = 0, br = 6; // (as Collapser::cost_range: a valid split also where every cost is +inf)
     for (int k = 0; k < 7; k++) {
         const float c = cl[k] + cr[6 - k];
         if (c < cost_dist) {
@@ -439,7 +439,7 @@ inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + kBlock - 1) / kBloc
 
 bool collapse_encode_device(int device, const void *nodes, size_t n_nodes, uint32_t max_prims_per_leaf, float traversal_cost,
                             float prim_cost, std::vector<CwbvhNode> &out_nodes, std::vector<uint32_t> &out_prims,
-                            float *root_cost, double *seconds, std::string &err) {
+                            float *root_cost, double *seconds, std::string &err, uint32_t *levels) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
         err = "no HIP device " + std::to_string(device) + " for the GPU build stage";
@@ -534,6 +534,7 @@ bool collapse_encode_device(int device, const void *nodes, size_t n_nodes, uint3
         level8.push_back(state[0]);
     }
     const uint32_t n_recs = level8.back();
+    if (levels) *levels = (uint32_t)level8.size() - 1u;
     // 4. subtree sizes, 5. output offsets
     for (size_t L = level8.size() - 1; L-- > 0;)
         hipLaunchKernelGGL(k8_sizes, grid_for(level8[L + 1] - level8[L]), dim3(kBlock), 0, nullptr, b.recs, level8[L], level8[L + 1]);

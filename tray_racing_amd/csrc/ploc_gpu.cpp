@@ -30,10 +30,12 @@ __device__ __forceinline__ float half_area_dev(const Aabb &b) {
     if (!(dx >= 0.f) || !(dy >= 0.f) || !(dz >= 0.f)) return 0.f;
     return dx * dy + dy * dz + dz * dx;
 }
+// std::min / std::max of the host's grow(), spelled out: the same result for every input, signed zeros included
+// (fminf(+0, -0) is -0 on the device, std::min(+0, -0) keeps its first argument, and a node's origin is its box minimum)
 __device__ __forceinline__ void grow_dev(Aabb &a, const Aabb &b) {
     for (int k = 0; k < 3; k++) {
-        a.mn[k] = fminf(a.mn[k], b.mn[k]);
-        a.mx[k] = fmaxf(a.mx[k], b.mx[k]);
+        a.mn[k] = b.mn[k] < a.mn[k] ? b.mn[k] : a.mn[k];
+        a.mx[k] = a.mx[k] < b.mx[k] ? b.mx[k] : a.mx[k];
     }
 }
 
@@ -97,18 +99,21 @@ __global__ void k_nearest(const Aabb *cbox, uint32_t m, uint32_t r, uint32_t *nn
     if (i >= m) return;
     const Aabb bi = cbox[i];
     const uint32_t j0 = i > r ? i - r : 0u, j1 = min(m - 1u, i + r);
-    float best = std::numeric_limits<float>::infinity();
+    float best = std::numeric_limits<float>::infinity(), pair_area = -1.f;
     uint32_t best_j = i == 0 ? 1u : i - 1u;
+    const uint32_t pair = i ^ 1u;
     for (uint32_t j = j0; j <= j1; j++) {
         if (j == i) continue;
         Aabb u = bi;
         grow_dev(u, cbox[j]);
         const float a = half_area_dev(u);
-        if (a < best) { // first of equals: the lowest index
+        if (j == pair) pair_area = a;
+        if (a < best) { // first of equals: the lowest index ...
             best = a;
             best_j = j;
         }
     }
+    if (pair_area == best) best_j = pair; // ... unless i ^ 1 is one of the equals (PlocBuilder::run says why)
     nn[i] = best_j;
 }
 

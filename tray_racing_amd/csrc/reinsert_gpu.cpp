@@ -70,7 +70,7 @@ __device__ __forceinline__ bool search_dev(const DevNode *nodes, uint2 *stk, uin
             id = e.y;
         }
         have = false;
-        if (g - area <= best_gain) continue; // even a zero-growth insertion cannot win
+        if (!(g - area > best_gain)) continue; // even a zero-growth insertion cannot win (nor a NaN: Reinserter::search)
         const DevNode dst = load_node(nodes, id);
         Aabb merged = dst.box;
         grow_dev(merged, box);
@@ -82,7 +82,7 @@ __device__ __forceinline__ bool search_dev(const DevNode *nodes, uint2 *stk, uin
         if (dst.count > 1) {
             // going below dst instead grows dst to `merged`
             const float below = here + half_area_dev(dst.box);
-            if (below - area <= best_gain) continue;
+            if (!(below - area > best_gain)) continue;
             // the host pushes left, then right, and pops right first: right is walked now, left waits
             if (sp + 1 > kStackCap) return false;
             stk[(size_t)sp * stride] = make_uint2(__float_as_uint(below), dst.left);
@@ -112,6 +112,10 @@ __global__ void __launch_bounds__(kBlock) k_find(const DevNode *nodes, const uin
         float gain = half_area_dev(pn.box); // p disappears
         float best_gain = 0.f;
         uint32_t best_to = kReinsertNone;
+        if (!(gain < INFINITY)) { // overflowed half-areas: the node stays (Reinserter::find)
+            found[k] = kReinsertNone;
+            continue;
+        }
         uint32_t sib = pn.left == from ? pn.right : pn.left;
         bool ok = search_dev(nodes, stk, stride, sib, gain, box, area, best_to, best_gain);
         Aabb shrunk = load_node(nodes, sib).box; // what the path node looks like without `from`
@@ -124,6 +128,7 @@ __global__ void __launch_bounds__(kBlock) k_find(const DevNode *nodes, const uin
             ok = search_dev(nodes, stk, stride, sib, gain, box, area, best_to, best_gain);
             grow_dev(shrunk, load_node(nodes, sib).box);
             gain += half_area_dev(un.box) - half_area_dev(shrunk);
+            if (!(gain < INFINITY)) break;
             cur = up;
         }
         found[k] = ok ? best_to : kReinsertOverflow;
@@ -280,8 +285,9 @@ __global__ void __launch_bounds__(kBlock) k_apply(const Six *six, const uint8_t 
     atomicAdd(moved, 1u);
 }
 
-// Boxes of the inner nodes, level by level from the deepest: box = left's grown by right's (min / max: the value does not
-// depend on the order, so this is what refit_up leaves on the host).
+// Boxes of the inner nodes, level by level from the deepest: box = left's grown by right's.  The value does not depend on
+// the order but the sign of a zero does (the first operand's), so Reinserter::run_whole_iterations puts every box into this
+// form before the first iteration; refit_up then leaves these very bits on the host.
 __device__ __forceinline__ uint32_t wave_append2(uint32_t *counter, uint32_t want) {
     const uint32_t lane = __lane_id();
     uint32_t scan = want;
