@@ -1,6 +1,7 @@
 """Seeded generators of degenerate geometry for the builder tests (host: test_builder_adversarial.py, device:
 test_gpu_builder_adversarial.py): exact ties of the PLOC merge areas, zero extents, duplicates, areas that underflow
-to 0 or overflow to +inf, signed zeros and non-finite coordinates.  Every function returns float32 vertices [n, 9].
+to 0 or overflow to +inf, a box extent that overflows, signed zeros and non-finite coordinates.  Every function returns
+float32 vertices [n, 9].
 
 The sizes are the smallest that reach the device build stage (kDevicePlocMinPrims = 32768) and its block edges:
 32768 is the threshold itself, 32769 one past it, 40001 no multiple of the 256-thread block."""
@@ -96,6 +97,15 @@ def overflow_1e19(n=N_THRESHOLD, seed=9):
     return soup(n, seed) * np.float32(1e19)
 
 
+def extent_overflow_x(n=N_THRESHOLD, seed=14):
+    """The soup with its x coordinates rescaled to [-3e38, 3e38]: every vertex is finite, but the x extent of the root's
+    box (6e38) is +inf in binary32, where the encoder's quantisation step must still come out finite."""
+    v = soup(n, seed).reshape(n, 3, 3).astype(np.float64)
+    x = v[:, :, 0]
+    v[:, :, 0] = (2.0 * (x - x.min()) / (x.max() - x.min()) - 1.0) * 3e38
+    return np.ascontiguousarray(v.reshape(n, 9).astype(np.float32))
+
+
 def points_every_50th(n=N_ODD, seed=10):
     """Every 50th triangle of a soup collapsed to its first vertex."""
     v = soup(n, seed)
@@ -154,6 +164,7 @@ FINITE = {
     "all_identical": all_identical,
     "underflow_1e-30": underflow_1e30,
     "overflow_1e19": overflow_1e19,
+    "extent_overflow_x": extent_overflow_x,
     "points_every_50th": points_every_50th,
     "signed_zero": signed_zero,
 }

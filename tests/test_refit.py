@@ -58,6 +58,19 @@ def test_identity_single_level(trx, name, n):
     assert np.array_equal(trx.refit_nodes(flat, flat.tri_verts), flat.nodes)
 
 
+def test_identity_where_the_root_extent_overflows(trx):
+    """Finite vertices whose x range (6e38) is +inf in binary32: the refit and the builder take the same quantisation
+    step there, a finite one (exponent byte 255 would be +inf)."""
+    import adversarial_scenes as A
+    verts = A.extent_overflow_x(3000)
+    with np.errstate(over="ignore"):
+        assert np.isfinite(verts).all() and np.isinf(verts[:, 0::3].max() - verts[:, 0::3].min())
+    flat = trx.flat_build(verts, np.array([verts.shape[0]], dtype=np.uint64))
+    assert np.array_equal(trx.refit_nodes(flat, flat.tri_verts), flat.nodes)
+    root_e = np.ascontiguousarray(flat.nodes).view(np.uint8).reshape(-1, 80)[0, 12:15]
+    assert root_e[0] < 255, root_e
+
+
 def test_identity_device_pipeline_builder(trx):
     """The preset pipeline's encoder (k8_encode's host twin) agrees with the refit too."""
     verts, counts = trx.gen_scene("bistro", 40000, 2)

@@ -1,7 +1,7 @@
 // api_build.cpp - host side: builders, the flat-buffer assembly of cwbvh_gpu_runner (src/rt_gpu/mod.rs:16-112),
 // scene generators and loaders.
 #include "api_internal.h"
-#include "refit_gpu.h"
+#include "build_rules.h"
 
 namespace {
 
@@ -526,7 +526,7 @@ static int flat_build_impl(const float *verts, const uint64_t *object_tri_counts
             if (instance_object) {
                 tlas_boxes.assign(n_instances, Aabb{});
                 for (uint32_t k = 0; k < n_instances; k++) {
-                    // (the rule trx_scene_refit applies to the refitted BLAS boxes, refit_gpu.h)
+                    // (the rule trx_scene_refit applies to the refitted BLAS boxes too, build_rules.h)
                     instance_world_box(blas_aabb[blas_of_object[instance_object[k]]], instance_o2w ? instance_o2w + (size_t)k * 16 : nullptr,
                                        tlas_boxes[k]);
                 }

@@ -1,5 +1,6 @@
 // builder.cpp — CPU construction of the 80-byte CWBVH (see builder.h).
 #include "builder.h"
+#include "build_rules.h"
 #include "ploc_gpu.h"
 #include "collapse_gpu.h"
 #include "reinsert_gpu.h"
@@ -107,24 +108,6 @@ class BigVec {
 inline Aabb empty_box() {
     return Aabb{{kInf, kInf, kInf}, {-kInf, -kInf, -kInf}};
 }
-inline void grow(Aabb &a, const Aabb &b) {
-    for (int k = 0; k < 3; k++) {
-        a.mn[k] = std::min(a.mn[k], b.mn[k]);
-        a.mx[k] = std::max(a.mx[k], b.mx[k]);
-    }
-}
-inline void grow_pt(Aabb &a, const float *p) {
-    for (int k = 0; k < 3; k++) {
-        a.mn[k] = std::min(a.mn[k], p[k]);
-        a.mx[k] = std::max(a.mx[k], p[k]);
-    }
-}
-inline float half_area(const Aabb &b) {
-    float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
-    if (!(dx >= 0.f) || !(dy >= 0.f) || !(dz >= 0.f)) return 0.f;
-    return dx * dy + dy * dz + dz * dx;
-}
-
 // (a spin-wait hint where the target has one; api_traverse.cpp carries the same helper)
 inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
@@ -211,14 +194,6 @@ struct PhasePool {
 // ---- BVH2 ------------------------------------------------------------------
 // Nodes are laid out in DFS pre-order: a subtree over n primitives owns exactly
 // 2n-1 consecutive nodes, so the layout is independent of the thread schedule.
-struct Node2 {
-    Aabb box;
-    uint32_t left;  // inner: index of left child (== self + 1)
-    uint32_t right; // inner: index of right child
-    uint32_t prim;  // leaf: primitive id
-    uint32_t count; // primitives below this node (1 = leaf)
-};
-
 struct Task {
     uint32_t node, begin, end;
 };
@@ -690,19 +665,6 @@ void relayout_dfs(BigVec<Node2> &nodes, uint32_t root, int threads) {
 // Deterministic for any thread count: the searches only read, the merges happen in index order.
 struct PlocBuilder {
     typedef unsigned __int128 u128;
-    static inline uint64_t spread21(uint64_t x) { // 21 bits -> every third bit
-        x &= 0x1fffffull;
-        x = (x | x << 32) & 0x1f00000000ffffull;
-        x = (x | x << 16) & 0x1f0000ff0000ffull;
-        x = (x | x << 8) & 0x100f00f00f00f00full;
-        x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-        x = (x | x << 2) & 0x1249249249249249ull;
-        return x;
-    }
-    static inline u128 spread42(uint64_t x) { // 42 bits -> every third bit of 126
-        return (u128)spread21(x & 0x1fffffull) | ((u128)spread21(x >> 21) << 63);
-    }
-
     template <class Key>
     static void radix_sort(std::vector<Key> &keys, std::vector<uint32_t> &idx, int key_bits) {
         const size_t n = keys.size();
@@ -734,31 +696,28 @@ struct PlocBuilder {
         if (n == 0) return;
         nodes.resize(2 * (size_t)n - 1);
         // Morton order of the box centres
-        float lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
-        for (uint32_t i = 0; i < n; i++)
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::min(lo[k], cen[3 * (size_t)i + k]);
-                hi[k] = std::max(hi[k], cen[3 * (size_t)i + k]);
-            }
         std::vector<uint32_t> order(n);
         for (uint32_t i = 0; i < n; i++) order[i] = i;
-        const int bits = sort_bits == 128 ? 42 : 21;
-        double scale[3];
-        for (int k = 0; k < 3; k++) {
-            const double ext = (double)hi[k] - (double)lo[k];
-            scale[k] = ext > 0.0 ? ((double)((1ull << bits) - 1ull)) / ext : 0.0;
-        }
-        auto quant = [&](uint32_t i, int k) -> uint64_t {
-            const double q = ((double)cen[3 * (size_t)i + k] - (double)lo[k]) * scale[k];
-            return q <= 0.0 ? 0ull : (uint64_t)q;
+        const MortonFrame mf = morton_frame(cen, n, sort_bits == 128 ? 42 : 21);
+        auto quant = [&](uint32_t i, uint64_t *q) {
+            for (int k = 0; k < 3; k++) q[k] = morton_quant(cen[3 * (size_t)i + k], mf.lo[k], mf.scale[k]);
         };
         if (sort_bits == 128) {
             std::vector<u128> keys(n);
-            for (uint32_t i = 0; i < n; i++) keys[i] = spread42(quant(i, 0)) | (spread42(quant(i, 1)) << 1) | (spread42(quant(i, 2)) << 2);
+            for (uint32_t i = 0; i < n; i++) {
+                uint64_t q[3], l, h;
+                quant(i, q);
+                morton_key42(q, l, h);
+                keys[i] = (u128)l | ((u128)h << 63);
+            }
             radix_sort(keys, order, 128);
         } else {
             std::vector<uint64_t> keys(n);
-            for (uint32_t i = 0; i < n; i++) keys[i] = spread21(quant(i, 0)) | (spread21(quant(i, 1)) << 1) | (spread21(quant(i, 2)) << 2);
+            for (uint32_t i = 0; i < n; i++) {
+                uint64_t q[3];
+                quant(i, q);
+                keys[i] = morton_key21(q);
+            }
             radix_sort(keys, order, 64);
         }
         // leaves, in curve order, fill the first n entries; inner nodes follow in creation order
@@ -779,31 +738,7 @@ struct PlocBuilder {
             const uint32_t r = round < depth_threshold ? 1u : std::max(1u, radius);
             nn.resize(m);
             auto search = [&](uint32_t begin, uint32_t end) {
-                for (uint32_t i = begin; i < end; i++) {
-                    const Aabb &bi = nodes[cur[i]].box;
-                    const uint32_t j0 = i > r ? i - r : 0u, j1 = std::min(m - 1u, i + r);
-                    float best = kInf, pair_area = -1.f;
-                    uint32_t best_j = i == 0 ? 1u : i - 1u;
-                    const uint32_t pair = i ^ 1u; // (always within the window: r >= 1; past the end for the last of an odd m)
-                    for (uint32_t j = j0; j <= j1; j++) {
-                        if (j == i) continue;
-                        Aabb u = bi;
-                        grow(u, nodes[cur[j]].box);
-                        const float a = half_area(u);
-                        if (j == pair) pair_area = a;
-                        if (a < best) { // first of equals: the lowest index ...
-                            best = a;
-                            best_j = j;
-                        }
-                    }
-                    // ... unless the pair partner i ^ 1 is one of the equals: then i and i ^ 1 choose each other whenever
-                    // neither has a strictly better neighbour, so a run of tied clusters (duplicates, boxes without
-                    // area, areas that are all 0 or all +inf) halves every round.  With the lowest index alone every
-                    // cluster of such a run points at i - r, only the first two are mutual, and the tree becomes a chain
-                    // built in O(n) rounds.  A cluster whose candidate areas are all different chooses as before.
-                    if (pair_area == best) best_j = pair;
-                    nn[i] = best_j;
-                }
+                for (uint32_t i = begin; i < end; i++) nn[i] = ploc_nearest(i, m, r, [&](uint32_t j) -> const Aabb & { return nodes[cur[j]].box; });
             };
             const int use = (int)std::min<uint32_t>((uint32_t)threads, std::max(1u, m / 4096u));
             if (use <= 1) {
@@ -1371,12 +1306,6 @@ struct Reinserter {
 };
 
 // ---- BVH2 -> BVH8 collapse (Ylitie et al. 2017, section 4.2) ------------------
-enum : uint8_t { kLeaf = 0, kInternal = 1, kDistribute = 2 };
-struct Decision {
-    float cost;
-    uint8_t type, dl, dr, pad;
-};
-
 struct Collapser {
     const BigVec<Node2> &n2;
     BigVec<Decision> dec; // 7 per BVH2 node
@@ -1428,68 +1357,33 @@ struct Collapser {
         // children have larger indices than their parent (pre-order layout)
         for (size_t ni = end; ni-- > begin;) {
             const Node2 &nd = n2[ni];
-            Decision *d = &dec[ni * 7];
-            float area = half_area(nd.box);
-            if (nd.count == 1) {
-                for (int i = 0; i < 7; i++) d[i] = Decision{area * params.prim_cost, kLeaf, 0xff, 0xff, 0};
-                continue;
-            }
-            const Decision *dl = &dec[(size_t)nd.left * 7], *dr = &dec[(size_t)nd.right * 7];
-            float cost_leaf = nd.count <= params.max_prims_per_leaf
-                                  ? area * (float)nd.count * params.prim_cost
-                                  : kInf;
-            float cost_dist = kInf;
-            // (1 + 7 slots unless a split costs less: where the children's costs have overflowed to +inf none does, and the
-            // 0xff these started as sent get_children to decision 255 of the children - another node's entries)
-            uint8_t bl = 0, br = 6;
-            for (int k = 0; k < 7; k++) {
-                float c = dl[k].cost + dr[6 - k].cost;
-                if (c < cost_dist) {
-                    cost_dist = c;
-                    bl = (uint8_t)k;
-                    br = (uint8_t)(6 - k);
+            float cl[7], cr[7];
+            if (nd.count != 1)
+                for (int k = 0; k < 7; k++) {
+                    cl[k] = dec[(size_t)nd.left * 7 + k].cost;
+                    cr[k] = dec[(size_t)nd.right * 7 + k].cost;
                 }
-            }
-            float cost_internal = cost_dist + area * params.traversal_cost;
-            if (cost_leaf < cost_internal)
-                d[0] = Decision{cost_leaf, kLeaf, bl, br, 0};
-            else
-                d[0] = Decision{cost_internal, kInternal, bl, br, 0};
-            for (int i = 1; i < 7; i++) {
-                float best = d[i - 1].cost;
-                uint8_t l = 0xff, r = 0xff;
-                for (int k = 0; k < i; k++) {
-                    float c = dl[k].cost + dr[i - k - 1].cost;
-                    if (c < best) {
-                        best = c;
-                        l = (uint8_t)k;
-                        r = (uint8_t)(i - k - 1);
-                    }
-                }
-                if (l != 0xff)
-                    d[i] = Decision{best, kDistribute, l, r, 0};
-                else
-                    d[i] = d[i - 1];
-            }
+            collapse_costs(half_area(nd.box), nd.count, cl, cr, params.max_prims_per_leaf, params.traversal_cost, params.prim_cost, &dec[ni * 7]);
         }
     }
 
-    void get_children(uint32_t ni, int i, uint32_t *children, int &count) const {
-        const Node2 &nd = n2[ni];
-        if (nd.count == 1) {
-            children[count++] = ni;
+    // the children of the 8-wide node made from ni, in their slots: slots[s] = BVH2 node, or kNoChild
+    static constexpr uint32_t kNoChild = 0xffffffffu;
+    void slot_children(uint32_t ni, uint32_t slots[8]) const {
+        uint32_t children[8];
+        const int count = collapsed_children(
+            ni, [&](uint32_t i, uint32_t &left, uint32_t &right, uint32_t &cnt) { left = n2[i].left, right = n2[i].right, cnt = n2[i].count; },
+            [&](size_t k) { return dec[k]; }, children);
+        int slot_child[8];
+        if (count > 8) { // not a table collapse_costs wrote; emit may run on a worker thread, so emit_all reports it
+            broken.store(true);
+            for (int s = 0; s < 8; s++) slots[s] = kNoChild;
             return;
         }
-        const Decision &d = dec[(size_t)ni * 7 + i];
-        if (dec[(size_t)nd.left * 7 + d.dl].type == kDistribute)
-            get_children(nd.left, d.dl, children, count);
-        else
-            children[count++] = nd.left;
-        if (dec[(size_t)nd.right * 7 + d.dr].type == kDistribute)
-            get_children(nd.right, d.dr, children, count);
-        else
-            children[count++] = nd.right;
+        assign_slots(n2[ni].box, [&](int c) -> const Aabb & { return n2[children[c]].box; }, count, slot_child);
+        for (int s = 0; s < 8; s++) slots[s] = slot_child[s] < 0 ? kNoChild : children[slot_child[s]];
     }
+    bool inner(uint32_t child) const { return dec[(size_t)child * 7].type == kInternal; }
 
     void collect_prims(uint32_t ni, std::vector<uint32_t> &prims) const {
         // pre-order layout: the leaves below ni are the count==1 nodes of its 2c-1 block
@@ -1497,69 +1391,6 @@ struct Collapser {
         size_t last = (size_t)ni + 2 * (size_t)nd.count - 1;
         for (size_t k = ni; k < last; k++)
             if (n2[k].count == 1) prims.push_back(n2[k].prim);
-    }
-
-    struct Child {
-        uint32_t n2 = 0;
-        bool used = false;
-        bool inner = false;
-    };
-
-    // Greedy octant-slot assignment, embree/src/bvh_embree.rs:284-349.
-    void order_children(const Aabb &box, const uint32_t *children, int count, Child slots[8]) const {
-        float pc[3] = {0.5f * (box.mn[0] + box.mx[0]), 0.5f * (box.mn[1] + box.mx[1]),
-                       0.5f * (box.mn[2] + box.mx[2])};
-        float cost[8][8];
-        for (int c = 0; c < count; c++) {
-            const Aabb &cb = n2[children[c]].box;
-            float d[3] = {0.5f * (cb.mn[0] + cb.mx[0]) - pc[0], 0.5f * (cb.mn[1] + cb.mx[1]) - pc[1],
-                          0.5f * (cb.mn[2] + cb.mx[2]) - pc[2]};
-            for (int s = 0; s < 8; s++) {
-                float sx = (s & 4) ? -1.f : 1.f, sy = (s & 2) ? -1.f : 1.f, sz = (s & 1) ? -1.f : 1.f;
-                cost[c][s] = d[0] * sx + d[1] * sy + d[2] * sz;
-            }
-        }
-        int assignment[8];
-        bool filled[8] = {false, false, false, false, false, false, false, false};
-        for (int c = 0; c < 8; c++) assignment[c] = -1;
-        for (;;) {
-            float min_cost = std::numeric_limits<float>::max();
-            int min_slot = -1, min_index = -1;
-            for (int c = 0; c < count; c++) {
-                if (assignment[c] != -1) continue;
-                for (int s = 0; s < 8; s++) {
-                    if (!filled[s] && cost[c][s] < min_cost) {
-                        min_cost = cost[c][s];
-                        min_slot = s;
-                        min_index = c;
-                    }
-                }
-            }
-            if (min_slot < 0) break;
-            filled[min_slot] = true;
-            assignment[min_index] = min_slot;
-        }
-        for (int c = 0; c < count; c++) {
-            int s = assignment[c];
-            if (s < 0) { // non-finite centre: first free slot
-                for (s = 0; s < 8 && filled[s]; s++) {}
-                filled[s] = true;
-            }
-            slots[s].n2 = children[c];
-            slots[s].used = true;
-            slots[s].inner = dec[(size_t)children[c] * 7].type == kInternal;
-        }
-    }
-
-    // Node encoding, embree/src/bvh_embree_to_cwbvh.rs:85-186.
-    static float quant_scale(float extent, float lo, float hi_world) {
-        (void)lo;
-        (void)hi_world;
-        float x = std::max(extent, 1e-20f) * (1.0f / 255.0f);
-        int k;
-        float m = std::frexp(x, &k); // x = m * 2^k, m in [0.5, 1)
-        float e = std::ldexp(1.0f, m == 0.5f ? k - 1 : k);
-        return e;
     }
 
     // Where emit writes: the CwBvh itself, or the private buffers of a subtree task.
@@ -1579,20 +1410,19 @@ struct Collapser {
     // on it.  Nothing downstream takes such a tree either - validators and traversal stacks are sized for
     // kMaxCwbvhDepth levels - so the emission stops descending there and the build is refused (TreeTooDeep).
     std::atomic<bool> too_deep{false};
+    mutable std::atomic<bool> broken{false}; // slot_children met a node with more than eight children
+    void check_emitted() const {
+        if (broken.load()) throw std::logic_error("the collapse decisions give a node more than eight children");
+        if (too_deep.load()) throw TreeTooDeep();
+    }
 
     // The inner (CWBVH-node) children of the node that BVH2 node `ni` becomes, in slot order.
-    void inner_children(uint32_t ni, uint32_t *inner, int &n_inner) const {
-        uint32_t children[8];
-        int count = 0;
-        if (n2[ni].count == 1)
-            children[count++] = ni;
-        else
-            get_children(ni, 0, children, count);
-        Child slots[8];
-        order_children(n2[ni].box, children, count, slots);
+    void inner_children(uint32_t ni, uint32_t *out, int &n_inner) const {
+        uint32_t slots[8];
+        slot_children(ni, slots);
         n_inner = 0;
         for (int s = 0; s < 8; s++)
-            if (slots[s].used && slots[s].inner) inner[n_inner++] = slots[s].n2;
+            if (slots[s] != kNoChild && inner(slots[s])) out[n_inner++] = slots[s];
     }
 
     // Emission on every core.  The layout emit() produces is sequential by construction (a node's children are
@@ -1606,7 +1436,7 @@ struct Collapser {
         const uint32_t grain = std::max<uint32_t>(4096u, n2[0].count / (uint32_t)(std::max(threads, 1) * 16));
         if (threads <= 1 || n2[0].count <= grain || n2.size() < ((size_t)1 << 16)) {
             emit(global, 0, 0, 0, nullptr);
-            if (too_deep.load()) throw TreeTooDeep();
+            check_emitted();
             return;
         }
         std::vector<uint32_t> roots;
@@ -1643,7 +1473,7 @@ struct Collapser {
         emit(global, 0, 0, 0, nullptr);
         task_roots = nullptr;
         tasks = nullptr;
-        if (too_deep.load()) throw TreeTooDeep();
+        check_emitted();
     }
 
     // Puts a finished subtree where the sequential emission would have written it: root at out_idx, descendants and
@@ -1679,14 +1509,8 @@ struct Collapser {
             }
         }
         const Node2 &nd = n2[ni];
-        uint32_t children[8];
-        int count = 0;
-        if (nd.count == 1)
-            children[count++] = ni; // single-primitive scene: root with one leaf child
-        else
-            get_children(ni, 0, children, count);
-        Child slots[8];
-        order_children(nd.box, children, count, slots);
+        uint32_t slots[8];
+        slot_children(ni, slots); // (a single-primitive scene: the root with one leaf child)
 
         uint32_t child_base = (uint32_t)sink.nodes->size();
         uint32_t prim_base = (uint32_t)sink.prims->size();
@@ -1696,13 +1520,8 @@ struct Collapser {
         float e[3];
         for (int k = 0; k < 3; k++) {
             node.p[k] = nd.box.mn[k];
-            e[k] = quant_scale(nd.box.mx[k] - nd.box.mn[k], nd.box.mn[k], nd.box.mx[k]);
-            // make sure 255 steps reach the far plane after rounding
-            while (std::ceil(((double)nd.box.mx[k] - (double)nd.box.mn[k]) / (double)e[k]) > 255.0)
-                e[k] *= 2.0f;
-            uint32_t bits;
-            std::memcpy(&bits, &e[k], 4);
-            node.e[k] = (uint8_t)(bits >> 23);
+            e[k] = quant_step(nd.box.mn[k], nd.box.mx[k]);
+            node.e[k] = (uint8_t)(rf_bits(e[k]) >> 23);
         }
         node.child_base_idx = child_base;
         node.primitive_base_idx = prim_base;
@@ -1710,33 +1529,25 @@ struct Collapser {
         uint32_t n_inner = 0, total_tris = 0;
         std::vector<uint32_t> prims;
         for (int s = 0; s < 8; s++) {
-            if (!slots[s].used) continue;
-            const Aabb &cb = n2[slots[s].n2].box;
+            if (slots[s] == kNoChild) continue;
+            const Aabb &cb = n2[slots[s]].box;
             uint8_t *qmin[3] = {node.child_min_x, node.child_min_y, node.child_min_z};
             uint8_t *qmax[3] = {node.child_max_x, node.child_max_y, node.child_max_z};
             for (int k = 0; k < 3; k++) {
-                float rcp = 1.0f / e[k];
-                float lo = std::floor((cb.mn[k] - node.p[k]) * rcp);
-                float hi = std::ceil((cb.mx[k] - node.p[k]) * rcp);
-                lo = std::min(std::max(lo, 0.0f), 255.0f);
-                hi = std::min(std::max(hi, 0.0f), 255.0f);
-                // keep the decoded planes conservative under f32 rounding of (c - p)
-                while (lo > 0.0f && (double)node.p[k] + (double)lo * (double)e[k] > (double)cb.mn[k]) lo -= 1.0f;
-                while (hi < 255.0f && (double)node.p[k] + (double)hi * (double)e[k] < (double)cb.mx[k]) hi += 1.0f;
+                uint32_t lo, hi;
+                quant_planes(node.p[k], e[k], cb.mn[k], cb.mx[k], lo, hi);
                 qmin[k][s] = (uint8_t)lo;
                 qmax[k][s] = (uint8_t)hi;
             }
-            if (slots[s].inner) {
+            if (inner(slots[s])) {
                 node.imask |= (uint8_t)(1u << s);
-                node.child_meta[s] = (uint8_t)((24 + s) | 0x20);
+                node.child_meta[s] = inner_meta(s);
                 n_inner++;
             } else {
                 prims.clear();
-                collect_prims(slots[s].n2, prims);
-                uint32_t np = (uint32_t)prims.size();
-                static const uint8_t unary[4] = {0, 0x20, 0x60, 0xE0};
-                node.child_meta[s] = (uint8_t)(total_tris | unary[np]);
-                total_tris += np;
+                collect_prims(slots[s], prims);
+                node.child_meta[s] = leaf_meta(total_tris, (uint32_t)prims.size());
+                total_tris += (uint32_t)prims.size();
                 for (uint32_t p : prims) sink.prims->push_back(p);
             }
         }
@@ -1745,8 +1556,8 @@ struct Collapser {
         sink.nodes->resize(sink.nodes->size() + n_inner);
         uint32_t k = 0;
         for (int s = 0; s < 8; s++) {
-            if (slots[s].used && slots[s].inner) {
-                emit(sink, child_base + k, slots[s].n2, depth + 1, deepest);
+            if (slots[s] != kNoChild && inner(slots[s])) {
+                emit(sink, child_base + k, slots[s], depth + 1, deepest);
                 k++;
             }
         }
@@ -1790,7 +1601,6 @@ void build_from_boxes(const Aabb *boxes, const float *centroids, uint64_t n, con
     };
     if (params.ploc_search_distance > 0 && params.ploc_device >= 0 && n >= kDevicePlocMinPrims) {
         // Morton sort + PLOC rounds as kernels; the tree is the one PlocBuilder::run returns
-        static_assert(sizeof(Node2) == 40, "Node2 is shared with ploc_gpu.cpp");
         b2.nodes.resize(2 * (size_t)n - 1);
         uint32_t root = 0;
         std::string err;

@@ -10,37 +10,16 @@
 //   5. output offsets    top-down: the sequential emission (a node's children allocated when it is visited, its primitives
 //                        appended then, children visited in slot order) fixes every index as a function of those sizes
 //   6. encode            one thread per record: quantisation frame, child boxes, meta bytes, primitive indices
-// Same decisions, same tie rules, same binary32 / binary64 operations without contraction as Collapser in builder.cpp,
-// so the bytes are the host's bytes.
+// The decisions, the children of a node, their slots and the encoding are build_rules.h's, the very functions Collapser in
+// builder.cpp calls, so the bytes are the host's bytes.
 #include "collapse_gpu.h"
 
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <cstring>
+
+#include "build_levels.h"
 
 namespace trx {
 namespace {
-
-struct DevNode { // = Node2 of builder.cpp (40 bytes)
-    Aabb box;
-    uint32_t left, right, prim, count;
-};
-static_assert(sizeof(DevNode) == 40, "Node2 layout");
-
-enum : uint32_t { kLeaf = 0, kInternal = 1, kDistribute = 2 };
-struct Dec { // = Decision of builder.cpp
-    float cost;
-    uint32_t type, dl, dr;
-};
-// 8 bytes in memory: cost | type, dl, dr, 0
-__device__ __forceinline__ Dec load_dec(const uint2 *dec, size_t i) {
-    const uint2 v = dec[i];
-    return Dec{__uint_as_float(v.x), v.y & 0xffu, (v.y >> 8) & 0xffu, (v.y >> 16) & 0xffu};
-}
-__device__ __forceinline__ uint2 pack_dec(float cost, uint32_t type, uint32_t dl, uint32_t dr) {
-    return make_uint2(__float_as_uint(cost), type | (dl << 8) | (dr << 16));
-}
 
 struct Rec { // one per CWBVH node, in discovery order (level by level)
     uint32_t n2;          // the BVH2 node it is made from
@@ -52,201 +31,28 @@ struct Rec { // one per CWBVH node, in discovery order (level by level)
 };
 static_assert(sizeof(Rec) == 64, "record size");
 constexpr uint32_t kEmpty = 0xffffffffu;
-constexpr int kBlock = 256;
 
-__device__ __forceinline__ float half_area_dev(const Aabb &b) {
-    const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
-    if (!(dx >= 0.f) || !(dy >= 0.f) || !(dz >= 0.f)) return 0.f;
-    return dx * dy + dy * dz + dz * dx;
-}
-
-__device__ __forceinline__ DevNode load_node(const DevNode *nodes, uint32_t i) {
-    const uint2 *p = reinterpret_cast<const uint2 *>(nodes + i);
-    const uint2 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
-    DevNode n;
-    n.box.mn[0] = __uint_as_float(a.x); n.box.mn[1] = __uint_as_float(a.y); n.box.mn[2] = __uint_as_float(b.x);
-    n.box.mx[0] = __uint_as_float(b.y); n.box.mx[1] = __uint_as_float(c.x); n.box.mx[2] = __uint_as_float(c.y);
-    n.left = d.x; n.right = d.y; n.prim = e.x; n.count = e.y;
-    return n;
-}
-__device__ __forceinline__ void load_links(const DevNode *nodes, uint32_t i, uint32_t &left, uint32_t &right, uint32_t &prim, uint32_t &count) {
-    const uint2 *p = reinterpret_cast<const uint2 *>(nodes + i);
-    const uint2 d = p[3], e = p[4];
-    left = d.x; right = d.y; prim = e.x; count = e.y;
-}
-
-// `want` consecutive places at the end of a list whose length is *counter: one atomic per wave.
-__device__ __forceinline__ uint32_t wave_append(uint32_t *counter, uint32_t want) {
-    const uint32_t lane = __lane_id();
-    uint32_t scan = want; // inclusive prefix sum over the wave
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(scan, d, 64);
-        if ((int)lane >= d) scan += up;
-    }
-    const uint32_t total = __shfl(scan, 63, 64);
-    uint32_t base = 0;
-    if (lane == 63 && total) base = atomicAdd(counter, total);
-    base = __shfl(base, 63, 64);
-    return base + scan - want;
-}
-
-// ---- 1. BVH2 levels
-// (capacity = entries `out` can take; an append past it is dropped and the host, which reads the counter, reports the links)
-__global__ __launch_bounds__(kBlock) void k2_expand(const DevNode *nodes, const uint32_t *in, uint32_t n_in, uint32_t *out, uint32_t *counter,
-                                                     uint32_t capacity) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t left = 0, right = 0, prim, count = 0;
-    if (t < n_in) load_links(nodes, in[t], left, right, prim, count);
-    const bool inner = count > 1;
-    const uint32_t at = wave_append(counter, inner ? 2u : 0u);
-    if (inner && at + 2u <= capacity) {
-        out[at] = left;
-        out[at + 1] = right;
-    }
-}
-
-// ---- 2. cost table (Collapser::cost_range for one node)
-__global__ __launch_bounds__(kBlock) void k2_cost(DevNode *nodes, uint2 *dec, const uint32_t *list, uint32_t n, uint32_t max_prims,
+// ---- 2. cost table
+__global__ __launch_bounds__(kBlock) void k2_cost(Node2 *nodes, Decision *dec, const uint32_t *list, uint32_t n, uint32_t max_prims,
                                                     float traversal_cost, float prim_cost) {
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= n) return;
     const uint32_t ni = list[t];
-    DevNode nd = load_node(nodes, ni);
+    Node2 nd = load_node(nodes, ni);
+    float cl[7], cr[7];
     if (nd.count != 1) { // primitives below: the children (a level down) have theirs; the caller's may be stale
         nd.count = nodes[nd.left].count + nodes[nd.right].count;
         nodes[ni].count = nd.count;
-    }
-    uint2 *d = dec + (size_t)ni * 7;
-    const float area = half_area_dev(nd.box);
-    if (nd.count == 1) {
-        const uint2 v = pack_dec(area * prim_cost, kLeaf, 0xff, 0xff);
-        for (int i = 0; i < 7; i++) d[i] = v;
-        return;
-    }
-    float cl[7], cr[7];
-    for (int k = 0; k < 7; k++) {
-        cl[k] = __uint_as_float(dec[(size_t)nd.left * 7 + k].x);
-        cr[k] = __uint_as_float(dec[(size_t)nd.right * 7 + k].x);
-    }
-    const float inf = __builtin_inff();
-    const float cost_leaf = nd.count <= max_prims ? area * (float)nd.count * prim_cost : inf;
-    float cost_dist = inf;
-    uint32_t bl = 0, br = 6; // (as Collapser::cost_range: a valid split also where every cost is +inf)
-    for (int k = 0; k < 7; k++) {
-        const float c = cl[k] + cr[6 - k];
-        if (c < cost_dist) {
-            cost_dist = c;
-            bl = (uint32_t)k;
-            br = (uint32_t)(6 - k);
+        for (int k = 0; k < 7; k++) {
+            cl[k] = dec[(size_t)nd.left * 7 + k].cost;
+            cr[k] = dec[(size_t)nd.right * 7 + k].cost;
         }
     }
-    const float cost_internal = cost_dist + area * traversal_cost;
-    uint2 prev = cost_leaf < cost_internal ? pack_dec(cost_leaf, kLeaf, bl, br) : pack_dec(cost_internal, kInternal, bl, br);
-    d[0] = prev;
-    for (int i = 1; i < 7; i++) {
-        float best = __uint_as_float(prev.x);
-        uint32_t l = 0xff, r = 0xff;
-        for (int k = 0; k < i; k++) {
-            const float c = cl[k] + cr[i - k - 1];
-            if (c < best) {
-                best = c;
-                l = (uint32_t)k;
-                r = (uint32_t)(i - k - 1);
-            }
-        }
-        if (l != 0xff) prev = pack_dec(best, kDistribute, l, r);
-        d[i] = prev;
-    }
+    collapse_costs(half_area(nd.box), nd.count, cl, cr, max_prims, traversal_cost, prim_cost, dec + (size_t)ni * 7);
 }
 
 // ---- 3. CWBVH levels
-// Collapser::get_children(ni, 0): the BVH2 nodes that become the children of the CWBVH node made from ni, left to right.
-__device__ __forceinline__ int children_of(const DevNode *nodes, const uint2 *dec, uint32_t ni, uint32_t *children) {
-    // pending visits, the next one on top: {node, decision index | expand flag << 8}
-    uint32_t st_n[16], st_i[16];
-    int sp = 0, count = 0;
-    st_n[0] = ni;
-    st_i[0] = 0x100u;
-    sp = 1;
-    while (sp > 0) {
-        sp--;
-        const uint32_t n = st_n[sp], ii = st_i[sp];
-        if (!(ii & 0x100u)) {
-            if (count < 8) children[count] = n;
-            count++;
-            continue;
-        }
-        uint32_t left, right, prim, cnt;
-        load_links(nodes, n, left, right, prim, cnt);
-        if (cnt == 1) {
-            if (count < 8) children[count] = n;
-            count++;
-            continue;
-        }
-        const Dec d = load_dec(dec, (size_t)n * 7 + (ii & 0xffu));
-        const bool xr = load_dec(dec, (size_t)right * 7 + d.dr).type == kDistribute;
-        const bool xl = load_dec(dec, (size_t)left * 7 + d.dl).type == kDistribute;
-        if (sp + 2 > 16) return 9; // cannot happen: at most eight children, a pending visit per child
-        st_n[sp] = right;
-        st_i[sp] = xr ? (0x100u | d.dr) : 0u;
-        sp++;
-        st_n[sp] = left;
-        st_i[sp] = xl ? (0x100u | d.dl) : 0u;
-        sp++;
-    }
-    return count;
-}
-
-// Collapser::order_children: greedy octant-slot assignment (embree/src/bvh_embree.rs:284-349).  slot[s] = index into
-// children or -1.
-__device__ __forceinline__ void order_children_dev(const DevNode *nodes, const Aabb &box, const uint32_t *children, int count, int *slot_child) {
-    const float pc[3] = {0.5f * (box.mn[0] + box.mx[0]), 0.5f * (box.mn[1] + box.mx[1]), 0.5f * (box.mn[2] + box.mx[2])};
-    float cost[8][8];
-    for (int c = 0; c < count; c++) {
-        const DevNode ch = load_node(nodes, children[c]);
-        const float d[3] = {0.5f * (ch.box.mn[0] + ch.box.mx[0]) - pc[0], 0.5f * (ch.box.mn[1] + ch.box.mx[1]) - pc[1],
-                            0.5f * (ch.box.mn[2] + ch.box.mx[2]) - pc[2]};
-        for (int s = 0; s < 8; s++) {
-            const float sx = (s & 4) ? -1.f : 1.f, sy = (s & 2) ? -1.f : 1.f, sz = (s & 1) ? -1.f : 1.f;
-            cost[c][s] = d[0] * sx + d[1] * sy + d[2] * sz;
-        }
-    }
-    int assignment[8];
-    bool filled[8];
-    for (int c = 0; c < 8; c++) {
-        assignment[c] = -1;
-        filled[c] = false;
-        slot_child[c] = -1;
-    }
-    for (;;) {
-        float min_cost = 3.402823466e+38f;
-        int min_slot = -1, min_index = -1;
-        for (int c = 0; c < count; c++) {
-            if (assignment[c] != -1) continue;
-            for (int s = 0; s < 8; s++) {
-                if (!filled[s] && cost[c][s] < min_cost) {
-                    min_cost = cost[c][s];
-                    min_slot = s;
-                    min_index = c;
-                }
-            }
-        }
-        if (min_slot < 0) break;
-        filled[min_slot] = true;
-        assignment[min_index] = min_slot;
-    }
-    for (int c = 0; c < count; c++) {
-        int s = assignment[c];
-        if (s < 0) { // non-finite centre: first free slot
-            for (s = 0; s < 8 && filled[s]; s++) {}
-            if (s > 7) s = 7;
-            filled[s] = true;
-        }
-        slot_child[s] = c;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k8_expand(const DevNode *nodes, const uint2 *dec, Rec *recs, uint32_t begin, uint32_t end,
+__global__ __launch_bounds__(kBlock) void k8_expand(const Node2 *nodes, const Decision *dec, Rec *recs, uint32_t begin, uint32_t end,
                                                       uint32_t *n_recs, uint32_t *trouble) {
     const uint32_t r = begin + blockIdx.x * kBlock + threadIdx.x;
     uint32_t n_inner = 0, imask = 0, total_tris = 0;
@@ -255,18 +61,19 @@ __global__ __launch_bounds__(kBlock) void k8_expand(const DevNode *nodes, const 
     if (r < end) {
         const uint32_t ni = recs[r].n2;
         uint32_t children[8];
-        const int count = children_of(nodes, dec, ni, children);
+        const int count = collapsed_children(
+            ni, [&](uint32_t i, uint32_t &left, uint32_t &right, uint32_t &cnt) { uint32_t prim; load_links(nodes, i, left, right, prim, cnt); },
+            [&](size_t k) { return dec[k]; }, children);
         if (count > 8) {
             atomicOr(trouble, 1u);
         } else {
-            const DevNode nd = load_node(nodes, ni);
             int slot_child[8];
-            order_children_dev(nodes, nd.box, children, count, slot_child);
+            assign_slots(load_node(nodes, ni).box, [&](int c) { return load_node(nodes, children[c]).box; }, count, slot_child);
             for (int s = 0; s < 8; s++) {
                 if (slot_child[s] < 0) continue;
                 const uint32_t c = children[slot_child[s]];
                 slot_n2[s] = c;
-                if (load_dec(dec, (size_t)c * 7).type == kInternal) {
+                if (dec[(size_t)c * 7].type == kInternal) {
                     imask |= 1u << s;
                     n_inner++;
                 } else {
@@ -330,22 +137,16 @@ __global__ __launch_bounds__(kBlock) void k8_offsets(Rec *recs, uint32_t begin, 
 }
 
 // ---- 6. encode (Collapser::emit for one node; embree/src/bvh_embree_to_cwbvh.rs:85-186)
-__global__ __launch_bounds__(kBlock) void k8_encode(const DevNode *nodes, const Rec *recs, uint32_t n_recs, uint4 *out_nodes, uint32_t *out_prims) {
+__global__ __launch_bounds__(kBlock) void k8_encode(const Node2 *nodes, const Rec *recs, uint32_t n_recs, uint4 *out_nodes, uint32_t *out_prims) {
     const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
     if (r >= n_recs) return;
     const Rec rec = recs[r];
-    const DevNode nd = load_node(nodes, rec.n2);
+    const Node2 nd = load_node(nodes, rec.n2);
     float e[3], p[3];
     uint32_t ebyte[3];
     for (int k = 0; k < 3; k++) {
         p[k] = nd.box.mn[k];
-        // quant_scale: the smallest power of two >= max(extent, 1e-20) / 255
-        const float extent = nd.box.mx[k] - nd.box.mn[k];
-        const float x = (extent < 1e-20f ? 1e-20f : extent) * (1.0f / 255.0f);
-        const uint32_t xb = __float_as_uint(x);
-        e[k] = __uint_as_float((xb & 0x7fffffu) ? ((xb >> 23) + 1u) << 23 : xb);
-        // make sure 255 steps reach the far plane after rounding
-        while (ceil(((double)nd.box.mx[k] - (double)nd.box.mn[k]) / (double)e[k]) > 255.0) e[k] *= 2.0f;
+        e[k] = quant_step(nd.box.mn[k], nd.box.mx[k]);
         ebyte[k] = (__float_as_uint(e[k]) >> 23) & 0xffu;
     }
     const uint32_t imask = rec.info & 0xffu;
@@ -354,24 +155,16 @@ __global__ __launch_bounds__(kBlock) void k8_encode(const DevNode *nodes, const 
     for (int s = 0; s < 8; s++) {
         const uint32_t c = rec.slot_n2[s];
         if (c == kEmpty) continue;
-        const DevNode ch = load_node(nodes, c);
+        const Node2 ch = load_node(nodes, c);
         for (int k = 0; k < 3; k++) {
-            const float rcp = 1.0f / e[k];
-            float lo = floorf((ch.box.mn[k] - p[k]) * rcp);
-            float hi = ceilf((ch.box.mx[k] - p[k]) * rcp);
-            lo = lo < 0.0f ? 0.0f : lo; // std::min(std::max(v, 0), 255)
-            lo = 255.0f < lo ? 255.0f : lo;
-            hi = hi < 0.0f ? 0.0f : hi;
-            hi = 255.0f < hi ? 255.0f : hi;
-            // keep the decoded planes conservative under f32 rounding of (c - p)
-            while (lo > 0.0f && (double)p[k] + (double)lo * (double)e[k] > (double)ch.box.mn[k]) lo -= 1.0f;
-            while (hi < 255.0f && (double)p[k] + (double)hi * (double)e[k] < (double)ch.box.mx[k]) hi += 1.0f;
-            q[2 * k][s >> 2] |= ((uint32_t)lo & 0xffu) << (8 * (s & 3));
-            q[2 * k + 1][s >> 2] |= ((uint32_t)hi & 0xffu) << (8 * (s & 3));
+            uint32_t lo, hi;
+            quant_planes(p[k], e[k], ch.box.mn[k], ch.box.mx[k], lo, hi);
+            q[2 * k][s >> 2] |= lo << (8 * (s & 3));
+            q[2 * k + 1][s >> 2] |= hi << (8 * (s & 3));
         }
         uint32_t m;
         if (imask & (1u << s)) {
-            m = (24u + (uint32_t)s) | 0x20u;
+            m = inner_meta(s);
         } else {
             // Collapser::collect_prims: the leaves below c in pre-order (left before right); at most three
             uint32_t st[4];
@@ -389,8 +182,7 @@ __global__ __launch_bounds__(kBlock) void k8_encode(const DevNode *nodes, const 
                     st[sp++] = left;
                 }
             }
-            const uint32_t unary = np == 1 ? 0x20u : np == 2 ? 0x60u : np == 3 ? 0xE0u : 0u;
-            m = (total_tris | unary) & 0xffu;
+            m = leaf_meta(total_tris, np);
             total_tris += np;
         }
         meta[s >> 2] |= m << (8 * (s & 3));
@@ -404,118 +196,54 @@ __global__ __launch_bounds__(kBlock) void k8_encode(const DevNode *nodes, const 
     o[4] = make_uint4(q[4][0], q[4][1], q[5][0], q[5][1]);
 }
 
-#define CG_TRY(expr)                                                     \
-    do {                                                                 \
-        hipError_t e_ = (expr);                                          \
-        if (e_ != hipSuccess) {                                          \
-            err = std::string(#expr) + ": " + hipGetErrorString(e_);     \
-            return false;                                                \
-        }                                                                \
-    } while (0)
-
-struct Buffers {
-    DevNode *nodes = nullptr;
-    uint2 *dec = nullptr;
-    uint32_t *list = nullptr, *counter = nullptr, *out_prims = nullptr;
-    Rec *recs = nullptr;
-    uint4 *out_nodes = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~Buffers() {
-        if (nodes) (void)hipFree(nodes);
-        if (dec) (void)hipFree(dec);
-        if (list) (void)hipFree(list);
-        if (counter) (void)hipFree(counter);
-        if (out_prims) (void)hipFree(out_prims);
-        if (recs) (void)hipFree(recs);
-        if (out_nodes) (void)hipFree(out_nodes);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-
-inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
 } // namespace
 
 bool collapse_encode_device(int device, const void *nodes, size_t n_nodes, uint32_t max_prims_per_leaf, float traversal_cost,
                             float prim_cost, std::vector<CwbvhNode> &out_nodes, std::vector<uint32_t> &out_prims,
                             float *root_cost, double *seconds, std::string &err, uint32_t *levels) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        err = "no HIP device " + std::to_string(device) + " for the GPU build stage";
-        return false;
-    }
+    DeviceScope scope;
+    if (!scope.enter(device, err)) return false;
     if (n_nodes < 3 || n_nodes > 0x7fffffffull || (n_nodes & 1) == 0) {
         err = "collapse_encode_device: needs a tree of 2n-1 nodes, n >= 2";
         return false;
     }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    struct Guard {
-        int prev;
-        ~Guard() {
-            if (prev >= 0) (void)hipSetDevice(prev);
-        }
-    } guard{prev};
-    CG_TRY(hipSetDevice(device));
     const uint32_t n = (uint32_t)n_nodes, n_prims = (n + 1) / 2;
-    Buffers b;
-    CG_TRY(hipMalloc(&b.nodes, (size_t)n * sizeof(DevNode)));
-    CG_TRY(hipMalloc(&b.dec, (size_t)n * 7 * sizeof(uint2)));
-    CG_TRY(hipMalloc(&b.list, (size_t)n * 4));
-    CG_TRY(hipMalloc(&b.counter, 16));
+    DevBuf<Node2> d_nodes;
+    DevBuf<Decision> d_dec;
+    DevBuf<uint32_t> d_list, d_counter, d_out_prims;
+    DevBuf<Rec> d_recs;
+    DevBuf<uint4> d_out_nodes;
+    Event ev0, ev1;
+    TRX_BUILD_TRY(d_nodes.alloc(n));
+    TRX_BUILD_TRY(d_dec.alloc((size_t)n * 7));
+    TRX_BUILD_TRY(d_list.alloc(n));
+    TRX_BUILD_TRY(d_counter.alloc(4));
     // a CWBVH node has at least two children unless it is the root of a one-primitive scene, so there are fewer nodes than
     // primitives
-    CG_TRY(hipMalloc(&b.recs, (size_t)n_prims * sizeof(Rec)));
-    CG_TRY(hipMalloc(&b.out_prims, (size_t)n_prims * 4));
-    CG_TRY(hipEventCreate(&b.ev0));
-    CG_TRY(hipEventCreate(&b.ev1));
-    CG_TRY(hipMemcpy(b.nodes, nodes, (size_t)n * sizeof(DevNode), hipMemcpyHostToDevice));
-    CG_TRY(hipEventRecord(b.ev0, nullptr));
+    TRX_BUILD_TRY(d_recs.alloc(n_prims));
+    TRX_BUILD_TRY(d_out_prims.alloc(n_prims));
+    TRX_BUILD_TRY(ev0.create());
+    TRX_BUILD_TRY(ev1.create());
+    TRX_BUILD_TRY(hipMemcpy(d_nodes.get(), nodes, (size_t)n * sizeof(Node2), hipMemcpyHostToDevice));
+    TRX_BUILD_TRY(hipEventRecord(ev0.get(), nullptr));
 
-    // 1. BVH2 levels
-    std::vector<uint32_t> level{0u, 1u}; // level L = list[level[L] .. level[L + 1])
-    {
-        const uint32_t zero = 0;
-        CG_TRY(hipMemcpy(b.list, &zero, 4, hipMemcpyHostToDevice));
-    }
-    for (;;) {
-        const uint32_t begin = level[level.size() - 2], end = level.back();
-        if (end == begin) {
-            level.pop_back();
-            break;
-        }
-        if (end >= n) break; // every node is listed: the last level holds leaves only
-        CG_TRY(hipMemsetAsync(b.counter, 0, 4, nullptr));
-        hipLaunchKernelGGL(k2_expand, grid_for(end - begin), dim3(kBlock), 0, nullptr, b.nodes, b.list + begin, end - begin, b.list + end, b.counter,
-                           (uint32_t)(n - end));
-        CG_TRY(hipGetLastError());
-        uint32_t made = 0;
-        CG_TRY(hipMemcpy(&made, b.counter, 4, hipMemcpyDeviceToHost));
-        if ((size_t)end + made > n) {
-            err = "collapse_encode_device: the links do not describe a tree of n_nodes nodes";
-            return false;
-        }
-        level.push_back(end + made);
-    }
-    if (level.back() != n) {
-        err = "collapse_encode_device: " + std::to_string(n - level.back()) + " nodes are not reachable from node 0";
-        return false;
-    }
+    // 1. BVH2 levels: level L = list[level[L] .. level[L + 1])
+    std::vector<uint32_t> level;
+    if (!expand_levels("collapse_encode_device", d_nodes.get(), n, d_list.get(), d_counter.get(), level, err)) return false;
     // 2. cost table, deepest level first
     for (size_t L = level.size() - 1; L-- > 0;) {
         const uint32_t begin = level[L], end = level[L + 1];
-        hipLaunchKernelGGL(k2_cost, grid_for(end - begin), dim3(kBlock), 0, nullptr, b.nodes, b.dec, b.list + begin, end - begin,
+        hipLaunchKernelGGL(k2_cost, grid_for(end - begin), dim3(kBlock), 0, nullptr, d_nodes.get(), d_dec.get(), d_list.get() + begin, end - begin,
                            max_prims_per_leaf, traversal_cost, prim_cost);
     }
-    CG_TRY(hipGetLastError());
+    TRX_BUILD_TRY(hipGetLastError());
     // 3. CWBVH levels
     std::vector<uint32_t> level8{0u, 1u};
     {
         const uint32_t first[2] = {1u, 0u}; // records so far; trouble flags
-        CG_TRY(hipMemcpy(b.counter, first, 8, hipMemcpyHostToDevice));
+        TRX_BUILD_TRY(hipMemcpy(d_counter.get(), first, 8, hipMemcpyHostToDevice));
         const uint32_t zero = 0;
-        CG_TRY(hipMemcpy(&b.recs[0].n2, &zero, 4, hipMemcpyHostToDevice));
+        TRX_BUILD_TRY(hipMemcpy(&d_recs.get()->n2, &zero, 4, hipMemcpyHostToDevice));
     }
     for (;;) {
         const uint32_t begin = level8[level8.size() - 2], end = level8.back();
@@ -523,10 +251,10 @@ bool collapse_encode_device(int device, const void *nodes, size_t n_nodes, uint3
             level8.pop_back();
             break;
         }
-        hipLaunchKernelGGL(k8_expand, grid_for(end - begin), dim3(kBlock), 0, nullptr, b.nodes, b.dec, b.recs, begin, end, b.counter, b.counter + 1);
-        CG_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k8_expand, grid_for(end - begin), dim3(kBlock), 0, nullptr, d_nodes.get(), d_dec.get(), d_recs.get(), begin, end, d_counter.get(), d_counter.get() + 1);
+        TRX_BUILD_TRY(hipGetLastError());
         uint32_t state[2] = {0, 0};
-        CG_TRY(hipMemcpy(state, b.counter, 8, hipMemcpyDeviceToHost));
+        TRX_BUILD_TRY(hipMemcpy(state, d_counter.get(), 8, hipMemcpyDeviceToHost));
         if (state[1] || state[0] > n_prims || state[0] < end) {
             err = "collapse_encode_device: the decisions give a node more than eight children or 24 primitives";
             return false;
@@ -537,33 +265,34 @@ bool collapse_encode_device(int device, const void *nodes, size_t n_nodes, uint3
     if (levels) *levels = (uint32_t)level8.size() - 1u;
     // 4. subtree sizes, 5. output offsets
     for (size_t L = level8.size() - 1; L-- > 0;)
-        hipLaunchKernelGGL(k8_sizes, grid_for(level8[L + 1] - level8[L]), dim3(kBlock), 0, nullptr, b.recs, level8[L], level8[L + 1]);
+        hipLaunchKernelGGL(k8_sizes, grid_for(level8[L + 1] - level8[L]), dim3(kBlock), 0, nullptr, d_recs.get(), level8[L], level8[L + 1]);
     for (size_t L = 0; L + 1 < level8.size(); L++)
-        hipLaunchKernelGGL(k8_offsets, grid_for(level8[L + 1] - level8[L]), dim3(kBlock), 0, nullptr, b.recs, level8[L], level8[L + 1]);
-    CG_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k8_offsets, grid_for(level8[L + 1] - level8[L]), dim3(kBlock), 0, nullptr, d_recs.get(), level8[L], level8[L + 1]);
+    TRX_BUILD_TRY(hipGetLastError());
     // 6. encode
-    CG_TRY(hipMalloc(&b.out_nodes, (size_t)n_recs * sizeof(CwbvhNode)));
-    hipLaunchKernelGGL(k8_encode, grid_for(n_recs), dim3(kBlock), 0, nullptr, b.nodes, b.recs, n_recs, b.out_nodes, b.out_prims);
-    CG_TRY(hipGetLastError());
-    CG_TRY(hipEventRecord(b.ev1, nullptr));
+    static_assert(sizeof(CwbvhNode) == 5 * sizeof(uint4), "a node is five uint4");
+    TRX_BUILD_TRY(d_out_nodes.alloc((size_t)n_recs * 5));
+    hipLaunchKernelGGL(k8_encode, grid_for(n_recs), dim3(kBlock), 0, nullptr, d_nodes.get(), d_recs.get(), n_recs, d_out_nodes.get(), d_out_prims.get());
+    TRX_BUILD_TRY(hipGetLastError());
+    TRX_BUILD_TRY(hipEventRecord(ev1.get(), nullptr));
     Rec root;
-    CG_TRY(hipMemcpy(&root, b.recs, sizeof(Rec), hipMemcpyDeviceToHost));
+    TRX_BUILD_TRY(hipMemcpy(&root, d_recs.get(), sizeof(Rec), hipMemcpyDeviceToHost));
     if (root.sub_nodes != n_recs || root.sub_prims != n_prims) {
         err = "collapse_encode_device: subtree sizes do not add up";
         return false;
     }
     out_nodes.resize(n_recs);
     out_prims.resize(n_prims);
-    CG_TRY(hipMemcpy(out_nodes.data(), b.out_nodes, (size_t)n_recs * sizeof(CwbvhNode), hipMemcpyDeviceToHost));
-    CG_TRY(hipMemcpy(out_prims.data(), b.out_prims, (size_t)n_prims * 4, hipMemcpyDeviceToHost));
+    TRX_BUILD_TRY(hipMemcpy(out_nodes.data(), d_out_nodes.get(), (size_t)n_recs * sizeof(CwbvhNode), hipMemcpyDeviceToHost));
+    TRX_BUILD_TRY(hipMemcpy(out_prims.data(), d_out_prims.get(), (size_t)n_prims * 4, hipMemcpyDeviceToHost));
     if (root_cost) {
-        uint2 d0;
-        CG_TRY(hipMemcpy(&d0, b.dec, 8, hipMemcpyDeviceToHost));
-        std::memcpy(root_cost, &d0.x, 4);
+        Decision d0;
+        TRX_BUILD_TRY(hipMemcpy(&d0, d_dec.get(), sizeof(Decision), hipMemcpyDeviceToHost));
+        *root_cost = d0.cost;
     }
     if (seconds) {
         float ms = 0.f;
-        CG_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
+        TRX_BUILD_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
         *seconds += ms * 1e-3;
     }
     return true;

@@ -9,7 +9,7 @@
 
 namespace trx {
 
-// `nodes`: n_nodes Node2 records (builder.cpp layout, 40 bytes), root at index 0; the layout is otherwise free (children are
+// `nodes`: n_nodes Node2 records (build_rules.h), root at index 0; the layout is otherwise free (children are
 // followed through left/right) and `count` need only tell leaves (1) from inner nodes (> 1): it is recomputed here.  On
 // return out_nodes / out_prims hold what Collapser::compute_costs + emit_all of builder.cpp write for the same tree in
 // pre-order layout - byte for byte (tests/test_gpu_builder.py) - and *root_cost the collapse cost of the root (Decision 0

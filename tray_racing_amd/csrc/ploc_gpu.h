@@ -9,7 +9,7 @@ namespace trx {
 
 // Builds the BVH2 over `n` >= 2 boxes on `device`: Morton sort of the centroids at sort_bits (64 | 128), then PLOC
 // rounds with the given search radius (1 for the first depth_threshold rounds).  nodes_out receives 2n-1 Node2 records
-// (builder.cpp layout: box, left, right, prim, count) in creation order — leaves 0..n-1 in curve order, inner nodes
+// (build_rules.h: box, left, right, prim, count) in creation order — leaves 0..n-1 in curve order, inner nodes
 // after them, every child before its parent, `count` of inner nodes left 0 — and *root_out the root's index.
 // Returns false with `err` set on any failure (no device, out of memory): the caller reports it, nothing falls back.
 bool ploc_bvh2_device(int device, const Aabb *boxes, const float *centroids, uint32_t n, uint32_t radius,

@@ -2,74 +2,24 @@
 // topology of the node buffer kept, every quantisation frame and child box recomputed bottom-up.
 //
 // The per-node work is ONE __host__ __device__ function (refit_node) that the host twin (api_refit.cpp) and the device
-// kernels (refit_gpu.cpp) both call, so that the two produce the same bytes.  It restates the builder's rules:
+// kernels (refit_gpu.cpp) both call, so that the two produce the same bytes.  Where it does what the builder does it calls
+// the builder's own rules (build_rules.h), which is why a refit with the build's own inputs returns the build's bytes
+// (tests/test_refit.py):
 //   triangle record  convert_tris for TRX_TRI_VERTS_36 (api.cpp): e1 = v0 - v1, e2 = v2 - v0, ng = e1 x e2
-//   leaf box         min / max over the three vertices of every triangle of the slot (builder, api_build.cpp refs.box)
+//   leaf box         min / max over the three vertices of every triangle of the slot, the first of equal ones as grow_pt
+//                    keeps it (builder, api_build.cpp refs.box)
 //   inner box        the union of the boxes of the child node's own children (the f32 box array below, never the bytes)
-//   encoding         Collapser::emit (builder.cpp) and k8_encode (collapse_gpu.cpp): quant_scale, the doubling while
-//                    255 steps do not reach the far plane, floor / ceil with the reciprocal, the clamp, the two
-//                    conservative correction loops
-//   TLAS leaf box    the refit box of BLAS node instance_offsets[k] + entry[k]; with instance transforms its 8 corners
-//                    go through object_to_world[k] and the result is padded (instance_world_box, shared with
-//                    trx_flat_build_instanced)
-// The builder's own encoders are left as they are (the golden buffers pin their bytes); tests/test_refit.py shows the
-// three agree: a refit with the build's own inputs returns the build's bytes.
+//   encoding         quant_step and quant_planes, as Collapser::emit (builder.cpp) and k8_encode (collapse_gpu.cpp)
+//   TLAS leaf box    the refit box of BLAS node instance_offsets[k] + entry[k]; with instance transforms it goes through
+//                    instance_world_box, as in trx_flat_build_instanced
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
-#include "cwbvh_format.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define TRX_HD __host__ __device__
-#else
-#define TRX_HD
-#endif
+#include "build_rules.h"
 
 namespace trx {
-
-// min / max with std::min / std::max's answer for equal operands (the first one), so that signed zeros come out as the
-// builder's do
-TRX_HD inline float rf_min(float a, float b) { return b < a ? b : a; }
-TRX_HD inline float rf_max(float a, float b) { return a < b ? b : a; }
-
-TRX_HD inline uint32_t rf_bits(float f) {
-    union { float f; uint32_t u; } c;
-    c.f = f;
-    return c.u;
-}
-TRX_HD inline float rf_float(uint32_t u) {
-    union { float f; uint32_t u; } c;
-    c.u = u;
-    return c.f;
-}
-
-// The box of one instance in world space: the 8 corners of its BLAS box through the column-major affine object_to_world
-// (NULL = identity), ((m0 x + m4 y) + m8 z) + m12 per row, then padded by a few ulps of its magnitude (the ray is taken
-// to object space by the rounded INVERSE, which does not commute exactly with transforming the box forward).
-TRX_HD inline void instance_world_box(const Aabb &bb, const float *m, Aabb &wb) {
-    for (int a = 0; a < 3; a++) {
-        wb.mn[a] = 3.402823466e+38f;
-        wb.mx[a] = -3.402823466e+38f;
-    }
-    for (int c = 0; c < 8; c++) {
-        const float p[3] = {c & 1 ? bb.mx[0] : bb.mn[0], c & 2 ? bb.mx[1] : bb.mn[1], c & 4 ? bb.mx[2] : bb.mn[2]};
-        float q[3] = {p[0], p[1], p[2]};
-        if (m)
-            for (int r = 0; r < 3; r++) q[r] = m[r] * p[0] + m[4 + r] * p[1] + m[8 + r] * p[2] + m[12 + r];
-        for (int a = 0; a < 3; a++) {
-            wb.mn[a] = rf_min(wb.mn[a], q[a]);
-            wb.mx[a] = rf_max(wb.mx[a], q[a]);
-        }
-    }
-    for (int a = 0; a < 3; a++) {
-        const float pad = 1e-5f * (rf_max(fabsf(wb.mn[a]), fabsf(wb.mx[a])) + (wb.mx[a] - wb.mn[a])) + 1e-30f;
-        wb.mn[a] -= pad;
-        wb.mx[a] += pad;
-    }
-}
 
 // One 48-byte device triangle record from 9 vertex floats, exactly as convert_tris writes it for TRX_TRI_VERTS_36.
 TRX_HD inline void refit_tri_record(const float *v, TriDev &t) {
@@ -96,39 +46,6 @@ struct RefitCtx {
     const float *o2w;         // n_inst column-major 4x4, or null (no transforms: instance boxes unpadded)
     uint32_t n_inst, tlas_start;
 };
-
-TRX_HD inline uint32_t leaf_count(uint8_t m) {
-    const uint32_t bits = m >> 5;
-    return bits == 1 ? 1u : bits == 3 ? 2u : bits == 7 ? 3u : 0u;
-}
-
-// The encoder rule of Collapser::emit for one axis: quantisation step of a node whose box spans [mn, mx].
-TRX_HD inline float refit_quant_step(float mn, float mx) {
-    // quant_scale: the smallest power of two >= max(extent, 1e-20) / 255
-    const float extent = mx - mn;
-    const float x = (extent < 1e-20f ? 1e-20f : extent) * (1.0f / 255.0f);
-    const uint32_t xb = rf_bits(x);
-    float e = rf_float((xb & 0x7fffffu) ? ((xb >> 23) + 1u) << 23 : xb);
-    // make sure 255 steps reach the far plane after rounding
-    while (ceil(((double)mx - (double)mn) / (double)e) > 255.0) e *= 2.0f;
-    return e;
-}
-
-// ... and the two planes of a child box [cmn, cmx] in that frame.
-TRX_HD inline void refit_quant_planes(float p, float e, float cmn, float cmx, uint32_t &qlo, uint32_t &qhi) {
-    const float rcp = 1.0f / e;
-    float lo = floorf((cmn - p) * rcp);
-    float hi = ceilf((cmx - p) * rcp);
-    lo = lo < 0.0f ? 0.0f : lo; // std::min(std::max(v, 0), 255)
-    lo = 255.0f < lo ? 255.0f : lo;
-    hi = hi < 0.0f ? 0.0f : hi;
-    hi = 255.0f < hi ? 255.0f : hi;
-    // keep the decoded planes conservative under f32 rounding of (c - p)
-    while (lo > 0.0f && (double)p + (double)lo * (double)e > (double)cmn) lo -= 1.0f;
-    while (hi < 255.0f && (double)p + (double)hi * (double)e < (double)cmx) hi += 1.0f;
-    qlo = (uint32_t)lo & 0xffu;
-    qhi = (uint32_t)hi & 0xffu;
-}
 
 // Refits node i: child boxes from the triangles / instances / children's boxes, a new frame, new child bytes; imask,
 // bases, child_meta and the bytes of empty slots kept.  A node without children (the empty scene's root) is left as it
@@ -186,17 +103,11 @@ TRX_HD inline void refit_node(const RefitCtx &c, uint32_t i) {
                         pb.mx[a] = rf_max(v[a], rf_max(v[3 + a], v[6 + a]));
                     }
                 }
-                for (int a = 0; a < 3; a++) {
-                    b.mn[a] = rf_min(b.mn[a], pb.mn[a]);
-                    b.mx[a] = rf_max(b.mx[a], pb.mx[a]);
-                }
+                grow(b, pb);
             }
         }
         cb[s] = b;
-        for (int a = 0; a < 3; a++) {
-            nb.mn[a] = rf_min(nb.mn[a], b.mn[a]);
-            nb.mx[a] = rf_max(nb.mx[a], b.mx[a]);
-        }
+        grow(nb, b);
         any = true;
     }
     float *out_box = c.boxes + (size_t)i * 6;
@@ -209,7 +120,7 @@ TRX_HD inline void refit_node(const RefitCtx &c, uint32_t i) {
     uint32_t ebyte[3];
     for (int a = 0; a < 3; a++) {
         p[a] = nb.mn[a];
-        e[a] = refit_quant_step(nb.mn[a], nb.mx[a]);
+        e[a] = quant_step(nb.mn[a], nb.mx[a]);
         ebyte[a] = (rf_bits(e[a]) >> 23) & 0xffu;
     }
     // planes min_x,max_x,min_y,max_y,min_z,max_z as words {lo slots 0-3, slots 4-7}; empty slots keep their bytes
@@ -219,7 +130,7 @@ TRX_HD inline void refit_node(const RefitCtx &c, uint32_t i) {
         const uint32_t sh = 8u * (uint32_t)(s & 3), keep = ~(0xffu << sh);
         for (int a = 0; a < 3; a++) {
             uint32_t lo, hi;
-            refit_quant_planes(p[a], e[a], cb[s].mn[a], cb[s].mx[a], lo, hi);
+            quant_planes(p[a], e[a], cb[s].mn[a], cb[s].mx[a], lo, hi);
             q[2 * a][s >> 2] = (q[2 * a][s >> 2] & keep) | (lo << sh);
             q[2 * a + 1][s >> 2] = (q[2 * a + 1][s >> 2] & keep) | (hi << sh);
         }

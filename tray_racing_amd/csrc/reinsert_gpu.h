@@ -8,7 +8,7 @@ namespace trx {
 // Device-side copy of the tree being optimised and the scratch of the searches; lives for one reinsertion pass.
 struct ReinsertDevice;
 
-// Opens the context on `device` for a tree of n_nodes Node2 records (builder.cpp layout, 40 bytes).  false + err on failure.
+// Opens the context on `device` for a tree of n_nodes Node2 records (build_rules.h).  false + err on failure.
 bool reinsert_dev_open(int device, size_t n_nodes, ReinsertDevice **out, std::string &err);
 void reinsert_dev_close(ReinsertDevice *ctx);
 
