@@ -339,10 +339,38 @@ int trx_refit_nodes(const void *nodes, uint64_t n_nodes, const float *tri_verts,
                     const uint32_t *instance_offsets, uint32_t n_instances, uint32_t tlas_start,
                     const uint32_t *entry_nodes, const float *object_to_world, void *out_nodes);
 
-/* ---- camera ---------------------------------------------------------------
+/* ---- what the trace calls accept ----------------------------------------------
+ * Any bit pattern in a trx_ray or a trx_view: NaN, infinities, denormals, zero or un-normalised directions, tmin > tmax,
+ * negative or NaN ranges.  The results are the reference shader's arithmetic on those floats (the oracle's, bit for bit:
+ * tests/test_gpu_hostile_inputs.py), never a fault: no address depends on a ray's or a view's floats.  A non-finite or
+ * out-of-range ray never changes another ray's record (it may send its wave through slower arithmetic: the literal
+ * divisions), and it does not raise TRX_ERR_STACK_OVERFLOW: that error still means a tree deeper than 64 entries - or a
+ * single ray that ran past the step cap of 2^22 trips, which only a whole-tree walker (below) over several million nodes
+ * and triangles can reach.  The ids handed to the attribute, AO and filter passes are NOT covered: a `prim` or an
+ * instance id must come from a trace call over the same scene.
+ *   What the shader's arithmetic does with such rays, because its node test is max(near planes, 0.0001) <= min(far planes,
+ * t) with a max / min that drop NaN operands (query.hlsl:237-300):
+ *   - a negative tmin is accepted by the triangle test but no hit nearer than a box's clamped entry is ever looked for:
+ *     hits at t < 0.0001 are lost (a brute-force query would report them);
+ *   - an origin on, or within a rounding of, a triangle's plane loses that nearest hit the same way;
+ *   - a direction of length 2^12 or more shrinks every t by as much: hits nearer than 0.0001 in THOSE units are lost, and
+ *     at 2^40 nothing is ever hit.  Directions are not renormalised inside an instance, so an instance whose transform
+ *     scales the object-space direction past about 2^10 (a scale of 2^-10 or less, a near-singular shear) loses the near
+ *     hits of its geometry, as the reference does;
+ *   - a direction of length about 1e-38 has its hits at t near 1e38, where the box planes overflow first: they are lost;
+ *   - a ray with a NaN on all three axes (any NaN in a view does that to every primary ray, through the normalisation)
+ *     passes every box test and fails every triangle test: it reports a miss after visiting every node and testing every
+ *     triangle of the scene.  Callers that cannot rule NaNs out should filter them: such a frame costs
+ *     (nodes + triangles) per pixel.
+ *
+ * ---- camera ---------------------------------------------------------------
  * ViewUniform::from_camera (src/main.rs:602-616): proj_inv =
  * inverse(perspective_infinite_reverse_rh(fov_deg->rad, w/h, 0.01)),
- * view_inv = inverse(look_at_rh(eye, look_at, +Y)). */
+ * view_inv = inverse(look_at_rh(eye, look_at, +Y)).
+ * eye == look_at and a view direction parallel to +Y are refused with TRX_ERR_INVALID (*out holds no usable view: zeros
+ * and a proj_inv); the reference's
+ * unchecked from_camera returns a view_inv of NaNs there (the oracle's orc_view_from_camera does; tests/test_hostile_inputs.py),
+ * and such a view, handed to a trace call as it is, hits nothing. */
 int trx_view_from_camera(const float eye[3], const float look_at[3], float fov_deg,
                          float width, float height, trx_view *out);
 

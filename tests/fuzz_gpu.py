@@ -3,7 +3,10 @@ cameras, image sizes, semantics, triangle formats, TLAS on/off, shards, batch la
 query kinds (primary, AO, explicit rays).  Test infrastructure (it drives the oracle); not collected by
 pytest — tests/test_gpu_parity.py runs a short fixed-seed slice of it.
 
-    python tests/fuzz_gpu.py --minutes 10 [--seed 1]
+    python tests/fuzz_gpu.py --minutes 10 [--seed 1] [--hostile]
+
+--hostile swaps hostile rays and hostile views (tests/hostile_inputs.py) into the explicit-ray and host-entry-point cases;
+what it draws comes from a generator stream of its own, so the case sequence of a seed is the same with and without it.
 """
 import argparse
 import os
@@ -30,6 +33,7 @@ def differs(got, want):
 
 
 BIG = False   # --big: few large cases (up to 1 M triangles, up to 1920x1080) instead of many small ones
+HOSTILE = None   # --hostile: a numpy Generator of its own (never the case stream's)
 
 
 def instanced_case(T, O, rng, case):
@@ -163,12 +167,24 @@ def one_case(T, O, rng, case):
             bad += [("frame primary", differs(D.int64_to_hits(d_p), wp)), ("frame ao", differs(D.int64_to_hits(d_a), wa))]
         elif kind == 0:      # primary + AO, host entry point
             frame, eps = int(rng.integers(0, 5000)), float(rng.choice([0.01, 0.0001]))
+            if HOSTILE is not None and w * h <= 4096:   # (a whole-tree view costs every triangle for every pixel)
+                import ctypes as C
+                import hostile_inputs as H
+                views = H.hostile_views(T, flat, w, h)
+                vname, raw = views[int(HOSTILE.integers(len(views)))]
+                C.memmove(C.byref(view), raw, C.sizeof(view))
+                ov = O.view_from_bytes(raw)
+                desc += " view=" + vname
             prim, ao, _ = sc.trace_primary_ao(view, w, h, sem=sem, frame=frame, ao_eps=eps)
             wp, _ = osc.trace_primary(ov, w, h, sem=sem)
             wa, _ = osc.trace_ao(ov, w, h, wp, sem=sem, frame=frame, ao_eps=eps)
             bad += [("primary", differs(prim, wp)), ("ao", differs(ao, wa))]
         elif kind == 1:    # explicit rays
             rays = random_rays(T, flat, int(rng.integers(1, 1500000 if BIG else 30000)), seed)
+            if HOSTILE is not None:
+                import hostile_inputs as H
+                rays = H.hostile_rays(T, flat, min(rays.shape[0], 20000), int(HOSTILE.integers(1 << 30)))[0]
+                desc += " hostile rays"
             got, _ = sc.trace_rays(rays, sem=sem)
             want = osc.trace_rays(rays, sem=sem)[0]
             bad += [("rays", differs(got, want))]
@@ -199,10 +215,12 @@ def one_case(T, O, rng, case):
     return desc + " kind=%d" % kind, bad
 
 
-def run(minutes=1.0, seed=1, max_cases=1 << 30, verbose=True):
+def run(minutes=1.0, seed=1, max_cases=1 << 30, verbose=True, hostile=False):
+    global HOSTILE
     import tray_racing_amd as T
     from oracle import binding as O
     rng = np.random.default_rng(seed)
+    HOSTILE = np.random.default_rng([seed, 0x4057]) if hostile else None
     t_end = time.time() + 60.0 * minutes
     case, failures = 0, []
     while time.time() < t_end and case < max_cases:
@@ -222,7 +240,8 @@ if __name__ == "__main__":
     ap.add_argument("--minutes", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--big", action="store_true")
+    ap.add_argument("--hostile", action="store_true")
     a = ap.parse_args()
     BIG = a.big
-    _, fails = run(a.minutes, a.seed)
+    _, fails = run(a.minutes, a.seed, hostile=a.hostile)
     sys.exit(1 if fails else 0)
