@@ -605,6 +605,58 @@ int trx_count_ao(trx_scene *scene, const trx_view *view, uint32_t width, uint32_
 int trx_count_rays(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays,
                    uint32_t semantics, trx_hit *d_hits, trx_stats *stats);
 
+/* Per-ray counts of a counting pass: every ray's own share of trx_stats.n_node and trx_stats.n_tri.
+ *   n_node  node visits of this ray (the reference's aabb_hit_count / 8); on a two-level scene both levels count
+ *   n_tri   triangle tests of this ray (the reference's tri_hit_count)
+ * each saturated at 65535.  The sums of the records a pass writes are its trx_stats.n_node / n_tri (short of saturation).
+ * The three calls are trx_count_primary / trx_count_ao / trx_count_rays - same arguments, same per-scene lock, same
+ * synchronous protocol on the null stream, same trx_stats and hit records - with one more output: d_cost, device memory
+ * indexed exactly like the hit buffer of the call (both layouts, any shard).  Records of other shards, of pixels outside
+ * the image and past the end of the buffer are left as they were; an AO pixel whose primary record is a miss gets {0, 0}.
+ * d_hits / d_ao may be NULL (the records go to the scene's scratch).  A null d_cost is refused with TRX_ERR_INVALID before
+ * anything is enqueued.  Counting passes are never timed; fused frames and the ray service have no per-ray counts. */
+typedef struct trx_ray_cost {
+    uint16_t n_node;
+    uint16_t n_tri;
+} trx_ray_cost; /* 4 bytes */
+int trx_count_primary_per_ray(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                              uint32_t semantics, trx_hit *d_hits, trx_ray_cost *d_cost, trx_stats *stats);
+int trx_count_ao_per_ray(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                         uint32_t semantics, uint32_t frame, float ao_eps, const trx_hit *d_primary, trx_hit *d_ao,
+                         trx_ray_cost *d_cost, trx_stats *stats);
+int trx_count_rays_per_ray(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, uint32_t semantics, trx_hit *d_hits,
+                           trx_ray_cost *d_cost, trx_stats *stats);
+
+/* The PROFILE_RT heat map (the reference's profiling build of its pixel program, rt_gpu_software.hlsl:84-102): a colour
+ * per record from its per-ray counts.  Elementwise over n_records records in ANY layout, like the shades above: 4 bytes
+ * {r, g, b, 255} per record at d_rgba (n_records * 4 bytes, 4-byte aligned; nothing beyond them is written).
+ *   TRX_HEAT_NODES  x = (float)(8 * n_node) * scale   (the reference: aabb_hit_count * 0.002)
+ *   TRX_HEAT_TRIS   x = (float)n_tri * scale          (the reference's commented-out alternative: tri_hit_count * 0.01)
+ * The colour of x is the reference's `temperature` (sampling.hlsl:54-83) as a rule; every operation in binary32, rounded
+ * once, no contraction, the division an IEEE division:
+ *   s = x * 10;  cur = min((int)s, 9) (truncation);  prv = max(cur - 1, 0);  nxt = min(cur + 1, 9);
+ *   S(a, b, v): q = clamp((v - a) / (b - a), 0, 1), result (q * q) * (3 - 2 * q);
+ *   c = (float)cur;  lo = S(c - 0.8f, c + 0.8f, s);  hi = S((c + 1) - 0.8f, (c + 1) + 0.8f, s);
+ *   wc = lo * (1 - hi);  wp = 1 - lo;  wn = hi;
+ *   per channel r = (wc * P[cur] + wp * P[prv]) + wn * P[nxt], clamped to [0, 1], with the ten palette rows P = k / 255.0f,
+ *   k = (0,2,91) (0,108,251) (0,221,221) (51,221,0) (255,252,0) (255,180,0) (255,104,0) (226,22,0) (191,0,83) (145,0,65);
+ *   the byte is (uint8_t)floorf(r * 255.0f + 0.5f) (the unorm8 store of an rgba8 target); alpha is 255.
+ * No pow is applied (the reference's pow(col, 2.2) belongs to its other branch).  At the reference scales the image is
+ * constant from n_node = 61 (61 distinct colours) and from n_tri = 98 (97 distinct colours) on.
+ * Refused with TRX_ERR_INVALID before anything is enqueued, the output untouched: a null scene or - with n_records != 0 - a
+ * null buffer, a misaligned d_rgba, which > 1, a scale that is NaN, negative or infinite.  n_records == 0 does nothing. */
+#define TRX_HEAT_NODES 0u
+#define TRX_HEAT_TRIS 1u
+#define TRX_HEAT_SCALE_NODES 0.002f
+#define TRX_HEAT_SCALE_TRIS 0.01f
+int trx_shade_heat_dev(trx_scene *scene, const trx_ray_cost *d_cost, uint64_t n_records, uint32_t which, float scale,
+                       uint8_t *d_rgba, void *stream);
+/* Host-buffer form for a whole image (synchronous, under the per-scene lock): the counted primary pass and the heat shade;
+ * only the width * height * 4 bytes of out_rgba (may be NULL) cross the bus; out_stats (may be NULL) takes the pass's
+ * trx_stats.  Every argument is validated before the first pass. */
+int trx_render_heat_image(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                          uint32_t which, float scale, uint8_t *out_rgba, trx_stats *out_stats);
+
 /* Status of the most recent trace on this scene (stack overflow is detected
  * in-kernel and latched in device memory).  Synchronises `stream`. */
 int trx_scene_check(trx_scene *scene, void *stream);

@@ -31,6 +31,10 @@ SEM_CPU = 3
 MAX_AO_SAMPLES = 64
 AO_NO_SURFACE = 0xFF
 MAX_AO_FILTER_RADIUS = 4
+HEAT_NODES = 0
+HEAT_TRIS = 1
+HEAT_SCALE_NODES = 0.002
+HEAT_SCALE_TRIS = 0.01
 
 
 class TrxError(RuntimeError):
@@ -60,6 +64,11 @@ class HitAttr(C.Structure):
 class AoTerm(C.Structure):
     """trx_ao_term: the filtered AO term of a pixel - unoccluded samples over samples of the accepted window pixels."""
     _fields_ = [("unoccluded", C.c_uint16), ("samples", C.c_uint16)]
+
+
+class RayCost(C.Structure):
+    """trx_ray_cost: one ray's node visits and triangle tests in a counting pass, each saturated at 65535."""
+    _fields_ = [("n_node", C.c_uint16), ("n_tri", C.c_uint16)]
 
 
 class RayHit(C.Structure):
@@ -153,6 +162,11 @@ SIGNATURES = {
     "trx_count_primary": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _P, C.POINTER(Stats)]),
     "trx_count_ao": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _f, _P, _P, C.POINTER(Stats)]),
     "trx_count_rays": (_i, [_P, _P, _u64, _u32, _P, C.POINTER(Stats)]),
+    "trx_count_primary_per_ray": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _P, _P, C.POINTER(Stats)]),
+    "trx_count_ao_per_ray": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _f, _P, _P, _P, C.POINTER(Stats)]),
+    "trx_count_rays_per_ray": (_i, [_P, _P, _u64, _u32, _P, _P, C.POINTER(Stats)]),
+    "trx_shade_heat_dev": (_i, [_P, _P, _u64, _u32, _f, _P, _P]),
+    "trx_render_heat_image": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _f, _P, C.POINTER(Stats)]),
     "trx_scene_check": (_i, [_P, _P]),
     "trx_trace_primary": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _P, C.POINTER(_f)]),
     "trx_trace_primary_ao": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _f, _P, _P, C.POINTER(_f)]),

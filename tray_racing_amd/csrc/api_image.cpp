@@ -1,6 +1,7 @@
 // api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_shade_*_dev / trx_render_image): the edge-aware
 // filter over the AO visibility pass's counts and the shading to RGBA8 (k_ao_filter, k_shade, image.hip), and the table of
-// code thresholds the shade searches instead of evaluating pow.  Image passes after the walk: none reads scene data, but
+// code thresholds the shade searches instead of evaluating pow; the PROFILE_RT heat map of a counting pass's per-ray counts
+// (trx_shade_heat_dev / trx_render_heat_image, k_heat).  Image passes after the walk: none reads scene data, but
 // each takes a launch slot of the scene like the attribute pass, so trx_scene_refit waits for them.
 #include "api_internal.h"
 
@@ -107,6 +108,12 @@ int enqueue_shade(trx_scene *s, ShadeParams base, int mode, uint64_t n, hipStrea
     });
 }
 
+int check_heat(uint32_t which, float scale) {
+    if (which > TRX_HEAT_TRIS) return fail(TRX_ERR_INVALID, "heat map of %u: TRX_HEAT_NODES or TRX_HEAT_TRIS", which);
+    if (!(scale >= 0.0f) || scale > FLT_MAX) return fail(TRX_ERR_INVALID, "heat scale %g: must be finite and >= 0", (double)scale);
+    return TRX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -167,6 +174,49 @@ int trx_shade_ao_term_dev(trx_scene *s, const trx_ao_term *d_term, uint64_t n, u
     p.term = d_term;
     p.rgba = d_rgba;
     return enqueue_shade(s, p, kShadeTerm, n, (hipStream_t)stream);
+}
+
+int trx_shade_heat_dev(trx_scene *s, const trx_ray_cost *d_cost, uint64_t n, uint32_t which, float scale, uint8_t *d_rgba,
+                       void *stream) {
+    if (int rc = check_heat(which, scale)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_rgba) & 3u) return fail(TRX_ERR_INVALID, "d_rgba is not 4-byte aligned");
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    if (n == 0) return TRX_OK;
+    if (!d_cost || !d_rgba) return fail(TRX_ERR_INVALID, "null argument");
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        const uint64_t chunk = 1ull << 30;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            HeatParams p;
+            p.cost = d_cost + off;
+            p.rgba = d_rgba + off * 4;
+            p.n_items = (uint32_t)std::min(chunk, n - off);
+            p.which = which;
+            p.scale = scale;
+            HIP_TRY(launch_heat(p, (hipStream_t)stream));
+        }
+        return TRX_OK;
+    });
+}
+
+int trx_render_heat_image(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t which, float scale,
+                          uint8_t *out_rgba, trx_stats *out_stats) {
+    if (int rc = check_heat(which, scale)) return rc;
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !view) return fail(TRX_ERR_INVALID, "null argument");
+    const uint64_t n = (uint64_t)w * h;
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (trx_count_primary_per_ray takes it again: the image scratch is under it too)
+    HIP_TRY(hipSetDevice(s->device));
+    // the image scratch: the per-ray counts, then the image
+    HIP_TRY(s->scratch_img.grow(n * 8));
+    trx_ray_cost *const d_cost = reinterpret_cast<trx_ray_cost *>(s->scratch_img.get());
+    uint8_t *const d_rgba = s->scratch_img.get() + n * 4;
+    if (int rc = trx_count_primary_per_ray(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, nullptr, d_cost, out_stats)) return rc;
+    if (int rc = trx_shade_heat_dev(s, d_cost, n, which, scale, d_rgba, nullptr)) return rc;
+    // (a blocking copy, or a wait: the shade has finished when this returns)
+    if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost));
+    else HIP_TRY(hipStreamSynchronize(nullptr));
+    return TRX_OK;
 }
 
 int trx_render_image(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame0, uint32_t n_samples,

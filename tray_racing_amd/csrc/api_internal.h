@@ -8,7 +8,7 @@
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
 //   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts
-//   api_image.cpp    trx_ao_filter_dev / trx_shade_*_dev / trx_render_image: the image passes after the walk (image.hip)
+//   api_image.cpp    trx_ao_filter_dev / trx_shade_*_dev / trx_render_image / trx_render_heat_image: the image passes after the walk (image.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -75,6 +75,7 @@ struct Slot {
     bool pinned = false;               // a resident kernel (the ray service) runs on this slot: never recycled for another stream
     hipStream_t last_stream = nullptr; // stream of the last launch on this slot
     uint64_t last_use = 0;             // launch counter at that time (oldest slot is recycled first)
+    bool ray_cost_set = false;         // ctr->ray_cost may be non-null: the next counting launch on the slot rewrites it
     // tile-cost feedback: the previous frame of a kind (primary / AO) traced on this slot measured every tile; the
     // next one of that kind with the same image geometry starts its heaviest tiles first.  One state per kind: the
     // reference's frame loop runs both passes on one queue, and each has its own order.
@@ -174,6 +175,7 @@ struct trx_scene {
     int cu_count = 0;
     trxapi::DevBuf<unsigned long long> wave_times; // diagnostics only (trx_debug_wave_timeline)
     uint32_t *dbg_cost = nullptr, *dbg_iters = nullptr; // diagnostics only: trx_debug_tile_profile's buffers while it runs
+    trx_ray_cost *count_cost = nullptr; // trx_count_*_per_ray's record buffer while the call runs (under host_mu), else null
     trxapi::Slot slots[trxapi::kSlots];
     uint64_t launches = 0;
     std::mutex mu;      // launch slots (every enqueue)

@@ -291,6 +291,13 @@ int enqueue_locked(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool co
     if (p.tune & 0x10000u) pipe = false;
 #endif
     if (mode == kModeService) pipe = false;
+    if (count && (s->count_cost || slot.ray_cost_set)) {
+        // where the counting kernel puts its per-ray counts (SlotCounters::ray_cost), or null again after a call that had
+        // some: a blocking copy on the null stream, which counting passes run on (count_pass), behind the slot's set-up
+        trx_ray_cost *const d_cost = s->count_cost;
+        HIP_TRY(hipMemcpy(&slot.ctr.get()->ray_cost, &d_cost, sizeof(d_cost), hipMemcpyHostToDevice));
+        slot.ray_cost_set = d_cost != nullptr;
+    }
     TraceParamsTlas kp;
     static_cast<TraceParams &>(kp) = p;
     kp.inst_mask = inst_mask;

@@ -233,6 +233,7 @@ static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint3
     z.n_wave_node = z.n_wave_tri = 0;
     z.max_stack = 0;
     z.overflow = 0;
+    z.ray_cost = nullptr;
     std::memset(z.hist_max, 0, sizeof(z.hist_max));
     std::memset(z.hist_total, 0, sizeof(z.hist_total));
     if (hist) {
@@ -260,18 +261,24 @@ static int finish_count(trx_scene *s, SlotCounters *ctr, trx_stats *stats, uint3
 
 // A counted pass on the null stream, timed from an idle device: the kernel counts into its slot's counters, which
 // finish_count reads into stats / hist and zeroes.  (count = false: the normal kernel, whose diagnostic histograms a
-// development build may file.)
+// development build may file.)  d_cost (trx_count_*_per_ray): where the kernel puts its per-ray counts - enqueue hands it
+// to the slot's counters - or null; the callers hold host_mu.
 static int count_pass(trx_scene *s, TraceParams &p, int mode, uint32_t sem, trx_stats *stats, uint32_t *hist = nullptr,
-                      bool count = true) {
+                      bool count = true, trx_ray_cost *d_cost = nullptr) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipEventRecord(s->ev0.get(), nullptr));
     SlotCounters *ctr = nullptr;
-    if (int rc = enqueue(s, p, mode, sem, count, nullptr, &ctr)) return rc;
+    s->count_cost = d_cost;
+    const int rc = enqueue(s, p, mode, sem, count, nullptr, &ctr);
+    s->count_cost = nullptr;
+    if (rc) return rc;
     return finish_count(s, ctr, stats, hist);
 }
 
-int trx_count_primary(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
-                      trx_hit *d_hits, trx_stats *stats) {
+// (want_cost: the per-ray form, which refuses a null d_cost before anything is enqueued)
+static int count_primary_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                              trx_hit *d_hits, bool want_cost, trx_ray_cost *d_cost, trx_stats *stats) {
+    if (want_cost && !d_cost) return fail(TRX_ERR_INVALID, "d_cost is null");
     if (!s) return fail(TRX_ERR_INVALID, "null scene");
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     HIP_TRY(hipSetDevice(s->device));
@@ -285,7 +292,17 @@ int trx_count_primary(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
         d_hits = s->scratch_a.get();
     }
     p.out = d_hits;
-    return count_pass(s, p, kModePrimary, sem, stats);
+    return count_pass(s, p, kModePrimary, sem, stats, nullptr, true, d_cost);
+}
+
+int trx_count_primary(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                      trx_hit *d_hits, trx_stats *stats) {
+    return count_primary_impl(s, view, w, h, shard, sem, d_hits, false, nullptr, stats);
+}
+
+int trx_count_primary_per_ray(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                              trx_hit *d_hits, trx_ray_cost *d_cost, trx_stats *stats) {
+    return count_primary_impl(s, view, w, h, shard, sem, d_hits, true, d_cost, stats);
 }
 
 // Compulsory footprint of one primary frame: distinct nodes fetched and distinct triangles tested.
@@ -352,7 +369,31 @@ int trx_count_ao(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx
     return count_pass(s, p, kModeAo, sem, stats);
 }
 
-int trx_count_rays(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, trx_stats *stats) {
+int trx_count_ao_per_ray(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                         uint32_t frame, float ao_eps, const trx_hit *d_primary, trx_hit *d_ao, trx_ray_cost *d_cost,
+                         trx_stats *stats) {
+    if (!d_cost) return fail(TRX_ERR_INVALID, "d_cost is null");
+    if (!s || !d_primary) return fail(TRX_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
+    HIP_TRY(hipSetDevice(s->device));
+    TraceParams p;
+    int rc = image_params(p, view, w, h, shard);
+    if (rc) return rc;
+    if (!d_ao) { // (the second record buffer: d_primary may be the first)
+        rc = ensure_scratch(s, std::max<uint64_t>((uint64_t)w * h, (uint64_t)p.n_items), 0);
+        if (rc) return rc;
+        d_ao = s->scratch_b.get();
+    }
+    p.primary = d_primary;
+    p.out = d_ao;
+    p.frame = frame;
+    p.ao_eps = ao_eps;
+    return count_pass(s, p, kModeAo, sem, stats, nullptr, true, d_cost);
+}
+
+static int count_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, bool want_cost,
+                           trx_ray_cost *d_cost, trx_stats *stats) {
+    if (want_cost && !d_cost) return fail(TRX_ERR_INVALID, "d_cost is null");
     if (!s || !d_rays || n == 0 || n > (1ull << 30)) return fail(TRX_ERR_INVALID, "bad ray batch");
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // serialises users of the shared scratch / events
     HIP_TRY(hipSetDevice(s->device));
@@ -366,7 +407,16 @@ int trx_count_rays(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem
     p.rays = d_rays;
     p.out = d_hits;
     p.n_items = (uint32_t)n;
-    return count_pass(s, p, kModeRays, sem, stats);
+    return count_pass(s, p, kModeRays, sem, stats, nullptr, true, d_cost);
+}
+
+int trx_count_rays(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, trx_stats *stats) {
+    return count_rays_impl(s, d_rays, n, sem, d_hits, false, nullptr, stats);
+}
+
+int trx_count_rays_per_ray(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, trx_ray_cost *d_cost,
+                           trx_stats *stats) {
+    return count_rays_impl(s, d_rays, n, sem, d_hits, true, d_cost, stats);
 }
 
 int trx_scene_check(trx_scene *s, void *stream) {

@@ -48,6 +48,9 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // (trx_render_image): the counts through the edge-aware filter of radius R (0: unfiltered), shaded to RGBA8 there
     int ao_filter = -1; // -1: not given, save_png's host loop stays as it is
     float ao_depth_tol = 0.02f, ao_normal_cos = 0.9f;
+    // --profile-rt nodes|tris [--profile-rt-scale x]: with --png the image is the PROFILE_RT heat map (trx_render_heat_image)
+    int profile_rt = -1; // -1: not given, else TRX_HEAT_NODES / TRX_HEAT_TRIS
+    float profile_rt_scale = -1.0f; // (not given: the reference's scale of the mode)
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -80,6 +83,9 @@ void usage() {
               "  [--ao-samples 1..64] [--ao-radius r] (with --png: AO term = unoccluded samples / N of the any-hit visibility pass)\n"
               "  [--ao-filter 0..4] [--ao-depth-tol x] [--ao-normal-cos c] (with --png --ao-samples: edge-aware filter of that radius\n"
               "   over the AO counts, image shaded on the device; only the RGBA8 bytes are copied back)\n"
+              "  [--profile-rt nodes|tris] [--profile-rt-scale x] (with --png: the PROFILE_RT heat map of a counted primary pass -\n"
+              "   box tests (8 per node visit) x 0.002 or triangle tests x 0.01 through the reference's colour ramp - instead of\n"
+              "   the shaded frame; not together with --ao-samples or --ao-filter)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -130,6 +136,15 @@ Options parse_args(int argc, char **argv) {
             o.ao_normal_cos = (float)std::atof(need(i));
             if (o.ao_normal_cos != o.ao_normal_cos) die("--ao-normal-cos must be a number");
         }
+        else if (a == "--profile-rt") {
+            const std::string m = need(i);
+            if (m == "nodes") o.profile_rt = (int)TRX_HEAT_NODES;
+            else if (m == "tris") o.profile_rt = (int)TRX_HEAT_TRIS;
+            else die("--profile-rt takes nodes or tris");
+        } else if (a == "--profile-rt-scale") {
+            o.profile_rt_scale = (float)std::atof(need(i));
+            if (!(o.profile_rt_scale >= 0.0f) || o.profile_rt_scale > std::numeric_limits<float>::max()) die("--profile-rt-scale must be finite and >= 0");
+        }
         else if (a == "-h" || a == "--help") {
             usage();
             std::exit(0);
@@ -161,6 +176,8 @@ Options parse_args(int argc, char **argv) {
     if (o.cpu) die("--cpu is the reference's own rt_cpu path; the HIP backend has no CPU traversal");
     if (o.hardware) die("--hardware needs ray-tracing hardware; MI355X (CDNA4) has none");
     if (o.ao_filter >= 0 && o.ao_samples == 0) die("--ao-filter filters the counts of --ao-samples N");
+    if (o.profile_rt >= 0 && (o.ao_samples != 0 || o.ao_filter >= 0)) die("--profile-rt draws the heat map: not together with --ao-samples or --ao-filter");
+    if (o.profile_rt < 0 && o.profile_rt_scale >= 0.0f) die("--profile-rt-scale scales the heat map of --profile-rt nodes|tris");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -212,6 +229,18 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
     std::vector<unsigned char> rgba(n * 4);
     const std::string path = name + "_rend.png";
     float ms = 0;
+    if (o.profile_rt >= 0) {
+        // where the tree is expensive: the per-ray counts of a counted primary pass as colours, made on the device
+        const float scale = o.profile_rt_scale >= 0.0f ? o.profile_rt_scale : o.profile_rt == (int)TRX_HEAT_TRIS ? TRX_HEAT_SCALE_TRIS : TRX_HEAT_SCALE_NODES;
+        trx_stats st;
+        check(trx_render_heat_image(scene, &view, o.width, o.height, o.semantics, (uint32_t)o.profile_rt, scale, rgba.data(), &st), "heat map");
+        if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
+        if (o.verbose)
+            std::printf("saved %s (heat map of %s, scale %g: %.2f node visits, %.2f triangle tests per ray)\n", path.c_str(),
+                        o.profile_rt == (int)TRX_HEAT_TRIS ? "triangle tests" : "box tests", (double)scale,
+                        (double)st.n_node / (double)std::max<uint64_t>(st.n_rays, 1), (double)st.n_tri / (double)std::max<uint64_t>(st.n_rays, 1));
+        return;
+    }
     if (o.ao_samples != 0 || o.ao_radius > 0.0f) {
         // the AO term a renderer would use: the share of N bounded any-hit AO rays that reach nothing
         const unsigned samples = o.ao_samples ? o.ao_samples : 1u;

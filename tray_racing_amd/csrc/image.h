@@ -39,4 +39,15 @@ struct ShadeParams {
 };
 hipError_t launch_shade(const ShadeParams &p, int mode, hipStream_t stream);
 
+// k_heat: the PROFILE_RT heat map (trx_shade_heat_dev) - one lane per record, 4 bytes of per-ray counts read, 4 bytes
+// {r, g, b, 255} written.  No table in LDS, no pow: the colour is arithmetic on the count.
+struct HeatParams {
+    const trx_ray_cost *cost;
+    uint8_t *rgba;
+    uint32_t n_items;
+    uint32_t which; // TRX_HEAT_NODES / TRX_HEAT_TRIS
+    float scale;
+};
+hipError_t launch_heat(const HeatParams &p, hipStream_t stream);
+
 } // namespace trx

@@ -4,7 +4,7 @@
 //
 // Arithmetic contract (DESIGN.md "Numerics"): binary32, no contraction, IEEE divide, dot = (ax*bx + ay*by) + az*bz.  The
 // filter compares in float and sums in integers, the shade divides once and then only compares, so a host twin
-// (tests/image_twin.py) gives the same bits.
+// (tests/image_twin.py) gives the same bits; the heat map is a fixed sequence of such operations (tests/heat_twin.py).
 #include "image.h"
 
 #pragma clang fp contract(off)
@@ -130,7 +130,51 @@ __global__ void __launch_bounds__(256) k_shade(const ShadeParams P) {
     reinterpret_cast<uint32_t *>(P.rgba)[i] = c * 0x00010101u | 0xFF000000u; // {c, c, c, 255}
 }
 
+// The heat map's ten colours (include/trx.h, trx_shade_heat_dev): binary32 k / 255.0f, the division done by the compiler.
+__device__ const float kHeatPalette[10][3] = {
+    {0 / 255.0f, 2 / 255.0f, 91 / 255.0f},    {0 / 255.0f, 108 / 255.0f, 251 / 255.0f}, {0 / 255.0f, 221 / 255.0f, 221 / 255.0f},
+    {51 / 255.0f, 221 / 255.0f, 0 / 255.0f},  {255 / 255.0f, 252 / 255.0f, 0 / 255.0f}, {255 / 255.0f, 180 / 255.0f, 0 / 255.0f},
+    {255 / 255.0f, 104 / 255.0f, 0 / 255.0f}, {226 / 255.0f, 22 / 255.0f, 0 / 255.0f},  {191 / 255.0f, 0 / 255.0f, 83 / 255.0f},
+    {145 / 255.0f, 0 / 255.0f, 65 / 255.0f}};
+
+// S(a, b, v) of the rule: q = clamp((v - a) / (b - a), 0, 1), (q * q) * (3 - 2 * q)
+__device__ __forceinline__ float heat_step(float a, float b, float v) {
+    const float q = fminf(fmaxf(__fdiv_rn(v - a, b - a), 0.0f), 1.0f);
+    return (q * q) * (3.0f - 2.0f * q);
+}
+
+// The PROFILE_RT heat map (trx_shade_heat_dev; the rule is stated in include/trx.h): a record's count, scaled, picks one of
+// ten colours and blends it with its two neighbours.  Each operation is one binary32 operation of the rule, in its order -
+// tests/heat_twin.py evaluates the same ones in numpy and the bytes are compared for every count there is.
+__global__ void __launch_bounds__(256) k_heat(const HeatParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    const trx_ray_cost rc = P.cost[i];
+    const float x = (P.which == TRX_HEAT_NODES ? (float)(8u * (uint32_t)rc.n_node) : (float)rc.n_tri) * P.scale;
+    const float s = x * 10.0f;
+    const int cur = s >= 9.0f ? 9 : (int)s; // min((int)s, 9), also where s is beyond the integers (s is never NaN or negative)
+    const int prv = cur > 0 ? cur - 1 : 0, nxt = cur < 9 ? cur + 1 : 9;
+    const float c = (float)cur;
+    const float lo = heat_step(c - 0.8f, c + 0.8f, s);
+    const float hi = heat_step((c + 1.0f) - 0.8f, (c + 1.0f) + 0.8f, s);
+    const float wc = lo * (1.0f - hi), wp = 1.0f - lo, wn = hi;
+    uint32_t px = 0xFF000000u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        float r = (wc * kHeatPalette[cur][ch] + wp * kHeatPalette[prv][ch]) + wn * kHeatPalette[nxt][ch];
+        r = fminf(fmaxf(r, 0.0f), 1.0f);
+        px |= (uint32_t)(uint8_t)floorf(r * 255.0f + 0.5f) << (8 * ch);
+    }
+    reinterpret_cast<uint32_t *>(P.rgba)[i] = px;
+}
+
 } // namespace
+
+hipError_t launch_heat(const HeatParams &p, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_heat, dim3((p.n_items + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_ao_filter(const AoFilterParams &p, hipStream_t stream) {
     const uint64_t tiles = (uint64_t)((p.width + kFilterTileW - 1u) / kFilterTileW) * ((p.height + kFilterTileH - 1u) / kFilterTileH);

@@ -104,6 +104,11 @@ struct SlotCounters {
     // self-tuning of the frame schedule, one state per pass kind (0 = primary, 1 = AO: a frame loop runs both on one stream)
     FbState fb[2];
     unsigned int lpt_sel[2]; // which of a kind's two tile-list sets holds the order to read (TraceParams::lpt_sel)
+    // COUNT kernels only (trx_count_*_per_ray): one trx_ray_cost per record, indexed like the pass's hit buffer, or null.  It
+    // travels here and not in TraceParams, which has no eight bytes to spare (its size is fixed, below) and no field that a
+    // timed kernel does not read; enqueue_locked writes it ahead of a counting launch that has such a buffer, finish_count
+    // clears it.
+    trx_ray_cost *ray_cost;
 };
 
 struct TraceParams {

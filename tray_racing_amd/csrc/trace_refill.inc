@@ -236,6 +236,8 @@
                                 miss.prim = TRX_INVALID;
                                 P.out[out_index] = miss;
                                 if (TLAS && P.out_inst) P.out_inst[out_index] = TRX_INVALID;
+                                if constexpr (COUNT)
+                                    if (ray_cost) ray_cost[out_index] = trx_ray_cost{0u, 0u}; // (no ray: nothing visited)
                             }
                         }
                         if (MODE != kModeRays) {
@@ -251,6 +253,10 @@
                     prim = TRX_INVALID;
                     sp = 0;
                     steps = trip; // the wave trip this ray starts at
+                    if constexpr (COUNT) {
+                        r_node = c_node;
+                        r_tri = c_tri;
+                    }
                     overflow = 0u;
                     cur = make_uint2(0u, 0x80000000u);
                     if (TLAS) {

@@ -78,6 +78,10 @@
             c_rays++;
             c_hits += prim != TRX_INVALID;
         }
+        // this ray's share of n_node / n_tri, saturated like the per-ray counters of the CPU restatement
+        // (if constexpr: in the timed kernels the lambda then names - and captures - nothing more than it did)
+        if constexpr (COUNT)
+            if (ray_cost) ray_cost[out_index] = trx_ray_cost{(uint16_t)min(c_node - r_node, 65535u), (uint16_t)min(c_tri - r_tri, 65535u)};
         c_over += overflow;
         has_ray = false;
     };

@@ -126,4 +126,9 @@
     uint32_t c_node = 0, c_tri = 0, c_rays = 0, c_hits = 0, c_maxsp = 0, c_over = 0;
     uint32_t c_wnode = 0, c_wtri = 0; // wave-level executions (leader lane only): SIMD-efficiency denominators
     uint32_t s_wnode = 0, s_wtri = 0; // their values when the current tile started
+    // per-ray counts (SlotCounters::ray_cost): a counting kernel has no thin waves, no ray merging and no drain, so a ray keeps
+    // its lane from the refill that publishes it to finish_lane, and cooperative triangle rounds credit their tests to the
+    // owning lane - a ray's own node visits and triangle tests are what the lane's counters gained in between
+    trx_ray_cost *const ray_cost = COUNT ? P.ctr->ray_cost : nullptr;
+    uint32_t r_node = 0, r_tri = 0; // c_node / c_tri when the lane's ray was published
 

@@ -19,6 +19,7 @@ RAYHIT_DTYPE = np.dtype([("primitive_id", "<u4"), ("geometry_id", "<u4"), ("inst
 HIT_ATTR_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("_pad", "<u4")])
 # trx_ao_term: the edge-aware AO filter's output per pixel
 AO_TERM_DTYPE = np.dtype([("unoccluded", "<u2"), ("samples", "<u2")])
+RAY_COST_DTYPE = np.dtype([("n_node", "<u2"), ("n_tri", "<u2")])
 MISS_PRIM = 0xFFFFFFFF
 
 
@@ -510,6 +511,17 @@ class Scene:
                                            filter_radius, depth_tol, normal_cos, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
+        """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
+        of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
+        crosses the bus."""
+        if scale is None:
+            scale = L.HEAT_SCALE_TRIS if which == L.HEAT_TRIS else L.HEAT_SCALE_NODES
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        st = L.Stats()
+        L.check(self._lib.trx_render_heat_image(self._h, C.byref(view), width, height, sem, which, scale, _ptr(rgba), C.byref(st)))
+        return rgba, st
+
     def traverse(self, origin, direction, tmin=0.0, tmax=3.4028234663852886e38, sem=L.SEM_HLSL):
         """Traversable::traverse (traversable/src/lib.rs:17-21) for one ray."""
         ray = L.Ray((C.c_float * 3)(*origin), tmin, (C.c_float * 3)(*direction), tmax)
@@ -555,6 +567,29 @@ class Scene:
         """Node steps / triangle tests of one explicit-ray batch (counting kernel)."""
         st = L.Stats()
         L.check(self._lib.trx_count_rays(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_hits), C.byref(st)))
+        return st
+
+    def count_primary_per_ray(self, view, width, height, d_cost, d_hits=0, sem=L.SEM_HLSL, shard=(0, 1)):
+        """trx_count_primary_per_ray: count_primary, and one RAY_COST_DTYPE record per pixel at d_cost, laid out by the shard like
+        the hit buffer (d_hits 0: the hit records go to the scene's scratch)."""
+        st = L.Stats()
+        L.check(self._lib.trx_count_primary_per_ray(self._h, C.byref(view), width, height, L.Shard(*shard), sem, C.c_void_p(d_hits),
+                                                    C.c_void_p(d_cost), C.byref(st)))
+        return st
+
+    def count_ao_per_ray(self, view, width, height, d_primary, d_cost, d_ao=0, sem=L.SEM_HLSL, frame=0, ao_eps=0.01, shard=(0, 1)):
+        """trx_count_ao_per_ray: count_ao, and one RAY_COST_DTYPE record per AO ray at d_cost ({0, 0} where the primary record
+        is a miss)."""
+        st = L.Stats()
+        L.check(self._lib.trx_count_ao_per_ray(self._h, C.byref(view), width, height, L.Shard(*shard), sem, frame, ao_eps,
+                                               C.c_void_p(d_primary), C.c_void_p(d_ao), C.c_void_p(d_cost), C.byref(st)))
+        return st
+
+    def count_rays_per_ray(self, d_rays, n, d_cost, d_hits=0, sem=L.SEM_HLSL):
+        """trx_count_rays_per_ray: count_rays, and one RAY_COST_DTYPE record per ray at d_cost."""
+        st = L.Stats()
+        L.check(self._lib.trx_count_rays_per_ray(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_hits), C.c_void_p(d_cost),
+                                                 C.byref(st)))
         return st
 
     def fetch_rate(self, tris_per_node=0.0, steps=400):
@@ -692,6 +727,12 @@ class Scene:
     def shade_ao_term_dev(self, d_term, n, d_rgba, stream=0):
         """trx_shade_ao_term_dev: unoccluded / samples of n filtered terms (0 where samples == 0) as RGBA8."""
         L.check(self._lib.trx_shade_ao_term_dev(self._h, C.c_void_p(d_term), n, C.c_void_p(d_rgba), C.c_void_p(stream)))
+
+    def shade_heat_dev(self, d_cost, n, d_rgba, which=L.HEAT_NODES, scale=None, stream=0):
+        """trx_shade_heat_dev: the PROFILE_RT heat map of n per-ray count records as RGBA8 (scale None: the reference's)."""
+        if scale is None:
+            scale = L.HEAT_SCALE_TRIS if which == L.HEAT_TRIS else L.HEAT_SCALE_NODES
+        L.check(self._lib.trx_shade_heat_dev(self._h, C.c_void_p(d_cost), n, which, scale, C.c_void_p(d_rgba), C.c_void_p(stream)))
 
     def check(self, stream=0):
         L.check(self._lib.trx_scene_check(self._h, C.c_void_p(stream)))
