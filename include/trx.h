@@ -531,6 +531,26 @@ int trx_trace_ao_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t
                                 float ao_eps, float ao_radius, const trx_hit *d_primary,
                                 const uint32_t *d_primary_inst, uint8_t *d_unoccluded, void *stream);
 
+/* The SPARSE visibility pass: the visibility pass at one pixel in every stride x stride block.  Whole-image only: d_primary
+ * and d_primary_inst are FULL-resolution image-layout records (y * width + x); there is no shard argument, for the reason
+ * the filter below has none.  stride s is 1..TRX_MAX_AO_STRIDE, phase is 0..s*s-1 with px0 = phase % s, py0 = phase / s.
+ * The low grid is Wlo = ceil(width / s) by Hlo = ceil(height / s) cells; d_unoccluded_lo holds Wlo * Hlo bytes in image
+ * layout (Y * Wlo + X), nothing beyond them is written.  Cell (X, Y) stands for the full-resolution pixel
+ * (X * s + px0, Y * s + py0): a cell whose pixel lies outside the image gets TRX_AO_NO_SURFACE, every other cell gets, byte
+ * for byte, what trx_trace_ao_visibility_dev writes for that pixel under the same semantics, frame0, n_samples, ao_eps and
+ * ao_radius - the rays are that pass's rays bit for bit (the ray direction and the noise are those of the full-resolution
+ * pixel coordinates in the full width x height image; a low-resolution view does not give them).  A caller that rotates
+ * phase over frames visits every pixel in s*s frames; stride 1 is the dense pass.
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): stride 0 or above the maximum,
+ * phase >= s*s, and everything trx_trace_ao_visibility_dev refuses - a missing d_primary_inst on a scene with instance
+ * transforms among it.  Scratch, chunking, stream and ordering are the dense pass's: the same launch slot's scratch
+ * ([tile][sample][64] over the 8 x 8 tiles of the low grid) under the same cap. */
+#define TRX_MAX_AO_STRIDE 4
+int trx_trace_ao_visibility_sparse_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                       uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t frame0,
+                                       uint32_t n_samples, float ao_eps, float ao_radius, const trx_hit *d_primary,
+                                       const uint32_t *d_primary_inst, uint8_t *d_unoccluded_lo, void *stream);
+
 /* ---- the frame's image: the AO term filtered, the frame shaded to RGBA8 on the device ------------------------------------
  * The reference's pixel program ends by storing a colour into an rgba8 output_texture in the same dispatch
  * (rt_gpu_software.hlsl:91,130-142).  These are the image passes after the walk: with them a frame leaves the device as
@@ -561,6 +581,31 @@ typedef struct trx_ao_term {
 int trx_ao_filter_dev(trx_scene *scene, uint32_t width, uint32_t height, const trx_hit *d_primary,
                       const trx_hit_attr *d_attr, const uint8_t *d_unoccluded, uint32_t n_samples, uint32_t radius,
                       float depth_tol, float normal_cos, trx_ao_term *d_term, void *stream);
+/* The edge-aware UPSAMPLE of the sparse visibility pass: the full-resolution AO term rebuilt from the low grid's counts
+ * under the filter's acceptance rule.  d_primary, d_attr (may be NULL: no normal test) and d_term are whole-image,
+ * image-layout, FULL-resolution buffers; d_unoccluded_lo is what trx_trace_ao_visibility_sparse_dev wrote for the same
+ * width, height, stride s and phase (Wlo * Hlo bytes, px0 = phase % s, py0 = phase / s).
+ *  - Surface pixels are the filter's: t < FLT_MAX && prim != 0xFFFFFFFF.  Any other pixel gets {0, 0}.
+ *  - The WINDOW of pixel p = (x, y) is the set of low cells (x / s + dx, y / s + dy) with |dx|, |dy| <= radius (integer
+ *    divisions), clipped to the low grid.
+ *  - Cell q is a SURFACE CELL iff its pixel (X * s + px0, Y * s + py0) is inside the image and is a surface pixel.
+ *  - Cell q is ACCEPTED iff it is a surface cell, fabsf(t_q - t_p) <= depth_tol * t_p and - with d_attr -
+ *    (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z >= normal_cos: the filter's expressions, every operation rounded once
+ *    in binary32, no contraction, t_q and n_q the full-resolution records of q's pixel.  The cell whose pixel is p itself
+ *    is accepted unconditionally.
+ *  - If at least one cell is accepted: unoccluded = the sum of the accepted cells' counts, samples = n_samples * (number
+ *    of accepted cells).
+ *  - FALLBACK: no cell is accepted but the window holds surface cells - the same sums over ALL surface cells of the window.
+ *  - EMPTY: the window holds no surface cell - {0, 0}.
+ * The largest sum is 25 * 255: uint16_t cannot overflow.  At stride 1 every pixel is its own cell and the terms are exactly
+ * trx_ao_filter_dev's for the same radius.  Only the comparisons are done in float; the sums are integers.
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): everything the filter refuses,
+ * stride 0 or above TRX_MAX_AO_STRIDE, phase >= s*s, radius > TRX_MAX_AO_UPSAMPLE_RADIUS. */
+#define TRX_MAX_AO_UPSAMPLE_RADIUS 2
+int trx_ao_upsample_dev(trx_scene *scene, uint32_t width, uint32_t height, uint32_t stride, uint32_t phase,
+                        const trx_hit *d_primary, const trx_hit_attr *d_attr, const uint8_t *d_unoccluded_lo,
+                        uint32_t n_samples, uint32_t radius, float depth_tol, float normal_cos, trx_ao_term *d_term,
+                        void *stream);
 /* Shading to RGBA8: elementwise over n_records records in ANY layout (image or TRX_LAYOUT_SHARD; the output is laid out
  * like the input), 4 bytes {c, c, c, 255} per record at d_rgba (n_records * 4 bytes, 4-byte aligned; nothing beyond them is
  * written).  The colour per record, every division a single IEEE division:
@@ -593,6 +638,14 @@ int trx_shade_ao_term_dev(trx_scene *scene, const trx_ao_term *d_term, uint64_t 
 int trx_render_image(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
                      uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius, uint32_t filter_radius,
                      float depth_tol, float normal_cos, uint8_t *out_rgba, float *out_ms);
+
+/* trx_render_image with the AO term traced sparsely: the primary pass, the attribute pass, the sparse visibility pass at
+ * (ao_stride, ao_phase), the upsample at upsample_radius with normals, the term shade; 4 bytes per pixel copied back.
+ * n_samples is 1..TRX_MAX_AO_SAMPLES here.  Every argument is validated before the first pass is enqueued. */
+int trx_render_image_sparse(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                            uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius, uint32_t ao_stride,
+                            uint32_t ao_phase, uint32_t upsample_radius, float depth_tol, float normal_cos,
+                            uint8_t *out_rgba, float *out_ms);
 
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */

@@ -31,6 +31,8 @@ SEM_CPU = 3
 MAX_AO_SAMPLES = 64
 AO_NO_SURFACE = 0xFF
 MAX_AO_FILTER_RADIUS = 4
+MAX_AO_STRIDE = 4
+MAX_AO_UPSAMPLE_RADIUS = 2
 HEAT_NODES = 0
 HEAT_TRIS = 1
 HEAT_SCALE_NODES = 0.002
@@ -150,6 +152,9 @@ SIGNATURES = {
     "trx_ao_rays_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _f, _f, _P, _P, _P, _P]),
     "trx_trace_ao_visibility_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _u32, _f, _f, _P, _P, _P, _P]),
     "trx_trace_ao_visibility": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, C.POINTER(_f)]),
+    "trx_trace_ao_visibility_sparse_dev": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _f, _f, _P, _P, _P, _P]),
+    "trx_ao_upsample_dev": (_i, [_P, _u32, _u32, _u32, _u32, _P, _P, _P, _u32, _u32, _f, _f, _P, _P]),
+    "trx_render_image_sparse": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _u32, _u32, _u32, _f, _f, _P, C.POINTER(_f)]),
     "trx_ao_filter_dev": (_i, [_P, _u32, _u32, _P, _P, _P, _u32, _u32, _f, _f, _P, _P]),
     "trx_image_code_table": (_i, [_P]),
     "trx_shade_reference_dev": (_i, [_P, _P, _P, _u64, _P, _P]),

@@ -1,9 +1,10 @@
-// api_ao.cpp - AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility*): the AO pass's rays written out as
+// api_ao.cpp - AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility* / trx_trace_ao_visibility_sparse_dev): the AO pass's rays written out as
 // explicit rays (k_ao_rays, kernels.hip), walked by the any-hit rays launch every trx_trace_occluded*_dev call uses, and
 // their flags added into one count per pixel (k_ao_reduce).  A composition around the shipped walk: no traversal kernel
 // knows about it.  Everything of one call runs on the caller's stream, on that stream's launch slot of the scene - the slot
 // owns the ray scratch, so concurrent calls on other streams have their own - and trx_scene_refit waits for it like for any
-// other launch of the slot.
+// other launch of the slot.  The sparse pass is the same chain over the tiles of a low grid whose cells name every
+// stride-th pixel of the full image (kernels.h, AoRaysParams): same scratch, same cap, same chunk loops.
 #include "api_internal.h"
 
 #include <cfloat>
@@ -40,6 +41,16 @@ int need_inst(const trx_scene *s, const uint32_t *d_primary_inst) {
     return TRX_OK;
 }
 
+// the sparse pass's grid: cell (X, Y) of the ceil(w / stride) x ceil(h / stride) low grid is pixel (X * stride + px0, Y * stride + py0)
+struct SparseGrid {
+    uint32_t stride, phase;
+};
+int check_sparse(uint32_t stride, uint32_t phase) {
+    if (stride == 0 || stride > TRX_MAX_AO_STRIDE) return fail(TRX_ERR_INVALID, "stride %u outside 1..%d", stride, TRX_MAX_AO_STRIDE);
+    if (phase >= stride * stride) return fail(TRX_ERR_INVALID, "phase %u outside 0..%u (stride %u)", phase, stride * stride - 1, stride);
+    return TRX_OK;
+}
+
 // hipEvents around the three phases of every chunk (trx_debug_ao_visibility_phases)
 struct Phases {
     std::vector<Event> ev; // 4 per chunk: before the rays, after them, after the walk, after the reduce
@@ -53,8 +64,10 @@ struct Phases {
 
 int visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t frame0,
                     uint32_t n_samples, float ao_eps, float ao_radius, const trx_hit *d_primary,
-                    const uint32_t *d_primary_inst, uint8_t *d_unoccluded, hipStream_t stream, Phases *phases) {
+                    const uint32_t *d_primary_inst, uint8_t *d_unoccluded, hipStream_t stream, Phases *phases,
+                    const SparseGrid *sparse = nullptr) {
     if (!s || !d_primary || !d_unoccluded) return fail(TRX_ERR_INVALID, "null argument");
+    if (sparse) if (int rc = check_sparse(sparse->stride, sparse->phase)) return rc;
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
     if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
         return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
@@ -63,6 +76,16 @@ int visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, 
     float tmax = 0.f;
     if (int rc = radius_tmax(ao_radius, tmax)) return rc;
     if (int rc = ao_geometry(g, view, w, h, shard, tiles)) return rc;
+    if (sparse) {
+        // (the full image's geometry stays in g.geom and g.view: the rays are its rays; the tiles are the low grid's)
+        AoRaysParams lo;
+        const uint32_t st = sparse->stride;
+        if (int rc = ao_geometry(lo, view, (w + st - 1) / st, (h + st - 1) / st, shard, tiles)) return rc;
+        g.lo = lo.geom;
+        g.stride = st;
+        g.px0 = sparse->phase % st;
+        g.py0 = sparse->phase / st;
+    }
     if (int rc = need_inst(s, d_primary_inst)) return rc;
     if (tiles == 0) return TRX_OK;
     HIP_TRY(hipSetDevice(s->device));
@@ -165,6 +188,14 @@ int trx_trace_ao_visibility_dev(trx_scene *s, const trx_view *view, uint32_t w, 
                                 const uint32_t *d_primary_inst, uint8_t *d_unoccluded, void *stream) {
     return visibility_impl(s, view, w, h, shard, sem, frame0, n_samples, ao_eps, ao_radius, d_primary, d_primary_inst,
                            d_unoccluded, (hipStream_t)stream, nullptr);
+}
+
+int trx_trace_ao_visibility_sparse_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t stride, uint32_t phase,
+                                       uint32_t sem, uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius,
+                                       const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_unoccluded_lo, void *stream) {
+    const SparseGrid grid{stride, phase};
+    return visibility_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, frame0, n_samples, ao_eps, ao_radius, d_primary, d_primary_inst,
+                           d_unoccluded_lo, (hipStream_t)stream, nullptr, &grid);
 }
 
 int trx_trace_ao_visibility(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame0,

@@ -1,5 +1,6 @@
-// api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_shade_*_dev / trx_render_image): the edge-aware
-// filter over the AO visibility pass's counts and the shading to RGBA8 (k_ao_filter, k_shade, image.hip), and the table of
+// api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev /
+// trx_render_image*): the edge-aware filter over the AO visibility pass's counts, the edge-aware upsample of the sparse
+// pass's counts and the shading to RGBA8 (k_ao_filter, k_ao_upsample, k_shade, image.hip), and the table of
 // code thresholds the shade searches instead of evaluating pow; the PROFILE_RT heat map of a counting pass's per-ray counts
 // (trx_shade_heat_dev / trx_render_heat_image, k_heat).  Image passes after the walk: none reads scene data, but
 // each takes a launch slot of the scene like the attribute pass, so trx_scene_refit waits for them.
@@ -52,6 +53,13 @@ int check_filter(uint32_t radius, float depth_tol, float normal_cos) {
     if (radius > TRX_MAX_AO_FILTER_RADIUS) return fail(TRX_ERR_INVALID, "filter radius %u beyond %d", radius, TRX_MAX_AO_FILTER_RADIUS);
     if (!(depth_tol >= 0.0f)) return fail(TRX_ERR_INVALID, "depth_tol %g: must be >= 0 (+inf allowed)", (double)depth_tol);
     if (normal_cos != normal_cos) return fail(TRX_ERR_INVALID, "normal_cos is NaN");
+    return TRX_OK;
+}
+
+int check_sparse(uint32_t stride, uint32_t phase, uint32_t radius) {
+    if (stride == 0 || stride > TRX_MAX_AO_STRIDE) return fail(TRX_ERR_INVALID, "stride %u outside 1..%d", stride, TRX_MAX_AO_STRIDE);
+    if (phase >= stride * stride) return fail(TRX_ERR_INVALID, "phase %u outside 0..%u (stride %u)", phase, stride * stride - 1, stride);
+    if (radius > TRX_MAX_AO_UPSAMPLE_RADIUS) return fail(TRX_ERR_INVALID, "upsample radius %u beyond %d", radius, TRX_MAX_AO_UPSAMPLE_RADIUS);
     return TRX_OK;
 }
 
@@ -145,6 +153,37 @@ int trx_ao_filter_dev(trx_scene *s, uint32_t w, uint32_t h, const trx_hit *d_pri
     p.normal_cos = normal_cos;
     return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
         HIP_TRY(launch_ao_filter(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
+int trx_ao_upsample_dev(trx_scene *s, uint32_t w, uint32_t h, uint32_t stride, uint32_t phase, const trx_hit *d_primary,
+                        const trx_hit_attr *d_attr, const uint8_t *d_unoccluded_lo, uint32_t n_samples, uint32_t radius, float depth_tol,
+                        float normal_cos, trx_ao_term *d_term, void *stream) {
+    if (int rc = check_sparse(stride, phase, radius)) return rc;
+    if (int rc = check_filter(radius, depth_tol, normal_cos)) return rc;
+    if (int rc = check_samples(n_samples)) return rc;
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !d_primary || !d_unoccluded_lo || !d_term) return fail(TRX_ERR_INVALID, "null argument");
+    AoUpsampleParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.primary = d_primary;
+    p.attr = d_attr;
+    p.counts_lo = d_unoccluded_lo;
+    p.out = d_term;
+    p.width = w;
+    p.height = h;
+    p.lo_width = (w + stride - 1u) / stride;
+    p.lo_height = (h + stride - 1u) / stride;
+    p.stride = stride;
+    p.px0 = phase % stride;
+    p.py0 = phase / stride;
+    p.n_samples = n_samples;
+    p.radius = radius;
+    p.depth_tol = depth_tol;
+    p.normal_cos = normal_cos;
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        HIP_TRY(launch_ao_upsample(p, (hipStream_t)stream));
         return TRX_OK;
     });
 }
@@ -260,6 +299,47 @@ int trx_render_image(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h,
             if (rc) return rc;
             rc = trx_ao_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), d_counts(), n_samples, filter_radius, depth_tol,
                                    normal_cos, d_term(), nullptr);
+            if (rc) return rc;
+            return trx_shade_ao_term_dev(s, d_term(), n, d_rgba(), nullptr);
+        },
+        [&]() -> int {
+            if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
+}
+
+int trx_render_image_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t frame0,
+                            uint32_t n_samples, float ao_eps, float ao_radius, uint32_t ao_stride, uint32_t ao_phase,
+                            uint32_t upsample_radius, float depth_tol, float normal_cos, uint8_t *out_rgba, float *out_ms) {
+    if (int rc = check_samples(n_samples)) return rc;
+    if (!(ao_radius > 0.0f)) return fail(TRX_ERR_INVALID, "ao_radius %g: must be > 0 (+inf allowed)", (double)ao_radius);
+    if (int rc = check_sparse(ao_stride, ao_phase, upsample_radius)) return rc;
+    if (int rc = check_filter(upsample_radius, depth_tol, normal_cos)) return rc;
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !view) return fail(TRX_ERR_INVALID, "null argument");
+    const uint64_t n = (uint64_t)w * h;
+    const trx_shard whole{0, 1, 0, 0};
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
+    HIP_TRY(hipSetDevice(s->device));
+    // the image scratch: the upsampled terms, then the image
+    HIP_TRY(s->scratch_img.grow(n * 8));
+    auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
+    auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
+    // (the low grid's counts go where trx_trace_ao_visibility puts the dense ones: at most n bytes of the second record buffer)
+    auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
+    return host_call(
+        s, n, nullptr, 0, n, out_ms,
+        [&] {
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, s->scratch_a.get(), s->scratch_ia.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_trace_ao_visibility_sparse_dev(s, view, w, h, ao_stride, ao_phase, sem, frame0, n_samples, ao_eps, ao_radius,
+                                                    s->scratch_a.get(), s->scratch_ia.get(), d_counts(), nullptr);
+            if (rc) return rc;
+            rc = trx_ao_upsample_dev(s, w, h, ao_stride, ao_phase, s->scratch_a.get(), s->scratch_attr.get(), d_counts(), n_samples,
+                                     upsample_radius, depth_tol, normal_cos, d_term(), nullptr);
             if (rc) return rc;
             return trx_shade_ao_term_dev(s, d_term(), n, d_rgba(), nullptr);
         },

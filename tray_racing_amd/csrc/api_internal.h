@@ -8,7 +8,7 @@
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
 //   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts
-//   api_image.cpp    trx_ao_filter_dev / trx_shade_*_dev / trx_render_image / trx_render_heat_image: the image passes after the walk (image.hip)
+//   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H

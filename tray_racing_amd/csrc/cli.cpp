@@ -49,6 +49,10 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     int ao_filter = -1; // -1: not given, save_png's host loop stays as it is
     float ao_depth_tol = 0.02f, ao_normal_cos = 0.9f;
     // --profile-rt nodes|tris [--profile-rt-scale x]: with --png the image is the PROFILE_RT heat map (trx_render_heat_image)
+    // --ao-stride S [--ao-phase P] [--ao-upsample R]: with --png --ao-samples N the AO term is traced at one pixel in S x S
+    // and rebuilt at full resolution by the edge-aware upsample of radius R (trx_render_image_sparse), on the device
+    int ao_stride = -1; // -1: not given, everything stays as it is
+    int ao_phase = -1, ao_upsample = -1; // (not given: phase 0, radius 1)
     int profile_rt = -1; // -1: not given, else TRX_HEAT_NODES / TRX_HEAT_TRIS
     float profile_rt_scale = -1.0f; // (not given: the reference's scale of the mode)
     int device = 0;
@@ -83,6 +87,9 @@ void usage() {
               "  [--ao-samples 1..64] [--ao-radius r] (with --png: AO term = unoccluded samples / N of the any-hit visibility pass)\n"
               "  [--ao-filter 0..4] [--ao-depth-tol x] [--ao-normal-cos c] (with --png --ao-samples: edge-aware filter of that radius\n"
               "   over the AO counts, image shaded on the device; only the RGBA8 bytes are copied back)\n"
+              "  [--ao-stride 1..4] [--ao-phase 0..S*S-1] [--ao-upsample 0..2] (with --png --ao-samples: AO rays at one pixel in\n"
+              "   S x S, the full-resolution term by the edge-aware upsample of that radius (default 1) under --ao-depth-tol and\n"
+              "   --ao-normal-cos, image shaded on the device; not together with --ao-filter)\n"
               "  [--profile-rt nodes|tris] [--profile-rt-scale x] (with --png: the PROFILE_RT heat map of a counted primary pass -\n"
               "   box tests (8 per node visit) x 0.002 or triangle tests x 0.01 through the reference's colour ramp - instead of\n"
               "   the shaded frame; not together with --ao-samples or --ao-filter)\n"
@@ -136,6 +143,16 @@ Options parse_args(int argc, char **argv) {
             o.ao_normal_cos = (float)std::atof(need(i));
             if (o.ao_normal_cos != o.ao_normal_cos) die("--ao-normal-cos must be a number");
         }
+        else if (a == "--ao-stride") {
+            o.ao_stride = std::atoi(need(i));
+            if (o.ao_stride < 1 || o.ao_stride > TRX_MAX_AO_STRIDE) die("--ao-stride takes 1.." + std::to_string(TRX_MAX_AO_STRIDE));
+        } else if (a == "--ao-phase") {
+            o.ao_phase = std::atoi(need(i));
+            if (o.ao_phase < 0) die("--ao-phase takes 0..S*S-1 of --ao-stride S");
+        } else if (a == "--ao-upsample") {
+            o.ao_upsample = std::atoi(need(i));
+            if (o.ao_upsample < 0 || o.ao_upsample > TRX_MAX_AO_UPSAMPLE_RADIUS) die("--ao-upsample takes 0.." + std::to_string(TRX_MAX_AO_UPSAMPLE_RADIUS));
+        }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
             if (m == "nodes") o.profile_rt = (int)TRX_HEAT_NODES;
@@ -176,6 +193,10 @@ Options parse_args(int argc, char **argv) {
     if (o.cpu) die("--cpu is the reference's own rt_cpu path; the HIP backend has no CPU traversal");
     if (o.hardware) die("--hardware needs ray-tracing hardware; MI355X (CDNA4) has none");
     if (o.ao_filter >= 0 && o.ao_samples == 0) die("--ao-filter filters the counts of --ao-samples N");
+    if (o.ao_stride < 0 && (o.ao_phase >= 0 || o.ao_upsample >= 0)) die("--ao-phase and --ao-upsample go with --ao-stride S");
+    if (o.ao_stride >= 0 && o.ao_samples == 0) die("--ao-stride thins the rays of --ao-samples N");
+    if (o.ao_stride >= 0 && o.ao_filter >= 0) die("--ao-stride rebuilds the term with --ao-upsample: not together with --ao-filter");
+    if (o.ao_stride >= 0 && o.ao_phase >= o.ao_stride * o.ao_stride) die("--ao-phase takes 0..S*S-1 of --ao-stride S");
     if (o.profile_rt >= 0 && (o.ao_samples != 0 || o.ao_filter >= 0)) die("--profile-rt draws the heat map: not together with --ao-samples or --ao-filter");
     if (o.profile_rt < 0 && o.profile_rt_scale >= 0.0f) die("--profile-rt-scale scales the heat map of --profile-rt nodes|tris");
     if (o.passes == 0) o.passes = 1;
@@ -245,6 +266,16 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         // the AO term a renderer would use: the share of N bounded any-hit AO rays that reach nothing
         const unsigned samples = o.ao_samples ? o.ao_samples : 1u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
+        if (o.ao_stride >= 0) {
+            // the AO rays of one pixel in stride x stride, the term rebuilt and shaded on the device, 4 bytes per pixel back
+            const uint32_t phase = o.ao_phase >= 0 ? (uint32_t)o.ao_phase : 0u, up = o.ao_upsample >= 0 ? (uint32_t)o.ao_upsample : 1u;
+            check(trx_render_image_sparse(scene, &view, o.width, o.height, o.semantics, frame_count, samples, 0.0001f, radius,
+                                          (uint32_t)o.ao_stride, phase, up, o.ao_depth_tol, o.ao_normal_cos, rgba.data(), &ms), "png frame");
+            if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
+            if (o.verbose)
+                std::printf("saved %s (device image, AO stride %d phase %u, upsample radius %u, %.3f ms)\n", path.c_str(), o.ao_stride, phase, up, ms);
+            return;
+        }
         if (o.ao_filter >= 0) {
             // the image made on the device: filter and shade there, 4 bytes per pixel back
             check(trx_render_image(scene, &view, o.width, o.height, o.semantics, frame_count, samples, 0.0001f, radius,

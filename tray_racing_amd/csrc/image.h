@@ -24,6 +24,26 @@ struct AoFilterParams {
 };
 hipError_t launch_ao_filter(const AoFilterParams &p, hipStream_t stream);
 
+// k_ao_upsample (trx_ao_upsample_dev): the filter's shape - one workgroup of 256 lanes per kFilterTileW x kFilterTileH tile of
+// FULL-resolution pixels - over the cells of the sparse visibility pass's low grid (cell (X, Y) = pixel (X * stride + px0,
+// Y * stride + py0)).  LDS holds the low cells under the tile and a halo of `radius` cells: 32 consecutive pixels cover
+// floor((a + 31) / s) - floor(a / s) + 1 cells, 32 at s = 1 and at most 17 beyond, so stride 1 at the largest radius is the
+// largest case: (32 + 2r) x (8 + 2r) cells.
+constexpr uint32_t kUpsampleMaxStride = TRX_MAX_AO_STRIDE;
+constexpr uint32_t kUpsampleMaxRadius = TRX_MAX_AO_UPSAMPLE_RADIUS;
+constexpr uint32_t kUpsampleMaxCells = (kFilterTileW + 2 * kUpsampleMaxRadius) * (kFilterTileH + 2 * kUpsampleMaxRadius); // 432
+struct AoUpsampleParams {
+    const trx_hit *primary;   // whole FULL-resolution image, y * width + x
+    const trx_hit_attr *attr; // or null: no normal test
+    const uint8_t *counts_lo; // the low grid, Y * lo_width + X
+    trx_ao_term *out;         // full resolution
+    uint32_t width, height, lo_width, lo_height;
+    uint32_t stride, px0, py0;
+    uint32_t n_samples, radius;
+    float depth_tol, normal_cos;
+};
+hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream);
+
 // k_shade: one lane per record, 4 bytes {c, c, c, 255} written per record; c by an 8-step search of the 256 thresholds
 // (trx_image_code_table) each workgroup first copies into LDS.
 enum ShadeMode : int { kShadeReference = 0, kShadeCounts = 1, kShadeTerm = 2 };

@@ -1,5 +1,6 @@
 // image.hip - gfx950 (MI355X, wave64) image passes after the walk (include/trx.h, "the frame's image"): the edge-aware
-// filter over the AO visibility pass's counts and the shading of a frame's records to RGBA8.  A translation unit of its
+// filter over the AO visibility pass's counts, the edge-aware upsample of the sparse pass's counts and the shading of a
+// frame's records to RGBA8.  A translation unit of its
 // own: nothing here is seen by kernels.hip, whose instructions stay what they were.
 //
 // Arithmetic contract (DESIGN.md "Numerics"): binary32, no contraction, IEEE divide, dot = (ax*bx + ay*by) + az*bz.  The
@@ -96,6 +97,107 @@ __global__ void __launch_bounds__(256) k_ao_filter(const AoFilterParams P) {
     P.out[(size_t)py * P.width + px] = out;
 }
 
+// The edge-aware upsample of the sparse visibility pass's counts (trx_ao_upsample_dev; the rules are stated in include/trx.h).
+// The filter's shape: one workgroup per 32 x 8 tile of full-resolution pixels, lane l is pixel (l & 31, l >> 5).
+//   phase 1: the low cells under the tile - columns (32 tx) / s .. (32 tx + 31) / s, rows likewise - and a halo of r cells
+// into LDS as separate arrays (depth, count word, three normal components).  A cell's depth and normal are the
+// full-resolution records of its pixel (X s + px0, Y s + py0), a gather at a pitch of s records; its count is the low
+// grid's byte.  A cell outside the low grid, whose pixel is outside the image, or without a surface gets kNotSurface.
+// At most kUpsampleMaxCells cells (image.h): 8.6 KB with normals, 3.5 KB without.
+//   phase 2: every lane reads its own pixel's depth and normal from memory (consecutive records) and walks the (2r + 1)^2
+// cells around cell (x / s, y / s) out of LDS.  A 32-lane half is one row of pixels and reads, per window step, the dwords
+// row * pitch + x / s + const: s neighbouring lanes name the same dword (one broadcast), the distinct dwords are at most 32
+// CONSECUTIVE ones, and ds_read_b32 banks a half over (address / 4) mod 32 - so no two distinct dwords of a half share a
+// bank, whatever the row pitch (it is 8 .. 36 dwords here) and whatever s.
+template <bool NORMALS>
+__global__ void __launch_bounds__(256) k_ao_upsample(const AoUpsampleParams P) {
+    __shared__ float s_t[kUpsampleMaxCells];
+    __shared__ uint32_t s_cnt[kUpsampleMaxCells];
+    __shared__ float s_n[NORMALS ? 3 * kUpsampleMaxCells : 1];
+    const uint32_t r = P.radius, st = P.stride;
+    const uint32_t tiles_x = (P.width + kFilterTileW - 1u) / kFilterTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const uint32_t cx_first = (tx * kFilterTileW) / st, cy_first = (ty * kFilterTileH) / st;
+    const uint32_t hw = (tx * kFilterTileW + kFilterTileW - 1u) / st - cx_first + 1u + 2u * r;
+    const uint32_t hh = (ty * kFilterTileH + kFilterTileH - 1u) / st - cy_first + 1u + 2u * r;
+    const uint32_t cells = hw * hh; // <= kUpsampleMaxCells for st >= 1, r <= kUpsampleMaxRadius (image.h)
+    const int x0 = (int)cx_first - (int)r, y0 = (int)cy_first - (int)r;
+    for (uint32_t c = threadIdx.x; c < cells; c += 256u) {
+        const uint32_t cy = c / hw, cx = c - cy * hw;
+        const int X = x0 + (int)cx, Y = y0 + (int)cy;
+        float t = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        uint32_t cnt = kNotSurface;
+        if (X >= 0 && Y >= 0 && (uint32_t)X < P.lo_width && (uint32_t)Y < P.lo_height) {
+            const uint32_t gx = (uint32_t)X * st + P.px0, gy = (uint32_t)Y * st + P.py0;
+            if (gx < P.width && gy < P.height) {
+                const size_t i = (size_t)gy * P.width + gx;
+                const trx_hit h = P.primary[i];
+                if (h.t < TRX_F32_MAX && h.prim != TRX_INVALID) {
+                    t = h.t;
+                    cnt = P.counts_lo[(size_t)Y * P.lo_width + (uint32_t)X];
+                    if constexpr (NORMALS) {
+                        const float *n = P.attr[i].normal;
+                        nx = n[0]; ny = n[1]; nz = n[2];
+                    }
+                }
+            }
+        }
+        s_t[c] = t;
+        s_cnt[c] = cnt;
+        if constexpr (NORMALS) {
+            s_n[c] = nx;
+            s_n[kUpsampleMaxCells + c] = ny;
+            s_n[2u * kUpsampleMaxCells + c] = nz;
+        }
+    }
+    __syncthreads();
+    const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
+    const uint32_t px = tx * kFilterTileW + lx, py = ty * kFilterTileH + ly;
+    if (px >= P.width || py >= P.height) return;
+    const size_t ip = (size_t)py * P.width + px;
+    const trx_hit hp = P.primary[ip];
+    trx_ao_term out;
+    out.unoccluded = 0;
+    out.samples = 0;
+    if (hp.t < TRX_F32_MAX && hp.prim != TRX_INVALID) {
+        const float tp = hp.t, tol = P.depth_tol * tp;
+        float npx = 0.0f, npy = 0.0f, npz = 0.0f;
+        if constexpr (NORMALS) {
+            const float *n = P.attr[ip].normal;
+            npx = n[0]; npy = n[1]; npz = n[2];
+        }
+        // the window's first cell, and the cell whose pixel is p itself (none when p is not a pixel of this phase)
+        const uint32_t qx = px / st, qy = py / st;
+        const uint32_t wx = qx - cx_first, wy = qy - cy_first;
+        const uint32_t own = (px - qx * st == P.px0 && py - qy * st == P.py0) ? (wy + r) * hw + wx + r : kNotSurface;
+        uint32_t sum = 0u, accepted = 0u, sum_all = 0u, surfaces = 0u;
+        for (uint32_t dy = 0; dy <= 2u * r; dy++) {
+            const uint32_t row = (wy + dy) * hw + wx;
+            for (uint32_t dx = 0; dx <= 2u * r; dx++) {
+                const uint32_t c = row + dx;
+                const uint32_t cq = s_cnt[c];
+                const bool surf = cq != kNotSurface;
+                bool ok = surf && __builtin_fabsf(s_t[c] - tp) <= tol;
+                if constexpr (NORMALS)
+                    ok = ok && (npx * s_n[c] + npy * s_n[kUpsampleMaxCells + c]) + npz * s_n[2u * kUpsampleMaxCells + c] >= P.normal_cos;
+                ok = ok || c == own;
+                sum += ok ? cq : 0u;
+                accepted += ok ? 1u : 0u;
+                sum_all += surf ? cq : 0u;
+                surfaces += surf ? 1u : 0u;
+            }
+        }
+        // no cell accepted: every surface cell of the window (FALLBACK); none of those either: {0, 0} (EMPTY)
+        if (accepted == 0u) {
+            sum = sum_all;
+            accepted = surfaces;
+        }
+        out.unoccluded = (uint16_t)sum;
+        out.samples = (uint16_t)(P.n_samples * accepted);
+    }
+    P.out[ip] = out;
+}
+
 // Shading to RGBA8 (trx_shade_*_dev): one lane per record.  The colour is one IEEE division at most; its 8-bit code is the
 // number of thresholds thr[1..255] it reaches (trx_image_code_table: the host's powf(col, 2.2f) * 255 truncated, turned
 // into the smallest binary32 of every code), found in 8 steps in the workgroup's copy of the table in LDS - the device
@@ -182,6 +284,18 @@ hipError_t launch_ao_filter(const AoFilterParams &p, hipStream_t stream) {
     if (tiles > 0x7fffffffull || p.radius > kFilterMaxRadius) return hipErrorInvalidValue;
     if (p.attr) hipLaunchKernelGGL(k_ao_filter<true>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(k_ao_filter<false>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream) {
+    const uint64_t tiles = (uint64_t)((p.width + kFilterTileW - 1u) / kFilterTileW) * ((p.height + kFilterTileH - 1u) / kFilterTileH);
+    if (tiles == 0) return hipSuccess;
+    // (what bounds the kernel's LDS indices and its reads of the low grid)
+    if (tiles > 0x7fffffffull || p.radius > kUpsampleMaxRadius || p.stride == 0 || p.stride > kUpsampleMaxStride || p.px0 >= p.stride ||
+        p.py0 >= p.stride || p.lo_width != (p.width + p.stride - 1u) / p.stride || p.lo_height != (p.height + p.stride - 1u) / p.stride)
+        return hipErrorInvalidValue;
+    if (p.attr) hipLaunchKernelGGL(k_ao_upsample<true>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(k_ao_upsample<false>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -223,6 +223,11 @@ hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream)
 //   scratch layout (scratch == 1): rays[((tile - tile0) * n_samples + sample) * 64 + pixel-in-tile] for the shard's local
 // tiles tile0 .. tile0 + n_tiles - 1 and the seeds frame .. frame + n_samples - 1; EVERY entry is written (pixels outside the
 // image and primary misses get the inert ray), because the rays launch walks all of them.
+//   sparse (stride != 0, trx_trace_ao_visibility_sparse_dev; scratch layout, whole image): the tiles are those of the LOW
+// grid `lo` (ceil(width / stride) x ceil(height / stride) cells); cell (X, Y) stands for pixel (X * stride + px0,
+// Y * stride + py0) of the full image `geom`, whose record and coordinates the ray is built from exactly as in the dense
+// pass; a cell whose pixel leaves the image gets the inert ray and the count TRX_AO_NO_SURFACE.  counts holds one byte per
+// cell, Y * lo.width + X.  The dense launches leave stride 0 and run the kernels' dense instantiations.
 constexpr uint32_t kAoNoSurface = 0xffu;        // TRX_AO_NO_SURFACE
 constexpr uint32_t kAoUnitBytes = 64u * 32u + 64u; // scratch per (tile, sample): 64 rays and their 64 flags
 struct AoRaysParams {
@@ -239,6 +244,8 @@ struct AoRaysParams {
     uint32_t frame;
     float ao_eps, tmax;
     ViewDev view;
+    uint32_t stride, px0, py0;    // sparse: 1..TRX_MAX_AO_STRIDE and the phase's pixel in the stride x stride block (dense: 0)
+    TileGeom lo;                  // sparse: the low grid (whole image, image layout)
 };
 hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream);
 hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream);

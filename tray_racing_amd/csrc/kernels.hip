@@ -920,13 +920,26 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
 // tmax = the AO radius.  Its own: the addressing and the inert ray - a pixel whose primary record is a miss gets it (all
 // words 0 but tmax = -1: no walk commits a hit on it, every walk starts from min(tmax, FLT_MAX)).  A streaming kernel: 8 B of
 // primary record, 48 B of triangle (and 48 B of rows) read per ray, 32 B written.
+//   SPARSE (trx_trace_ao_visibility_sparse_dev): the addressing alone differs - the tile is one of the low grid, its cell
+// names the pixel of the full image whose ray this is; everything from the primary record on is the dense pass's statement.
+template <bool SPARSE>
 __global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
     const uint32_t item = blockIdx.x * 256u + threadIdx.x;
     if (item >= P.n_tiles * P.n_samples * 64u) return;
     const uint32_t unit = item >> 6, k = item & 63u;
     const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
     uint32_t px, py, rec;
-    const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+    bool inside;
+    if constexpr (SPARSE) {
+        uint32_t cx, cy, cell;
+        inside = tile_pixel(P.lo, P.tile0 + lt, k, cx, cy, cell);
+        px = cx * P.stride + P.px0;
+        py = cy * P.stride + P.py0;
+        inside = inside && px < P.geom.width && py < P.geom.height;
+        rec = py * P.geom.width + px;
+    } else {
+        inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+    }
     if (!inside && !P.scratch) return; // (the trace writes no record for it either)
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
     trx_hit ph;
@@ -958,12 +971,15 @@ __global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
 
 // One lane per pixel of the chunk's tiles: the samples of the chunk whose ray was NOT occluded, set (first samples of the
 // tile: TRX_AO_NO_SURFACE where the primary record is a miss - the inert ray names it) or added to the pixel's count.
+//   SPARSE: one lane per cell of the low grid's tiles, the count at the cell's place in the low grid; a cell whose pixel
+// leaves the image carries the inert ray too, so it gets TRX_AO_NO_SURFACE.
+template <bool SPARSE>
 __global__ void __launch_bounds__(256) k_ao_reduce(const AoRaysParams P) {
     const uint32_t item = blockIdx.x * 256u + threadIdx.x;
     if (item >= P.n_tiles * 64u) return;
     const uint32_t lt = item >> 6, k = item & 63u;
     uint32_t px, py, rec;
-    if (!tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec)) return;
+    if (!tile_pixel(SPARSE ? P.lo : P.geom, P.tile0 + lt, k, px, py, rec)) return;
     const uint32_t base = lt * P.n_samples * 64u + k;
     const bool surface = !(P.rays[base].tmax < 0.0f);
     uint32_t n = 0u;
@@ -978,13 +994,24 @@ hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream) {
     const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
     if (n == 0) return hipSuccess;
     if (n > 0xffffff00ull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ao_rays, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    const dim3 grid((uint32_t)((n + 255u) / 256u));
+    if (p.stride) {
+        // (the sparse form exists for the scratch layout of a whole image only)
+        if (!p.scratch || p.stride > TRX_MAX_AO_STRIDE || p.px0 >= p.stride || p.py0 >= p.stride || p.lo.shard_count != 1u || p.lo.compact ||
+            p.geom.shard_count != 1u || p.geom.compact)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_ao_rays<true>, grid, dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(k_ao_rays<false>, grid, dim3(256), 0, stream, p);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream) {
     if (p.n_tiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ao_reduce, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    const dim3 grid((p.n_tiles * 64u + 255u) / 256u);
+    if (p.stride) hipLaunchKernelGGL(k_ao_reduce<true>, grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(k_ao_reduce<false>, grid, dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -511,6 +511,17 @@ class Scene:
                                            filter_radius, depth_tol, normal_cos, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_image_sparse(self, view, width, height, n_samples, ao_stride, ao_phase=0, upsample_radius=1, sem=L.SEM_HLSL, frame0=0,
+                            ao_eps=0.01, ao_radius=float("inf"), depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_sparse - the AO visibility pass at one pixel in every
+        ao_stride x ao_stride block (the pixel ao_phase names), the full-resolution term rebuilt by the edge-aware upsample of
+        upsample_radius low cells (with normals), shaded to RGBA8 on the device; only the image crosses the bus."""
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_sparse(self._h, C.byref(view), width, height, sem, frame0, n_samples, ao_eps, ao_radius,
+                                                  ao_stride, ao_phase, upsample_radius, depth_tol, normal_cos, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
         """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
         of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
@@ -692,6 +703,17 @@ class Scene:
                                                       C.c_void_p(d_primary_inst), C.c_void_p(d_unoccluded),
                                                       C.c_void_p(stream)))
 
+    def trace_ao_visibility_sparse_dev(self, view, width, height, stride, phase, d_primary, d_unoccluded_lo, n_samples, ao_radius,
+                                       sem=L.SEM_HLSL, frame0=0, ao_eps=0.01, d_primary_inst=0, stream=0):
+        """trx_trace_ao_visibility_sparse_dev: the visibility pass at pixel (X * stride + phase % stride, Y * stride + phase //
+        stride) of every cell (X, Y) of the ceil(width / stride) x ceil(height / stride) low grid, one byte per cell at
+        d_unoccluded_lo - that pixel's byte of trx_trace_ao_visibility_dev, L.AO_NO_SURFACE where the pixel leaves the image.
+        d_primary / d_primary_inst are whole-image, image-layout, full-resolution records."""
+        L.check(self._lib.trx_trace_ao_visibility_sparse_dev(self._h, C.byref(view), width, height, stride, phase, sem, frame0,
+                                                             n_samples, ao_eps, ao_radius, C.c_void_p(d_primary),
+                                                             C.c_void_p(d_primary_inst), C.c_void_p(d_unoccluded_lo),
+                                                             C.c_void_p(stream)))
+
     def hit_attributes_rays_dev(self, d_rays, n, d_hits, d_attr, d_inst=0, stream=0):
         """trx_hit_attributes_rays_dev: n trx_hit_attr records at d_attr for the hits d_hits of the rays d_rays (d_inst: the
         hits' instance ids, required on scenes with instance transforms)."""
@@ -713,6 +735,16 @@ class Scene:
         L.check(self._lib.trx_ao_filter_dev(self._h, width, height, C.c_void_p(d_primary), C.c_void_p(d_attr),
                                             C.c_void_p(d_unoccluded), n_samples, radius, depth_tol, normal_cos,
                                             C.c_void_p(d_term), C.c_void_p(stream)))
+
+    def ao_upsample_dev(self, width, height, stride, phase, d_primary, d_unoccluded_lo, d_term, n_samples, radius, depth_tol=0.02,
+                        normal_cos=0.9, d_attr=0, stream=0):
+        """trx_ao_upsample_dev: one trx_ao_term per full-resolution pixel at d_term from the sparse pass's low-grid counts -
+        the counts of the accepted low cells of the (2 * radius + 1)^2 window around cell (x // stride, y // stride) summed
+        (accepted as in the filter, on the full-resolution records of the cell's pixel); every surface cell of the window
+        where none is accepted."""
+        L.check(self._lib.trx_ao_upsample_dev(self._h, width, height, stride, phase, C.c_void_p(d_primary), C.c_void_p(d_attr),
+                                              C.c_void_p(d_unoccluded_lo), n_samples, radius, depth_tol, normal_cos,
+                                              C.c_void_p(d_term), C.c_void_p(stream)))
 
     def shade_reference_dev(self, d_primary, d_ao, n, d_rgba, stream=0):
         """trx_shade_reference_dev: the reference's grey image of n primary / AO record pairs, 4 bytes per record."""
