@@ -61,6 +61,14 @@ int trx_debug_service_stats(trx_scene *scene, uint64_t *out_rays, uint64_t *out_
  * be NULL. */
 int trx_debug_scene_info(trx_scene *scene, uint32_t *out_exp_exact, float *out_scene_diag, uint32_t *out_refit_levels);
 
+/* Which walk the shipped library launches for a trace mode on this scene: 0 = the plain walk, 1 = the pipelined walk
+ * (the next node's fetch issued under the triangle phase; single-level scenes past 32 MiB of nodes and triangle records,
+ * every mode but the primary pass and the ray service).  mode: 0 primary, 1 AO (its batch and counting passes too), 2 explicit
+ * rays (closest hit, any hit, trx_traverse_batch, the AO visibility passes), 3 the one-launch frame, 4 the ray service behind
+ * trx_traverse1.  This is the decision the launch path itself takes; the forcing bits of development builds (TRX_DEV_TUNE)
+ * are not reported.  A negative return is an error code. */
+int trx_debug_walk_kind(trx_scene *scene, uint32_t mode);
+
 /* Measuring aid: the reference's CPU pixel loop over the literal Traversable::traverse (src/rt_cpu/rt_cpu.rs:35-57) -
  * `threads` host threads, thread k calls trx_traverse1 for rays k, k + threads, ... - with the loop's wall-clock seconds and
  * the launches its calls shared. */

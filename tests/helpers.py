@@ -249,3 +249,70 @@ def aimed_rays(T, tri_verts, n, seed):
     rays["tmin"] = 0.0
     rays["tmax"] = F32_MAX
     return rays
+
+
+# ---- padded twins: a small scene on the pipelined walk ------------------------------------------------------------------
+
+# The library takes the pipelined walk for single-level scenes whose nodes (80 B each) and triangle records (48 B each on
+# the device, whatever format they were handed over in) exceed 32 MiB together.  The tests do not rely on these numbers:
+# every one that uses a twin asks the library which walk it launches (assert_walk_kinds).
+_NODE_BYTES, _TRI_DEV_BYTES, _PIPE_MIN_BYTES = 80, 48, 32 << 20
+
+
+def padded_flat(T, flat):
+    """The padded twin of a single-level FlatScene: a copy whose tri_verts is followed by the smallest number of all-zero
+    triangles that makes n_nodes * 80 + n_tris * 48 > 32 MiB, everything else shared.  No leaf's primitive range reaches the
+    appended records, so no walk can read them: node indices, primitive ids and every derived launch word are the original's,
+    and the oracle's answers on the unpadded scene hold for the twin - which the library walks with the pipelined kernels."""
+    if flat.has_tlas:
+        raise ValueError("padded_flat: a two-level scene never takes the pipelined walk")
+    need = _PIPE_MIN_BYTES + 1 - flat.n_nodes * _NODE_BYTES
+    n_total = max(-(-need // _TRI_DEV_BYTES), flat.n_tris)
+    verts = np.zeros((n_total, 9), dtype=np.float32)
+    verts[:flat.n_tris] = flat.tri_verts
+    return T.FlatScene(flat.nodes, verts, flat.instance_offsets, flat.tlas_start, flat.tri_source, flat.blas_tri_start,
+                       flat.blas_build_s, flat.tlas_build_s, flat.tri_boxes, flat.instance_source, flat.instance_transforms,
+                       flat.instance_entry)
+
+
+def padded_records(padded, records):
+    """padded_flat's companion for Scene(tri_bytes=...): `records` ([n, k] words of the unpadded scene in any triangle
+    format, 24 or 36 bytes each) followed by all-zero records up to padded.n_tris."""
+    records = np.ascontiguousarray(records)
+    out = np.zeros((padded.n_tris,) + records.shape[1:], dtype=records.dtype)
+    out[:records.shape[0]] = records
+    return out
+
+
+def assert_walk_kinds(T, plain, twin, mode):
+    """What every test of a padded twin asserts first: the library launches the pipelined walk for `mode` on the twin and
+    the plain walk on the original scene, and the primary pass takes the plain walk on both."""
+    assert twin.walk_kind(mode) == T.WALK_PIPELINED, "the padded twin does not take the pipelined walk in mode %d" % mode
+    assert plain.walk_kind(mode) == T.WALK_PLAIN, "the original scene does not take the plain walk in mode %d" % mode
+    assert plain.walk_kind(T.MODE_PRIMARY) == T.WALK_PLAIN and twin.walk_kind(T.MODE_PRIMARY) == T.WALK_PLAIN
+
+
+def leg_scene(T, flat, padded, modes, tri_format=None, tri_bytes=None):
+    """The device scene of one leg of a test that runs twice over one oracle answer: the scene itself (the plain walk), or
+    with `padded` its twin (the pipelined walk in every mode of `modes`, asserted here against the original's)."""
+    kw = {} if tri_format is None else {"tri_format": tri_format}
+    plain = T.Scene(flat, tri_bytes=tri_bytes, **kw)
+    if not padded:
+        return plain
+    try:
+        pf = padded_flat(T, flat)
+        twin = T.Scene(pf, tri_bytes=None if tri_bytes is None else padded_records(pf, tri_bytes), **kw)
+        try:
+            for mode in modes:
+                assert_walk_kinds(T, plain, twin, mode)
+        except BaseException:
+            twin.close()
+            raise
+        return twin
+    finally:
+        plain.close()
+
+
+def is_twin(name):
+    """Scene names ending in _pipe are the padded twins: (base name, padded)."""
+    return (name[:-len("_pipe")], True) if name.endswith("_pipe") else (name, False)

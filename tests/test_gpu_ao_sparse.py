@@ -12,7 +12,7 @@ import pytest
 from ao_sparse_twin import ACCEPTED, EMPTY, FALLBACK, NO_SURFACE, ao_upsample, cell_pixels, class_counts, lo_size, sparse_counts
 from helpers import ALL_SEMS, random_rays
 from image_twin import TERM_DTYPE, ao_filter, shade_term, surface
-from test_gpu_ao_visibility import UNIT, Case
+from test_gpu_ao_visibility import UNIT, Case, make_case
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -48,42 +48,60 @@ def cases(trx, orc):
 
     def get(name):
         if name not in made:
-            made[name] = Case(trx, orc, name)
-            made[name].radius = RADIUS.get(name, made[name].radius)
-        return made[name]
+            base = name[:-len("_pipe")] if name.endswith("_pipe") else name
+            plain = make_case(trx, orc, made, base)
+            plain.radius = RADIUS.get(base, plain.radius)
+            make_case(trx, orc, made, name)          # (a padded twin takes its base case's radius, as it stands now)
+        return make_case(trx, orc, made, name)      # (which asks the library again which walk a twin takes)
     yield get
     trx.load().trx_debug_ao_scratch_cap(0)
     for c in made.values():
         c.close()
 
 
+def _on_the_unpadded_scene_too(case, run):
+    """run(scene) on the case's scene; on a padded twin (the pipelined walk) also on the unpadded scene (the plain walk), which
+    must give the same bytes."""
+    got = run(case.sc)
+    if case.base is not None:
+        plain = run(case.base.sc)
+        assert (got == plain).all(), "%s: %d bytes differ from the unpadded scene's" % (case.name, (got != plain).sum())
+    return got
+
+
 def _dense(case, d_prim, d_inst, n, radius, sem, frame0):
     torch = _torch()
-    d_out = _buf(case.w * case.h)
-    case.sc.trace_ao_visibility_dev(case.view, case.w, case.h, d_prim.data_ptr(), d_out.data_ptr(), n, radius, sem=sem, frame0=frame0,
-                                    ao_eps=EPS, d_primary_inst=d_inst.data_ptr())
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy()
+
+    def run(sc):
+        d_out = _buf(case.w * case.h)
+        sc.trace_ao_visibility_dev(case.view, case.w, case.h, d_prim.data_ptr(), d_out.data_ptr(), n, radius, sem=sem, frame0=frame0,
+                                   ao_eps=EPS, d_primary_inst=d_inst.data_ptr())
+        torch.cuda.synchronize()
+        return d_out.cpu().numpy()
+    return _on_the_unpadded_scene_too(case, run)
 
 
 def _sparse(case, d_prim, d_inst, stride, phase, n, radius, sem, frame0, stream=0):
     """The low grid's bytes, after checking that the 64 bytes past them kept their fill."""
     torch = _torch()
     wlo, hlo = lo_size(case.w, case.h, stride)
-    d_out = _buf(wlo * hlo + 64)
-    case.sc.trace_ao_visibility_sparse_dev(case.view, case.w, case.h, stride, phase, d_prim.data_ptr(), d_out.data_ptr(), n, radius,
-                                           sem=sem, frame0=frame0, ao_eps=EPS, d_primary_inst=d_inst.data_ptr() if d_inst is not None else 0,
-                                           stream=stream)
-    torch.cuda.synchronize()
-    case.sc.check()
-    raw = d_out.cpu().numpy()
-    assert (raw[wlo * hlo:] == FILL).all(), "bytes past Wlo * Hlo were written"
-    return raw[:wlo * hlo]
+
+    def run(sc):
+        d_out = _buf(wlo * hlo + 64)
+        sc.trace_ao_visibility_sparse_dev(case.view, case.w, case.h, stride, phase, d_prim.data_ptr(), d_out.data_ptr(), n, radius,
+                                          sem=sem, frame0=frame0, ao_eps=EPS, d_primary_inst=d_inst.data_ptr() if d_inst is not None else 0,
+                                          stream=stream)
+        torch.cuda.synchronize()
+        sc.check()
+        raw = d_out.cpu().numpy()
+        assert (raw[wlo * hlo:] == FILL).all(), "bytes past Wlo * Hlo were written"
+        return raw[:wlo * hlo]
+    return _on_the_unpadded_scene_too(case, run)
 
 
 # ---- 1. the sparse counts ------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", ["soup_52x44", "cornell_tlas_48", "instanced"])
+@pytest.mark.parametrize("name", ["soup_52x44", "cornell_tlas_48", "instanced", "soup_52x44_pipe"])
 def test_sparse_counts_are_the_dense_passs_bytes_and_the_twins(trx, orc, cases, name):
     """Strides 1..4 (every phase of 2, the first and last of 3 and 4), 1 / 8 / 64 samples, a finite radius and +inf under
     TRX_SEM_HLSL and TRX_SEM_CPU (64 samples under TRX_SEM_CPU); stride 2 under all eight semantics words; a non-null stream."""
@@ -127,19 +145,22 @@ def test_sparse_counts_are_the_dense_passs_bytes_and_the_twins(trx, orc, cases, 
 def test_chunk_loops_give_the_same_cells(trx, orc, cases):
     """A scratch cap below the pass's need: samples in several chunks, tiles in several chunks, both; restored afterwards."""
     lib = trx.load()
-    case = cases("instanced")
-    d_prim, d_inst, _, _ = case.primary(SEM)
     try:
-        for stride, phase in ((2, 3), (3, 0)):
-            wlo, hlo = lo_size(case.w, case.h, stride)
-            tiles = ((wlo + 7) // 8) * ((hlo + 7) // 8)
-            assert tiles >= 6
-            want = _sparse(case, d_prim, d_inst, stride, phase, 8, case.radius, SEM, 0)
-            assert ((want > 0) & (want < 8)).any()
-            for cap in (UNIT * tiles * 3, UNIT * tiles, UNIT * 4, UNIT * (tiles // 2 + 1) * 2, 1):
-                lib.trx_debug_ao_scratch_cap(cap)
-                got = _sparse(case, d_prim, d_inst, stride, phase, 8, case.radius, SEM, 0)
-                assert (got == want).all(), "stride %d cap %d: %d cells differ" % (stride, cap, (got != want).sum())
+        # (the transformed two-level scene, and the padded twin of the soup golden: chunks of the pipelined any-hit walk)
+        for name, grids in (("instanced", ((2, 3), (3, 0))), ("soup_52x44_pipe", ((2, 3), (4, 5)))):
+            case = cases(name)
+            d_prim, d_inst, _, _ = case.primary(SEM)
+            for stride, phase in grids:
+                wlo, hlo = lo_size(case.w, case.h, stride)
+                tiles = ((wlo + 7) // 8) * ((hlo + 7) // 8)
+                assert tiles >= (6 if name == "instanced" else 4)
+                lib.trx_debug_ao_scratch_cap(0)
+                want = _sparse(case, d_prim, d_inst, stride, phase, 8, case.radius, SEM, 0)
+                assert ((want > 0) & (want < 8)).any()
+                for cap in (UNIT * tiles * 3, UNIT * tiles, UNIT * 4, UNIT * (tiles // 2 + 1) * 2, 1):
+                    lib.trx_debug_ao_scratch_cap(cap)
+                    got = _sparse(case, d_prim, d_inst, stride, phase, 8, case.radius, SEM, 0)
+                    assert (got == want).all(), "%s stride %d cap %d: %d cells differ" % (name, stride, cap, (got != want).sum())
     finally:
         lib.trx_debug_ao_scratch_cap(0)
 

@@ -2,7 +2,11 @@
 inert ray, trx_trace_ao_visibility_dev the twin's counts - fed the device's own primary records, which test_gpu_parity.py and
 test_gpu_instances.py hold to the oracle - on single-level, two-level and transformed scenes, in both layouts, for 1, 8 and
 64 samples, a finite radius and +inf, every semantics word, and with a scratch cap small enough that the chunk loops run.
-No record is left out of any comparison."""
+No record is left out of any comparison.
+
+cornell_64_pipe and soup_52x44_pipe are the padded twins of those goldens (helpers.padded_flat): the pass's any-hit rays
+launch takes the pipelined walk on them.  A twin shares its base case's Python twin answers, and every count it produces is
+also compared byte for byte with what the unpadded scene gives for the same arguments."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +14,7 @@ import pytest
 
 from ao_visibility_twin import (THREADS, GOLDEN_RADIUS, INSTANCED_RADIUS, INVALID, NO_SURFACE, ao_rays, golden_case, instanced_case,
                                 record_map, stored_tmax, visibility_counts)
-from helpers import ALL_SEMS
+from helpers import ALL_SEMS, assert_walk_kinds, padded_flat
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -37,13 +41,14 @@ class Case:
             from tray_racing_amd import _lib
             self.osc, self.oview, self.w, self.h, g = golden_case(trx, orc, name)
             n = g["tri_verts"].shape[0]
-            self.sc = trx.Scene(trx.FlatScene(g["nodes"], g["tri_verts"], g["instance_offsets"], int(g["tlas_start"]),
-                                              np.arange(n), [0, n]))
+            self.flat = trx.FlatScene(g["nodes"], g["tri_verts"], g["instance_offsets"], int(g["tlas_start"]), np.arange(n), [0, n])
+            self.sc = trx.Scene(self.flat)
             self.view = _lib.View()
             C.memmove(C.byref(self.view), g["view"].tobytes(), C.sizeof(self.view))
             self.radius = GOLDEN_RADIUS.get(name, 1.0)
         self.transformed = name == "instanced"
-        self._rays = {}
+        self.base = None          # (a padded twin: the case of the unpadded scene)
+        self._rays, self._unoccluded = {}, {}
 
     def close(self):
         self.sc.close()
@@ -69,6 +74,9 @@ class Case:
 
     def unoccluded(self, sem, prim, inst, frame0, n_samples, radius, eps=0.01):
         """[n_samples, w * h] bool: the twin's answer per seed (rays are built once per seed and reused across radii)."""
+        whole = (sem, frame0, n_samples, radius, eps, hash(prim.tobytes()), hash(inst.tobytes()))
+        if whole in self._unoccluded:      # (asked before, by this case or by its padded twin)
+            return self._unoccluded[whole]
         out = np.zeros((n_samples, self.w * self.h), dtype=bool)
         for f in range(n_samples):
             key = (frame0 + f, eps, hash(prim.tobytes()), hash(inst.tobytes()))
@@ -80,7 +88,33 @@ class Case:
             hits, _ = self.osc.trace_rays(rays, sem=sem, threads=THREADS)
             assert (hits["prim"][~surface] == INVALID).all()
             out[f] = hits["prim"] == INVALID
+        self._unoccluded[whole] = (out, surface)
         return out, surface
+
+
+class PaddedCase(Case):
+    """The padded twin of a single-level golden case: the base case's oracle scene, views and cached twin answers (the very
+    dictionaries), and a padded scene on the device whose explicit-ray launches take the pipelined walk."""
+
+    def __init__(self, base):
+        self.__dict__.update(base.__dict__)
+        self.base, self.name = base, base.name + "_pipe"
+        self.sc = self.trx.Scene(padded_flat(self.trx, base.flat))
+        self.assert_walks()
+
+    def assert_walks(self):
+        """Asked again by every test that takes the twin (make_case)."""
+        for mode in (self.trx.MODE_RAYS, self.trx.MODE_AO):
+            assert_walk_kinds(self.trx, self.base.sc, self.sc, mode)
+
+
+def make_case(trx, orc, made, name):
+    """The case `name` of a module's `made` dictionary; a name ending in _pipe is the padded twin of the case before it."""
+    if name not in made:
+        made[name] = PaddedCase(make_case(trx, orc, made, name[:-len("_pipe")])) if name.endswith("_pipe") else Case(trx, orc, name)
+    if made[name].base is not None:
+        made[name].assert_walks()
+    return made[name]
 
 
 def _expected_counts(unocc, surface, n, shard, w, h, fill):
@@ -93,16 +127,21 @@ def _expected_counts(unocc, surface, n, shard, w, h, fill):
 
 
 def _visibility(case, d_prim, d_inst, n, radius, sem, shard, frame0=0, stream=0, fill=0x5A, eps=0.01):
+    """The pass's output buffer; on a padded twin also checked, byte for byte, against the unpadded scene's."""
     torch = _torch()
     _, _, size = record_map(case.w, case.h, shard)
-    d_out = torch.full((size,), fill, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    case.sc.trace_ao_visibility_dev(case.view, case.w, case.h, d_prim.data_ptr(), d_out.data_ptr(), n, radius, sem=sem,
-                                    frame0=frame0, ao_eps=eps, d_primary_inst=d_inst.data_ptr() if d_inst is not None else 0,
-                                    shard=(*shard, 0), stream=stream)
-    torch.cuda.synchronize()
-    case.sc.check()
-    return d_out.cpu().numpy()
+    outs = []
+    for sc in (case.sc,) if case.base is None else (case.sc, case.base.sc):
+        d_out = torch.full((size,), fill, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        sc.trace_ao_visibility_dev(case.view, case.w, case.h, d_prim.data_ptr(), d_out.data_ptr(), n, radius, sem=sem,
+                                   frame0=frame0, ao_eps=eps, d_primary_inst=d_inst.data_ptr() if d_inst is not None else 0,
+                                   shard=(*shard, 0), stream=stream)
+        torch.cuda.synchronize()
+        sc.check()
+        outs.append(d_out.cpu().numpy())
+    assert len(outs) == 1 or (outs[0] == outs[1]).all(), "%s: %d bytes differ from the unpadded scene's" % (case.name, (outs[0] != outs[1]).sum())
+    return outs[0]
 
 
 @pytest.fixture(scope="module")
@@ -110,9 +149,7 @@ def cases(trx, orc):
     made = {}
 
     def get(name):
-        if name not in made:
-            made[name] = Case(trx, orc, name)
-        return made[name]
+        return make_case(trx, orc, made, name)
     yield get
     trx.load().trx_debug_ao_scratch_cap(0)
     for c in made.values():
@@ -174,7 +211,7 @@ def test_ao_rays_and_visibility_need_instance_ids_on_transformed_scenes(trx, cas
 
 # ---- trx_trace_ao_visibility_dev --------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", ["cornell_64", "cornell_tlas_48", "instanced"])
+@pytest.mark.parametrize("name", ["cornell_64", "cornell_tlas_48", "instanced", "cornell_64_pipe"])
 def test_visibility_counts_equal_the_twin(trx, orc, cases, name):
     """Single-level, two-level and transformed scenes; image and shard layouts, shard (1, 3) among them; 1, 8 and 64 samples;
     the finite radius of tests/test_ao_visibility.py and +inf; every semantics word (64 samples under TRX_SEM_HLSL and
@@ -200,7 +237,7 @@ def test_visibility_counts_equal_the_twin(trx, orc, cases, name):
                     assert ((surf > 0) & (surf < 8)).mean() >= 0.05 and (surf == 0).any() and (surf == 8).any()
 
 
-@pytest.mark.parametrize("name", ["cornell_64", "instanced"])
+@pytest.mark.parametrize("name", ["cornell_64", "instanced", "cornell_64_pipe"])
 def test_chunk_loops_give_the_same_counts(trx, orc, cases, name):
     """A scratch cap below the pass's need: samples in several chunks (counts added to), tiles in several chunks, both."""
     lib = trx.load()
@@ -219,7 +256,7 @@ def test_chunk_loops_give_the_same_counts(trx, orc, cases, name):
         lib.trx_debug_ao_scratch_cap(0)
 
 
-@pytest.mark.parametrize("name", ["cornell_64", "soup_52x44", "cornell_tlas_48", "instanced"])
+@pytest.mark.parametrize("name", ["cornell_64", "soup_52x44", "cornell_tlas_48", "instanced", "cornell_64_pipe", "soup_52x44_pipe"])
 def test_infinite_radius_counts_are_the_misses_of_the_ao_batch(trx, cases, name):
     torch = _torch()
     case = cases(name)

@@ -23,10 +23,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MISS = 0xFFFFFFFF
 REBRAID_DEFAULT = 1.0 / 4096.0
 SLACK = 37   # records past the end of an output buffer: must stay as they were
-# the incoherent single-level passes take the pipelined walk (trace_walk_pipe.inc) only over scenes larger than this
-# (api_launch.cpp, TRX_PIPE_MIN_BYTES; 80-byte nodes, 48-byte device triangles): the hairball-class cases are built past
-# it, so both walks' counting kernels are under test
-PIPE_MIN_BYTES = 32 << 20
+# the incoherent single-level passes take the pipelined walk (trace_walk_pipe.inc) only over scenes past a size threshold
+# (api_launch.cpp, pipelined_walk): the hairball-class cases are built past it - the library says so itself
+# (Scene.walk_kind) - so both walks' counting kernels are under test
 HAIRBALL_TRIS = 700000
 
 
@@ -105,8 +104,8 @@ def build_case(trx, orc, name, n, w, h, tlas=False, rebraid=None):
     return flat, view, orc.Scene.from_flat(flat), orc.view_from_bytes(view)
 
 
-def assert_past_pipe_threshold(flat):
-    assert flat.n_nodes * 80 + flat.n_tris * 48 > PIPE_MIN_BYTES, "the hairball-class scene no longer reaches the pipelined walk"
+def assert_takes_the_pipelined_walk(trx, sc, mode):
+    assert sc.walk_kind(mode) == trx.WALK_PIPELINED, "the hairball-class scene no longer reaches the pipelined walk"
 
 
 def mixed_rays(trx, flat, n, seed, tri_verts=None):
@@ -155,9 +154,9 @@ def test_ao_counting_pass_equals_the_oracle(trx, orc, name, n, w, h, tlas, rebra
     import torch
     from tray_racing_amd import dist as D
     flat, view, osc, ov = build_case(trx, orc, name, n, w, h, tlas, rebraid)
-    if name == "hairball":
-        assert_past_pipe_threshold(flat)
     sc = trx.Scene(flat)
+    if name == "hairball":
+        assert_takes_the_pipelined_walk(trx, sc, trx.MODE_AO)
     npx = w * h
     try:
         d_prim, d_ao, d_ref = filled(npx), filled(npx + SLACK), filled(npx + SLACK)
@@ -308,7 +307,7 @@ def test_ray_counting_pass_equals_the_oracle(trx, orc, name, n_tris, tlas):
         def oracle(rays, sem):
             return osc.trace_rays(rays, sem=sem)
     if name == "hairball":
-        assert_past_pipe_threshold(flat)
+        assert_takes_the_pipelined_walk(trx, sc, trx.MODE_RAYS)
     from tray_racing_amd import dist as D
     try:
         for n in RAY_SIZES:

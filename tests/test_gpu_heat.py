@@ -24,7 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "tray_racing_amd", "tray_racing_hip")
 SLACK = 37                 # records past the end of an output buffer: must stay as they were
 SENTINEL = 0x5A5A5A5A      # a cost record no pass writes here: n_node = n_tri = 23130, far above any count of these frames
-PIPE_MIN_BYTES = 32 << 20  # api_launch.cpp, TRX_PIPE_MIN_BYTES: incoherent single-level passes over larger scenes take the pipelined walk
 HAIRBALL_TRIS = 700000
 ZERO = np.zeros(1, dtype=H.COST_DTYPE)
 
@@ -186,7 +185,6 @@ def test_ray_per_ray_counts_through_the_pipelined_walk(trx, orc):
     their sums."""
     verts, counts = trx.gen_scene("hairball", HAIRBALL_TRIS, 1)
     flat = trx.flat_build(verts, counts)
-    assert flat.n_nodes * 80 + flat.n_tris * 48 > PIPE_MIN_BYTES, "the hairball-class scene no longer reaches the pipelined walk"
     osc = orc.Scene.from_flat(flat)
     n = 2048
     n_aimed = (n + 2) // 3
@@ -194,6 +192,7 @@ def test_ray_per_ray_counts_through_the_pipelined_walk(trx, orc):
     subset = np.sort(np.random.default_rng(5).choice(n, size=512, replace=False))
     sc = trx.Scene(flat)
     try:
+        assert sc.walk_kind(trx.MODE_RAYS) == trx.WALK_PIPELINED, "the hairball-class scene no longer reaches the pipelined walk"
         for sem in (0, 3):
             got, ost = check_ray_batch(trx, sc, osc, rays, sem, "hairball sem %d" % sem, subset)
             assert 0.02 < ost.n_hits / n < 0.99 and ost.n_tri > 0

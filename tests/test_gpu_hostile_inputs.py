@@ -21,15 +21,22 @@ on the Cornell-class scene and the instanced soup, and on the 8 x 8 image of the
 every pass below; the kernels take the same path whatever the image size (a tile of NaN rays fails `fits`).
 
 The decode-once diagnostic switch (include/trx_dev.h, tune bits 0x40000 / 0x80000) is compiled into development builds only
-(api_launch.cpp, TRX_DEV_TUNE): the shipped library does not honour it, so there is no leg with the step switched off."""
+(api_launch.cpp, TRX_DEV_TUNE): the shipped library does not honour it, so there is no leg with the step switched off.
+
+The names ending in _pipe are the padded twins of the three single-level scenes (helpers.padded_flat): the same nodes and
+triangles followed by unreferenced zero records, which the library walks with the pipelined kernels (trace_walk_pipe.inc) in
+every mode but the primary pass and the ray service.  A twin shares its base case's rays, views and oracle answers - the
+oracle walks the unpadded scene, once - and differs only in the scene on the device; the calls that never take the pipelined
+walk (bare primary passes, the ray service, the attribute pass over a primary frame) are left to the base case."""
 import ctypes as C
+import hashlib
 
 import numpy as np
 import pytest
 
 import hostile_inputs as H
 from ao_visibility_twin import visibility_counts
-from helpers import ALL_SEMS, bits, instanced_scene, make_scene, w2o_rows
+from helpers import ALL_SEMS, assert_walk_kinds, bits, instanced_scene, make_scene, padded_flat, w2o_rows
 from hit_attr_twin import attr_bits, hit_attrs, primary_dirs, primary_origins, primary_pixels, tri_records
 
 pytestmark = pytest.mark.gpu
@@ -39,8 +46,11 @@ N_RAYS = 4096
 # the oracle's workers per call (0 would be one per core of the machine, woken for every one of a few thousand small calls)
 THREADS, FEW = 8, 2
 SIZES = [(8, 8), (16, 16), (48, 24), (33, 47)]
-SCENES = ["cornell", "kitchen", "bistro", "bistro_tlas", "instanced"]
-CAMERA_SCENES = ["cornell", "kitchen", "bistro", "bistro_tlas"]
+PIPE_SCENES = ["cornell_pipe", "kitchen_pipe", "bistro_pipe"]
+SCENES = ["cornell", "kitchen", "bistro", "bistro_tlas", "instanced"] + PIPE_SCENES
+CAMERA_SCENES = ["cornell", "kitchen", "bistro", "bistro_tlas"] + PIPE_SCENES
+# the passes that never take the pipelined walk run on the base cases only
+PRIMARY_SCENES = ["cornell", "kitchen", "bistro", "bistro_tlas"]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -85,6 +95,8 @@ class Case:
     def __init__(self, trx, orc, name):
         self.trx, self.orc, self.name = trx, orc, name
         self.instanced = name == "instanced"
+        self.padded = False
+        self._memo = {}
         if self.instanced:
             mats, mcls = H.hostile_affines(np.random.default_rng(7), 16)
             self.flat, _o2w, world, self.first, _b = instanced_scene(trx, n_objects=3, tris_per_object=300, matrices=mats)
@@ -105,13 +117,26 @@ class Case:
         self.rays, self.classes = H.hostile_rays(trx, self.flat, N_RAYS, 5, tri_verts=self.aim)
         self._want, self._views, self._frames, self._tame = {}, {}, {}, {}
 
+    def memo(self, key, arrays, compute):
+        """compute() once per (key, contents of `arrays`): a padded twin asks what its base case asked."""
+        h = hashlib.sha1()
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+        key = key + (h.digest(),)
+        if key not in self._memo:
+            self._memo[key] = compute()
+        return self._memo[key]
+
     def oracle(self, rays, sem):
-        """(hits, instance ids or None, stats)"""
+        """(hits, instance ids or None, stats), computed once per batch and semantics word"""
         threads = THREADS if rays.shape[0] > 256 else FEW
-        if self.instanced:
-            return self.osc.trace_rays_inst(rays, sem=sem, threads=threads)
-        hits, st = self.osc.trace_rays(rays, sem=sem, threads=threads)
-        return hits, None, st
+
+        def compute():
+            if self.instanced:
+                return self.osc.trace_rays_inst(rays, sem=sem, threads=threads)
+            hits, st = self.osc.trace_rays(rays, sem=sem, threads=threads)
+            return hits, None, st
+        return self.memo(("rays", sem), (rays,), compute)
 
     def want(self, sem):
         if sem not in self._want:
@@ -149,7 +174,36 @@ class Case:
         return self._frames[key]
 
     def oracle_ao(self, ov, w, h, prim, sem, frame, eps):
-        return self.osc.trace_ao(ov, w, h, prim, sem=sem, frame=frame, ao_eps=eps, threads=FEW)[0]
+        return self.memo(("ao", id(ov), w, h, sem, frame, eps), (prim,),
+                         lambda: self.osc.trace_ao(ov, w, h, prim, sem=sem, frame=frame, ao_eps=eps, threads=FEW)[0])
+
+    def visibility(self, ov, w, h, hits, sem, frame0, n_samples, eps, radius):
+        """The AO visibility twin's counts over `hits` (pixel by pixel in Python: once per frame)."""
+        return self.memo(("vis", id(ov), w, h, sem, frame0, n_samples, eps, radius), (hits,),
+                         lambda: visibility_counts(self.orc, self.osc, ov, w, h, hits, None, sem, frame0, n_samples, eps, radius))
+
+    def close(self):
+        self.sc.close()
+
+
+class PaddedCase:
+    """The padded twin of a single-level case: everything is the base case's - rays, classes, views, the unpadded triangles
+    and every cached oracle answer - but `sc`, the padded scene on the device, which takes the pipelined walk."""
+
+    def __init__(self, base, name):
+        assert not base.instanced and not base.flat.has_tlas
+        self.base, self.name, self.padded = base, name, True
+        self.sc = base.trx.Scene(padded_flat(base.trx, base.flat))
+        self.assert_walks()
+
+    def assert_walks(self):
+        """Asked again by every test that takes the twin (the `cases` fixture): pipelined on the twin, plain on the base
+        scene, in the three modes these tests launch; the primary pass plain on both."""
+        for mode in (self.base.trx.MODE_AO, self.base.trx.MODE_RAYS, self.base.trx.MODE_FUSED):
+            assert_walk_kinds(self.base.trx, self.base.sc, self.sc, mode)
+
+    def __getattr__(self, attr):        # (only what the twin does not hold itself)
+        return getattr(self.base, attr)
 
     def close(self):
         self.sc.close()
@@ -161,7 +215,9 @@ def cases(trx, orc):
 
     def get(name):
         if name not in made:
-            made[name] = Case(trx, orc, name)
+            made[name] = PaddedCase(get(name[:-len("_pipe")]), name) if name.endswith("_pipe") else Case(trx, orc, name)
+        if made[name].padded:
+            made[name].assert_walks()
         return made[name]
     yield get
     trx.load().trx_set_kernel_variant(0)
@@ -250,7 +306,8 @@ def test_hit_attributes_of_the_calls_own_records(cases, trx, name):
 @pytest.mark.parametrize("name", SCENES)
 def test_the_ray_service_and_the_batch_traverse(cases, name):
     """trx_traverse_batch, and trx_traverse1 from 1 and from 8 host threads (the resident ray service, both levels), on
-    600 rays: t bit for bit, primitive / geometry / instance ids as the oracle's records translate."""
+    600 rays: t bit for bit, primitive / geometry / instance ids as the oracle's records translate.  (A padded twin: the
+    batch alone - the ray service takes the plain walk whatever the scene's size.)"""
     c = cases(name)
     rays, cls = c.rays[:600], c.classes[:600]
     flat = c.flat
@@ -259,7 +316,8 @@ def test_the_ray_service_and_the_batch_traverse(cases, name):
         want, winst = want[:600], None if winst is None else winst[:600]
         hit = want["prim"] != MISS
         batch, _ = c.sc.traverse_batch(rays, sem=sem)
-        answers = [("batch", batch)] + [("%d threads" % n, c.sc.traverse_threads(rays, threads=n, sem=sem)[0]) for n in (1, 8)]
+        answers = [("batch", batch)] + [("%d threads" % n, c.sc.traverse_threads(rays, threads=n, sem=sem)[0])
+                                        for n in (() if c.padded else (1, 8))]
         for how, got in answers:
             bad = bits(got["t"]) != bits(want["t"])
             bad |= (got["primitive_id"] == MISS) != ~hit
@@ -317,7 +375,7 @@ def test_a_hostile_neighbour_never_changes_a_tame_rays_record(cases, trx, name, 
     c = cases(name)
     tame = c.rays[c.classes == H.TAME][:256]
     hostile = c.rays[c.classes != H.TAME]
-    _isolation(c, trx, name, sem, tame, hostile, service=True)
+    _isolation(c, trx, name, sem, tame, hostile, service=not c.padded)
     # Beside rays of every class almost every wave holds an out-of-range DIRECTION and divides six times a node step.  The
     # middle path - e * (1/d) kept, (p - o) / d divided: a wave with an out-of-range ORIGIN and no such direction, on a
     # scene that admits both shortcuts (kernels.hip, finish_ray_dir and pow2_exact) - needs neighbours of that kind alone.
@@ -377,7 +435,8 @@ def _primary_dev(c, view, w, h, sem, shard=(0, 1), n=None):
 @pytest.mark.parametrize("name", CAMERA_SCENES)
 def test_primary_ao_and_fused_frames_under_every_hostile_view(cases, name, w, h):
     """trx_trace_primary, trx_trace_primary_ao (AO epsilon 0.01 and 1e-4) and trx_trace_frame_dev, every hostile view,
-    semantics 0, 3 and 4: the oracle's records, pixel for pixel; a switched-off view hits nothing."""
+    semantics 0, 3 and 4: the oracle's records, pixel for pixel; a switched-off view hits nothing.  (A padded twin: the AO
+    passes and the one-launch frame - the bare primary pass is the base case's.)"""
     c = cases(name)
     n = w * h
     px = np.full(n, "pixel")
@@ -385,10 +444,11 @@ def test_primary_ao_and_fused_frames_under_every_hostile_view(cases, name, w, h)
         for sem in (0, 3, 4):
             what = "%s %dx%d %s sem %d" % (name, w, h, vname, sem)
             want, _, _st = c.oracle_primary(ov, w, h, sem)
-            got, _ = c.sc.trace_primary(view, w, h, sem=sem)
-            assert_records(got, want, px, what + " primary")
-            if not H.is_alive(vname):
-                assert (got["prim"] == MISS).all(), what
+            if not c.padded:
+                got, _ = c.sc.trace_primary(view, w, h, sem=sem)
+                assert_records(got, want, px, what + " primary")
+                if not H.is_alive(vname):
+                    assert (got["prim"] == MISS).all(), what
             for frame, eps in ((1, 0.01), (7, 1e-4)):
                 gp, gao, _ = c.sc.trace_primary_ao(view, w, h, sem=sem, frame=frame, ao_eps=eps)
                 wao = c.oracle_ao(ov, w, h, gp, sem, frame, eps)
@@ -402,7 +462,7 @@ def test_primary_ao_and_fused_frames_under_every_hostile_view(cases, name, w, h)
 
 
 @pytest.mark.parametrize("w,h", SIZES)
-@pytest.mark.parametrize("name", CAMERA_SCENES)
+@pytest.mark.parametrize("name", PRIMARY_SCENES)
 def test_batches_mix_hostile_and_tame_views_and_shards_assemble(cases, trx, name, w, h):
     """trx_trace_primary_batch_dev with hostile and tame views in one launch (eight frames a launch, a tame one first and
     fifth): every frame is the oracle's and the tame frames are their single-frame launches'.  trx_trace_primary_dev over
@@ -444,7 +504,8 @@ def test_batches_mix_hostile_and_tame_views_and_shards_assemble(cases, trx, name
 @pytest.mark.parametrize("name", CAMERA_SCENES)
 def test_hit_attributes_and_ao_visibility_over_hostile_primary_frames(cases, name, w, h):
     """trx_hit_attributes_primary_dev against its twin, and trx_trace_ao_visibility_dev with four samples against its
-    twin, both fed the records a primary launch of this test wrote under the same view."""
+    twin, both fed the records a primary launch of this test wrote under the same view.  (A padded twin: the visibility
+    pass, whose any-hit rays launch takes the pipelined walk; the attribute pass walks nothing.)"""
     c = cases(name)
     recs = tri_records(c.flat.tri_verts)
     torch = _torch()
@@ -455,20 +516,21 @@ def test_hit_attributes_and_ao_visibility_over_hostile_primary_frames(cases, nam
             what = "%s %dx%d %s sem %d" % (name, w, h, vname, sem)
             d_hits, d_inst = _primary_dev(c, view, w, h, sem)
             hits = _hits(d_hits)
-            d_attr = torch.full((n * 24,), 0xAB, dtype=torch.uint8, device="cuda")
-            c.sc.hit_attributes_primary_dev(view, w, h, d_hits.data_ptr(), d_attr.data_ptr(), d_inst=d_inst.data_ptr())
-            c.sc.check()
-            attr = d_attr.cpu().numpy().view(c.trx.HIT_ATTR_DTYPE)
-            twin = hit_attrs(recs, primary_origins(view, rec.size), primary_dirs(view, w, h, ppx, ppy), hits["prim"][rec])
-            bad = (attr_bits(attr[rec]) != attr_bits(twin)).any(1)
-            assert not bad.any(), (what, int(bad.sum()), (ppx[bad][:3], ppy[bad][:3]))
+            if not c.padded:
+                d_attr = torch.full((n * 24,), 0xAB, dtype=torch.uint8, device="cuda")
+                c.sc.hit_attributes_primary_dev(view, w, h, d_hits.data_ptr(), d_attr.data_ptr(), d_inst=d_inst.data_ptr())
+                c.sc.check()
+                attr = d_attr.cpu().numpy().view(c.trx.HIT_ATTR_DTYPE)
+                twin = hit_attrs(recs, primary_origins(view, rec.size), primary_dirs(view, w, h, ppx, ppy), hits["prim"][rec])
+                bad = (attr_bits(attr[rec]) != attr_bits(twin)).any(1)
+                assert not bad.any(), (what, int(bad.sum()), (ppx[bad][:3], ppy[bad][:3]))
             if sem == 4 and n > 256:     # (the twin builds its AO rays pixel by pixel in Python: semantics 4 on the two small images)
                 continue
             d_out = torch.full((n,), 0x5A, dtype=torch.uint8, device="cuda")
             c.sc.trace_ao_visibility_dev(view, w, h, d_hits.data_ptr(), d_out.data_ptr(), 4, float("inf"), sem=sem, frame0=3,
                                          ao_eps=0.01, d_primary_inst=d_inst.data_ptr())
             c.sc.check()
-            want = visibility_counts(c.orc, c.osc, ov, w, h, hits, None, sem, 3, 4, 0.01, float("inf"))
+            want = c.visibility(ov, w, h, hits, sem, 3, 4, 0.01, float("inf"))
             assert (d_out.cpu().numpy() == want).all(), what + ": visibility counts"
 
 

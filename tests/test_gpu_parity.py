@@ -1,7 +1,12 @@
 """Parity tests proper: the HIP path, called through the C-ABI, against the oracle.
 
 Bar: bit-exact t (IEEE-754 binary32, same operation order on both sides) and
-exact primitive indices.  Run with `-m gpu` on an MI355X."""
+exact primitive indices.  Run with `-m gpu` on an MI355X.
+
+Cases named *_pipe, and the "pipelined walk" legs inside the tests without parameters, run the same checks on the padded twin
+of the scene (helpers.padded_flat): the same nodes and triangles followed by unreferenced zero records, which the library
+walks with the pipelined kernels (trace_walk_pipe.inc) in every mode but the primary pass.  A twin is compared with the
+oracle's answer for the unpadded scene, computed once and shared with the plain leg (the `once` fixture)."""
 import ctypes as C
 import os
 import threading
@@ -9,7 +14,8 @@ import threading
 import numpy as np
 import pytest
 
-from helpers import (ALL_SEMS, F32_MAX, assert_hits_equal, bits, deep_chain_scene, golden_inputs, make_scene, random_rays)
+from helpers import (ALL_SEMS, F32_MAX, assert_hits_equal, bits, deep_chain_scene, golden_inputs, is_twin, leg_scene, make_scene,
+                     random_rays)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +29,23 @@ def need_gpu(trx):
     buf = C.create_string_buffer(64)
     lib.trx_device_name(0, buf, 64)
     assert buf.value.startswith(b"gfx950"), buf.value
+
+
+@pytest.fixture(scope="module")
+def once():
+    """once(key, compute): compute() the first time `key` is asked for - a scene, its oracle twin and the oracle's answers,
+    shared between the plain leg of a test and the leg on the padded twin, and never modified."""
+    memo = {}
+
+    def get(key, compute):
+        if key not in memo:
+            memo[key] = compute()
+        return memo[key]
+    yield get
+    memo.clear()
+
+
+LEGS = (("plain walk", False), ("pipelined walk", True))
 
 
 class GoldenFlat:
@@ -40,10 +63,13 @@ def load_view(trx, raw):
 
 # ---- golden fixtures -----------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", ["cornell_64", "cornell_tlas_48", "soup_52x44", "box14_tlas_48"])
+@pytest.mark.parametrize("name", ["cornell_64", "cornell_tlas_48", "soup_52x44", "box14_tlas_48", "cornell_64_pipe", "soup_52x44_pipe"])
 def test_golden_images(trx, name):
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    sc = trx.Scene(GoldenFlat(trx, g).flat)
+    """(The twins of the single-level goldens: the AO records, whose pass takes the pipelined walk; the counting primary
+    pass is the base case's.)"""
+    base, padded = is_twin(name)
+    g = np.load(os.path.join(GOLDEN, base + ".npz"))
+    sc = leg_scene(trx, GoldenFlat(trx, g).flat, padded, (trx.MODE_AO,))
     w, h = int(g["width"]), int(g["height"])
     view = load_view(trx, g["view"])
     for sem in (0, 3):
@@ -51,6 +77,8 @@ def test_golden_images(trx, name):
         assert ms > 0
         assert_hits_equal(prim, g["orc_primary_sem%d" % sem], "%s sem %d primary" % (name, sem))
         assert_hits_equal(ao, g["orc_ao_sem%d" % sem], "%s sem %d ao" % (name, sem))
+        if padded:
+            continue
         st = sc.count_primary(view, w, h, sem=sem)
         assert [st.n_node, st.n_tri, st.n_hits, st.max_stack] == list(g["orc_counts_sem%d" % sem])
         assert st.n_rays == w * h and st.overflow == 0
@@ -59,21 +87,24 @@ def test_golden_images(trx, name):
     sc.close()
 
 
-@pytest.mark.parametrize("name,tris", [("hairball", 60000), ("bistro", 150000), ("cornell", 0)])
-def test_thin_waves_a_handful_of_rays_eight_lanes_each(trx, orc, name, tris):
+@pytest.mark.parametrize("name,tris", [("hairball", 60000), ("bistro", 150000), ("cornell", 0), ("hairball_pipe", 60000), ("cornell_pipe", 0)])
+def test_thin_waves_a_handful_of_rays_eight_lanes_each(trx, orc, once, name, tris):
     """A dry wave that is down to eight rays or fewer gives every ray eight lanes (one child of the node each, a leaf's
     triangles eight at a time: kernels.hip, thin_walk).  Batches of 1 ... 100 rays run (almost) wholly that way - a
     64-ray wave goes thin once 56 rays are through - and must equal the oracle bit for bit under all eight semantics,
     closest hit and any hit, with zero direction components, ranged rays and exact ties in the mix; the switch off
-    (variant bit 28) must give the same records."""
-    flat, _view, osc, _ov = make_scene(trx, orc, name, tris, 64, 64)
-    sc = trx.Scene(flat)
+    (variant bit 28) must give the same records.  Batches of 128, 129 and 200 rays are two full waves of one workgroup (and
+    a little more) that run dry together: the second hands its last rays to the first (trace_drain.inc) - on the twins with
+    the pipelined walk's pending triangle group and fetch flag in the parcel."""
+    base, padded = is_twin(name)
+    flat, _view, osc, _ov = once(("scene", base, tris, 64, 64), lambda: make_scene(trx, orc, base, tris, 64, 64))
+    sc = leg_scene(trx, flat, padded, (trx.MODE_RAYS,))
     lib = trx.load()
     try:
-        for n in (1, 2, 3, 7, 8, 9, 13, 64, 65, 100):
+        for n in (1, 2, 3, 7, 8, 9, 13, 64, 65, 100, 128, 129, 200):
             rays = random_rays(trx, flat, n, 1000 + n, zero_dirs=True)
             for sem in ALL_SEMS:
-                want, _ = osc.trace_rays(rays, sem=sem)
+                want, _ = once(("thin", base, tris, n, sem), lambda: osc.trace_rays(rays, sem=sem, threads=2))   # (a handful of rays: no worker per core)
                 got, _ = sc.trace_rays(rays, sem=sem)
                 assert_hits_equal(got, want, "%s %d rays sem %d" % (name, n, sem))
                 if sem in (0, 3):
@@ -90,12 +121,13 @@ def test_thin_waves_a_handful_of_rays_eight_lanes_each(trx, orc, name, tris):
 
 def test_golden_ties_and_zero_directions(trx):
     g = np.load(os.path.join(GOLDEN, "ties_rays.npz"))
-    sc = trx.Scene(GoldenFlat(trx, g).flat)
-    for sem in (0, 3):
-        hits, _ = sc.trace_rays(g["rays"], sem=sem)
-        assert_hits_equal(hits, g["orc_rays_sem%d" % sem], "ties sem %d" % sem)
-        assert (bits(hits["t"]) == bits(g["bf_rays_sem%d" % sem]["t"])).all()
-    sc.close()
+    for leg, padded in LEGS:
+        sc = leg_scene(trx, GoldenFlat(trx, g).flat, padded, (trx.MODE_RAYS,))
+        for sem in (0, 3):
+            hits, _ = sc.trace_rays(g["rays"], sem=sem)
+            assert_hits_equal(hits, g["orc_rays_sem%d" % sem], "ties sem %d, %s" % (sem, leg))
+            assert (bits(hits["t"]) == bits(g["bf_rays_sem%d" % sem]["t"])).all(), leg
+        sc.close()
 
 
 def test_golden_f16_tlas_rays(trx):
@@ -146,23 +178,36 @@ def test_scenes_all_semantics(trx, orc, name, n, w, h, tlas):
 
 
 def test_triangle_formats(trx, orc):
+    """The three triangle record formats a scene can be created from: the primary pass as before, and - the passes that
+    take the pipelined walk on the padded twin, whose zero records are 36, 36 and 24 bytes - the AO pass over it and 4096
+    explicit rays, each format against the oracle over the same records, on the scene and on its twin."""
     flat, view, osc, ov = make_scene(trx, orc, "kitchen", 12000, 96, 64)
     want, _ = osc.trace_primary(ov, 96, 64, sem=0)
-    # f32 {v0,e1,e2} handed over directly
-    edges = osc.tris.copy()
-    sc = trx.Scene(flat, tri_format=trx.TRI_EDGES_36, tri_bytes=edges)
-    assert_hits_equal(sc.trace_primary(view, 96, 64, sem=0)[0], want, "TRI_EDGES_36")
-    sc.close()
+    rays = random_rays(trx, flat, 4096, 17)
+    want_ao, want_rays = osc.trace_ao(ov, 96, 64, want, sem=0, frame=4, ao_eps=0.01)[0], osc.trace_rays(rays, sem=0)[0]
     # the reference's 24-byte f16 triangles (RtCompressedTriangle): parity against the oracle
     # decoding the same bytes; against f32 geometry t moves by ~1e-3 relative (f16 edges)
     packed = trx.pack_tris_f16(flat.tri_verts)
     osc16 = orc.Scene(flat.nodes, tri_f16=packed)
-    sc = trx.Scene(flat, tri_format=trx.TRI_F16_24, tri_bytes=packed)
-    got, _ = sc.trace_primary(view, 96, 64, sem=0)
-    assert_hits_equal(got, osc16.trace_primary(ov, 96, 64, sem=0)[0], "TRI_F16_24")
-    both = np.isfinite(got["t"]) & np.isfinite(want["t"])
-    assert both.mean() > 0.9 and np.median(np.abs(got["t"][both] - want["t"][both]) / want["t"][both]) < 5e-3
-    sc.close()
+    want16 = osc16.trace_primary(ov, 96, 64, sem=0)[0]
+    want16_ao, want16_rays = osc16.trace_ao(ov, 96, 64, want16, sem=0, frame=4, ao_eps=0.01)[0], osc16.trace_rays(rays, sem=0)[0]
+    edges = osc.tris.copy()     # f32 {v0,e1,e2} handed over directly
+    for leg, padded in LEGS:
+        for what, fmt, records, (wp, wa, wr) in (("TRI_VERTS_36", trx.TRI_VERTS_36, flat.tri_verts, (want, want_ao, want_rays)),
+                                                 ("TRI_EDGES_36", trx.TRI_EDGES_36, edges, (want, want_ao, want_rays)),
+                                                 ("TRI_F16_24", trx.TRI_F16_24, packed, (want16, want16_ao, want16_rays))):
+            what = "%s, %s" % (what, leg)
+            sc = leg_scene(trx, flat, padded, (trx.MODE_AO, trx.MODE_RAYS), tri_format=fmt, tri_bytes=records)
+            got, _ = sc.trace_primary(view, 96, 64, sem=0)
+            assert_hits_equal(got, wp, what)
+            gp, gao, _ = sc.trace_primary_ao(view, 96, 64, sem=0, frame=4, ao_eps=0.01)
+            assert_hits_equal(gp, wp, what + " primary of primary_ao")
+            assert_hits_equal(gao, wa, what + " ao")
+            assert_hits_equal(sc.trace_rays(rays, sem=0)[0], wr, what + " rays")
+            if fmt == trx.TRI_F16_24:
+                both = np.isfinite(got["t"]) & np.isfinite(want["t"])
+                assert both.mean() > 0.9 and np.median(np.abs(got["t"][both] - want["t"][both]) / want["t"][both]) < 5e-3
+            sc.close()
 
 
 # ---- shards, layouts, odd sizes ------------------------------------------------------------------
@@ -233,17 +278,19 @@ def test_shards_and_layouts(trx, orc):
 
 
 @pytest.mark.parametrize("name,tris,tlas,w,h", [("kitchen", 20000, False, 100, 52), ("cornell", 0, False, 33, 47),
-                                               ("san_miguel", 60000, True, 120, 72), ("bistro", 400000, False, 256, 144)])
-def test_ao_batch_is_n_separate_ao_passes(trx, orc, name, tris, tlas, w, h):
+                                               ("san_miguel", 60000, True, 120, 72), ("bistro", 400000, False, 256, 144),
+                                               ("kitchen_pipe", 20000, False, 100, 52), ("cornell_pipe", 0, False, 33, 47)])
+def test_ao_batch_is_n_separate_ao_passes(trx, orc, once, name, tris, tlas, w, h):
     """trx_trace_ao_batch_dev (BASELINE.json configs[3]'s "4 spp" = AO frames with seeds frame0 .. frame0 + n - 1 over
     one view and one primary hit buffer, as ONE launch): every frame of the batch equals the oracle's AO pass with that
     seed, bit for bit; n = 2, 3, 4, 8, image sizes whose tile count is not a multiple of eight (the queues are padded),
     a two-level scene, and a compact tile shard."""
     import torch
     from tray_racing_amd import dist as D
-    flat, view, osc, ov = make_scene(trx, orc, name, tris, w, h, tlas=tlas)
-    sc = trx.Scene(flat)
-    op, _ = osc.trace_primary(ov, w, h, sem=3)
+    base, padded = is_twin(name)
+    flat, view, osc, ov = once(("scene", base, tris, w, h, tlas), lambda: make_scene(trx, orc, base, tris, w, h, tlas=tlas))
+    sc = leg_scene(trx, flat, padded, (trx.MODE_AO,))
+    op, _ = once(("primary", base, tris, w, h, tlas, 3), lambda: osc.trace_primary(ov, w, h, sem=3))
     d_prim = torch.empty(w * h, dtype=torch.int64, device="cuda")
     sc.trace_primary_dev(view, w, h, d_prim.data_ptr(), sem=3)
     for n, frame0 in ((2, 0), (3, 7), (4, 0), (8, 1021)):
@@ -253,7 +300,8 @@ def test_ao_batch_is_n_separate_ao_passes(trx, orc, name, tris, tlas, w, h):
         torch.cuda.synchronize()
         sc.check()
         for f in range(n):
-            want, _ = osc.trace_ao(ov, w, h, op, sem=3, frame=frame0 + f, ao_eps=0.01)
+            want, _ = once(("ao", base, tris, w, h, tlas, 3, frame0 + f, 0.01),
+                           lambda: osc.trace_ao(ov, w, h, op, sem=3, frame=frame0 + f, ao_eps=0.01))
             assert_hits_equal(D.int64_to_hits(d_ao[f * stride: f * stride + w * h]), want, "%s ao batch of %d, frame %d" % (name, n, f))
             assert bool((d_ao[f * stride + w * h: (f + 1) * stride] == -1).all())    # nothing written between frames
     # a compact tile shard: rank 1 of 3 traces its tiles of the primary frame and of a 4-frame AO batch
@@ -276,22 +324,24 @@ def test_ao_batch_is_n_separate_ao_passes(trx, orc, name, tris, tlas, w, h):
 
 @pytest.mark.parametrize("name,tris,tlas,w,h", [("kitchen", 20000, False, 100, 52), ("cornell", 0, False, 33, 47),
                                                ("san_miguel", 60000, True, 120, 72), ("bistro", 400000, False, 256, 144),
-                                               ("hairball", 100000, False, 160, 96)])
-def test_one_launch_frame_is_the_two_pass_frame(trx, orc, name, tris, tlas, w, h):
+                                               ("hairball", 100000, False, 160, 96),
+                                               ("kitchen_pipe", 20000, False, 100, 52), ("cornell_pipe", 0, False, 33, 47)])
+def test_one_launch_frame_is_the_two_pass_frame(trx, orc, once, name, tris, tlas, w, h):
     """trx_trace_frame_dev (the reference's single dispatch, rt_gpu_software.hlsl:47-144: a lane whose primary ray hits
     goes on as the pixel's AO ray): the primary and the AO records are the oracle's, bit for bit, under both semantics
     presets, for every refill / conversion threshold, in image layout and in a compact tile shard."""
     import torch
     from tray_racing_amd import dist as D
-    flat, view, osc, ov = make_scene(trx, orc, name, tris, w, h, tlas=tlas)
-    sc = trx.Scene(flat)
+    base, padded = is_twin(name)
+    flat, view, osc, ov = once(("scene", base, tris, w, h, tlas), lambda: make_scene(trx, orc, base, tris, w, h, tlas=tlas))
+    sc = leg_scene(trx, flat, padded, (trx.MODE_FUSED, trx.MODE_AO))
     lib = trx.load()
     d_p = torch.empty(w * h, dtype=torch.int64, device="cuda")
     d_a = torch.empty(w * h, dtype=torch.int64, device="cuda")
     try:
         for sem, frame, eps in ((3, 0, 0.01), (0, 5, 0.0001)):
-            op, _ = osc.trace_primary(ov, w, h, sem=sem)
-            oa, _ = osc.trace_ao(ov, w, h, op, sem=sem, frame=frame, ao_eps=eps)
+            op, _ = once(("primary", base, tris, w, h, tlas, sem), lambda: osc.trace_primary(ov, w, h, sem=sem))
+            oa, _ = once(("ao", base, tris, w, h, tlas, sem, frame, eps), lambda: osc.trace_ao(ov, w, h, op, sem=sem, frame=frame, ao_eps=eps))
             for variant in (0, 64, 1, 24 | (1 << 14), 48 | (3 << 14)):
                 lib.trx_set_kernel_variant(variant)
                 d_p.fill_(-1)
@@ -375,13 +425,15 @@ def test_degenerate_triangles_and_ray_ranges(trx, orc):
     rays["direction"] = [(0, 0, -1)] * 6 + [(0, 0, 1), (0, 0, -1), (0, 0, -1)]
     rays["tmin"] = [0, 5.0, 5.5, 0, 0, 0, 0, 0, 0]
     rays["tmax"] = [F32_MAX, F32_MAX, F32_MAX, 4.9, np.inf, F32_MAX, F32_MAX, F32_MAX, F32_MAX]
-    sc = trx.Scene(flat)
-    for sem in (0, 3):
-        got, _ = sc.trace_rays(rays, sem=sem)
-        assert_hits_equal(got, osc.trace_rays(rays, sem=sem)[0], "degenerate sem %d" % sem)
-    assert got["t"][0] == 5.0 and got["t"][1] == 5.0 and np.isinf(got["t"][2]) and np.isinf(got["t"][3])
-    assert np.isinf(got["t"][8]) and got["prim"][8] == 0xFFFFFFFF
-    sc.close()
+    want = {sem: osc.trace_rays(rays, sem=sem)[0] for sem in (0, 3)}
+    for leg, padded in LEGS:
+        sc = leg_scene(trx, flat, padded, (trx.MODE_RAYS,))
+        for sem in (0, 3):
+            got, _ = sc.trace_rays(rays, sem=sem)
+            assert_hits_equal(got, want[sem], "degenerate sem %d, %s" % (sem, leg))
+        assert got["t"][0] == 5.0 and got["t"][1] == 5.0 and np.isinf(got["t"][2]) and np.isinf(got["t"][3]), leg
+        assert np.isinf(got["t"][8]) and got["prim"][8] == 0xFFFFFFFF, leg
+        sc.close()
 
 
 def test_any_hit_query_equals_closest_hit_occupancy(trx, orc):
@@ -390,20 +442,26 @@ def test_any_hit_query_equals_closest_hit_occupancy(trx, orc):
     import torch
     for name, n, tlas in (("kitchen", 30000, False), ("bistro", 60000, True), ("hairball", 50000, False)):
         flat, _view, osc, _ov = make_scene(trx, orc, name, n, 32, 32, tlas=tlas)
-        sc = trx.Scene(flat)
-        rays = random_rays(trx, flat, 40000, 11)
-        for sem in (0, 3, 5, 6):
-            want = osc.trace_rays(rays, sem=sem)[0]["prim"] != trx.MISS_PRIM
-            flags, ms = sc.trace_occluded(rays, sem=sem)
-            assert ms > 0 and set(np.unique(flags)) <= {0, 1}
-            assert (flags.astype(bool) == want).all(), (name, sem, int((flags.astype(bool) != want).sum()))
-            assert 0.02 < want.mean() < 0.99
-        d_rays = torch.from_numpy(rays.view(np.uint8).reshape(-1)).cuda()
-        d_flags = torch.full((rays.shape[0] + 8,), 7, dtype=torch.uint8, device="cuda")
-        sc.trace_occluded_dev(d_rays.data_ptr(), rays.shape[0], d_flags.data_ptr(), sem=3)
-        sc.check()
-        assert (d_flags[:rays.shape[0]].cpu().numpy() == flags_for(sc, rays, 3)).all() and (d_flags[rays.shape[0]:] == 7).all()
-        sc.close()
+        all_rays = random_rays(trx, flat, 40000, 11)
+        all_want = {sem: osc.trace_rays(all_rays, sem=sem)[0]["prim"] != trx.MISS_PRIM for sem in (0, 3, 5, 6)}
+        # (the single-level scenes again on their padded twins: the first 4096 of the rays, an any-hit exit of the pipelined
+        # walk drops a fetch in flight)
+        for leg, padded in LEGS[:1] if tlas else LEGS:
+            sc = leg_scene(trx, flat, padded, (trx.MODE_RAYS,))
+            rays = all_rays[:4096] if padded else all_rays
+            for sem in (0, 3, 5, 6):
+                want = all_want[sem][:rays.shape[0]]
+                flags, ms = sc.trace_occluded(rays, sem=sem)
+                assert ms > 0 and set(np.unique(flags)) <= {0, 1}
+                assert (flags.astype(bool) == want).all(), (name, leg, sem, int((flags.astype(bool) != want).sum()))
+                assert 0.02 < want.mean() < 0.99
+            d_rays = torch.from_numpy(rays.view(np.uint8).reshape(-1).copy()).cuda()
+            d_flags = torch.full((rays.shape[0] + 8,), 7, dtype=torch.uint8, device="cuda")
+            sc.trace_occluded_dev(d_rays.data_ptr(), rays.shape[0], d_flags.data_ptr(), sem=3)
+            sc.check()
+            assert (d_flags[:rays.shape[0]].cpu().numpy() == flags_for(sc, rays, 3)).all() and (d_flags[rays.shape[0]:] == 7).all(), (name, leg)
+            assert (flags_for(sc, rays, 3).astype(bool) == all_want[3][:rays.shape[0]]).all(), (name, leg)
+            sc.close()
 
 
 def flags_for(sc, rays, sem):
@@ -425,18 +483,22 @@ def test_stack_spill_to_hbm_and_overflow_detection(trx, orc):
         osc = orc.Scene(nodes, tris)
         want, ost = osc.trace_rays(rays, sem=0)
         assert ost.overflow == 0 and ost.max_stack == depth - 1
-        sc = trx.Scene(flat)
-        got, _ = sc.trace_rays(rays, sem=0)
-        assert_hits_equal(got, want, "depth %d" % depth)
-        assert got["t"][0] == 1.0 and got["prim"][0] == 0
-        sc.close()
+        for leg, padded in LEGS:
+            sc = leg_scene(trx, flat, padded, (trx.MODE_RAYS,))
+            got, _ = sc.trace_rays(rays, sem=0)
+            assert_hits_equal(got, want, "depth %d, %s" % (depth, leg))
+            assert got["t"][0] == 1.0 and got["prim"][0] == 0, leg
+            sc.close()
     nodes, tris = deep_chain_scene(70)
-    sc = trx.Scene(trx.FlatScene(nodes, tris, [], 0, np.arange(70), [0, 70]))
-    with pytest.raises(trx.TrxError) as e:
-        sc.trace_rays(rays, sem=0)
-    assert e.value.code == -4 and "overflowed" in str(e.value)
-    got, _ = sc.trace_rays(rays[1:2], sem=0)  # the scene stays usable; the flag was cleared
-    sc.close()
+    one_want, _ = orc.Scene(nodes, tris).trace_rays(rays[1:2], sem=0)
+    for leg, padded in LEGS:     # (the pipelined walk has an overflow path of its own: "past the last entry: finish")
+        sc = leg_scene(trx, trx.FlatScene(nodes, tris, [], 0, np.arange(70), [0, 70]), padded, (trx.MODE_RAYS,))
+        with pytest.raises(trx.TrxError) as e:
+            sc.trace_rays(rays, sem=0)
+        assert e.value.code == -4 and "overflowed" in str(e.value), leg
+        got, _ = sc.trace_rays(rays[1:2], sem=0)  # the scene stays usable; the flag was cleared
+        assert_hits_equal(got, one_want, "one ray after the overflow, %s" % leg)
+        sc.close()
 
 
 def test_the_ray_service_walks_deep_stacks_and_reports_overflow_per_call(trx, orc):
@@ -641,6 +703,11 @@ def test_traverse_batch_is_traverse_for_every_ray(trx, orc):
         empty, _ = sc.traverse_batch(rays[:0], sem=3)
         assert empty.shape[0] == 0
         sc.close()
+        if not tlas:    # the batch again on the padded twin (the pipelined walk; trx_traverse1 never takes it)
+            sc = leg_scene(trx, flat, True, (trx.MODE_RAYS,))
+            twin, _ = sc.traverse_batch(rays, sem=3)
+            assert twin.tobytes() == got.tobytes(), "trx_traverse_batch on the padded twin"
+            sc.close()
 
 
 def test_bench_primary_times_what_hip_events_around_the_same_launches_see(trx, orc):

@@ -37,6 +37,9 @@ HEAT_NODES = 0
 HEAT_TRIS = 1
 HEAT_SCALE_NODES = 0.002
 HEAT_SCALE_TRIS = 0.01
+# trace modes as trx_debug_walk_kind numbers them
+MODE_PRIMARY, MODE_AO, MODE_RAYS, MODE_FUSED, MODE_SERVICE = 0, 1, 2, 3, 4
+WALK_PLAIN, WALK_PIPELINED = 0, 1
 
 
 class TrxError(RuntimeError):
@@ -183,6 +186,7 @@ SIGNATURES = {
     "trx_traverse1": (_i, [_P, C.POINTER(Ray), _u32, C.POINTER(RayHit)]),
     "trx_debug_traverse1_stats": (_i, [_P, C.POINTER(_u64), C.POINTER(_u64)]),
     "trx_debug_scene_info": (_i, [_P, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_u32)]),
+    "trx_debug_walk_kind": (_i, [_P, _u32]),
     "trx_debug_fetch_rate": (_i, [_P, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "trx_debug_copy_rate": (_i, [_i, _u64, _u32, C.POINTER(C.c_double)]),
     "trx_debug_service_stats": (_i, [_P] + [C.POINTER(_u64)] * 5),

@@ -225,6 +225,8 @@ int enqueue(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool coun
 // ... the same for a caller that holds s->mu and has set the device and checked `sem` (a pass of several launches on one slot)
 int enqueue_locked(trx_scene *s, trx::TraceParams &p, int mode, uint32_t sem, bool count, hipStream_t stream, trx::SlotCounters **ctr_out);
 // an image pass's kernel parameters: p zeroed, then the geometry of `view` / w x h / shard
+// whether a launch of `mode` on the scene takes the pipelined walk (api_launch.cpp); the shipped decision, no tuning bits
+bool pipelined_walk(const trx_scene *s, int mode);
 int image_params(trx::TraceParams &p, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard);
 int read_overflow(trx_scene *s, trx::SlotCounters *ctr);
 // structural validation of an untrusted node buffer (api.cpp): every index a walk can form is in range

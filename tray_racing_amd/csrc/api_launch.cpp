@@ -65,6 +65,19 @@ int acquire_slot(trx_scene *s, hipStream_t stream, Slot *&out) {
     return TRX_OK;
 }
 
+// The pipelined walk (next node's fetch issued under the triangle phase) pays where a node fetch leaves the L2s:
+// incoherent passes over scenes larger than the eight L2s together (measured: hairball-class AO -4..-6 %, dense
+// bistro-class -3 %, a 3 MB kitchen-class scene +4 %; coherent primary rays +-1 %: DESIGN.md section 4).
+#ifndef TRX_PIPE_MIN_BYTES
+#define TRX_PIPE_MIN_BYTES (32ull << 20) // (tuning builds: 0 = always)
+#endif
+// Which walk a launch of `mode` takes on this scene: the one decision, asked by enqueue_locked and by trx_debug_walk_kind.
+// The primary pass and the ray service always take the plain walk, and so does every pass over a two-level scene.
+bool pipelined_walk(const trx_scene *s, int mode) {
+    return mode != kModePrimary && mode != kModeService && !s->tlas &&
+           s->n_nodes * TRX_NODE_BYTES + s->n_tris * sizeof(TriDev) >= (size_t)TRX_PIPE_MIN_BYTES + 1u;
+}
+
 // Enqueue one traversal kernel on a launch slot.  Slots make the scene
 // re-entrant (Traversable requires Sync, src/rt_cpu/rt_cpu.rs:17-20): a slot is
 // reused only after the stream has waited for its previous kernel.
@@ -279,18 +292,11 @@ int enqueue_locked(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool co
         p.cost = s->dbg_cost;
         p.tile_iters = s->dbg_iters;
     }
-    // The pipelined walk (next node's fetch issued under the triangle phase) pays where a node fetch leaves the L2s:
-    // incoherent passes over scenes larger than the eight L2s together (measured: hairball-class AO -4..-6 %, dense
-    // bistro-class -3 %, a 3 MB kitchen-class scene +4 %; coherent primary rays +-1 %: DESIGN.md section 4).
-#ifndef TRX_PIPE_MIN_BYTES
-#define TRX_PIPE_MIN_BYTES (32ull << 20) // (tuning builds: 0 = always)
-#endif
-    bool pipe = mode != kModePrimary && !s->tlas && s->n_nodes * TRX_NODE_BYTES + s->n_tris * sizeof(TriDev) >= (size_t)TRX_PIPE_MIN_BYTES + 1u;
+    bool pipe = pipelined_walk(s, mode);
 #ifdef TRX_DEV_TUNE
-    if (p.tune & 0x1000u) pipe = true;
+    if ((p.tune & 0x1000u) && mode != kModeService) pipe = true; // (the ray service has no pipelined instantiation)
     if (p.tune & 0x10000u) pipe = false;
 #endif
-    if (mode == kModeService) pipe = false;
     if (count && (s->count_cost || slot.ray_cost_set)) {
         // where the counting kernel puts its per-ray counts (SlotCounters::ray_cost), or null again after a call that had
         // some: a blocking copy on the null stream, which counting passes run on (count_pass), behind the slot's set-up
@@ -348,3 +354,9 @@ int read_overflow(trx_scene *s, SlotCounters *ctr) {
 }
 
 } // namespace trxapi
+
+extern "C" int trx_debug_walk_kind(trx_scene *s, uint32_t mode) {
+    if (!s) return trxapi::fail(TRX_ERR_INVALID, "null scene");
+    if (mode > (uint32_t)trx::kModeService) return trxapi::fail(TRX_ERR_INVALID, "unknown trace mode %u", mode);
+    return trxapi::pipelined_walk(s, (int)mode) ? 1 : 0; // (the scene's sizes and levels are fixed at creation: no lock)
+}

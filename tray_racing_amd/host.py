@@ -378,6 +378,14 @@ class Scene:
         L.check(self._lib.trx_debug_scene_info(self._h, C.byref(e), C.byref(d), C.byref(lv)))
         return {"exp_exact": e.value, "scene_diag": d.value, "refit_levels": lv.value}
 
+    def walk_kind(self, mode):
+        """L.WALK_PLAIN or L.WALK_PIPELINED: the walk the library launches for trace mode `mode` (L.MODE_PRIMARY, MODE_AO,
+        MODE_RAYS, MODE_FUSED, MODE_SERVICE) on this scene (trx_debug_walk_kind)."""
+        kind = self._lib.trx_debug_walk_kind(self._h, mode)
+        if kind < 0:
+            L.check(kind)
+        return kind
+
     def read_nodes(self):
         """[n_nodes, 20] u32: the node buffer as the kernels now see it (trx_scene_read_nodes)."""
         out = np.empty((self.flat.n_nodes, 20), dtype=np.uint32)
