@@ -647,6 +647,100 @@ int trx_render_image_sparse(trx_scene *scene, const trx_view *view, uint32_t wid
                             uint32_t ao_phase, uint32_t upsample_radius, float depth_tol, float normal_cos,
                             uint8_t *out_rgba, float *out_ms);
 
+/* ---- direct light: masked shadow rays, the light term, the lit image ------------------------------------------------------
+ * "Is this point lit": per pixel and light, shadow rays from the primary hit toward the light, walked by the any-hit rays
+ * launch of trx_trace_occluded*_dev - with a ray mask, so that an instance can cast no shadow (trx_scene_set_instance_masks) -
+ * then the usual split of direct lighting: the unshadowed analytic term times the traced visibility.  Intensities are
+ * scalars: the image stays the reference's grey image.
+ *
+ * A light.  kind DIRECTIONAL: position = the direction TOWARD the light, any non-zero length.  POINT: position.  RECT:
+ * position = a corner, the light is corner + u * edge1 + v * edge2, u, v in [0, 1].  _pad must be 0, every float finite. */
+#define TRX_LIGHT_DIRECTIONAL 0u
+#define TRX_LIGHT_POINT 1u
+#define TRX_LIGHT_RECT 2u
+#define TRX_MAX_LIGHTS 8
+typedef struct trx_light {
+    uint32_t kind;
+    float position[3];
+    float edge1[3];
+    float edge2[3];
+    float intensity;
+    uint32_t _pad[5];
+} trx_light;
+/* THE SHADOW RAY of (pixel (px, py), light k, sample f).  Every operation is rounded once in binary32, no contraction;
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *  - A pixel is a SURFACE pixel iff its primary record has t < FLT_MAX and prim != 0xFFFFFFFF (the AO pass's and the
+ *    filter's rule).  Any other pixel gets the INERT ray of trx_ao_rays_dev: all words 0 except tmax = -1.0f.
+ *  - d = the pixel's primary direction.  n = the hit triangle's geometric normal as trx_hit_attr.normal has it (the
+ *    record's cross(e1, e2), through the instance's rows on a scene with instance transforms - d_primary_inst is REQUIRED
+ *    there - times 1.0f / sqrtf(dot3(ng, ng))), flipped toward the viewer: n *= sg,
+ *    sg = copysignf(1.0f, (n.x*-d.x + n.y*-d.y) + n.z*-d.z).
+ *  - Origin: o[i] = (eye[i] + d[i]*t) - d[i]*shadow_eps.
+ *  - Light point L: POINT: position.  RECT: u1 = hash_noise(px, py, seed), u2 = hash_noise(px, py, seed + 1024u) with
+ *    seed = frame0 + k*64u + f and the AO ray's hash, L[i] = (position[i] + u1*edge1[i]) + u2*edge2[i].
+ *  - POINT, RECT: v = L - o, q = dot3(v, v), dist = sqrtf(q), inv = 1.0f / dist, l = v * inv, tmax = fminf(dist, FLT_MAX).
+ *    DIRECTIONAL: l = position * (1.0f / sqrtf(dot3(position, position))), tmax = FLT_MAX.  tmin = 0 either way.
+ *  - Facing: c = dot3(n, l).  If !(c > 0.0f) the sample gets the inert ray and counts as NOT LIT: a light behind the
+ *    surface, a light at the hit point (dist == 0 gives NaN), any NaN.
+ *
+ * trx_light_rays_dev writes the shadow rays of ONE light (`light`, whose index among the pass's lights is light_index) and
+ * ONE sample as explicit rays: one trx_ray per record, laid out by `shard` exactly as for trx_ao_rays_dev; records outside
+ * the shard or the image are left untouched.  Refused (TRX_ERR_INVALID, nothing enqueued): what the pass below refuses of
+ * a light, light_index >= TRX_MAX_LIGHTS, sample >= TRX_MAX_AO_SAMPLES, a bad shadow_eps, null buffers, a missing
+ * d_primary_inst on a scene with instance transforms. */
+int trx_light_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                       const trx_light *light, uint32_t light_index, uint32_t frame0, uint32_t sample, float shadow_eps,
+                       const trx_hit *d_primary, const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream);
+/* The light visibility pass.  d_lit holds n_lights planes of `records` bytes, plane k at k * records, each laid out like
+ * the hit buffers for `shard` (records = width * height in image layout, trx_shard_tiles() * 64 in TRX_LAYOUT_SHARD).  In
+ * plane k a surface pixel gets the number of samples whose shadow ray toward light k was cast (not inert) and is NOT
+ * occluded - "occluded" is what trx_trace_occluded_dev answers for that ray, with ray_mask != 0 what
+ * trx_trace_occluded_masked_dev answers; a pixel without a surface gets TRX_AO_NO_SURFACE; records outside the shard or
+ * the image are untouched.  POINT and DIRECTIONAL lights have one ray per pixel: it is traced once and their plane holds
+ * 0 or 1 whatever n_samples is.  RECT lights take n_samples (1..TRX_MAX_AO_SAMPLES) samples f = 0..n_samples-1.
+ * ray_mask 0: the unmasked launch, the instance mask table is not read; 1..255: the masked launch - an instance with
+ * (mask & ray_mask) == 0 casts no shadow (on a single-level scene and on a scene without a table: the unmasked answer).
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): n_lights outside
+ * 1..TRX_MAX_LIGHTS, an unknown kind, non-zero _pad, any non-finite light field, a directional light of zero length,
+ * n_samples out of range, ray_mask > 255, shadow_eps NaN or negative, unknown semantics bits, null buffers, a missing
+ * d_primary_inst on a scene with instance transforms.
+ * Mechanics, stream and ordering are trx_trace_ao_visibility_dev's, once per light: the same launch slot's scratch
+ * ([tile][sample][64]) under the same cap, the same chunk loops, no host synchronisation; a trx_scene_refit* called after
+ * this call has returned waits for the pass. */
+int trx_trace_light_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                   trx_shard shard, uint32_t semantics, uint32_t ray_mask, const trx_light *lights,
+                                   uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float shadow_eps,
+                                   const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_lit, void *stream);
+/* The light term: one float per record at d_value, laid out by `shard` like the other record buffers (d_primary, d_attr,
+ * d_term and every plane of d_lit - planes at k * records as above - share that layout).  A pixel without a surface gets
+ * 0.0f.  A surface pixel: n = d_attr.normal * sg (sg as above), P[i] = eye[i] + d[i]*t, E = ambient * a with a = 1.0f
+ * when d_term is NULL, otherwise a = samples == 0 ? 0.0f : (float)unoccluded / (float)samples.  Then for k ascending:
+ *   DIRECTIONAL  g = dot3(n, l), l as above.
+ *   POINT, RECT  C = position (POINT) or C[i] = (position[i] + 0.5f*edge1[i]) + 0.5f*edge2[i] (RECT); v = C - P,
+ *                q = dot3(v, v), inv = 1.0f / sqrtf(q), g = dot3(n, v*inv) / q.
+ *   if g > 0.0f: E = E + (intensity_k * g) * ((float)count_k / (float)N_k), N_k = n_samples for a RECT light and 1
+ *   otherwise, count_k = plane k's byte, TRX_AO_NO_SURFACE taken as 0.
+ * Every operation rounded once in binary32, no contraction.  Refused (TRX_ERR_INVALID): what the visibility pass refuses of
+ * lights, n_lights and n_samples, a non-finite ambient, null scene, view, d_primary, d_attr, d_lit or d_value. */
+int trx_light_term_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                       const trx_light *lights, uint32_t n_lights, uint32_t n_samples, const trx_hit *d_primary,
+                       const trx_hit_attr *d_attr, const uint8_t *d_lit, const trx_ao_term *d_term, float ambient,
+                       float *d_value, void *stream);
+/* Shading of float values to RGBA8: elementwise over n_records values in any layout, {c, c, c, 255} with c the code of the
+ * value exactly as the other shades derive it (0 for negative or NaN, 255 for >= 1).  Refusals as for the other shades. */
+int trx_shade_value_dev(trx_scene *scene, const float *d_value, uint64_t n_records, uint8_t *d_rgba, void *stream);
+/* Host-buffer form for a whole image (synchronous, like trx_render_image): the primary pass, the attribute pass, the light
+ * visibility pass (ray_mask, frame0, light_samples, shadow_eps), the light term and the value shade; with ao_samples >= 1
+ * also the AO visibility pass (seeds frame0 .., ao_eps, ao_radius) and the filter at filter_radius (0..4, with normals),
+ * whose term scales `ambient`; with ao_samples == 0 the ambient is unoccluded (ao_eps .. normal_cos are not looked at).
+ * 4 bytes per pixel are copied back (out_rgba may be NULL), out_ms as for trx_render_image.  Every argument is validated
+ * before the first pass is enqueued. */
+int trx_render_image_lit(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                         uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                         uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                         float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos, uint8_t *out_rgba,
+                         float *out_ms);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,

@@ -96,6 +96,11 @@ int trx_debug_ao_visibility_phases(trx_scene *scene, const trx_view *view, uint3
                                    uint32_t semantics, uint32_t frame0, uint32_t n_samples, float ao_eps, float ao_radius,
                                    const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_unoccluded,
                                    float out_ms[3]);
+/* The same for one whole-image trx_trace_light_visibility_dev pass; out_ms summed over the lights and their chunks. */
+int trx_debug_light_visibility_phases(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                      uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
+                                      uint32_t frame0, uint32_t n_samples, float shadow_eps, const trx_hit *d_primary,
+                                      const uint32_t *d_primary_inst, uint8_t *d_lit, float out_ms[3]);
 
 /* Kernel variant selection (tuning aid; 0 = default).  Returns the previous
  * value.  Variants compute identical results. */

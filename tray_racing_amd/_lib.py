@@ -33,6 +33,8 @@ AO_NO_SURFACE = 0xFF
 MAX_AO_FILTER_RADIUS = 4
 MAX_AO_STRIDE = 4
 MAX_AO_UPSAMPLE_RADIUS = 2
+LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_RECT = 0, 1, 2
+MAX_LIGHTS = 8
 HEAT_NODES = 0
 HEAT_TRIS = 1
 HEAT_SCALE_NODES = 0.002
@@ -69,6 +71,13 @@ class HitAttr(C.Structure):
 class AoTerm(C.Structure):
     """trx_ao_term: the filtered AO term of a pixel - unoccluded samples over samples of the accepted window pixels."""
     _fields_ = [("unoccluded", C.c_uint16), ("samples", C.c_uint16)]
+
+
+class Light(C.Structure):
+    """trx_light: a directional (position = the direction toward it), point or rect (corner + u * edge1 + v * edge2) light of
+    scalar intensity; 64 bytes, _pad must be 0."""
+    _fields_ = [("kind", C.c_uint32), ("position", C.c_float * 3), ("edge1", C.c_float * 3), ("edge2", C.c_float * 3),
+                ("intensity", C.c_float), ("_pad", C.c_uint32 * 5)]
 
 
 class RayCost(C.Structure):
@@ -164,6 +173,14 @@ SIGNATURES = {
     "trx_shade_ao_counts_dev": (_i, [_P, _P, _u32, _u64, _P, _P]),
     "trx_shade_ao_term_dev": (_i, [_P, _P, _u64, _P, _P]),
     "trx_render_image": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _P, C.POINTER(_f)]),
+    "trx_light_rays_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, C.POINTER(Light), _u32, _u32, _u32, _f, _P, _P, _P, _P]),
+    "trx_trace_light_visibility_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _P, _u32, _u32, _u32, _f, _P, _P, _P, _P]),
+    "trx_light_term_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _P, _u32, _u32, _P, _P, _P, _P, _f, _P, _P]),
+    "trx_shade_value_dev": (_i, [_P, _P, _u64, _P, _P]),
+    "trx_render_image_lit": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32, _f, _f,
+                                  _P, C.POINTER(_f)]),
+    "trx_debug_light_visibility_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _P, _P, _P,
+                                               C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),
     "trx_debug_ao_visibility_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, _P, _P,
                                             C.POINTER(_f)]),

@@ -147,7 +147,126 @@ int visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, 
     return TRX_OK;
 }
 
+
+// ---- direct light (include/trx.h, "direct light"): the pass above once per light, with a ray mask ----------------------------
+
+int check_eps(float shadow_eps) {
+    if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
+    return TRX_OK;
+}
+
+void light_scene(LightRaysParams &g, const trx_scene *s, const trx_hit *d_primary, const uint32_t *d_primary_inst) {
+    g.tris = s->tris.get();
+    g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
+    g.primary = d_primary;
+    g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+}
+
+// visibility_impl's sibling: its chunk loops and slot bookkeeping statement for statement, per light, with k_light_rays /
+// k_light_reduce around the rays launch and p.ray_mask set.  The AO pass's own path is left as it was.
+int light_visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
+                          const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float shadow_eps,
+                          const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_lit, hipStream_t stream, Phases *phases) {
+    if (!s || !d_primary || !d_lit) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
+    if (int rc = check_eps(shadow_eps)) return rc;
+    AoRaysParams geom;
+    uint32_t tiles = 0;
+    if (int rc = ao_geometry(geom, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    if (tiles == 0) return TRX_OK;
+    const uint64_t records = geom.geom.compact ? (uint64_t)tiles * 64u : (uint64_t)w * h;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, stream, slot)) return rc;
+    LightRaysParams g;
+    std::memset(&g, 0, sizeof(g));
+    g.geom = geom.geom;
+    g.view = geom.view;
+    light_scene(g, s, d_primary, d_primary_inst);
+    g.scratch = 1u;
+    g.shadow_eps = shadow_eps;
+    // chunks: as many tiles as the scratch holds, and for them as many samples as it holds; the scratch is sized once, for the
+    // light with the most samples
+    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / kAoUnitBytes, 1), 1ull << 24);
+    const uint32_t tile_chunk = (uint32_t)std::min<uint64_t>(tiles, units);
+    auto samples_of = [&](const trx_light &l) { return l.kind == TRX_LIGHT_RECT ? n_samples : 1u; }; // (one ray per pixel reaches a point or a direction)
+    auto sample_chunk_of = [&](uint32_t n_k) { return (uint32_t)std::min<uint64_t>(n_k, std::max<uint64_t>(units / tile_chunk, 1)); };
+    uint32_t most = 1u;
+    for (uint32_t k = 0; k < n_lights; k++) most = std::max(most, samples_of(lights[k]));
+    const uint64_t rays = (uint64_t)tile_chunk * sample_chunk_of(most) * 64;
+    if (slot->ao_rays.count() < rays) {
+        // (the slot's previous kernel may still be walking the old scratch)
+        if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
+        slot->ao_flags.reset();
+        HIP_TRY(slot->ao_rays.alloc(rays));
+        HIP_TRY(slot->ao_flags.alloc(rays));
+    }
+    for (uint32_t k = 0; k < n_lights; k++) {
+        const uint32_t n_k = samples_of(lights[k]), sample_chunk = sample_chunk_of(n_k);
+        g.rays = slot->ao_rays.get();
+        g.flags = slot->ao_flags.get();
+        g.counts = d_lit + k * records;
+        g.light = lights[k];
+        for (uint32_t tile0 = 0; tile0 < tiles; tile0 += tile_chunk) {
+            for (uint32_t s0 = 0; s0 < n_k; s0 += sample_chunk) {
+                g.tile0 = tile0;
+                g.n_tiles = std::min(tile_chunk, tiles - tile0);
+                g.n_samples = std::min(sample_chunk, n_k - s0);
+                g.seed0 = frame0 + k * 64u + s0;
+                g.first = s0 == 0 ? 1u : 0u;
+                if (phases) if (int rc = phases->mark(stream)) return rc;
+                HIP_TRY(launch_light_rays(g, stream));
+                // (from here on the slot is this stream's: the rays launch below finds it by its stream)
+                slot->last_stream = stream;
+                slot->last_use = ++s->launches;
+                HIP_TRY(hipEventRecord(slot->done.get(), stream));
+                slot->used = true;
+                if (phases) if (int rc = phases->mark(stream)) return rc;
+                TraceParams p;
+                std::memset(&p, 0, sizeof(p));
+                p.rays = g.rays;
+                p.out = reinterpret_cast<trx_hit *>(slot->ao_flags.get());
+                p.any_hit = 1u;
+                p.ray_mask = ray_mask; // (0: the unmasked launch; enqueue_locked hands a masked one the scene's table)
+                p.n_items = g.n_tiles * g.n_samples * 64u;
+                SlotCounters *ctr = nullptr;
+                if (int rc = enqueue_locked(s, p, kModeRays, sem, false, stream, &ctr)) return rc;
+                if (ctr != slot->ctr.get()) return fail(TRX_ERR_INVALID, "internal: the rays launch left the pass's launch slot");
+                if (phases) if (int rc = phases->mark(stream)) return rc;
+                HIP_TRY(launch_light_reduce(g, stream));
+                HIP_TRY(hipEventRecord(slot->done.get(), stream));
+                if (phases) if (int rc = phases->mark(stream)) return rc;
+            }
+        }
+    }
+    return TRX_OK;
+}
+
 } // namespace
+
+// what every light entry point refuses of its lights and sample count (api_image.cpp's trx_render_image_lit asks too)
+int trxapi::check_lights(const trx_light *lights, uint32_t n_lights, uint32_t n_samples) {
+    if (n_lights == 0 || n_lights > TRX_MAX_LIGHTS) return fail(TRX_ERR_INVALID, "n_lights %u outside 1..%d", n_lights, TRX_MAX_LIGHTS);
+    if (!lights) return fail(TRX_ERR_INVALID, "null lights");
+    if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    for (uint32_t k = 0; k < n_lights; k++) {
+        const trx_light &l = lights[k];
+        if (l.kind > TRX_LIGHT_RECT) return fail(TRX_ERR_INVALID, "light %u: unknown kind %u", k, l.kind);
+        for (uint32_t pad : l._pad)
+            if (pad != 0u) return fail(TRX_ERR_INVALID, "light %u: _pad must be 0", k);
+        bool finite = std::isfinite(l.intensity);
+        for (int i = 0; i < 3; i++) finite = finite && std::isfinite(l.position[i]) && std::isfinite(l.edge1[i]) && std::isfinite(l.edge2[i]);
+        if (!finite) return fail(TRX_ERR_INVALID, "light %u: a field is not finite", k);
+        if (l.kind == TRX_LIGHT_DIRECTIONAL && l.position[0] == 0.0f && l.position[1] == 0.0f && l.position[2] == 0.0f)
+            return fail(TRX_ERR_INVALID, "light %u: a directional light of zero length", k);
+    }
+    return TRX_OK;
+}
 
 extern "C" {
 
@@ -223,6 +342,89 @@ int trx_trace_ao_visibility(trx_scene *s, const trx_view *view, uint32_t w, uint
         });
 }
 
+// ---- direct light -----------------------------------------------------------------------------------------------------------
+
+int trx_light_rays_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, const trx_light *light,
+                       uint32_t light_index, uint32_t frame0, uint32_t sample, float shadow_eps, const trx_hit *d_primary,
+                       const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream) {
+    if (!s || !d_primary || !d_rays) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_lights(light, 1, 1)) return rc;
+    if (light_index >= TRX_MAX_LIGHTS) return fail(TRX_ERR_INVALID, "light_index %u outside 0..%d", light_index, TRX_MAX_LIGHTS - 1);
+    if (sample >= TRX_MAX_AO_SAMPLES) return fail(TRX_ERR_INVALID, "sample %u outside 0..%d", sample, TRX_MAX_AO_SAMPLES - 1);
+    if (int rc = check_eps(shadow_eps)) return rc;
+    AoRaysParams geom;
+    uint32_t tiles = 0;
+    if (int rc = ao_geometry(geom, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    if (tiles == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, (hipStream_t)stream, slot)) return rc;
+    LightRaysParams g;
+    std::memset(&g, 0, sizeof(g));
+    g.geom = geom.geom;
+    g.view = geom.view;
+    light_scene(g, s, d_primary, d_primary_inst);
+    g.rays = d_rays;
+    g.n_tiles = tiles;
+    g.n_samples = 1u;
+    g.seed0 = frame0 + light_index * 64u + sample;
+    g.shadow_eps = shadow_eps;
+    g.light = *light;
+    slot->last_stream = (hipStream_t)stream;
+    slot->last_use = ++s->launches;
+    HIP_TRY(launch_light_rays(g, (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(slot->done.get(), (hipStream_t)stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
+int trx_trace_light_visibility_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                                   uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
+                                   float shadow_eps, const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_lit,
+                                   void *stream) {
+    return light_visibility_impl(s, view, w, h, shard, sem, ray_mask, lights, n_lights, frame0, n_samples, shadow_eps, d_primary,
+                                 d_primary_inst, d_lit, (hipStream_t)stream, nullptr);
+}
+
+int trx_light_term_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, const trx_light *lights,
+                       uint32_t n_lights, uint32_t n_samples, const trx_hit *d_primary, const trx_hit_attr *d_attr,
+                       const uint8_t *d_lit, const trx_ao_term *d_term, float ambient, float *d_value, void *stream) {
+    if (!s || !d_primary || !d_attr || !d_lit || !d_value) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
+    if (!std::isfinite(ambient)) return fail(TRX_ERR_INVALID, "ambient %g is not finite", (double)ambient);
+    AoRaysParams geom;
+    uint32_t tiles = 0;
+    if (int rc = ao_geometry(geom, view, w, h, shard, tiles)) return rc;
+    if (tiles == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, (hipStream_t)stream, slot)) return rc;
+    LightTermParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.primary = d_primary;
+    p.attr = d_attr;
+    p.lit = d_lit;
+    p.term = d_term;
+    p.value = d_value;
+    p.n_tiles = tiles;
+    p.n_lights = n_lights;
+    p.n_samples = n_samples;
+    p.plane_stride = geom.geom.compact ? tiles * 64u : w * h;
+    p.ambient = ambient;
+    p.geom = geom.geom;
+    p.view = geom.view;
+    std::memcpy(p.lights, lights, n_lights * sizeof(trx_light));
+    slot->last_stream = (hipStream_t)stream;
+    slot->last_use = ++s->launches;
+    HIP_TRY(launch_light_term(p, (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(slot->done.get(), (hipStream_t)stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
 // ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------
 
 uint64_t trx_debug_ao_scratch_cap(uint64_t bytes) {
@@ -237,6 +439,26 @@ int trx_debug_ao_visibility_phases(trx_scene *s, const trx_view *view, uint32_t 
     Phases ph;
     if (int rc = visibility_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, frame0, n_samples, ao_eps, ao_radius, d_primary,
                                  d_primary_inst, d_unoccluded, nullptr, &ph))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    out_ms[0] = out_ms[1] = out_ms[2] = 0.f;
+    for (size_t c = 0; c + 3 < ph.ev.size(); c += 4)
+        for (int k = 0; k < 3; k++) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ph.ev[c + k].get(), ph.ev[c + k + 1].get()));
+            out_ms[k] += ms;
+        }
+    return trx_scene_check(s, nullptr);
+}
+
+int trx_debug_light_visibility_phases(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                                      const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float shadow_eps,
+                                      const trx_hit *d_primary, const uint32_t *d_primary_inst, uint8_t *d_lit, float out_ms[3]) {
+    if (!s || !out_ms) return fail(TRX_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    Phases ph;
+    if (int rc = light_visibility_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples,
+                                       shadow_eps, d_primary, d_primary_inst, d_lit, nullptr, &ph))
         return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     out_ms[0] = out_ms[1] = out_ms[2] = 0.f;

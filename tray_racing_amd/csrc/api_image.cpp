@@ -1,5 +1,5 @@
 // api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev /
-// trx_render_image*): the edge-aware filter over the AO visibility pass's counts, the edge-aware upsample of the sparse
+// trx_render_image*, trx_render_image_lit among them): the edge-aware filter over the AO visibility pass's counts, the edge-aware upsample of the sparse
 // pass's counts and the shading to RGBA8 (k_ao_filter, k_ao_upsample, k_shade, image.hip), and the table of
 // code thresholds the shade searches instead of evaluating pow; the PROFILE_RT heat map of a counting pass's per-ray counts
 // (trx_shade_heat_dev / trx_render_heat_image, k_heat).  Image passes after the walk: none reads scene data, but
@@ -96,7 +96,7 @@ int enqueue_shade(trx_scene *s, ShadeParams base, int mode, uint64_t n, hipStrea
     if (!s) return fail(TRX_ERR_INVALID, "null scene");
     if (n == 0) return TRX_OK;
     if (!base.rgba || (mode == kShadeReference && (!base.primary || !base.ao)) || (mode == kShadeCounts && !base.counts) ||
-        (mode == kShadeTerm && !base.term))
+        (mode == kShadeTerm && !base.term) || (mode == kShadeValue && !base.value))
         return fail(TRX_ERR_INVALID, "null argument");
     if (reinterpret_cast<uintptr_t>(base.rgba) & 3u) return fail(TRX_ERR_INVALID, "d_rgba is not 4-byte aligned");
     return enqueue_image(s, stream, true, [&]() -> int {
@@ -108,6 +108,7 @@ int enqueue_shade(trx_scene *s, ShadeParams base, int mode, uint64_t n, hipStrea
             if (p.ao) p.ao += off;
             if (p.counts) p.counts += off;
             if (p.term) p.term += off;
+            if (p.value) p.value += off;
             p.rgba += off * 4;
             p.n_items = (uint32_t)std::min(chunk, n - off);
             HIP_TRY(launch_shade(p, mode, stream));
@@ -213,6 +214,14 @@ int trx_shade_ao_term_dev(trx_scene *s, const trx_ao_term *d_term, uint64_t n, u
     p.term = d_term;
     p.rgba = d_rgba;
     return enqueue_shade(s, p, kShadeTerm, n, (hipStream_t)stream);
+}
+
+int trx_shade_value_dev(trx_scene *s, const float *d_value, uint64_t n, uint8_t *d_rgba, void *stream) {
+    ShadeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.value = d_value;
+    p.rgba = d_rgba;
+    return enqueue_shade(s, p, kShadeValue, n, (hipStream_t)stream);
 }
 
 int trx_shade_heat_dev(trx_scene *s, const trx_ray_cost *d_cost, uint64_t n, uint32_t which, float scale, uint8_t *d_rgba,
@@ -342,6 +351,63 @@ int trx_render_image_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint
                                      upsample_radius, depth_tol, normal_cos, d_term(), nullptr);
             if (rc) return rc;
             return trx_shade_ao_term_dev(s, d_term(), n, d_rgba(), nullptr);
+        },
+        [&]() -> int {
+            if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
+}
+
+int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                         const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                         float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                         float normal_cos, uint8_t *out_rgba, float *out_ms) {
+    if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
+    if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
+    if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
+    if (!std::isfinite(ambient)) return fail(TRX_ERR_INVALID, "ambient %g is not finite", (double)ambient);
+    if (ao_samples > TRX_MAX_AO_SAMPLES) return fail(TRX_ERR_INVALID, "ao_samples %u outside 0..%d", ao_samples, TRX_MAX_AO_SAMPLES);
+    if (ao_samples != 0) {
+        if (!(ao_radius > 0.0f)) return fail(TRX_ERR_INVALID, "ao_radius %g: must be > 0 (+inf allowed)", (double)ao_radius);
+        if (int rc = check_filter(filter_radius, depth_tol, normal_cos)) return rc;
+    }
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !view) return fail(TRX_ERR_INVALID, "null argument");
+    const uint64_t n = (uint64_t)w * h;
+    const trx_shard whole{0, 1, 0, 0};
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
+    HIP_TRY(hipSetDevice(s->device));
+    // the image scratch: the filter's terms, the image, the light term's values, then the lights' planes
+    HIP_TRY(s->scratch_img.grow(n * 12 + n * n_lights));
+    auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
+    auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
+    auto d_value = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 8); };
+    auto d_lit = [&] { return s->scratch_img.get() + n * 12; };
+    // (the AO counts go where trx_trace_ao_visibility puts them: n bytes of the second record buffer)
+    auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
+    return host_call(
+        s, n, nullptr, 0, n, out_ms,
+        [&] {
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, s->scratch_a.get(), s->scratch_ia.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_trace_light_visibility_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps,
+                                                s->scratch_a.get(), s->scratch_ia.get(), d_lit(), nullptr);
+            if (rc) return rc;
+            if (ao_samples != 0) {
+                rc = trx_trace_ao_visibility_dev(s, view, w, h, whole, sem, frame0, ao_samples, ao_eps, ao_radius, s->scratch_a.get(),
+                                                 s->scratch_ia.get(), d_counts(), nullptr);
+                if (rc) return rc;
+                rc = trx_ao_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), d_counts(), ao_samples, filter_radius, depth_tol,
+                                       normal_cos, d_term(), nullptr);
+                if (rc) return rc;
+            }
+            rc = trx_light_term_dev(s, view, w, h, whole, lights, n_lights, light_samples, s->scratch_a.get(), s->scratch_attr.get(),
+                                    d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
+            if (rc) return rc;
+            return trx_shade_value_dev(s, d_value(), n, d_rgba(), nullptr);
         },
         [&]() -> int {
             if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));

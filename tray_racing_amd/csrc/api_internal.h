@@ -7,7 +7,8 @@
 //   api_build.cpp    builders, flat-buffer assembly (cwbvh_gpu_runner's host half), scene generators and loaders
 //   api_refit.cpp    trx_scene_refit / trx_refit_nodes: the BVH refit's host twin and its device driver (refit_gpu.cpp)
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
-//   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts
+//   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts;
+//                    trx_light_rays_dev / trx_trace_light_visibility_dev / trx_light_term_dev: the same chain per light, and the light term
 //   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
@@ -240,6 +241,9 @@ uint64_t refit_state_bytes(const trx_scene *s);
 // (ray_mask != 0: a masked trace - enqueue() hands the kernel the scene's instance mask table)
 int trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t sem, trx_hit *d_hits, hipStream_t stream, bool count,
                     trx::SlotCounters **ctr, bool any_hit = false, uint32_t *d_inst = nullptr, uint32_t ray_mask = 0);
+
+// what the direct-light entry points refuse of their lights and sample count (api_ao.cpp)
+int check_lights(const trx_light *lights, uint32_t n_lights, uint32_t n_samples);
 
 // ---- the synchronous host-buffer entry points (api_trace.cpp, api_attr.cpp) ----
 // ev0, what `run` enqueues on the null stream, ev1; waits for ev1 and puts the elapsed time into *ms (may be null)

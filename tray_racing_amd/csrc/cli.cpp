@@ -55,6 +55,13 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     int ao_phase = -1, ao_upsample = -1; // (not given: phase 0, radius 1)
     int profile_rt = -1; // -1: not given, else TRX_HEAT_NODES / TRX_HEAT_TRIS
     float profile_rt_scale = -1.0f; // (not given: the reference's scale of the mode)
+    // --light point:x,y,z[:i] | dir:x,y,z[:i] | rect:cx,cy,cz:ax,ay,az:bx,by,bz[:i] (repeatable): with --png the image is the
+    // direct-light image (trx_render_image_lit): shadow rays toward every light, --light-samples N of them per rect light, cast
+    // with ray mask --light-mask M (0: unmasked) from --shadow-eps e behind the hit; --ambient a is scaled by the AO term of
+    // --ao-samples / --ao-filter when those are given
+    std::vector<trx_light> lights;
+    int light_samples = -1, light_mask = -1; // (not given: 1 sample, unmasked)
+    float shadow_eps = -1.0f, ambient = -1.0f; // (not given: 0.01, 0.1)
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -93,7 +100,52 @@ void usage() {
               "  [--profile-rt nodes|tris] [--profile-rt-scale x] (with --png: the PROFILE_RT heat map of a counted primary pass -\n"
               "   box tests (8 per node visit) x 0.002 or triangle tests x 0.01 through the reference's colour ramp - instead of\n"
               "   the shaded frame; not together with --ao-samples or --ao-filter)\n"
+              "  [--light point:x,y,z[:i] | dir:x,y,z[:i] | rect:cx,cy,cz:ax,ay,az:bx,by,bz[:i]] (repeatable, up to 8; with --png: the\n"
+              "   direct-light image - shadow rays toward every light, intensity i (default 1) - shaded on the device)\n"
+              "  [--light-samples 1..64] [--light-mask 0..255] [--shadow-eps e] [--ambient a] (with --light: samples per rect light,\n"
+              "   the shadow rays' instance mask, their offset, the ambient term - scaled by the AO term of --ao-samples /\n"
+              "   --ao-filter; not together with --ao-stride or --profile-rt)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
+}
+
+// point:x,y,z[:i] | dir:x,y,z[:i] | rect:cx,cy,cz:ax,ay,az:bx,by,bz[:i]
+trx_light parse_light(const std::string &text) {
+    const std::string form = "--light takes point:x,y,z[:i], dir:x,y,z[:i] or rect:cx,cy,cz:ax,ay,az:bx,by,bz[:i]";
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = text.find(':', at);
+        parts.push_back(text.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    trx_light l;
+    std::memset(&l, 0, sizeof(l));
+    l.intensity = 1.0f;
+    size_t vectors = 1;
+    if (parts[0] == "point") l.kind = TRX_LIGHT_POINT;
+    else if (parts[0] == "dir") l.kind = TRX_LIGHT_DIRECTIONAL;
+    else if (parts[0] == "rect") l.kind = TRX_LIGHT_RECT, vectors = 3;
+    else die(form);
+    if (parts.size() != 1 + vectors && parts.size() != 2 + vectors) die(form);
+    auto number = [&](const std::string &t) {
+        char *end = nullptr;
+        const float x = std::strtof(t.c_str(), &end);
+        if (t.empty() || *end != '\0' || !std::isfinite(x)) die(form);
+        return x;
+    };
+    float *dst[3] = {l.position, l.edge1, l.edge2};
+    for (size_t v = 0; v < vectors; v++) {
+        const std::string &t = parts[1 + v];
+        const size_t c1 = t.find(','), c2 = c1 == std::string::npos ? c1 : t.find(',', c1 + 1);
+        if (c2 == std::string::npos || t.find(',', c2 + 1) != std::string::npos) die(form);
+        dst[v][0] = number(t.substr(0, c1));
+        dst[v][1] = number(t.substr(c1 + 1, c2 - c1 - 1));
+        dst[v][2] = number(t.substr(c2 + 1));
+    }
+    if (parts.size() == 2 + vectors) l.intensity = number(parts[1 + vectors]);
+    if (l.kind == TRX_LIGHT_DIRECTIONAL && l.position[0] == 0.0f && l.position[1] == 0.0f && l.position[2] == 0.0f)
+        die("--light dir: takes a direction of non-zero length");
+    return l;
 }
 
 Options parse_args(int argc, char **argv) {
@@ -153,6 +205,22 @@ Options parse_args(int argc, char **argv) {
             o.ao_upsample = std::atoi(need(i));
             if (o.ao_upsample < 0 || o.ao_upsample > TRX_MAX_AO_UPSAMPLE_RADIUS) die("--ao-upsample takes 0.." + std::to_string(TRX_MAX_AO_UPSAMPLE_RADIUS));
         }
+        else if (a == "--light") {
+            if (o.lights.size() >= TRX_MAX_LIGHTS) die("--light: at most " + std::to_string(TRX_MAX_LIGHTS) + " lights");
+            o.lights.push_back(parse_light(need(i)));
+        } else if (a == "--light-samples") {
+            o.light_samples = std::atoi(need(i));
+            if (o.light_samples < 1 || o.light_samples > TRX_MAX_AO_SAMPLES) die("--light-samples takes 1.." + std::to_string(TRX_MAX_AO_SAMPLES));
+        } else if (a == "--light-mask") {
+            o.light_mask = std::atoi(need(i));
+            if (o.light_mask < 0 || o.light_mask > 255) die("--light-mask takes 0..255");
+        } else if (a == "--shadow-eps") {
+            o.shadow_eps = (float)std::atof(need(i));
+            if (!(o.shadow_eps >= 0.0f)) die("--shadow-eps must be >= 0");
+        } else if (a == "--ambient") {
+            o.ambient = (float)std::atof(need(i));
+            if (!(o.ambient >= 0.0f) || !std::isfinite(o.ambient)) die("--ambient must be finite and >= 0");
+        }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
             if (m == "nodes") o.profile_rt = (int)TRX_HEAT_NODES;
@@ -199,6 +267,10 @@ Options parse_args(int argc, char **argv) {
     if (o.ao_stride >= 0 && o.ao_phase >= o.ao_stride * o.ao_stride) die("--ao-phase takes 0..S*S-1 of --ao-stride S");
     if (o.profile_rt >= 0 && (o.ao_samples != 0 || o.ao_filter >= 0)) die("--profile-rt draws the heat map: not together with --ao-samples or --ao-filter");
     if (o.profile_rt < 0 && o.profile_rt_scale >= 0.0f) die("--profile-rt-scale scales the heat map of --profile-rt nodes|tris");
+    if (o.lights.empty() && (o.light_samples >= 0 || o.light_mask >= 0 || o.shadow_eps >= 0.0f || o.ambient >= 0.0f))
+        die("--light-samples, --light-mask, --shadow-eps and --ambient go with --light");
+    if (!o.lights.empty() && !o.png) die("--light lights the image of --png");
+    if (!o.lights.empty() && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--light draws the direct-light image: not together with --ao-stride or --profile-rt");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -260,6 +332,20 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
             std::printf("saved %s (heat map of %s, scale %g: %.2f node visits, %.2f triangle tests per ray)\n", path.c_str(),
                         o.profile_rt == (int)TRX_HEAT_TRIS ? "triangle tests" : "box tests", (double)scale,
                         (double)st.n_node / (double)std::max<uint64_t>(st.n_rays, 1), (double)st.n_tri / (double)std::max<uint64_t>(st.n_rays, 1));
+        return;
+    }
+    if (!o.lights.empty()) {
+        // the direct-light image, made on the device: shadow rays, the light term, the value shade; 4 bytes per pixel back
+        const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
+        const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
+        const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
+        check(trx_render_image_lit(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                   o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
+                                   o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
+                                   radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos, rgba.data(), &ms),
+              "png frame");
+        if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
+        if (o.verbose) std::printf("saved %s (device image, %zu lights, %.3f ms)\n", path.c_str(), o.lights.size(), ms);
         return;
     }
     if (o.ao_samples != 0 || o.ao_radius > 0.0f) {

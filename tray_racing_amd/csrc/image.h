@@ -45,8 +45,9 @@ struct AoUpsampleParams {
 hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream);
 
 // k_shade: one lane per record, 4 bytes {c, c, c, 255} written per record; c by an 8-step search of the 256 thresholds
-// (trx_image_code_table) each workgroup first copies into LDS.
-enum ShadeMode : int { kShadeReference = 0, kShadeCounts = 1, kShadeTerm = 2 };
+// (trx_image_code_table) each workgroup first copies into LDS.  kShadeValue (trx_shade_value_dev) launches k_value: the same
+// table, search and store over float values.
+enum ShadeMode : int { kShadeReference = 0, kShadeCounts = 1, kShadeTerm = 2, kShadeValue = 3 };
 struct ShadeParams {
     const float *thr;        // 256 floats, device memory
     const trx_hit *primary;  // kShadeReference
@@ -56,6 +57,7 @@ struct ShadeParams {
     uint8_t *rgba;
     uint32_t n_items;
     uint32_t n_samples;      // kShadeCounts
+    const float *value;      // kShadeValue (last: the fields the other modes read keep their offsets)
 };
 hipError_t launch_shade(const ShadeParams &p, int mode, hipStream_t stream);
 

@@ -232,6 +232,21 @@ __global__ void __launch_bounds__(256) k_shade(const ShadeParams P) {
     reinterpret_cast<uint32_t *>(P.rgba)[i] = c * 0x00010101u | 0xFF000000u; // {c, c, c, 255}
 }
 
+// The value shade (trx_shade_value_dev, kShadeValue): k_shade's table, search and store over float values taken as they are.
+// A kernel of its own name beside k_shade's three instantiations, which stay the parent commit's.
+__global__ void __launch_bounds__(256) k_value(const ShadeParams P) {
+    __shared__ float s_thr[256];
+    s_thr[threadIdx.x] = P.thr[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    const float col = P.value[i];
+    uint32_t c = 0u;
+#pragma unroll
+    for (uint32_t step = 128u; step != 0u; step >>= 1) c += col >= s_thr[c + step] ? step : 0u;
+    reinterpret_cast<uint32_t *>(P.rgba)[i] = c * 0x00010101u | 0xFF000000u; // {c, c, c, 255}
+}
+
 // The heat map's ten colours (include/trx.h, trx_shade_heat_dev): binary32 k / 255.0f, the division done by the compiler.
 __device__ const float kHeatPalette[10][3] = {
     {0 / 255.0f, 2 / 255.0f, 91 / 255.0f},    {0 / 255.0f, 108 / 255.0f, 251 / 255.0f}, {0 / 255.0f, 221 / 255.0f, 221 / 255.0f},
@@ -306,6 +321,7 @@ hipError_t launch_shade(const ShadeParams &p, int mode, hipStream_t stream) {
     case kShadeReference: hipLaunchKernelGGL(k_shade<kShadeReference>, grid, block, 0, stream, p); break;
     case kShadeCounts: hipLaunchKernelGGL(k_shade<kShadeCounts>, grid, block, 0, stream, p); break;
     case kShadeTerm: hipLaunchKernelGGL(k_shade<kShadeTerm>, grid, block, 0, stream, p); break;
+    case kShadeValue: hipLaunchKernelGGL(k_value, grid, block, 0, stream, p); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

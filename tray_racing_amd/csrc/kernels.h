@@ -250,6 +250,46 @@ struct AoRaysParams {
 hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream);
 hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream);
 
+// Direct light (trx_light_rays_dev / trx_trace_light_visibility_dev / trx_light_term_dev): the AO visibility pass's shape,
+// once per light.  k_light_rays writes the shadow rays of ONE light (carried by value) as explicit rays - record layout or
+// scratch layout exactly as AoRaysParams describes them, one lane per (tile, sample, pixel); the any-hit rays launch walks
+// them; k_light_reduce adds the flags into the light's plane of per-pixel counts (an inert ray counts as not lit; a pixel
+// without a surface - its primary record says so - gets TRX_AO_NO_SURFACE).
+struct LightRaysParams {
+    const float4 *tris;
+    const float4 *inst_xform;     // world-to-object rows per instance, or null (no instance transforms)
+    const trx_hit *primary;
+    const uint32_t *primary_inst; // read only with inst_xform
+    trx_ray *rays;
+    const uint8_t *flags;         // k_light_reduce: the occlusion flags of the scratch rays
+    uint8_t *counts;              // k_light_reduce: the light's plane, one byte per record, laid out by the shard
+    uint32_t tile0, n_tiles, n_samples, scratch;
+    uint32_t first;               // k_light_reduce: the first samples of these tiles (counts are set, not added to)
+    TileGeom geom;
+    uint32_t seed0;               // the seed of the chunk's first sample: frame0 + light_index * 64 + sample
+    float shadow_eps;
+    ViewDev view;
+    trx_light light;
+};
+hipError_t launch_light_rays(const LightRaysParams &p, hipStream_t stream);
+hipError_t launch_light_reduce(const LightRaysParams &p, hipStream_t stream);
+
+// The light term (k_light_term): one lane per pixel of the shard's tiles, every buffer laid out by the shard; the lights
+// by value, plane k of `lit` at k * plane_stride.
+struct LightTermParams {
+    const trx_hit *primary;
+    const trx_hit_attr *attr;
+    const uint8_t *lit;
+    const trx_ao_term *term; // or null: the ambient is unoccluded
+    float *value;
+    uint32_t n_tiles, n_lights, n_samples, plane_stride;
+    float ambient;
+    TileGeom geom;
+    ViewDev view;
+    trx_light lights[TRX_MAX_LIGHTS];
+};
+hipError_t launch_light_term(const LightTermParams &p, hipStream_t stream);
+
 // Resident waves the persistent kernel should be launched with on `device`.
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count);
 

@@ -988,6 +988,156 @@ __global__ void __launch_bounds__(256) k_ao_reduce(const AoRaysParams P) {
     else if (surface) P.counts[rec] = (uint8_t)(P.counts[rec] + n);
 }
 
+// Direct light (include/trx.h, "THE SHADOW RAY"; kernels.h, LightRaysParams).  The unit direction toward a directional light.
+__device__ __forceinline__ void light_toward(const trx_light &L, float &lx, float &ly, float &lz) {
+    const float inv = 1.0f / sqrtf(dot3(L.position[0], L.position[1], L.position[2], L.position[0], L.position[1], L.position[2]));
+    lx = L.position[0] * inv;
+    ly = L.position[1] * inv;
+    lz = L.position[2] * inv;
+}
+
+// The shadow ray of every (tile, sample, pixel) toward ONE light as an explicit ray: k_ao_rays' addressing, primary
+// direction, normal (the first five statements of TRX_AO_RAY, restated: the rest of that text is the AO direction) and
+// origin with shadow_eps for ao_eps; then the header's light point, direction, reach and facing test.  The inert ray goes to
+// pixels without a surface and to samples that do not face the light.  A streaming kernel like k_ao_rays: 8 B of primary
+// record, 48 B of triangle (and 48 B of rows) read per ray, 32 B written; the light is launch-uniform (scalar loads).
+__global__ void __launch_bounds__(256) k_light_rays(const LightRaysParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * P.n_samples * 64u) return;
+    const uint32_t unit = item >> 6, k = item & 63u;
+    const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
+    uint32_t px, py, rec;
+    const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+    if (!inside && !P.scratch) return; // (the trace writes no record for it either)
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    trx_hit ph;
+    ph.t = __builtin_inff();
+    ph.prim = TRX_INVALID;
+    if (inside) ph = P.primary[rec];
+    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
+        float dx, dy, dz;
+        primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
+        const float4 *tp = P.tris + (size_t)ph.prim * 3;
+        float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
+        if (P.inst_xform) {
+            const uint32_t pi = P.primary_inst[rec];
+            if (pi != TRX_INVALID) {
+                const float4 *m = P.inst_xform + (size_t)pi * 3;
+                const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
+                nx = w.x; ny = w.y; nz = w.z;
+            }
+        }
+        const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+        nx *= ninv; ny *= ninv; nz *= ninv;
+        const float nd = (nx * -dx + ny * -dy) + nz * -dz;
+        const float sg = copysignf(1.0f, nd);
+        nx *= sg; ny *= sg; nz *= sg;
+        const float ox = (P.view.eye[0] + dx * ph.t) - dx * P.shadow_eps;
+        const float oy = (P.view.eye[1] + dy * ph.t) - dy * P.shadow_eps;
+        const float oz = (P.view.eye[2] + dz * ph.t) - dz * P.shadow_eps;
+        float lx, ly, lz, tmax;
+        if (P.light.kind == TRX_LIGHT_DIRECTIONAL) {
+            light_toward(P.light, lx, ly, lz);
+            tmax = TRX_F32_MAX;
+        } else {
+            float Lx = P.light.position[0], Ly = P.light.position[1], Lz = P.light.position[2];
+            if (P.light.kind == TRX_LIGHT_RECT) {
+                const uint32_t seed = P.seed0 + sample;
+                const float u1 = hash_noise(px, py, seed);
+                const float u2 = hash_noise(px, py, seed + 1024u);
+                Lx = (Lx + u1 * P.light.edge1[0]) + u2 * P.light.edge2[0];
+                Ly = (Ly + u1 * P.light.edge1[1]) + u2 * P.light.edge2[1];
+                Lz = (Lz + u1 * P.light.edge1[2]) + u2 * P.light.edge2[2];
+            }
+            const float vx = Lx - ox, vy = Ly - oy, vz = Lz - oz;
+            const float dist = sqrtf(dot3(vx, vy, vz, vx, vy, vz));
+            const float inv = 1.0f / dist;
+            lx = vx * inv; ly = vy * inv; lz = vz * inv;
+            tmax = fminf(dist, TRX_F32_MAX);
+        }
+        if (dot3(nx, ny, nz, lx, ly, lz) > 0.0f) { // (false for NaN: a light at the hit point)
+            a.x = ox; a.y = oy; a.z = oz;
+            b = make_float4(lx, ly, lz, tmax);
+        }
+    }
+    float4 *out = reinterpret_cast<float4 *>(P.rays + (P.scratch ? item : rec));
+    out[0] = a;
+    out[1] = b;
+}
+
+// One lane per pixel of the chunk's tiles: the samples of the chunk whose shadow ray was cast (not inert) and NOT occluded,
+// set (first samples of the tile: TRX_AO_NO_SURFACE where the primary record is a miss) or added to the pixel's count in the
+// light's plane.  The surface comes from the primary record: an inert ray here may be a sample facing away.
+__global__ void __launch_bounds__(256) k_light_reduce(const LightRaysParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * 64u) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    uint32_t px, py, rec;
+    if (!tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec)) return;
+    const trx_hit ph = P.primary[rec];
+    const bool surface = ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID;
+    const uint32_t base = lt * P.n_samples * 64u + k;
+    uint32_t n = 0u;
+    for (uint32_t s = 0; s < P.n_samples; s++)
+        n += P.flags[base + s * 64u] == 0u && !(P.rays[base + s * 64u].tmax < 0.0f) ? 1u : 0u;
+    if (P.first) P.counts[rec] = (uint8_t)(surface ? n : kAoNoSurface);
+    else if (surface) P.counts[rec] = (uint8_t)(P.counts[rec] + n);
+}
+
+// The light term (include/trx.h, trx_light_term_dev): one lane per pixel of the shard's tiles.  The ambient times the
+// filtered AO term, then light after light the unshadowed analytic term times the traced visibility, in the header's order
+// of operations.  Streaming: 8 B of primary record, 24 B of attributes, one byte per light (and 4 B of AO term) read, 4 B
+// written; the lights are launch-uniform.
+__global__ void __launch_bounds__(256) k_light_term(const LightTermParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * 64u) return;
+    uint32_t px, py, rec;
+    if (!tile_pixel(P.geom, item >> 6, item & 63u, px, py, rec)) return;
+    const trx_hit ph = P.primary[rec];
+    float E = 0.0f;
+    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
+        float dx, dy, dz;
+        primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
+        const trx_hit_attr at = P.attr[rec];
+        float nx = at.normal[0], ny = at.normal[1], nz = at.normal[2];
+        const float nd = (nx * -dx + ny * -dy) + nz * -dz;
+        const float sg = copysignf(1.0f, nd);
+        nx *= sg; ny *= sg; nz *= sg;
+        const float Px = P.view.eye[0] + dx * ph.t, Py = P.view.eye[1] + dy * ph.t, Pz = P.view.eye[2] + dz * ph.t;
+        float amb = 1.0f;
+        if (P.term) {
+            const trx_ao_term tm = P.term[rec];
+            amb = tm.samples == 0 ? 0.0f : (float)tm.unoccluded / (float)tm.samples;
+        }
+        E = P.ambient * amb;
+        for (uint32_t li = 0; li < P.n_lights; li++) {
+            const trx_light &L = P.lights[li];
+            float g;
+            if (L.kind == TRX_LIGHT_DIRECTIONAL) {
+                float lx, ly, lz;
+                light_toward(L, lx, ly, lz);
+                g = dot3(nx, ny, nz, lx, ly, lz);
+            } else {
+                float Cx = L.position[0], Cy = L.position[1], Cz = L.position[2];
+                if (L.kind == TRX_LIGHT_RECT) {
+                    Cx = (Cx + 0.5f * L.edge1[0]) + 0.5f * L.edge2[0];
+                    Cy = (Cy + 0.5f * L.edge1[1]) + 0.5f * L.edge2[1];
+                    Cz = (Cz + 0.5f * L.edge1[2]) + 0.5f * L.edge2[2];
+                }
+                const float vx = Cx - Px, vy = Cy - Py, vz = Cz - Pz;
+                const float q = dot3(vx, vy, vz, vx, vy, vz);
+                const float inv = 1.0f / sqrtf(q);
+                g = dot3(nx, ny, nz, vx * inv, vy * inv, vz * inv) / q;
+            }
+            uint32_t cnt = P.lit[(size_t)li * P.plane_stride + rec];
+            cnt = cnt == kAoNoSurface ? 0u : cnt;
+            const float nk = (float)(L.kind == TRX_LIGHT_RECT ? P.n_samples : 1u);
+            if (g > 0.0f) E = E + (L.intensity * g) * ((float)cnt / nk);
+        }
+    }
+    P.value[rec] = E;
+}
+
 } // namespace
 
 hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream) {
@@ -1012,6 +1162,27 @@ hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream) {
     const dim3 grid((p.n_tiles * 64u + 255u) / 256u);
     if (p.stride) hipLaunchKernelGGL(k_ao_reduce<true>, grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(k_ao_reduce<false>, grid, dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_light_rays(const LightRaysParams &p, hipStream_t stream) {
+    const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
+    if (n == 0) return hipSuccess;
+    if (n > 0xffffff00ull || p.light.kind > TRX_LIGHT_RECT) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_light_rays, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_light_reduce(const LightRaysParams &p, hipStream_t stream) {
+    if (p.n_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_light_reduce, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_light_term(const LightTermParams &p, hipStream_t stream) {
+    if (p.n_tiles == 0) return hipSuccess;
+    if (p.n_lights > TRX_MAX_LIGHTS || p.n_tiles > 0x3ffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_light_term, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -101,6 +101,26 @@ def view_from_camera(eye, look_at, fov_deg, width, height):
 
 # ---- flat buffers (cwbvh_gpu_runner's assembly half) -----------------------------
 
+def light(kind, position, edge1=(0.0, 0.0, 0.0), edge2=(0.0, 0.0, 0.0), intensity=1.0):
+    """An L.Light (trx_light): kind L.LIGHT_DIRECTIONAL (position = the direction toward the light), L.LIGHT_POINT or
+    L.LIGHT_RECT (position = a corner, the light spans edge1 and edge2 from it)."""
+    out = L.Light()
+    out.kind = kind
+    out.position[:] = [float(x) for x in position]
+    out.edge1[:] = [float(x) for x in edge1]
+    out.edge2[:] = [float(x) for x in edge2]
+    out.intensity = float(intensity)
+    return out
+
+
+def light_array(lights):
+    """A contiguous ctypes array of L.Light from a sequence of them (or the array itself)."""
+    if isinstance(lights, C.Array):
+        return lights
+    lights = list(lights)
+    return (L.Light * len(lights))(*lights)
+
+
 class FlatScene:
     """The buffers rt_gpu_software::start receives: bvh_bytes, tri_bytes, instance_bytes, tlas_start."""
 
@@ -530,6 +550,19 @@ class Scene:
                                                   ao_stride, ao_phase, upsample_radius, depth_tol, normal_cos, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_image_lit(self, view, width, height, lights, sem=L.SEM_HLSL, ray_mask=0, frame0=0, light_samples=1, shadow_eps=0.01,
+                         ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"), filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_lit - the frame traced, shadow rays toward every light
+        (masked by ray_mask when it is not 0), the light term (ambient, scaled by the filtered AO term when ao_samples >= 1,
+        plus every light's analytic term times its visibility) shaded to RGBA8 on the device; only the image crosses the bus."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_lit(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0, light_samples,
+                                               shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius, depth_tol, normal_cos,
+                                               _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
         """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
         of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
@@ -721,6 +754,38 @@ class Scene:
                                                              n_samples, ao_eps, ao_radius, C.c_void_p(d_primary),
                                                              C.c_void_p(d_primary_inst), C.c_void_p(d_unoccluded_lo),
                                                              C.c_void_p(stream)))
+
+    def light_rays_dev(self, view, width, height, light, d_primary, d_rays, light_index=0, frame0=0, sample=0, shadow_eps=0.01,
+                       d_primary_inst=0, shard=(0, 1), stream=0):
+        """trx_light_rays_dev: the shadow rays toward `light` (an L.Light; its index among the pass's lights and the sample
+        pick a rect light's seed) as explicit rays at d_rays, one per record laid out like the hit buffers of `shard`; the
+        inert ray (tmax = -1) where there is no surface or the surface faces away."""
+        L.check(self._lib.trx_light_rays_dev(self._h, C.byref(view), width, height, L.Shard(*shard), C.byref(light), light_index,
+                                             frame0, sample, shadow_eps, C.c_void_p(d_primary), C.c_void_p(d_primary_inst),
+                                             C.c_void_p(d_rays), C.c_void_p(stream)))
+
+    def trace_light_visibility_dev(self, view, width, height, lights, d_primary, d_lit, n_samples=1, sem=L.SEM_HLSL, ray_mask=0,
+                                   frame0=0, shadow_eps=0.01, d_primary_inst=0, shard=(0, 1), stream=0):
+        """trx_trace_light_visibility_dev: one plane of one byte per record per light at d_lit - the samples (n_samples for a
+        rect light, one otherwise) whose shadow ray was cast and not occluded, L.AO_NO_SURFACE where there is no surface.
+        ray_mask 1..255: instances whose mask shares no bit with it cast no shadow."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_light_visibility_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask, arr,
+                                                         len(arr), frame0, n_samples, shadow_eps, C.c_void_p(d_primary),
+                                                         C.c_void_p(d_primary_inst), C.c_void_p(d_lit), C.c_void_p(stream)))
+
+    def light_term_dev(self, view, width, height, lights, d_primary, d_attr, d_lit, d_value, n_samples=1, ambient=0.0, d_term=0,
+                       shard=(0, 1), stream=0):
+        """trx_light_term_dev: one float per record at d_value - ambient (times the AO term at d_term, if given) plus every
+        light's unshadowed term times its visibility count / samples; 0 where there is no surface."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_light_term_dev(self._h, C.byref(view), width, height, L.Shard(*shard), arr, len(arr), n_samples,
+                                             C.c_void_p(d_primary), C.c_void_p(d_attr), C.c_void_p(d_lit), C.c_void_p(d_term), ambient,
+                                             C.c_void_p(d_value), C.c_void_p(stream)))
+
+    def shade_value_dev(self, d_value, n, d_rgba, stream=0):
+        """trx_shade_value_dev: n float values as RGBA8 through the code table (0 for negative or NaN, 255 from 1 upward)."""
+        L.check(self._lib.trx_shade_value_dev(self._h, C.c_void_p(d_value), n, C.c_void_p(d_rgba), C.c_void_p(stream)))
 
     def hit_attributes_rays_dev(self, d_rays, n, d_hits, d_attr, d_inst=0, stream=0):
         """trx_hit_attributes_rays_dev: n trx_hit_attr records at d_attr for the hits d_hits of the rays d_rays (d_inst: the
