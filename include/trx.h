@@ -741,6 +741,75 @@ int trx_render_image_lit(trx_scene *scene, const trx_view *view, uint32_t width,
                          float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos, uint8_t *out_rgba,
                          float *out_ms);
 
+/* ---- indirect light: one diffuse bounce - bounce rays, lit secondary hits, the GI image --------------------------------------
+ * The lit image shows only ambient * AO wherever no light reaches directly.  This pass adds what one diffuse bounce brings:
+ * per pixel and sample a cosine-hemisphere ray from the primary hit, traced closest-hit, and at the surface it finds the
+ * direct light of every light - a shadow ray and the analytic term, as above, with the bounce hit in the primary hit's place.
+ * A composition of calls above: trx_ao_rays_dev's rays, trx_trace_rays_inst_dev's walk, trx_hit_attributes_rays_dev's
+ * normals, trx_trace_occluded*_dev's any-hit walk.  Scalars throughout: the image stays grey.
+ *
+ * THE RULES, for the record of pixel (px, py), a sample f in 0..n_samples-1 (n_samples 1..TRX_MAX_AO_SAMPLES) and a light k.
+ * Every operation is rounded once in binary32, no contraction; dot3 as above.
+ *  1. BOUNCE RAY b_f: bit for bit the ray trx_ao_rays_dev writes for the pixel under seed frame0 + f with ao_eps = bounce_eps
+ *     and ao_radius = +inf (its tmax is FLT_MAX).  A pixel that is not a surface pixel gets the inert ray (tmax < 0 marks it).
+ *  2. BOUNCE HIT: what trx_trace_rays_inst_dev answers for b_f under `semantics` - closest-hit and UNMASKED: the mask applies
+ *     to the shadow rays only, as above.  The bounce HAS A SURFACE iff b_f is not inert, t < FLT_MAX and prim != 0xFFFFFFFF.
+ *     Its attribute record `attr` is what trx_hit_attributes_rays_dev writes for (ray, hit, instance id).
+ *  3. SECONDARY SHADOW RAY: the shadow ray above with the primary hit replaced by the bounce hit.  d = b_f's direction,
+ *     n = attr.normal * copysignf(1.0f, dot3(attr.normal, -d)), Q[i] = b_f.origin[i] + d[i]*t,
+ *     o[i] = Q[i] - d[i]*shadow_eps; the light point L, l, tmax and the facing test are THE SHADOW RAY's statements.  A rect
+ *     light takes ONE sample per bounce: u1 = hash_noise(px, py, seed), u2 = hash_noise(px, py, seed + 1024u) with
+ *     seed = frame0 + k*64u + f.  Where the bounce has no surface, or !(dot3(n, l) > 0.0f), the ray is the inert ray and
+ *     contributes nothing.
+ *  4. WEIGHT: g_k is trx_light_term_dev's g with P := Q and the flipped n above (DIRECTIONAL: g = dot3(n, l); POINT, RECT:
+ *     toward the centre C: v = C - Q, q = dot3(v, v), inv = 1.0f / sqrtf(q), g = dot3(n, v*inv) / q).  s_f = 0.0f; for k
+ *     ascending: if the shadow ray was cast and is NOT occluded and g_k > 0.0f then s_f = s_f + intensity_k * g_k.  "Not
+ *     occluded" is what trx_trace_occluded_dev answers for the ray, with ray_mask 1..255 what trx_trace_occluded_masked_dev
+ *     answers.
+ *  5. TERM: A = 0.0f; for f ascending: A = A + s_f.  out = base + (bounce_albedo * A) / (float)n_samples with
+ *     base = d_base[record], or 0.0f when d_base is NULL.  A pixel without a surface gets base.  The order holds whatever the
+ *     chunking.
+ *
+ * trx_bounce_light_rays_dev writes the secondary shadow rays of ONE light and ONE sample as explicit rays, so that all 32
+ * bytes of every ray can be held to rule 3: d_bounce_rays, d_bounce_hits, d_bounce_attr and d_rays hold one record per record
+ * of `shard`, laid out like every record buffer; records outside the shard or the image are untouched.  It takes no view and
+ * no instance ids: the attribute record carries the world-space normal.  Refused (TRX_ERR_INVALID, nothing enqueued): what
+ * trx_light_rays_dev refuses of light, light_index, sample and shadow_eps, an empty image or a bad shard, null buffers. */
+int trx_bounce_light_rays_dev(trx_scene *scene, uint32_t width, uint32_t height, trx_shard shard, const trx_light *light,
+                              uint32_t light_index, uint32_t frame0, uint32_t sample, float shadow_eps,
+                              const trx_ray *d_bounce_rays, const trx_hit *d_bounce_hits,
+                              const trx_hit_attr *d_bounce_attr, trx_ray *d_rays, void *stream);
+/* The pass: one float per record at d_value (rule 5), laid out by `shard` like d_primary and d_primary_inst; records outside
+ * the shard or the image are untouched.  d_base may be NULL, a buffer laid out alike, or d_value itself (every record's base
+ * is read before its value is written; the running sums sit in the pass's scratch).
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): everything
+ * trx_trace_light_visibility_dev refuses (lights, n_lights, ray_mask, shadow_eps, semantics bits, a missing d_primary_inst on
+ * a scene with instance transforms), n_samples outside 1..TRX_MAX_AO_SAMPLES, bounce_eps NaN or negative, a non-finite
+ * bounce_albedo, a null scene, view, d_primary or d_value.
+ * Mechanics: everything runs on `stream` without host synchronisation.  Per chunk of tiles and samples ([tile][sample][64
+ * pixels], as for trx_trace_ao_visibility_dev): the bounce rays, the closest-hit rays launch with instance ids, the attribute
+ * pass in rays mode; then light after light the shadow rays, the any-hit rays launch (masked when ray_mask != 0) and the
+ * weights; then the samples' sums are added to the tile's running sums.  Sample chunks and lights ascend, so rule 5's order
+ * holds under any cap.  The scratch (about 6.8 KiB per tile and sample) belongs to the stream's launch slot of the scene,
+ * shares the AO pass's rays and flags and its cap (288 MiB per slot), is counted once by trx_scene_device_bytes and
+ * released by trx_scene_destroy; growing it waits for the slot's previous launch.
+ * Ordering: as for the other passes - a trx_scene_refit* called after this call has returned waits for every launch of the
+ * pass, which sees the old geometry in full.  A stack overflow latches as for every rays launch (trx_scene_check). */
+int trx_trace_indirect_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                           uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
+                           uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps, float bounce_albedo,
+                           const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base, float *d_value,
+                           void *stream);
+/* trx_render_image_lit with one bounce: its passes up to the light term, then trx_trace_indirect_dev (bounce_samples
+ * 1..TRX_MAX_AO_SAMPLES, seeds frame0 .., bounce_eps, bounce_albedo; the lights, ray_mask and shadow_eps of the direct pass)
+ * with the light term's values as d_base and d_value, then the value shade.  4 bytes per pixel are copied back (out_rgba may
+ * be NULL).  Every argument is validated before the first pass is enqueued. */
+int trx_render_image_gi(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                        uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                        uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                        float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos,
+                        uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint8_t *out_rgba, float *out_ms);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,

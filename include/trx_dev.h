@@ -101,6 +101,14 @@ int trx_debug_light_visibility_phases(trx_scene *scene, const trx_view *view, ui
                                       uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
                                       uint32_t frame0, uint32_t n_samples, float shadow_eps, const trx_hit *d_primary,
                                       const uint32_t *d_primary_inst, uint8_t *d_lit, float out_ms[3]);
+/* One whole-image trx_trace_indirect_dev pass on the null stream (synchronous), hipEvents around its launches; out_ms summed
+ * over the chunks and lights: [0] the bounce rays, [1] the closest-hit walk over them, [2] their attributes, [3] the shadow
+ * rays, [4] the any-hit walk over them, [5] weight, gather and finish. */
+int trx_debug_indirect_phases(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                              uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                              uint32_t n_samples, float bounce_eps, float shadow_eps, float bounce_albedo,
+                              const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base,
+                              float *d_value, float out_ms[6]);
 
 /* Kernel variant selection (tuning aid; 0 = default).  Returns the previous
  * value.  Variants compute identical results. */

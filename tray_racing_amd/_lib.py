@@ -181,6 +181,12 @@ SIGNATURES = {
                                   _P, C.POINTER(_f)]),
     "trx_debug_light_visibility_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _P, _P, _P,
                                                C.POINTER(_f)]),
+    "trx_bounce_light_rays_dev": (_i, [_P, _u32, _u32, Shard, C.POINTER(Light), _u32, _u32, _u32, _f, _P, _P, _P, _P, _P]),
+    "trx_trace_indirect_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P, _P]),
+    "trx_render_image_gi": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32, _f, _f,
+                                 _u32, _f, _f, _P, C.POINTER(_f)]),
+    "trx_debug_indirect_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P,
+                                       C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),
     "trx_debug_ao_visibility_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _f, _f, _P, _P, _P,
                                             C.POINTER(_f)]),

@@ -246,6 +246,184 @@ int light_visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32
     return TRX_OK;
 }
 
+// ---- one-bounce indirect light (include/trx.h, "indirect light") ----------------------------------------------------------------
+
+// hipEvents around the launches of the indirect pass (trx_debug_indirect_phases): every mark but a chunk's first ends an
+// interval that belongs to one of the six phases
+enum BouncePhase : int { kPhStart = -1, kPhBounceRays = 0, kPhBounceWalk, kPhAttr, kPhShadowRays, kPhShadowWalk, kPhWeightGather, kPhCount };
+struct BouncePhases {
+    std::vector<Event> ev;
+    std::vector<int> ends;
+    int mark(hipStream_t stream, int phase) {
+        ev.emplace_back();
+        ends.push_back(phase);
+        HIP_TRY(ev.back().create());
+        HIP_TRY(hipEventRecord(ev.back().get(), stream));
+        return TRX_OK;
+    }
+};
+
+// the image geometry of a call that regenerates no primary ray: no view is needed (ao_geometry copies one)
+int bounce_geometry(TileGeom &geom, uint32_t w, uint32_t h, trx_shard shard, uint32_t &tiles) {
+    const trx_view none{};
+    AoRaysParams g;
+    if (int rc = ao_geometry(g, &none, w, h, shard, tiles)) return rc;
+    geom = g.geom;
+    return TRX_OK;
+}
+
+// light_visibility_impl's sibling for one diffuse bounce.  Per chunk of (tiles, samples), [tile][sample][64] like the AO
+// pass's scratch: k_ao_rays writes the bounce rays (tmax = FLT_MAX), the closest-hit rays launch walks them (unmasked, with
+// instance ids), k_hit_attr in rays mode gives every hit its normal; then light after light k_bounce_light_rays, the any-hit
+// rays launch with p.ray_mask, k_bounce_weight; k_bounce_gather adds the chunk's sums to the tiles' running sums, and after a
+// tile chunk's last samples k_bounce_finish writes the values.  Sample chunks ascend inside a tile chunk, lights ascend inside
+// a sample chunk: every float sum is formed in the header's order whatever the cap.
+int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
+                  const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps,
+                  float albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base, float *d_value,
+                  hipStream_t stream, BouncePhases *phases) {
+    if (!s || !d_primary || !d_value) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
+    if (!(bounce_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "bounce_eps %g: must be >= 0", (double)bounce_eps);
+    if (int rc = check_eps(shadow_eps)) return rc;
+    if (!std::isfinite(albedo)) return fail(TRX_ERR_INVALID, "bounce_albedo %g is not finite", (double)albedo);
+    AoRaysParams g;
+    uint32_t tiles = 0;
+    if (int rc = ao_geometry(g, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    if (tiles == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, stream, slot)) return rc;
+    // chunks: as many tiles as the scratch holds, and for them as many samples as it holds (a unit of its own: kBounceUnitBytes)
+    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / kBounceUnitBytes, 1), 1ull << 24);
+    const uint32_t tile_chunk = (uint32_t)std::min<uint64_t>(tiles, units);
+    const uint32_t sample_chunk = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(units / tile_chunk, 1));
+    const uint64_t rays = (uint64_t)tile_chunk * sample_chunk * 64, pixels = (uint64_t)tile_chunk * 64;
+    if (slot->ao_rays.count() < rays || slot->gi_rays.count() < rays || slot->gi_acc.count() < pixels) {
+        // (the slot's previous kernel may still be walking the old scratch)
+        if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
+        if (slot->ao_rays.count() < rays) {
+            slot->ao_flags.reset();
+            HIP_TRY(slot->ao_rays.alloc(rays));
+            HIP_TRY(slot->ao_flags.alloc(rays));
+        }
+        if (slot->gi_rays.count() < rays) {
+            // (the rays last: their count is what says that all five are there)
+            slot->gi_rays.reset();
+            HIP_TRY(slot->gi_hits.alloc(rays));
+            HIP_TRY(slot->gi_inst.alloc(rays));
+            HIP_TRY(slot->gi_attr.alloc(rays));
+            HIP_TRY(slot->gi_sum.alloc(rays));
+            HIP_TRY(slot->gi_rays.alloc(rays));
+        }
+        HIP_TRY(slot->gi_acc.grow(pixels));
+    }
+    const bool xf = s->tlas && s->inst_xform;
+    // the bounce rays: the AO pass's rays with bounce_eps for ao_eps and no radius
+    g.tris = s->tris.get();
+    g.inst_xform = xf ? s->inst_xform.get() : nullptr;
+    g.primary = d_primary;
+    g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.rays = slot->gi_rays.get();
+    g.scratch = 1u;
+    g.ao_eps = bounce_eps;
+    g.tmax = FLT_MAX;
+    HitAttrParams at;
+    std::memset(&at, 0, sizeof(at));
+    at.tris = s->tris.get();
+    at.inst_xform = g.inst_xform;
+    at.rays = slot->gi_rays.get();
+    at.hits = slot->gi_hits.get();
+    at.inst = xf ? slot->gi_inst.get() : nullptr;
+    at.out = slot->gi_attr.get();
+    at.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull);
+    at.n_inst = s->n_inst;
+    BounceParams b;
+    std::memset(&b, 0, sizeof(b));
+    b.bounce_rays = slot->gi_rays.get();
+    b.bounce_hits = slot->gi_hits.get();
+    b.bounce_attr = slot->gi_attr.get();
+    b.rays = slot->ao_rays.get();
+    b.flags = slot->ao_flags.get();
+    b.sum = slot->gi_sum.get();
+    b.acc = slot->gi_acc.get();
+    b.primary = d_primary;
+    b.base = d_base;
+    b.value = d_value;
+    b.scratch = 1u;
+    b.n_total = n_samples;
+    b.geom = g.geom;
+    b.shadow_eps = shadow_eps;
+    b.albedo = albedo;
+    // one rays launch on the pass's slot (the slot is this stream's once the first kernel of the chunk is recorded)
+    auto walk = [&](TraceParams &p) -> int {
+        SlotCounters *ctr = nullptr;
+        if (int rc = enqueue_locked(s, p, kModeRays, sem, false, stream, &ctr)) return rc;
+        if (ctr != slot->ctr.get()) return fail(TRX_ERR_INVALID, "internal: the rays launch left the pass's launch slot");
+        return TRX_OK;
+    };
+    for (uint32_t tile0 = 0; tile0 < tiles; tile0 += tile_chunk) {
+        for (uint32_t s0 = 0; s0 < n_samples; s0 += sample_chunk) {
+            g.tile0 = b.tile0 = tile0;
+            g.n_tiles = b.n_tiles = std::min(tile_chunk, tiles - tile0);
+            g.n_samples = b.n_samples = std::min(sample_chunk, n_samples - s0);
+            g.frame = frame0 + s0;
+            const uint32_t n_rays = g.n_tiles * g.n_samples * 64u;
+            if (phases) if (int rc = phases->mark(stream, kPhStart)) return rc;
+            HIP_TRY(launch_ao_rays(g, stream));
+            slot->last_stream = stream;
+            slot->last_use = ++s->launches;
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+            slot->used = true;
+            if (phases) if (int rc = phases->mark(stream, kPhBounceRays)) return rc;
+            {
+                TraceParams p;
+                std::memset(&p, 0, sizeof(p));
+                p.rays = slot->gi_rays.get();
+                p.out = slot->gi_hits.get();
+                p.out_inst = slot->gi_inst.get();
+                p.n_items = n_rays;
+                if (int rc = walk(p)) return rc;
+            }
+            if (phases) if (int rc = phases->mark(stream, kPhBounceWalk)) return rc;
+            at.n_items = n_rays;
+            HIP_TRY(launch_hit_attr(at, kAttrRays, stream));
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+            if (phases) if (int rc = phases->mark(stream, kPhAttr)) return rc;
+            for (uint32_t k = 0; k < n_lights; k++) {
+                b.light = lights[k];
+                b.seed0 = frame0 + k * 64u + s0;
+                b.first = k == 0 ? 1u : 0u;
+                HIP_TRY(launch_bounce_light_rays(b, stream));
+                HIP_TRY(hipEventRecord(slot->done.get(), stream));
+                if (phases) if (int rc = phases->mark(stream, kPhShadowRays)) return rc;
+                TraceParams p;
+                std::memset(&p, 0, sizeof(p));
+                p.rays = slot->ao_rays.get();
+                p.out = reinterpret_cast<trx_hit *>(slot->ao_flags.get());
+                p.any_hit = 1u;
+                p.ray_mask = ray_mask; // (0: the unmasked launch; enqueue_locked hands a masked one the scene's table)
+                p.n_items = n_rays;
+                if (int rc = walk(p)) return rc;
+                if (phases) if (int rc = phases->mark(stream, kPhShadowWalk)) return rc;
+                HIP_TRY(launch_bounce_weight(b, stream));
+                HIP_TRY(hipEventRecord(slot->done.get(), stream));
+                if (phases) if (int rc = phases->mark(stream, kPhWeightGather)) return rc;
+            }
+            b.first = s0 == 0 ? 1u : 0u;
+            HIP_TRY(launch_bounce_gather(b, stream));
+            if (s0 + g.n_samples == n_samples) HIP_TRY(launch_bounce_finish(b, stream));
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+            if (phases) if (int rc = phases->mark(stream, kPhWeightGather)) return rc;
+        }
+    }
+    return TRX_OK;
+}
+
 } // namespace
 
 // what every light entry point refuses of its lights and sample count (api_image.cpp's trx_render_image_lit asks too)
@@ -425,6 +603,50 @@ int trx_light_term_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t 
     return TRX_OK;
 }
 
+// ---- one-bounce indirect light ------------------------------------------------------------------------------------------------
+
+int trx_bounce_light_rays_dev(trx_scene *s, uint32_t w, uint32_t h, trx_shard shard, const trx_light *light, uint32_t light_index,
+                              uint32_t frame0, uint32_t sample, float shadow_eps, const trx_ray *d_bounce_rays,
+                              const trx_hit *d_bounce_hits, const trx_hit_attr *d_bounce_attr, trx_ray *d_rays, void *stream) {
+    if (!s || !d_bounce_rays || !d_bounce_hits || !d_bounce_attr || !d_rays) return fail(TRX_ERR_INVALID, "null argument");
+    if (int rc = check_lights(light, 1, 1)) return rc;
+    if (light_index >= TRX_MAX_LIGHTS) return fail(TRX_ERR_INVALID, "light_index %u outside 0..%d", light_index, TRX_MAX_LIGHTS - 1);
+    if (sample >= TRX_MAX_AO_SAMPLES) return fail(TRX_ERR_INVALID, "sample %u outside 0..%d", sample, TRX_MAX_AO_SAMPLES - 1);
+    if (int rc = check_eps(shadow_eps)) return rc;
+    BounceParams b;
+    std::memset(&b, 0, sizeof(b));
+    uint32_t tiles = 0;
+    if (int rc = bounce_geometry(b.geom, w, h, shard, tiles)) return rc;
+    if (tiles == 0) return TRX_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, (hipStream_t)stream, slot)) return rc;
+    b.bounce_rays = d_bounce_rays;
+    b.bounce_hits = d_bounce_hits;
+    b.bounce_attr = d_bounce_attr;
+    b.rays = d_rays;
+    b.n_tiles = tiles;
+    b.n_samples = 1u;
+    b.seed0 = frame0 + light_index * 64u + sample;
+    b.shadow_eps = shadow_eps;
+    b.light = *light;
+    slot->last_stream = (hipStream_t)stream;
+    slot->last_use = ++s->launches;
+    HIP_TRY(launch_bounce_light_rays(b, (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(slot->done.get(), (hipStream_t)stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
+int trx_trace_indirect_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
+                           const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps,
+                           float shadow_eps, float bounce_albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst,
+                           const float *d_base, float *d_value, void *stream) {
+    return indirect_impl(s, view, w, h, shard, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps, bounce_albedo,
+                         d_primary, d_primary_inst, d_base, d_value, (hipStream_t)stream, nullptr);
+}
+
 // ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------
 
 uint64_t trx_debug_ao_scratch_cap(uint64_t bytes) {
@@ -468,6 +690,27 @@ int trx_debug_light_visibility_phases(trx_scene *s, const trx_view *view, uint32
             HIP_TRY(hipEventElapsedTime(&ms, ph.ev[c + k].get(), ph.ev[c + k + 1].get()));
             out_ms[k] += ms;
         }
+    return trx_scene_check(s, nullptr);
+}
+
+int trx_debug_indirect_phases(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                              const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps,
+                              float shadow_eps, float bounce_albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst,
+                              const float *d_base, float *d_value, float out_ms[6]) {
+    if (!s || !out_ms) return fail(TRX_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    BouncePhases ph;
+    if (int rc = indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps,
+                               shadow_eps, bounce_albedo, d_primary, d_primary_inst, d_base, d_value, nullptr, &ph))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    for (int k = 0; k < kPhCount; k++) out_ms[k] = 0.f;
+    for (size_t i = 1; i < ph.ev.size(); i++) {
+        if (ph.ends[i] < 0) continue;
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ph.ev[i - 1].get(), ph.ev[i].get()));
+        out_ms[ph.ends[i]] += ms;
+    }
     return trx_scene_check(s, nullptr);
 }
 

@@ -358,10 +358,13 @@ int trx_render_image_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint
         });
 }
 
-int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
-                         const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
-                         float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
-                         float normal_cos, uint8_t *out_rgba, float *out_ms) {
+// trx_render_image_lit (bounce_samples == 0) and trx_render_image_gi (bounce_samples >= 1: the indirect pass between the light
+// term and the shade, the term's values its base and its output)
+static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                      const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                      float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                      float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint8_t *out_rgba,
+                      float *out_ms) {
     if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
     if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
@@ -407,12 +410,39 @@ int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_
             rc = trx_light_term_dev(s, view, w, h, whole, lights, n_lights, light_samples, s->scratch_a.get(), s->scratch_attr.get(),
                                     d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
             if (rc) return rc;
+            if (bounce_samples != 0) {
+                rc = trx_trace_indirect_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples, bounce_eps,
+                                            shadow_eps, bounce_albedo, s->scratch_a.get(), s->scratch_ia.get(), d_value(), d_value(), nullptr);
+                if (rc) return rc;
+            }
             return trx_shade_value_dev(s, d_value(), n, d_rgba(), nullptr);
         },
         [&]() -> int {
             if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));
             return TRX_OK;
         });
+}
+
+int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                         const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                         float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                         float normal_cos, uint8_t *out_rgba, float *out_ms) {
+    return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                      ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, out_rgba, out_ms);
+}
+
+int trx_render_image_gi(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                        const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                        float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                        float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint8_t *out_rgba,
+                        float *out_ms) {
+    if (int rc = check_lights(lights, n_lights, light_samples)) return rc; // (the lit image's refusals come first, in its order)
+    if (bounce_samples == 0 || bounce_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "bounce_samples %u outside 1..%d", bounce_samples, TRX_MAX_AO_SAMPLES);
+    if (!(bounce_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "bounce_eps %g: must be >= 0", (double)bounce_eps);
+    if (!std::isfinite(bounce_albedo)) return fail(TRX_ERR_INVALID, "bounce_albedo %g is not finite", (double)bounce_albedo);
+    return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, out_rgba, out_ms);
 }
 
 } // extern "C"

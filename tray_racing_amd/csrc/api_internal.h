@@ -9,6 +9,7 @@
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
 //   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts;
 //                    trx_light_rays_dev / trx_trace_light_visibility_dev / trx_light_term_dev: the same chain per light, and the light term
+//                    trx_bounce_light_rays_dev / trx_trace_indirect_dev: one diffuse bounce - closest-hit bounce rays, their attributes, shadow rays from the bounce hits
 //   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
@@ -72,6 +73,13 @@ struct Slot {
     Event done;          // everything enqueued for this slot has finished
     DevBuf<trx_ray> ao_rays;   // trx_trace_ao_visibility_dev on this slot's stream: the rays of one chunk of tiles and samples ...
     DevBuf<uint8_t> ao_flags;  // ... and their occlusion flags (api_ao.cpp)
+    // trx_trace_indirect_dev on this slot's stream: per (tile, sample, pixel) of a chunk the bounce ray, its hit, instance id
+    // and attribute record and the sample's sum s; per pixel of the chunk's tiles the running sum A (api_ao.cpp)
+    DevBuf<trx_ray> gi_rays;
+    DevBuf<trx_hit> gi_hits;
+    DevBuf<uint32_t> gi_inst;
+    DevBuf<trx_hit_attr> gi_attr;
+    DevBuf<float> gi_sum, gi_acc;
     bool used = false;
     bool pinned = false;               // a resident kernel (the ray service) runs on this slot: never recycled for another stream
     hipStream_t last_stream = nullptr; // stream of the last launch on this slot

@@ -62,6 +62,10 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     std::vector<trx_light> lights;
     int light_samples = -1, light_mask = -1; // (not given: 1 sample, unmasked)
     float shadow_eps = -1.0f, ambient = -1.0f; // (not given: 0.01, 0.1)
+    // --bounce-samples N [--bounce-albedo a] [--bounce-eps e]: with --png --light the image is the GI image
+    // (trx_render_image_gi): the direct-light image plus one diffuse bounce of N samples per pixel
+    int bounce_samples = -1; // -1: not given, everything stays as it is
+    float bounce_albedo = -1.0f, bounce_eps = -1.0f; // (not given: 0.5, 0.01)
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -105,6 +109,9 @@ void usage() {
               "  [--light-samples 1..64] [--light-mask 0..255] [--shadow-eps e] [--ambient a] (with --light: samples per rect light,\n"
               "   the shadow rays' instance mask, their offset, the ambient term - scaled by the AO term of --ao-samples /\n"
               "   --ao-filter; not together with --ao-stride or --profile-rt)\n"
+              "  [--bounce-samples 1..64] [--bounce-albedo a] [--bounce-eps e] (with --png --light: one diffuse bounce - N bounce rays\n"
+              "   per pixel, the direct light at what they hit times the albedo (default 0.5), added to the direct-light image;\n"
+              "   not together with --ao-stride or --profile-rt)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -221,6 +228,16 @@ Options parse_args(int argc, char **argv) {
             o.ambient = (float)std::atof(need(i));
             if (!(o.ambient >= 0.0f) || !std::isfinite(o.ambient)) die("--ambient must be finite and >= 0");
         }
+        else if (a == "--bounce-samples") {
+            o.bounce_samples = std::atoi(need(i));
+            if (o.bounce_samples < 1 || o.bounce_samples > TRX_MAX_AO_SAMPLES) die("--bounce-samples takes 1.." + std::to_string(TRX_MAX_AO_SAMPLES));
+        } else if (a == "--bounce-albedo") {
+            o.bounce_albedo = (float)std::atof(need(i));
+            if (!(o.bounce_albedo >= 0.0f) || !std::isfinite(o.bounce_albedo)) die("--bounce-albedo must be finite and >= 0");
+        } else if (a == "--bounce-eps") {
+            o.bounce_eps = (float)std::atof(need(i));
+            if (!(o.bounce_eps >= 0.0f)) die("--bounce-eps must be >= 0");
+        }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
             if (m == "nodes") o.profile_rt = (int)TRX_HEAT_NODES;
@@ -271,6 +288,9 @@ Options parse_args(int argc, char **argv) {
         die("--light-samples, --light-mask, --shadow-eps and --ambient go with --light");
     if (!o.lights.empty() && !o.png) die("--light lights the image of --png");
     if (!o.lights.empty() && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--light draws the direct-light image: not together with --ao-stride or --profile-rt");
+    if (o.bounce_samples < 0 && (o.bounce_albedo >= 0.0f || o.bounce_eps >= 0.0f)) die("--bounce-albedo and --bounce-eps go with --bounce-samples N");
+    if (o.bounce_samples >= 0 && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--bounce-samples draws the GI image: not together with --ao-stride or --profile-rt");
+    if (o.bounce_samples >= 0 && o.lights.empty()) die("--bounce-samples bounces the light of --light");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -339,11 +359,21 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
         const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
-        check(trx_render_image_lit(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
-                                   o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
-                                   o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
-                                   radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos, rgba.data(), &ms),
-              "png frame");
+        if (o.bounce_samples >= 0)
+            // ... and one diffuse bounce on top of it (the GI image)
+            check(trx_render_image_gi(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                      o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
+                                      o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
+                                      radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
+                                      (uint32_t)o.bounce_samples, o.bounce_eps >= 0.0f ? o.bounce_eps : 0.01f,
+                                      o.bounce_albedo >= 0.0f ? o.bounce_albedo : 0.5f, rgba.data(), &ms),
+                  "png frame");
+        else
+            check(trx_render_image_lit(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                       o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
+                                       o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
+                                       radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos, rgba.data(), &ms),
+                  "png frame");
         if (!write_png(path, rgba, o.width, o.height)) die("Failed to save image " + path);
         if (o.verbose) std::printf("saved %s (device image, %zu lights, %.3f ms)\n", path.c_str(), o.lights.size(), ms);
         return;

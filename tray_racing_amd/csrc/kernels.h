@@ -290,6 +290,46 @@ struct LightTermParams {
 };
 hipError_t launch_light_term(const LightTermParams &p, hipStream_t stream);
 
+// One-bounce indirect light (trx_bounce_light_rays_dev / trx_trace_indirect_dev; include/trx.h, "indirect light").  The
+// bounce rays are k_ao_rays' (scratch layout, tmax = FLT_MAX), walked by the closest-hit rays launch and given attributes by
+// k_hit_attr in rays mode; the kernels here work on those three buffers, indexed alike: in record layout (scratch == 0, one
+// sample) by the pixel's record, in scratch layout by ((tile - tile0) * n_samples + sample) * 64 + pixel-in-tile.
+//   k_bounce_light_rays  one lane per (tile, sample, pixel): the shadow ray from the bounce hit toward ONE light (by value)
+//                        at rays[index]; the inert ray where the bounce found no surface or the hit faces away.
+//   k_bounce_weight      one lane per (tile, sample, pixel): sum[index] (set to 0 for the first light) gets intensity * g
+//                        added where the shadow ray was cast, flags[index] == 0 and g > 0.
+//   k_bounce_gather      one lane per pixel of the chunk's tiles: acc[(tile - tile0) * 64 + pixel] (set to 0 for the first
+//                        samples of the tiles) gets the chunk's sum[] added, samples ascending.
+//   k_bounce_finish      one lane per pixel of the chunk's tiles: value[record] = base + (albedo * acc) / n_total, or base
+//                        where the primary record is no surface (base: base[record], 0 with a null pointer).  The running sum
+//                        sits in acc, not in value, so base may be value itself.
+// scratch per (tile, sample): the bounce rays, hits, instance ids, attributes and sums beside the AO pass's rays and flags,
+// and the tile's 64 running sums (one set per tile: counted here per sample, which is at most what they take)
+constexpr uint32_t kBounceUnitBytes = kAoUnitBytes + 64u * (32u + 8u + 4u + 24u + 4u + 4u);
+struct BounceParams {
+    const trx_ray *bounce_rays;
+    const trx_hit *bounce_hits;
+    const trx_hit_attr *bounce_attr;
+    trx_ray *rays;                // the shadow rays (k_bounce_light_rays writes, k_bounce_weight reads)
+    const uint8_t *flags;         // k_bounce_weight: the occlusion flags of the shadow rays
+    float *sum;                   // k_bounce_weight, k_bounce_gather: s of every (tile, sample, pixel)
+    float *acc;                   // k_bounce_gather, k_bounce_finish: A of every pixel of the chunk's tiles
+    const trx_hit *primary;       // k_bounce_finish
+    const float *base;            // k_bounce_finish, or null
+    float *value;                 // k_bounce_finish
+    uint32_t tile0, n_tiles, n_samples, scratch;
+    uint32_t first;               // k_bounce_weight: the first light; k_bounce_gather: the first samples of these tiles
+    uint32_t n_total;             // k_bounce_finish: the pass's n_samples
+    TileGeom geom;
+    uint32_t seed0;               // the seed of the chunk's first sample: frame0 + light_index * 64 + sample
+    float shadow_eps, albedo;
+    trx_light light;
+};
+hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream);
+hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream);
+hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream);
+hipError_t launch_bounce_finish(const BounceParams &p, hipStream_t stream);
+
 // Resident waves the persistent kernel should be launched with on `device`.
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count);
 

@@ -1138,7 +1138,164 @@ __global__ void __launch_bounds__(256) k_light_term(const LightTermParams P) {
     P.value[rec] = E;
 }
 
+// One-bounce indirect light (include/trx.h, "indirect light"; kernels.h, BounceParams).  What the shadow-ray kernel and the
+// weight kernel share of a bounce: the ray, its hit and its attribute record at `index`; false where the bounce found no
+// surface (an inert bounce ray, a miss).  d = the bounce direction, n = the attribute normal flipped against d, Q = the hit
+// point - the header's statements, one binary32 operation each.
+struct BounceHit {
+    float dx, dy, dz, nx, ny, nz, qx, qy, qz;
+};
+__device__ __forceinline__ bool bounce_hit(const BounceParams &P, uint32_t index, BounceHit &B) {
+    const float4 *rp = reinterpret_cast<const float4 *>(P.bounce_rays + index);
+    const float4 a = rp[0], b = rp[1];
+    const trx_hit bh = P.bounce_hits[index];
+    if (b.w < 0.0f || !(bh.t < TRX_F32_MAX) || bh.prim == TRX_INVALID) return false;
+    const trx_hit_attr at = P.bounce_attr[index];
+    B.dx = b.x; B.dy = b.y; B.dz = b.z;
+    const float nd = (at.normal[0] * -B.dx + at.normal[1] * -B.dy) + at.normal[2] * -B.dz;
+    const float sg = copysignf(1.0f, nd);
+    B.nx = at.normal[0] * sg; B.ny = at.normal[1] * sg; B.nz = at.normal[2] * sg;
+    B.qx = a.x + B.dx * bh.t;
+    B.qy = a.y + B.dy * bh.t;
+    B.qz = a.z + B.dz * bh.t;
+    return true;
+}
+
+// The shadow ray of every (tile, sample, pixel) from its bounce hit toward ONE light: k_light_rays with the primary hit
+// replaced by the bounce hit - the normal comes from the attribute record, so no triangle and no instance row is read.  A
+// streaming kernel: 32 B of bounce ray, 8 B of hit, 24 B of attributes read per ray, 32 B written; the light is launch-uniform.
+__global__ void __launch_bounds__(256) k_bounce_light_rays(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * P.n_samples * 64u) return;
+    const uint32_t unit = item >> 6, k = item & 63u;
+    const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
+    uint32_t px, py, rec;
+    const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+    if (!inside && !P.scratch) return; // (no record is there)
+    const uint32_t index = P.scratch ? item : rec;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    BounceHit B;
+    if (bounce_hit(P, index, B)) { // (scratch layout: a lane outside the image reads the inert bounce ray k_ao_rays wrote there)
+        const float ox = B.qx - B.dx * P.shadow_eps;
+        const float oy = B.qy - B.dy * P.shadow_eps;
+        const float oz = B.qz - B.dz * P.shadow_eps;
+        float lx, ly, lz, tmax;
+        if (P.light.kind == TRX_LIGHT_DIRECTIONAL) {
+            light_toward(P.light, lx, ly, lz);
+            tmax = TRX_F32_MAX;
+        } else {
+            float Lx = P.light.position[0], Ly = P.light.position[1], Lz = P.light.position[2];
+            if (P.light.kind == TRX_LIGHT_RECT) {
+                const uint32_t seed = P.seed0 + sample;
+                const float u1 = hash_noise(px, py, seed);
+                const float u2 = hash_noise(px, py, seed + 1024u);
+                Lx = (Lx + u1 * P.light.edge1[0]) + u2 * P.light.edge2[0];
+                Ly = (Ly + u1 * P.light.edge1[1]) + u2 * P.light.edge2[1];
+                Lz = (Lz + u1 * P.light.edge1[2]) + u2 * P.light.edge2[2];
+            }
+            const float vx = Lx - ox, vy = Ly - oy, vz = Lz - oz;
+            const float dist = sqrtf(dot3(vx, vy, vz, vx, vy, vz));
+            const float inv = 1.0f / dist;
+            lx = vx * inv; ly = vy * inv; lz = vz * inv;
+            tmax = fminf(dist, TRX_F32_MAX);
+        }
+        if (dot3(B.nx, B.ny, B.nz, lx, ly, lz) > 0.0f) { // (false for NaN: a light at the bounce hit)
+            a.x = ox; a.y = oy; a.z = oz;
+            b = make_float4(lx, ly, lz, tmax);
+        }
+    }
+    float4 *out = reinterpret_cast<float4 *>(P.rays + index);
+    out[0] = a;
+    out[1] = b;
+}
+
+// One lane per (tile, sample, pixel) of the scratch: s (0 before the first light) + intensity * g where the shadow ray toward
+// this light was cast and is not occluded and g > 0; g is the light term's, at the bounce hit, toward the light's centre.
+__global__ void __launch_bounds__(256) k_bounce_weight(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * P.n_samples * 64u) return;
+    float s = P.first ? 0.0f : P.sum[item];
+    BounceHit B;
+    if (!(P.rays[item].tmax < 0.0f) && P.flags[item] == 0u && bounce_hit(P, item, B)) {
+        const trx_light &L = P.light;
+        float g;
+        if (L.kind == TRX_LIGHT_DIRECTIONAL) {
+            float lx, ly, lz;
+            light_toward(L, lx, ly, lz);
+            g = dot3(B.nx, B.ny, B.nz, lx, ly, lz);
+        } else {
+            float Cx = L.position[0], Cy = L.position[1], Cz = L.position[2];
+            if (L.kind == TRX_LIGHT_RECT) {
+                Cx = (Cx + 0.5f * L.edge1[0]) + 0.5f * L.edge2[0];
+                Cy = (Cy + 0.5f * L.edge1[1]) + 0.5f * L.edge2[1];
+                Cz = (Cz + 0.5f * L.edge1[2]) + 0.5f * L.edge2[2];
+            }
+            const float vx = Cx - B.qx, vy = Cy - B.qy, vz = Cz - B.qz;
+            const float q = dot3(vx, vy, vz, vx, vy, vz);
+            const float inv = 1.0f / sqrtf(q);
+            g = dot3(B.nx, B.ny, B.nz, vx * inv, vy * inv, vz * inv) / q;
+        }
+        if (g > 0.0f) s = s + L.intensity * g;
+    }
+    P.sum[item] = s;
+}
+
+// One lane per pixel of the chunk's tiles (the lanes outside the image too: their sums are 0): A (0 before the first samples
+// of the tile) + the chunk's s, samples ascending.
+__global__ void __launch_bounds__(256) k_bounce_gather(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * 64u) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    const uint32_t from = lt * P.n_samples * 64u + k;
+    float A = P.first ? 0.0f : P.acc[item];
+    for (uint32_t s = 0; s < P.n_samples; s++) A = A + P.sum[from + s * 64u];
+    P.acc[item] = A;
+}
+
+// One lane per pixel of the chunk's tiles: the pass's value.  base is read before value is written, by the same lane: they
+// may be one buffer.
+__global__ void __launch_bounds__(256) k_bounce_finish(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * 64u) return;
+    uint32_t px, py, rec;
+    if (!tile_pixel(P.geom, P.tile0 + (item >> 6), item & 63u, px, py, rec)) return;
+    const trx_hit ph = P.primary[rec];
+    float out = P.base ? P.base[rec] : 0.0f;
+    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) out = out + (P.albedo * P.acc[item]) / (float)P.n_total;
+    P.value[rec] = out;
+}
+
 } // namespace
+
+hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream) {
+    const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
+    if (n == 0) return hipSuccess;
+    if (n > 0xffffff00ull || p.light.kind > TRX_LIGHT_RECT || (!p.scratch && p.n_samples != 1u)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bounce_light_rays, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream) {
+    const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
+    if (n == 0) return hipSuccess;
+    if (n > 0xffffff00ull || p.light.kind > TRX_LIGHT_RECT || !p.scratch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bounce_weight, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream) {
+    if (p.n_tiles == 0) return hipSuccess;
+    if (p.n_tiles > 0x3ffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bounce_gather, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounce_finish(const BounceParams &p, hipStream_t stream) {
+    if (p.n_tiles == 0) return hipSuccess;
+    if (p.n_tiles > 0x3ffffffu || p.n_total == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bounce_finish, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream) {
     const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;

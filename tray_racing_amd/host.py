@@ -563,6 +563,20 @@ class Scene:
                                                _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_image_gi(self, view, width, height, lights, bounce_samples, bounce_eps=0.01, bounce_albedo=0.5, sem=L.SEM_HLSL, ray_mask=0,
+                        frame0=0, light_samples=1, shadow_eps=0.01, ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"),
+                        filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_gi - render_image_lit's passes up to the light term, one
+        diffuse bounce of bounce_samples rays per pixel added to it (trace_indirect_dev), the value shade; only the image
+        crosses the bus."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_gi(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0, light_samples,
+                                              shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius, depth_tol, normal_cos,
+                                              bounce_samples, bounce_eps, bounce_albedo, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
         """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
         of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
@@ -704,6 +718,11 @@ class Scene:
         L.check(self._lib.trx_trace_rays_dev(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_hits),
                                              C.c_void_p(stream)))
 
+    def trace_rays_inst_dev(self, d_rays, n, d_hits, d_inst=0, sem=L.SEM_HLSL, stream=0):
+        """trx_trace_rays_inst_dev: trace_rays_dev with the instance id of every hit at d_inst (n u32; 0: not wanted)."""
+        L.check(self._lib.trx_trace_rays_inst_dev(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_hits), C.c_void_p(d_inst),
+                                                  C.c_void_p(stream)))
+
     def trace_occluded_dev(self, d_rays, n, d_flags, sem=L.SEM_HLSL, stream=0):
         L.check(self._lib.trx_trace_occluded_dev(self._h, C.c_void_p(d_rays), n, sem, C.c_void_p(d_flags),
                                                  C.c_void_p(stream)))
@@ -782,6 +801,25 @@ class Scene:
         L.check(self._lib.trx_light_term_dev(self._h, C.byref(view), width, height, L.Shard(*shard), arr, len(arr), n_samples,
                                              C.c_void_p(d_primary), C.c_void_p(d_attr), C.c_void_p(d_lit), C.c_void_p(d_term), ambient,
                                              C.c_void_p(d_value), C.c_void_p(stream)))
+
+    def bounce_light_rays_dev(self, width, height, light, d_bounce_rays, d_bounce_hits, d_bounce_attr, d_rays, light_index=0, frame0=0,
+                              sample=0, shadow_eps=0.01, shard=(0, 1), stream=0):
+        """trx_bounce_light_rays_dev: the shadow rays from the bounce hits (the rays at d_bounce_rays, their hits and attribute
+        records, one per record laid out like the hit buffers of `shard`) toward `light` as explicit rays at d_rays; the inert
+        ray where the bounce found no surface or the surface faces away."""
+        L.check(self._lib.trx_bounce_light_rays_dev(self._h, width, height, L.Shard(*shard), C.byref(light), light_index, frame0, sample,
+                                                    shadow_eps, C.c_void_p(d_bounce_rays), C.c_void_p(d_bounce_hits),
+                                                    C.c_void_p(d_bounce_attr), C.c_void_p(d_rays), C.c_void_p(stream)))
+
+    def trace_indirect_dev(self, view, width, height, lights, d_primary, d_value, n_samples=1, sem=L.SEM_HLSL, ray_mask=0, frame0=0,
+                           bounce_eps=0.01, shadow_eps=0.01, bounce_albedo=0.5, d_primary_inst=0, d_base=0, shard=(0, 1), stream=0):
+        """trx_trace_indirect_dev: one float per record at d_value - d_base's value (0 without one; d_base may be d_value) plus
+        bounce_albedo / n_samples times the direct light found at the hits of n_samples cosine-hemisphere bounce rays (seeds
+        frame0 ..); ray_mask masks the shadow rays from the bounce hits, not the bounce rays."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask, arr, len(arr),
+                                                 frame0, n_samples, bounce_eps, shadow_eps, bounce_albedo, C.c_void_p(d_primary),
+                                                 C.c_void_p(d_primary_inst), C.c_void_p(d_base), C.c_void_p(d_value), C.c_void_p(stream)))
 
     def shade_value_dev(self, d_value, n, d_rgba, stream=0):
         """trx_shade_value_dev: n float values as RGBA8 through the code table (0 for negative or NaN, 255 from 1 upward)."""
