@@ -113,6 +113,15 @@ __device__ __forceinline__ float4 unspecified4() {
     v = __builtin_nondeterministic_value(v);
     return make_float4(v.x, v.y, v.z, v.w);
 }
+// ... and one (the plain walk's per-trip words: a `= 0` at the head of the trip is a v_mov in every trip).  An empty
+// asm statement's output, not a frozen undef: where the value meets a computed one at a join the compiler gives a
+// frozen undef the value 0, and that is the v_mov again.  (volatile: not hoisted out of the loop, where it would hold
+// a register for the whole walk)
+__device__ __forceinline__ uint32_t unspecified1() {
+    uint32_t v;
+    asm volatile("" : "=v"(v));
+    return v;
+}
 
 // two planes at once: q * a + b on both halves (separate roundings unless NODE & 2)
 template <int NODE>
@@ -256,14 +265,17 @@ struct NodeFrame {
     float ax, ay, az, bx, by, bz;
 };
 template <int NODE>
-__device__ __forceinline__ NodeFrame node_frame(const Ray &r, const uint4 n0, const int pow2) {
+__device__ __forceinline__ NodeFrame node_frame(const Ray &r, uint4 n0, const int pow2) {
+    // (every lane holds the same record: the exponent word is a scalar, its three scale words are formed by the scalar
+    // unit - six shifts and ands a lane otherwise - and the multiplications take them as scalar operands; the same floats)
+    n0.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)n0.w);
     TRX_NODE_FRAME(r, n0, pow2)
     return NodeFrame{ax, ay, az, bx, by, bz};
 }
 template <int NODE>
 __device__ __forceinline__ uint32_t node_intersect_kept(const Ray &r, float max_distance, const NodeFrame f, const uint4 n1,
                                                         const float *dec_pos, const float *dec_neg, uint32_t keep) {
-    const float ax = f.ax, ay = f.ay, az = f.az, bx = f.bx, by = f.by, bz = f.bz;
+    float ax = f.ax, ay = f.ay, az = f.az, bx = f.bx, by = f.by, bz = f.bz;
     const float2 *const qx = reinterpret_cast<const float2 *>(r.dx < 0.0f ? dec_neg : dec_pos);
     const float2 *const qy = reinterpret_cast<const float2 *>((r.dy < 0.0f ? dec_neg : dec_pos) + 16);
     const float2 *const qz = reinterpret_cast<const float2 *>((r.dz < 0.0f ? dec_neg : dec_pos) + 32);
@@ -277,6 +289,10 @@ __device__ __forceinline__ uint32_t node_intersect_kept(const Ray &r, float max_
     for (uint32_t m = keep; m != 0u; m &= m - 1u) {
         const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__builtin_ctz(m))); // (wave-uniform: a scalar)
         const float2 x = qx[j], y = qy[j], z = qz[j]; // {near, far}
+        // (no instruction: the six operands are redefined inside the loop's block, where instruction selection sees the
+        // pairs {a, a}, {b, b} of plane2 and takes both halves from one register, op_sel_hi, as in node_intersect; formed
+        // ahead of the loop they were six register moves a step)
+        asm("" : "+v"(ax), "+v"(ay), "+v"(az), "+v"(bx), "+v"(by), "+v"(bz));
         const f32x2 tx = plane2<NODE>(f32x2{x.x, x.y}, ax, bx);
         const f32x2 ty = plane2<NODE>(f32x2{y.x, y.y}, ay, by);
         const f32x2 tz = plane2<NODE>(f32x2{z.x, z.y}, az, bz);

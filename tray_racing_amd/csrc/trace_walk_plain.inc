@@ -3,7 +3,7 @@
             for (;;) {
                 const bool act = has_ray;
                 const int pow2 = (NODE & 1) ? 0 : pow2_exact(P, r, act); // (literal-division variants only)
-                uint2 tri = make_uint2(0u, 0u);
+                uint2 tri = make_uint2(unspecified1(), 0u); // (.x: read where .y says there are triangles; no trip pays to zero it)
                 trip++;
                 if (!TLAS && MODE != kModePrimary && (trip & 7u) == 0u) old_ray_priority(); // (measured without effect in the two-level kernels)
                 // Coherent primary rays (BLAS only): when every lane that steps visits the SAME node - 47 % of the wave-level
@@ -15,6 +15,21 @@
                 // profiles/r05_ab_5_tlas.log)
                 constexpr bool kUni = MODE == kModePrimary && !COUNT;
                 bool uni_done = false;
+                // The node a lane steps to next, worked out ONCE per trip, for the look below and for either kind of step.
+                // (two-level walks: a lane may hold a parked triangle group instead of a node group, and node
+                // indices are absolute - rays inside different instances of one BLAS do share its nodes, each
+                // with its own object-space ray.  BLAS-only: a lane at the top of the loop always holds a node group -
+                // triangle groups are drained in the trip that found them; only the TLAS walk parks them on the stack.)
+                // Lanes without a group leave both words unspecified: nothing reads them there.
+                const bool group = act && (!TLAS || (cur.y & 0xff000000u) != 0u);
+                uint32_t node_index = unspecified1(), child_bit = unspecified1();
+                if (group) {
+                    const uint32_t hits_imask = cur.y; // != 0
+                    child_bit = 31u - (uint32_t)__builtin_clz(hits_imask);
+                    const uint32_t slot = (child_bit - 24u) ^ (r.oct_inv4 & 0xffu);
+                    node_index = cur.x + (uint32_t)__popc(hits_imask & ~(0xffffffffu << slot));
+                    if (TLAS) node_index += bvh_off;
+                }
                 if constexpr (kUni) {
                     // (the look itself is some thirty instructions.  Before the packet test a trip whose lanes wanted different
                     // nodes was followed by kUniCool = 1 trips that did not look - bistro-class frame -0.5 %, hairball-class
@@ -27,21 +42,16 @@
                         uni_cool--;
                     } else
                     if (P.uni_decode) {
-                        uint32_t node_index = 0u, child_bit = 0u;
-                        // (two-level walks: a lane may hold a parked triangle group instead of a node group, and node
-                        // indices are absolute - rays inside different instances of one BLAS do share its nodes, each
-                        // with its own object-space ray)
-                        const bool group = act && (!TLAS || (cur.y & 0xff000000u) != 0u);
-                        if (group) {
-                            const uint32_t hits_imask = cur.y;
-                            child_bit = 31u - (uint32_t)__builtin_clz(hits_imask);
-                            const uint32_t slot = (child_bit - 24u) ^ (r.oct_inv4 & 0xffu);
-                            node_index = cur.x + (uint32_t)__popc(hits_imask & ~(0xffffffffu << slot));
-                            if (TLAS) node_index += bvh_off;
-                        }
+                        // (`first` is a node of the scene whenever the step turns out uniform: the first stepping lane's, or
+                        // node 0 in a trip in which no lane steps - a scalar select)
                         const unsigned long long stepping = __ballot(act);
-                        const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)node_index, (int)(__ffsll((long long)stepping) - 1));
-                        if (__ballot(act && (!group || node_index != first)) == 0ull) { // wave-uniform: every lane takes this branch or none does
+                        uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)node_index, (int)(__ffsll((long long)stepping) - 1));
+                        if (stepping == 0ull) first = 0u;
+                        // (the lanes that differ as ONE comparison's mask, cut to the stepping lanes by the scalar unit: the
+                        // ballot of `act && ...` went through a 0 / 1 register and a second comparison)
+                        unsigned long long differ = ballot64(node_index != first);
+                        if (TLAS) differ |= ~ballot64((cur.y & 0xff000000u) != 0u);
+                        if ((differ & stepping) == 0ull) { // wave-uniform: every lane takes this branch or none does
                             const uint4 *np = P.nodes + (size_t)first * 5;
                             // 48 lanes convert one byte each (whether or not they hold a ray), LDS hands the floats to all
                             // (byte 32 + 8 p + c = plane p of child c, planes in the order min_x max_x min_y max_y min_z max_z; the
@@ -54,8 +64,9 @@
                             // table slots - one LDS round trip more - and the whole test in registers, DPP and v_readlane.)
                             const bool culling = kCull && cull_ok && ((NODE & 1) != 0 || pow2 == 2); // (literal divisions: where every ray of the step takes both shortcuts)
                             // (scalar-cache header reads: measured slower, profiles/r06_ab_uni_scalar.log)
-                            uint4 n0 = make_uint4(0u, 0u, 0u, 0u);
-                            if (culling || act) n0 = np[0];
+                            // (every lane loads the record, with or without a ray - one line, broadcast: no access more than for
+                            // the lanes that need it, and no zeroes for the others.  A variable of this trip only, DESIGN.md section 4.)
+                            const uint4 n0 = np[0];
                             // (the lane number taken afresh here, not as loop-invariant masks: measured slower, profiles/r06_ab_lane_spills.log)
                             const uint32_t dl = lane;
                             if (dl < 48u) {
@@ -116,17 +127,8 @@
                     }
                 }
                 if (act && !uni_done) {
-                    // BLAS-only: a lane at the top of the loop always holds a node group (triangle groups are drained
-                    // in the trip that found them; only the TLAS walk parks them on the stack)
-                    if (!TLAS || (cur.y & 0xff000000u)) {
-                        const uint32_t hits_imask = cur.y;
-                        const uint32_t child_bit = 31u - (uint32_t)__builtin_clz(hits_imask); // hits_imask != 0
-                        const uint32_t child_base = cur.x;
+                    if (group) { // (node_index, child_bit: from the head of the trip)
                         cur.y &= ~(1u << child_bit);
-                        const uint32_t slot = (child_bit - 24u) ^ (r.oct_inv4 & 0xffu);
-                        const uint32_t rel = (uint32_t)__popc(hits_imask & ~(0xffffffffu << slot));
-                        uint32_t node_index = child_base + rel;
-                        if (TLAS) node_index += bvh_off;
                         // (tried: when every lane wants the same node - 47 % of the wave-level steps on the bistro-class frame,
                         // 90 % on the kitchen-class one - one copy through the scalar cache instead of 64 through the vector
                         // path: no change in frame time; DESIGN.md section 4)
