@@ -110,6 +110,29 @@ int trx_debug_indirect_phases(trx_scene *scene, const trx_view *view, uint32_t w
                               const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base,
                               float *d_value, float out_ms[6]);
 
+/* Diagnostics: the scheduling state of the launch slot whose last launch ran on `stream` - what decides in which order,
+ * and by which schedule, the next image pass of `kind` (0 primary, 1 AO) on that stream deals out its tiles.  Hits never
+ * depend on it; the tests read it to know that the state they claim to exercise (an order learnt, replayed frozen,
+ * refiled, dropped; a tuner phase) was really reached. */
+typedef struct trx_schedule_state {
+    uint32_t have_slot;  /* a launch slot of the scene was last used by `stream` (everything below is 0 otherwise) */
+    uint32_t slot;       /* ... its index */
+    uint32_t have_lists; /* the slot holds tile lists of this kind (0: capacity .. other_sum, key are 0) */
+    uint32_t capacity;   /* tiles the lists are sized for */
+    uint32_t lpt_cap;    /* entries one of the 128 lists holds */
+    uint32_t lpt_sel;    /* which of the two list sets is on file (read by the next frame) */
+    uint32_t count_sum;  /* the set on file: sum of its 128 counts */
+    uint32_t n_over;     /* ... and how many of them exceed lpt_cap (a list that dropped entries) */
+    uint32_t other_sum;  /* sum of the 128 counts of the other set (0 between frames: it takes the next new order) */
+    uint32_t mode, frames, phase; /* the schedule tuner: mode the next frame runs in, frames of the phase so far, phase 0..3 */
+    uint64_t key;        /* the image geometry the order on file was learnt for (opaque; 0 = none) */
+} trx_schedule_state;
+/* Waits for `stream`, then fills *out and, with out_order non-null, writes the tile ids of the set on file in the order a
+ * frame reads them - lists (15 - b) * 8 + shard for b = 0..15, shard = 0..7, concatenated, each cut at lpt_cap - up to
+ * max_tiles of them (the rest of out_order is left alone).  Changes no state: neither the slot's nor the device's. */
+int trx_debug_schedule_state(trx_scene *scene, void *stream, uint32_t kind, trx_schedule_state *out, uint32_t *out_order,
+                             uint32_t max_tiles);
+
 /* Kernel variant selection (tuning aid; 0 = default).  Returns the previous
  * value.  Variants compute identical results. */
 uint32_t trx_set_kernel_variant(uint32_t variant);

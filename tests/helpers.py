@@ -316,3 +316,129 @@ def leg_scene(T, flat, padded, modes, tri_format=None, tri_bytes=None):
 def is_twin(name):
     """Scene names ending in _pipe are the padded twins: (base name, padded)."""
     return (name[:-len("_pipe")], True) if name.endswith("_pipe") else (name, False)
+
+
+# ---- poisoned frames: every launch writes into a buffer that holds nothing of the previous one ------------------------------
+
+# A record no trace writes: t = a NaN with every bit set, prim = 0xFFFFFFFF (a miss is {+inf, 0xFFFFFFFF}).  expect() asserts
+# that against every expected record and takes the second pattern where it does not hold.
+HIT_SENTINELS = (-1, 0x5A5A5A5A5A5A5A5A)
+INST_SENTINEL = 0x5A5A5A5A    # (0xFFFFFFFF is the instance id of a miss)
+
+
+def image_tile_of(w, h, stride=None):
+    """record index -> 8x8 tile id of an image-layout buffer (frames of `stride` records: tile ids continue frame after
+    frame, as the kernels number the chunks of a batch)."""
+    tx, ty = (w + 7) // 8, (h + 7) // 8
+
+    def tile_of(idx):
+        f, p = (idx // stride, idx % stride) if stride else (0, idx)
+        return f * tx * ty + (p // w // 8) * tx + (p % w) // 8
+    return tile_of
+
+
+def shard_pixels(w, h, index, count):
+    """[w * h] bool: the pixels of the tiles that shard `index` of `count` owns (tile t belongs to shard t % count)."""
+    tx = (w + 7) // 8
+    y, x = np.divmod(np.arange(w * h), w)
+    return ((y // 8) * tx + x // 8) % count == index
+
+
+class PoisonedFrames:
+    """Device buffers for the hit records of a launch (and, with `inst`, its instance ids) that are filled with a sentinel
+    on the launch stream before every launch and compared on the device after it: a tile the launch skipped still holds the
+    sentinel, whatever the previous launch wrote there.
+
+        pf = PoisonedFrames(n)                    # n records
+        want = pf.expect(oracle_hits)             # uploaded once; (hits, written=mask): the rest must stay untouched
+        pf.poison(stream); launch(pf.ptr, ...); pf.check(want, frame, stream)
+
+    `stream` is a torch.cuda.Stream or None (the null stream).  Equality is bit equality of t and prim (the 8-byte record)."""
+
+    def __init__(self, n, inst=False, tile_of=None, what=""):
+        import torch
+        self.torch, self.n, self.what = torch, int(n), what
+        self.tile_of = tile_of or (lambda idx: idx // 64)
+        self.sentinel = HIT_SENTINELS[0]
+        self.hits = torch.empty(self.n, dtype=torch.int64, device="cuda")
+        self.inst = torch.empty(self.n, dtype=torch.int32, device="cuda") if inst else None
+        self._armed = False     # poisoned once: the sentinel is settled
+        self._expected = 0
+
+    @property
+    def ptr(self):
+        return self.hits.data_ptr()
+
+    @property
+    def inst_ptr(self):
+        return self.inst.data_ptr() if self.inst is not None else 0
+
+    def _signed(self, pattern):
+        return pattern - (1 << 64) if pattern >= 1 << 63 else pattern
+
+    def expect(self, hits, inst=None, written=None):
+        """The expected content of the buffers after a launch, on the device: `hits` ({t, prim} records, as many as the
+        buffer holds or fewer - the rest is expected untouched), `inst` their instance ids (u32), `written` a bool mask of
+        the records the launch writes (default all of `hits`)."""
+        torch = self.torch
+        rec = np.ascontiguousarray(hits).view(np.int64).reshape(-1)
+        assert rec.size <= self.n
+        mask = np.ones(rec.size, dtype=bool) if written is None else np.asarray(written, dtype=bool).reshape(-1)
+        assert mask.size == rec.size
+        if (rec[mask] == self._signed(self.sentinel)).any():
+            assert not self._armed and not self._expected, "%s: an expected record equals the sentinel in use" % self.what
+            self.sentinel = HIT_SENTINELS[1]
+        assert not (rec[mask] == self._signed(self.sentinel)).any(), "%s: expected records equal both sentinels" % self.what
+        self._expected += 1
+        full = np.full(self.n, self._signed(self.sentinel), dtype=np.int64)
+        full[:rec.size][mask] = rec[mask]
+        out = [torch.from_numpy(full).cuda(), None]
+        if self.inst is not None:
+            ids = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
+            assert ids.size == rec.size and not (ids[mask] == INST_SENTINEL).any(), "%s: an instance id equals the sentinel" % self.what
+            full_i = np.full(self.n, INST_SENTINEL, dtype=np.uint32)
+            full_i[:ids.size][mask] = ids[mask]
+            out[1] = torch.from_numpy(full_i.view(np.int32)).cuda()
+        return tuple(out)
+
+    def _on(self, stream):
+        return self.torch.cuda.stream(stream) if stream is not None else self.torch.cuda.stream(self.torch.cuda.default_stream())
+
+    def poison(self, stream=None):
+        self._armed = True
+        with self._on(stream):
+            self.hits.fill_(self._signed(self.sentinel))
+            if self.inst is not None:
+                self.inst.fill_(INST_SENTINEL)
+
+    def check(self, expected, frame, stream=None):
+        """Compares on `stream` (behind the launch) and waits for the answer; a mismatch names the frame, how many records
+        still hold the sentinel, how many hold something else that is wrong, and the tiles they belong to."""
+        torch = self.torch
+        with self._on(stream):
+            ok = torch.equal(self.hits, expected[0]) and (self.inst is None or torch.equal(self.inst, expected[1]))
+            if ok:
+                return
+            msgs = []
+            for name, got, want, sentinel in (("hit records", self.hits, expected[0], self._signed(self.sentinel)),
+                                              ("instance ids", self.inst, expected[1], INST_SENTINEL)):
+                if got is None:
+                    continue
+                bad = got != want
+                stale = bad & (got == sentinel)
+                idx = torch.nonzero(bad).reshape(-1).cpu().numpy()
+                tiles = np.unique(self.tile_of(idx))
+                msgs.append("%s: %d still hold the sentinel, %d are wrong, in %d tiles %s" % (
+                    name, int(stale.sum()), int((bad & ~stale).sum()), tiles.size, tiles[:32].tolist()))
+        raise AssertionError("%s, frame %s: %s" % (self.what, frame, "; ".join(msgs)))
+
+
+def assert_tile_permutation(order, n_tiles, what=""):
+    """The order on file (Scene.schedule_state(...)["order"]) names every tile 0 .. n_tiles - 1 exactly once."""
+    order = np.asarray(order, dtype=np.int64)
+    assert order.size == n_tiles, "%s: %d tile ids on file for %d tiles" % (what, order.size, n_tiles)
+    seen = np.bincount(order[order < n_tiles], minlength=n_tiles)
+    missing, twice = np.flatnonzero(seen == 0), np.flatnonzero(seen > 1)
+    assert missing.size == 0 and twice.size == 0 and (order < n_tiles).all(), \
+        "%s: not a permutation of %d tiles: missing %s, more than once %s, out of range %s" % (
+            what, n_tiles, missing[:16].tolist(), twice[:16].tolist(), order[order >= n_tiles][:16].tolist())

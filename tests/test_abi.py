@@ -50,6 +50,37 @@ def test_struct_sizes_match_the_header(trx):
     assert trx.HIT_DTYPE.itemsize == 8 and trx.RAY_DTYPE.itemsize == 32
 
 
+def test_schedule_state_binding_matches_the_header(trx, tmp_path):
+    """trx_debug_schedule_state (include/trx_dev.h): the ctypes prototype has the header's parameters, and the ctypes struct
+    the size and field offsets a C compiler gives trx_schedule_state."""
+    from tray_racing_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "trx_dev.h")).read(), flags=re.S)
+    args = re.search(r"\btrx_debug_schedule_state\s*\(([^;{]*?)\)\s*;", text, flags=re.S).group(1)
+    kinds = ["ptr" if "*" in a else a.split()[0] for a in args.split(",")]
+    assert kinds == ["ptr", "ptr", "uint32_t", "ptr", "ptr", "uint32_t"]
+    res, argtypes = _lib.SIGNATURES["trx_debug_schedule_state"]
+    assert res is C.c_int
+    assert argtypes == [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(_lib.ScheduleState), C.c_void_p, C.c_uint32]
+    body = re.search(r"typedef struct trx_schedule_state \{(.*?)\} trx_schedule_state;", text, flags=re.S).group(1)
+    fields = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.strip().split(None, 1)[1].split(",")]
+    assert fields == [n for n, _ in _lib.ScheduleState._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "trx_dev.h"\nint main(void) {\n'
+                   '    printf("%zu", sizeof(trx_schedule_state));\n'
+                   + "".join('    printf(" %%zu", offsetof(trx_schedule_state, %s));\n' % n for n in fields)
+                   + "    return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c11", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           str(src), "-o", exe])
+    got = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    assert got == [C.sizeof(_lib.ScheduleState)] + [getattr(_lib.ScheduleState, n).offset for n in fields]
+    assert C.sizeof(_lib.ScheduleState) == 56
+    # without a scene the call reports an error, it does not crash
+    lib = trx.load()
+    st = _lib.ScheduleState()
+    assert lib.trx_debug_schedule_state(None, None, 0, C.byref(st), None, 0) == _lib.TRX_ERR_INVALID
+
+
 def test_product_never_references_the_oracle():
     """The product path must not import, link or call anything under oracle/."""
     pkg = os.path.join(ROOT, "tray_racing_amd")

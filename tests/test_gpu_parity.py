@@ -14,8 +14,8 @@ import threading
 import numpy as np
 import pytest
 
-from helpers import (ALL_SEMS, F32_MAX, assert_hits_equal, bits, deep_chain_scene, golden_inputs, is_twin, leg_scene, make_scene,
-                     random_rays)
+from helpers import (ALL_SEMS, F32_MAX, PoisonedFrames, assert_hits_equal, bits, deep_chain_scene, golden_inputs, image_tile_of,
+                     is_twin, leg_scene, make_scene, random_rays)
 
 pytestmark = pytest.mark.gpu
 
@@ -658,7 +658,11 @@ def test_device_pointers_streams_and_runner(trx, orc):
     out = torch.zeros(w * h, dtype=torch.int64, device="cuda")
     ao = torch.zeros(w * h, dtype=torch.int64, device="cuda")
     with torch.cuda.stream(stream):
-        for _ in range(6):  # more launches than launch slots: slot reuse is stream-ordered
+        # six launches on the stream's one launch slot, no host wait between them; the buffer is poisoned on the stream
+        # ahead of each, so that what is compared below is what the LAST launch - a frozen replay - wrote, not what an
+        # earlier one left (every frame checked: tests/test_gpu_schedule_state.py)
+        for _ in range(6):
+            out.fill_(-1)
             sc.trace_primary_dev(view, w, h, out.data_ptr(), sem=3, stream=stream.cuda_stream)
         sc.trace_ao_dev(view, w, h, out.data_ptr(), ao.data_ptr(), sem=3, frame=0, ao_eps=0.01,
                         stream=stream.cuda_stream)
@@ -1212,20 +1216,28 @@ def test_scheduling_variants_and_streams_do_not_change_results(trx, orc):
         NO_THIN = 1 << 28   # dry waves never switch to eight lanes per ray
         for variant in (0, NO_LPT, ONE_Q, NO_LPT | ONE_Q, never_compact, compact3, (1 << 22), 4 << 16, 12 << 8, NO_THIN, NO_THIN | (1 << 16)):
             lib.trx_set_kernel_variant(variant)
-            for rep in range(6):  # > kSlots launches: every slot gets to read its own feedback
+            # host-form calls all land on the null stream's launch slot (one of kSlots = 8): six frames there, the first
+            # files the tile order, the rest replay it.  (They write into the scene's scratch, which holds the previous
+            # frame: a skipped tile would not show here - tests/test_gpu_schedule_state.py poisons every frame.)
+            for rep in range(6):
                 got, ao, _ = sc.trace_primary_ao(view, w, h, sem=3, frame=4, ao_eps=0.01)
                 assert_hits_equal(got, want, "variant 0x%x rep %d" % (variant, rep))
                 assert_hits_equal(ao, want_ao, "variant 0x%x rep %d ao" % (variant, rep))
         lib.trx_set_kernel_variant(0)
         streams = [torch.cuda.Stream() for _ in range(3)]
-        outs = [torch.zeros(w * h, dtype=torch.int64, device="cuda") for _ in range(3)]
+        pfs = [PoisonedFrames(w * h, tile_of=image_tile_of(w, h), what="3 frames in flight, stream %d" % k) for k in range(3)]
+        wants = [pf.expect(want) for pf in pfs]
         for k in range(30):
             s = streams[k % 3]
-            sc.trace_primary_dev(view, w, h, outs[k % 3].data_ptr(), sem=3, stream=s.cuda_stream)
+            pfs[k % 3].poison(s)
+            sc.trace_primary_dev(view, w, h, pfs[k % 3].ptr, sem=3, stream=s.cuda_stream)
+            if k % 3 == 2:
+                for j in range(3):
+                    pfs[j].check(wants[j], k - 2 + j, streams[j])
         for s in streams:
             sc.check(s.cuda_stream)
-        for o in outs:
-            assert_hits_equal(D.int64_to_hits(o), want, "3 frames in flight")
+        for pf in pfs:
+            assert_hits_equal(D.int64_to_hits(pf.hits), want, "3 frames in flight")
     finally:
         lib.trx_set_kernel_variant(0)
         sc.close()
@@ -1310,12 +1322,22 @@ def test_camera_cuts_and_schedule_modes_never_change_the_hits(trx, orc):
             assert_hits_equal(sc.trace_primary(view, w, h, sem=3)[0], want[0], "every frame a cut, frame %d" % k)
         # the feedback tunes itself: 128 frames with it (the order of the first one replayed unchanged while the view is),
         # 4 without, 4 with mid-tile refills, then the fastest mode holds - whichever mode a frame runs in, and across the
-        # switches, the hits are the oracle's
+        # switches, the hits are the oracle's.  On the null stream's slot like the host-form calls above, but into a buffer
+        # that is poisoned before every frame and compared after it: the scene's scratch still holds the previous frame of
+        # this very view, which would hide a tile that a frame skipped.  (An A far A far loop would poison the scratch too,
+        # but every frame of it is a cut and restarts the tuner: the mode switches would never come.)
         lib.trx_set_kernel_variant(0)
+        pf = PoisonedFrames(w * h, tile_of=image_tile_of(w, h), what="self-tuning feedback")
+        expected = pf.expect(want[0])
         for k in range(150):
-            got = sc.trace_primary(view, w, h, sem=3)[0]
-            if k % 7 == 0 or 120 <= k < 142:
-                assert_hits_equal(got, want[0], "self-tuning feedback, frame %d" % k)
+            pf.poison()
+            sc.trace_primary_dev(view, w, h, pf.ptr, sem=3)
+            pf.check(expected, k)
+        st = sc.schedule_state(0)
+        # the last first-frame launch above left the tuner at frames = 1, so this loop's frame k is the tuner's frame k + 1:
+        # the probes start after frame 126, the decision falls in frame 134, and 15 frames have been held since
+        assert (st["phase"], st["frames"]) == (3, 15), st
+        sc.check()
     finally:
         lib.trx_set_kernel_variant(0)
         sc.close()

@@ -85,6 +85,14 @@ class RayCost(C.Structure):
     _fields_ = [("n_node", C.c_uint16), ("n_tri", C.c_uint16)]
 
 
+class ScheduleState(C.Structure):
+    """trx_schedule_state (include/trx_dev.h): a launch slot's tile-order lists and schedule tuner, read back."""
+    _fields_ = [("have_slot", C.c_uint32), ("slot", C.c_uint32), ("have_lists", C.c_uint32), ("capacity", C.c_uint32),
+                ("lpt_cap", C.c_uint32), ("lpt_sel", C.c_uint32), ("count_sum", C.c_uint32), ("n_over", C.c_uint32),
+                ("other_sum", C.c_uint32), ("mode", C.c_uint32), ("frames", C.c_uint32), ("phase", C.c_uint32),
+                ("key", C.c_uint64)]
+
+
 class RayHit(C.Structure):
     _fields_ = [("primitive_id", C.c_uint32), ("geometry_id", C.c_uint32), ("instance_id", C.c_uint32),
                 ("t", C.c_float)]
@@ -210,6 +218,7 @@ SIGNATURES = {
     "trx_debug_traverse1_stats": (_i, [_P, C.POINTER(_u64), C.POINTER(_u64)]),
     "trx_debug_scene_info": (_i, [_P, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_u32)]),
     "trx_debug_walk_kind": (_i, [_P, _u32]),
+    "trx_debug_schedule_state": (_i, [_P, _P, _u32, C.POINTER(ScheduleState), _P, _u32]),
     "trx_debug_fetch_rate": (_i, [_P, _u32, _u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "trx_debug_copy_rate": (_i, [_i, _u64, _u32, C.POINTER(C.c_double)]),
     "trx_debug_service_stats": (_i, [_P] + [C.POINTER(_u64)] * 5),

@@ -89,7 +89,7 @@ struct Slot {
     // next one of that kind with the same image geometry starts its heaviest tiles first.  One state per kind: the
     // reference's frame loop runs both passes on one queue, and each has its own order.
     struct Order {
-        DevBuf<uint32_t> lists; // two sets of {16 counts, 16 lists}
+        DevBuf<uint32_t> lists; // two sets of {128 counts, 128 lists}: 16 cost buckets x kLptShards shards (api_launch.cpp)
         uint32_t capacity = 0;  // tiles the lists are sized for
         bool have_views = false; // view[] holds the views of a previous launch
         uint64_t key = 0;    // (width, height, shard, mode) the lists were measured for; 0 = none

@@ -212,7 +212,7 @@ int enqueue_locked(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool co
     const uint32_t n_tiles = (p.n_items + 63u) >> 6;
     uint64_t key = 0;
     if (lpt) {
-        // per slot: two sets of {16 bucket counts, 16 lists of n_tiles tile ids}; a frame reads the
+        // per slot: two sets of {128 counts, 128 lists of list_cap tile ids} (16 buckets x kLptShards); a frame reads the
         // set the previous frame on this slot wrote and writes the other one
         const uint32_t n_lists = 16 * kLptShards;
         const uint32_t list_cap = n_tiles / 2 + 64; // a list holds ~1/8 of one bucket; overflow only drops the order
@@ -354,6 +354,61 @@ int read_overflow(trx_scene *s, SlotCounters *ctr) {
 }
 
 } // namespace trxapi
+
+// Read-only: the slot is looked up as acquire_slot looks it up, never set up, and nothing is written on either side.
+extern "C" int trx_debug_schedule_state(trx_scene *s, void *stream, uint32_t kind, trx_schedule_state *out, uint32_t *out_order,
+                                        uint32_t max_tiles) {
+    if (!s || !out) return trxapi::fail(TRX_ERR_INVALID, "null scene or state");
+    if (kind > 1u) return trxapi::fail(TRX_ERR_INVALID, "unknown pass kind %u (0 primary, 1 AO)", kind);
+    std::memset(out, 0, sizeof(*out));
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    const trxapi::Slot *slot = nullptr;
+    for (int i = 0; i < trxapi::kSlots && !slot; i++)
+        if (s->slots[i].used && s->slots[i].last_stream == (hipStream_t)stream) {
+            slot = &s->slots[i];
+            out->slot = (uint32_t)i;
+        }
+    if (!slot) return TRX_OK;
+    out->have_slot = 1u;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    trx::FbState fb;
+    unsigned int sel = 0;
+    HIP_TRY(hipMemcpy(&fb, &slot->ctr.get()->fb[kind], sizeof(fb), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&sel, &slot->ctr.get()->lpt_sel[kind], sizeof(sel), hipMemcpyDeviceToHost));
+    out->mode = fb.mode;
+    out->frames = fb.frames;
+    out->phase = fb.phase;
+    const trxapi::Slot::Order &ord = slot->order[kind];
+    if (!ord.lists || ord.capacity == 0u) return TRX_OK;
+    // the layout enqueue_locked gives the lists
+    const uint32_t n_lists = 16 * trx::kLptShards, list_cap = ord.capacity / 2 + 64;
+    const size_t set_words = n_lists + (size_t)n_lists * list_cap;
+    out->have_lists = 1u;
+    out->capacity = ord.capacity;
+    out->lpt_cap = list_cap;
+    out->lpt_sel = sel;
+    out->key = ord.key;
+    const uint32_t *on_file = ord.lists.get() + (sel ? set_words : 0), *other = ord.lists.get() + (sel ? 0 : set_words);
+    uint32_t counts[2][16 * trx::kLptShards];
+    HIP_TRY(hipMemcpy(counts[0], on_file, sizeof(counts[0]), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts[1], other, sizeof(counts[1]), hipMemcpyDeviceToHost));
+    for (uint32_t l = 0; l < n_lists; l++) {
+        out->count_sum += counts[0][l];
+        out->other_sum += counts[1][l];
+        if (counts[0][l] > list_cap) out->n_over++;
+    }
+    if (out_order) {
+        uint32_t n = 0;
+        for (uint32_t e = 0; e < n_lists && n < max_tiles; e++) {
+            const uint32_t list = (15u - (e >> 3)) * trx::kLptShards + (e & 7u);
+            const uint32_t take = std::min(std::min(counts[0][list], list_cap), max_tiles - n);
+            if (take) HIP_TRY(hipMemcpy(out_order + n, on_file + n_lists + (size_t)list * list_cap, take * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            n += take;
+        }
+    }
+    return TRX_OK;
+}
 
 extern "C" int trx_debug_walk_kind(trx_scene *s, uint32_t mode) {
     if (!s) return trxapi::fail(TRX_ERR_INVALID, "null scene");

@@ -406,6 +406,21 @@ class Scene:
             L.check(kind)
         return kind
 
+    def schedule_state(self, kind, stream=0, order=True):
+        """trx_debug_schedule_state: the scheduling state of the launch slot `stream` last used, for pass kind 0 (primary) or
+        1 (AO), as a dict of the struct's fields - after waiting for the stream, changing nothing.  With `order`, the key
+        "order" holds the tile ids of the set on file in the order a frame reads them (u32 array, empty without lists)."""
+        st = L.ScheduleState()
+        L.check(self._lib.trx_debug_schedule_state(self._h, C.c_void_p(stream), kind, C.byref(st), None, 0))
+        out = {name: int(getattr(st, name)) for name, _ in L.ScheduleState._fields_}
+        if order:
+            # room for every entry the counts name (a stale or overflowed set is returned as it stands, cut at lpt_cap per list)
+            ids = np.full(min(out["count_sum"], 128 * out["lpt_cap"]), 0xFFFFFFFF, dtype=np.uint32)
+            if ids.size:
+                L.check(self._lib.trx_debug_schedule_state(self._h, C.c_void_p(stream), kind, C.byref(st), _ptr(ids), ids.size))
+            out["order"] = ids
+        return out
+
     def read_nodes(self):
         """[n_nodes, 20] u32: the node buffer as the kernels now see it (trx_scene_read_nodes)."""
         out = np.empty((self.flat.n_nodes, 20), dtype=np.uint32)
