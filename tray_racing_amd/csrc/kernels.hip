@@ -284,6 +284,11 @@ __device__ __forceinline__ uint32_t node_intersect_kept(const Ray &r, float max_
     const uint32_t meta_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)n1.z), meta_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)n1.w);
     const uint32_t oct = r.oct_inv4 & 0xffu;
     uint32_t hit_mask = 0;
+    // (the eight meta bytes as ONE scalar pair: a child's byte is one 64-bit shift, not a compare, a select and a shift;
+    // and a step whose packet test leaves no child - one in five - is the branch that is taken, so that the loop's exit
+    // falls through into what follows.  profiles/walk_scalar_cost.log)
+    const unsigned long long meta = ((unsigned long long)meta_hi << 32) | meta_lo;
+    if (__builtin_expect(keep == 0u, 0)) return 0u;
     // (requesting the planes of the next child before this one's are used - the loop software-pipelined - measured slower,
     // profiles/r05_ab_19_cull_pipelined.log)
     for (uint32_t m = keep; m != 0u; m &= m - 1u) {
@@ -298,7 +303,7 @@ __device__ __forceinline__ uint32_t node_intersect_kept(const Ray &r, float max_
         const f32x2 tz = plane2<NODE>(f32x2{z.x, z.y}, az, bz);
         const float tmin = fmaxf(fmaxf(fmaxf(tx.x, ty.x), tz.x), 0.0001f);
         const float tmax = fminf(fminf(fminf(tx.y, ty.y), tz.y), max_distance);
-        const uint32_t mj = ((j < 4u ? meta_lo : meta_hi) >> (8u * (j & 3u))) & 0xffu;
+        const uint32_t mj = (uint32_t)(meta >> (8u * j)) & 0xffu;
         const uint32_t child_bits = mj >> 5;
         // child_bits << bit_index with bit_index = (meta ^ (oct & inner_mask)) & 0x1f, as in node_intersect
         uint32_t word;

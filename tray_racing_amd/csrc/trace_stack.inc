@@ -18,14 +18,21 @@
         sp += cond ? 1u : 0u;
         if (COUNT) c_maxsp = max(c_maxsp, sp);
     };
+    // (the pop has no `else`: a wave-uniform if / else whose arms hold per-lane branches reaches the assembly as two ifs in a
+    // row under a flag of the compiler's making, the common arm - the LDS read - behind a branch that is always taken.  The
+    // LDS read is unconditional - a lane past the LDS part reads its own last LDS entry and drops it - and the rare path
+    // is an if of its own.  The same form for the push - its common store behind an opaque flag - measured inside one
+    // spread and was not kept, profiles/walk_scalar_cost.log.)
     auto stack_pop = [&]() -> uint2 { // callers guarantee sp != 0
         sp--;
+        uint2 e = lds_ld(&lds_stack[min(sp, (uint32_t)(kLdsStack - 1)) * kWave + lane]);
         if (__builtin_expect(__ballot(sp >= (uint32_t)kLdsStack) != 0ull, 0)) {
-            if (sp < (uint32_t)kLdsStack) return lds_ld(&lds_stack[sp * kWave + lane]);
-            if (sp < (uint32_t)(kLdsStack + kSpillStack)) return spill[(sp - kLdsStack) * kWave + lane];
-            return make_uint2(0u, 0u);
+            if (sp >= (uint32_t)kLdsStack) {
+                e = make_uint2(0u, 0u); // (past the last entry: the sentinel)
+                if (sp < (uint32_t)(kLdsStack + kSpillStack)) e = spill[(sp - kLdsStack) * kWave + lane];
+            }
         }
-        return lds_ld(&lds_stack[sp * kWave + lane]);
+        return e;
     };
 
     // Finished ray: the hit record (or the any-hit flag) leaves the lane.

@@ -1,7 +1,13 @@
 // trace_walk_plain.inc - part of k_trace (kernels.hip), included as text inside the kernel: the plain walk (coherent primary rays, two-level scenes): fetch, test, triangles, pop
 // (One function for the compiler - the pieces share fifty live variables - several files for the reader.)
+            // the walk goes on while more lanes hold a ray than this: `alive != 0 && (exhausted || alive > keep)` as ONE
+            // comparison (nothing inside the walk changes `exhausted`; `keep` stays a runtime value)
+            // (the two-level kernels have no scalar to spare across the loop - it would be one more parked in a vector lane -
+            // and form the bound where they use it)
+            const uint32_t leave_at = TLAS ? 0u : exhausted ? 0u : keep;
             for (;;) {
                 const bool act = has_ray;
+                const unsigned long long act_mask = ballot64(act); // (once per trip: for the look and for the end of the trip)
                 const int pow2 = (NODE & 1) ? 0 : pow2_exact(P, r, act); // (literal-division variants only)
                 uint2 tri = make_uint2(unspecified1(), 0u); // (.x: read where .y says there are triangles; no trip pays to zero it)
                 trip++;
@@ -14,7 +20,7 @@
                 // copies out of the registers (kernels.h, kWaveScratch) it has 121 and the 4K frame runs 3.3 % faster,
                 // profiles/r05_ab_5_tlas.log)
                 constexpr bool kUni = MODE == kModePrimary && !COUNT;
-                bool uni_done = false;
+                uint32_t lane_step = 1u; // wave-uniform: 0 once the trip's step has been a uniform step
                 // The node a lane steps to next, worked out ONCE per trip, for the look below and for either kind of step.
                 // (two-level walks: a lane may hold a parked triangle group instead of a node group, and node
                 // indices are absolute - rays inside different instances of one BLAS do share its nodes, each
@@ -44,7 +50,7 @@
                     if (P.uni_decode) {
                         // (`first` is a node of the scene whenever the step turns out uniform: the first stepping lane's, or
                         // node 0 in a trip in which no lane steps - a scalar select)
-                        const unsigned long long stepping = __ballot(act);
+                        const unsigned long long stepping = act_mask;
                         uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)node_index, (int)(__ffsll((long long)stepping) - 1));
                         if (stepping == 0ull) first = 0u;
                         // (the lanes that differ as ONE comparison's mask, cut to the stepping lanes by the scalar unit: the
@@ -120,13 +126,21 @@
                                 tri.y = hitmask & 0x00ffffffu;
                             }
                             __builtin_amdgcn_wave_barrier();
-                            uni_done = true;
+                            lane_step = 0u;
                         } else if (kUniCool != 0u) {
                             uni_cool = kUniCool;
                         }
                     }
                 }
-                if (act && !uni_done) {
+                // (the per-lane step behind a scalar flag of its own.  The compiler must not know that the flag is the uniform
+                // step's: as `act && !uni_done` the test after a uniform step was a mask of zeroes, an exec save and a branch
+                // that is always taken, and as an if / else the two steps reach the assembly as two ifs under a mask of the
+                // compiler's making, every word they define copied into the join.  Nor may it merge the scalar test into
+                // the lanes' mask - four scalar instructions instead of a compare and a branch: the empty statement is a
+                // side effect between the two tests.)
+                asm("" : "+s"(lane_step));
+                if (lane_step != 0u) { asm volatile("");
+                if (act) {
                     if (group) { // (node_index, child_bit: from the head of the trip)
                         cur.y &= ~(1u << child_bit);
                         // (tried: when every lane wants the same node - 47 % of the wave-level steps on the bistro-class frame,
@@ -164,6 +178,7 @@
                         cur = make_uint2(0u, 0u);
                     }
                 }
+                } // (lane_step)
                 // instance masks (trx_trace_*_masked*): an instance of the TLAS leaf group whose mask misses the call's ray
                 // mask is dropped where the pick below would enter it, and the walk goes on as it would after entering an
                 // EMPTY instance: with the TLAS node group `cur` if it holds children (the rest of the leaf group parked
@@ -217,36 +232,63 @@
                 triangle_phase(tri);
                 TRX_STAMP(k_tri);
                 if constexpr (kStamps) k_iters++;
-                if (act) {
-                    // a lane whose node group is spent pops the next one, or is finished when its stack is empty
-                    const bool spent = (cur.y & 0xff000000u) == 0u;
-                    bool done = spent && sp == 0u;
-                    if (spent && sp != 0u) {
-                        if (TLAS && sp == tlas_sp) { // back to the TLAS (query_tlas.hlsl:480-486)
-                            tlas_sp = TRX_INVALID;
-                            bvh_off = P.tlas_start;
-                            cur_inst = TRX_INVALID;
-                            if (P.inst_xform) { // "Reset Ray to untransformed version" (query_tlas.hlsl:484)
-                                r.ox = wray[0 * kWave + lane]; r.oy = wray[1 * kWave + lane]; r.oz = wray[2 * kWave + lane];
-                                finish_ray_dir<(NODE & 1) == 0>(r, wray[3 * kWave + lane], wray[4 * kWave + lane], wray[5 * kWave + lane]);
-                                TRX_PUBLISH_RAY();
+                if constexpr (TLAS) {
+                    // (the two-level kernels keep the per-lane form: with the scalar `done` mask of the single-level walk they
+                    // park more scalars in vector lanes inside the loop than tests/test_kernel_resources.py allows)
+                    if (act) {
+                        // a lane whose node group is spent pops the next one, or is finished when its stack is empty
+                        const bool spent = (cur.y & 0xff000000u) == 0u;
+                        bool done = spent && sp == 0u;
+                        if (spent && sp != 0u) {
+                            if (sp == tlas_sp) { // back to the TLAS (query_tlas.hlsl:480-486)
+                                tlas_sp = TRX_INVALID;
+                                bvh_off = P.tlas_start;
+                                cur_inst = TRX_INVALID;
+                                if (P.inst_xform) { // "Reset Ray to untransformed version" (query_tlas.hlsl:484)
+                                    r.ox = wray[0 * kWave + lane]; r.oy = wray[1 * kWave + lane]; r.oz = wray[2 * kWave + lane];
+                                    finish_ray_dir<(NODE & 1) == 0>(r, wray[3 * kWave + lane], wray[4 * kWave + lane], wray[5 * kWave + lane]);
+                                    TRX_PUBLISH_RAY();
+                                }
+                            }
+                            cur = stack_pop();
+                            if (__builtin_expect(overflow != 0u, 0)) done = true; // past the last stack entry: the sentinel is not a group
+                        }
+                        // step cap (every wave reaches an exit whatever the tree): a ray's steps are bounded by the wave's
+                        // trips since it started; looked at once per 1024 trips, so the common trip pays nothing for it
+                        if (__builtin_expect((trip & 1023u) == 0u, 0)) {
+                            if (trip - steps > kMaxSteps) {
+                                overflow = 1u;
+                                done = true;
                             }
                         }
-                        cur = stack_pop();
-                        if (__builtin_expect(overflow != 0u, 0)) done = true; // past the last stack entry: the sentinel is not a group
+                        // any-hit query (intersects_bl_bvh, query.hlsl:440-445): the first accepted triangle settles it.
+                        // Until a hit is accepted the walk is the closest-hit walk, so hit / no hit is the same answer.
+                        if (MODE == kModeRays && P.any_hit != 0u && prim != TRX_INVALID) done = true;
+                        if (done) finish_lane();
                     }
-                    // step cap (every wave reaches an exit whatever the tree): a ray's steps are bounded by the wave's
-                    // trips since it started; looked at once per 1024 trips, so the common trip pays nothing for it
+                } else {
+                    // a lane whose node group is spent pops the next one, or is finished when its stack is empty - or
+                    // when it has gone past the last stack entry: the sentinel it pops is not a group
+                    // (layout: `done` is a scalar mask and the WAVE asks once whether any lane is done, so a trip in which
+                    // none finishes falls through - no branch round the overflow check after a pop, no exec save round the
+                    // end of a ray.  The mask is made of ballots of ONE comparison each, taken by every lane and cut to
+                    // the lanes with a ray by the scalar unit: the ballot of a combined condition goes through a 0 / 1
+                    // register and a second comparison, and a mask assigned under `if (act)` is a per-lane value to the
+                    // compiler - a register pair and a 64-bit vector comparison.)
+                    const bool spent = (cur.y & 0xff000000u) == 0u;
+                    unsigned long long done = ballot64(spent) & (ballot64(sp == 0u) | ballot64(overflow != 0u)) & act_mask;
+                    if (act && spent && sp != 0u) cur = stack_pop();
+                    // any-hit query, as above
+                    if (MODE == kModeRays && P.any_hit != 0u) done |= ballot64(prim != TRX_INVALID) & act_mask;
+                    // step cap, as above
                     if (__builtin_expect((trip & 1023u) == 0u, 0)) {
-                        if (trip - steps > kMaxSteps) {
-                            overflow = 1u;
-                            done = true;
-                        }
+                        const bool capped = trip - steps > kMaxSteps;
+                        if (act && capped) overflow = 1u;
+                        done |= ballot64(capped) & act_mask;
                     }
-                    // any-hit query (intersects_bl_bvh, query.hlsl:440-445): the first accepted triangle settles it.
-                    // Until a hit is accepted the walk is the closest-hit walk, so hit / no hit is the same answer.
-                    if (MODE == kModeRays && P.any_hit != 0u && prim != TRX_INVALID) done = true;
-                    if (done) finish_lane();
+                    if (__builtin_expect(done != 0ull, 0)) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(done)) finish_lane(); // (the scalar mask as the lanes' condition: one exec save, no lane-bit registers)
+                    }
                 }
                 const uint32_t alive = (uint32_t)__popcll(ballot64(has_ray));
                 TRX_STAMP(k_pop);
@@ -255,7 +297,7 @@
                     if (__ballot(has_ray) == 0ull) break;
                     continue;
                 }
-                if (alive == 0u || (!exhausted && alive <= keep)) break;
+                if (alive <= (TLAS ? (exhausted ? 0u : keep) : leave_at)) break; // (no lane left, or - queues not dry - few enough to go and refill)
                 // fused frame, queues dry: waiting lanes are turned into AO rays once enough of them have gathered
                 if (kFused && exhausted && (uint32_t)__popcll(__ballot(pend)) >= P.pend_min) break;
                 if (kThin && thin_now(alive)) {
