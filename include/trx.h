@@ -810,6 +810,55 @@ int trx_render_image_gi(trx_scene *scene, const trx_view *view, uint32_t width, 
                         float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos,
                         uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint8_t *out_rgba, float *out_ms);
 
+/* ---- the value filter: an edge-aware a-trous filter over a per-pixel float plane ----------------------------------------------
+ * At an affordable sample count the indirect term is Monte-Carlo noise.  This is the filter for it - and for any other
+ * per-pixel float plane: n_levels passes of a 5 x 5 B3-spline kernel whose taps lie 1, 2, 4, 8, 16 pixels apart, each tap
+ * taken only where the primary record's depth and the attribute record's normal say it lies on the pixel's own surface (the AO
+ * filter's acceptance rule).  All buffers hold WHOLE-IMAGE records in image layout (y * width + x); there is no shard argument
+ * and no sharded form, for the reason trx_ao_filter_dev has none.  None of it reads scene data.
+ *
+ * THE RULES.  Every operation is rounded once in binary32, no contraction, every division a single IEEE division.
+ *  - A pixel p is a SURFACE pixel iff t_p < FLT_MAX and prim_p != 0xFFFFFFFF (the AO filter's rule).
+ *  - LEVEL j (0 .. n_levels-1) has spacing s = 1 << j and maps a plane u to a plane u':
+ *      a pixel that is not a surface pixel gets u'[p] = u[p], its bits copied;
+ *      a surface pixel p = (x, y) starts from num = 0.0f, den = 0.0f and visits its taps for dy = -2..2 ascending and, inside
+ *      that, dx = -2..2 ascending: the tap is q = (x + dx*s, y + dy*s), its weight w = k[dy+2] * k[dx+2] with
+ *      k = {1, 4, 6, 4, 1} - one of the integers 1, 4, 6, 16, 24, 36 as a float.  A tap outside the image is skipped.  A tap is
+ *      ACCEPTED iff q is a surface pixel, fabsf(t_q - t_p) <= depth_tol * t_p and - with d_attr -
+ *      (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z >= normal_cos (the AO filter's expressions); p itself is accepted
+ *      unconditionally.  For an accepted tap: num = num + w * u[q]; den = den + w (den is an exact integer, at most 256).
+ *      u'[p] = num / den.
+ *  - THE PASS: u_0 = d_in, the levels are applied in ascending order, F = u_{n_levels}.  A surface pixel gets base + F (one
+ *    addition) with base = d_base[p], or F when d_base is NULL.  A pixel without a surface gets d_base[p], its bits copied, or
+ *    d_in[p] when d_base is NULL.
+ * Buffers: d_work holds width * height floats of the caller's; it is required when n_levels >= 2, may be NULL otherwise, and
+ * its contents afterwards are unspecified.  Nothing beyond width * height floats of d_out or d_work is written.  d_base may be
+ * d_out (every pixel's base is read before its value is written, and no earlier level writes d_out then: from three levels on
+ * the second intermediate plane of such a call sits in a plane of width * height floats that the stream's launch slot of the
+ * scene owns - counted by trx_scene_device_bytes, released by trx_scene_destroy; growing it waits for the slot's previous
+ * launch).  d_in is never written.
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): n_levels 0 or above
+ * TRX_MAX_VALUE_FILTER_LEVELS, depth_tol negative or NaN (+inf allowed), normal_cos NaN, width * height == 0 or beyond
+ * 2^31 - 1, a null scene, d_primary, d_in or d_out (d_attr may be NULL: no normal test), a null d_work with n_levels >= 2,
+ * d_in == d_out, d_work equal to d_in, d_out or d_base.
+ * Ordering: one launch per level on `stream`, no host synchronisation; every launch takes a launch slot of the scene, as the
+ * other image passes do, so a trx_scene_refit* called after this call has returned waits for it. */
+#define TRX_MAX_VALUE_FILTER_LEVELS 5
+int trx_value_filter_dev(trx_scene *scene, uint32_t width, uint32_t height, const trx_hit *d_primary,
+                         const trx_hit_attr *d_attr, const float *d_in, const float *d_base, uint32_t n_levels,
+                         float depth_tol, float normal_cos, float *d_work, float *d_out, void *stream);
+/* trx_render_image_gi with the indirect term filtered: the lit chain up to the light term V, trx_trace_indirect_dev without a
+ * base into a plane I, trx_value_filter_dev over I (bounce_filter_levels 0..TRX_MAX_VALUE_FILTER_LEVELS, bounce_depth_tol,
+ * bounce_normal_cos, the attribute pass's normals) with d_base = d_out = V, the value shade; 4 bytes per pixel are copied back
+ * (out_rgba may be NULL).  bounce_filter_levels == 0 is trx_render_image_gi itself (the two tolerances are not looked at).
+ * Every argument is validated before the first pass is enqueued. */
+int trx_render_image_gi_filtered(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                                 uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                                 uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                                 float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos,
+                                 uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint32_t bounce_filter_levels,
+                                 float bounce_depth_tol, float bounce_normal_cos, uint8_t *out_rgba, float *out_ms);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,

@@ -301,6 +301,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
         // the indirect pass's scratch (api_ao.cpp)
         bytes += sl.gi_rays.count() * sizeof(trx_ray) + sl.gi_hits.count() * sizeof(trx_hit) + sl.gi_inst.count() * sizeof(uint32_t) +
                  sl.gi_attr.count() * sizeof(trx_hit_attr) + (sl.gi_sum.count() + sl.gi_acc.count()) * sizeof(float);
+        bytes += sl.vf_plane.count() * sizeof(float); // the value filter's plane of an aliased base (api_image.cpp)
         for (const auto &o : sl.order) bytes += o.lists.count() * sizeof(uint32_t);
     }
     // trx_frame_loop's record buffers (four primary, one AO; instance ids beside them on two-level scenes)

@@ -1,6 +1,7 @@
 // api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev /
 // trx_render_image*, trx_render_image_lit among them): the edge-aware filter over the AO visibility pass's counts, the edge-aware upsample of the sparse
-// pass's counts and the shading to RGBA8 (k_ao_filter, k_ao_upsample, k_shade, image.hip), and the table of
+// pass's counts and the shading to RGBA8 (k_ao_filter, k_ao_upsample, k_shade, image.hip), the a-trous filter over float
+// planes (trx_value_filter_dev / trx_render_image_gi_filtered, k_atrous), and the table of
 // code thresholds the shade searches instead of evaluating pow; the PROFILE_RT heat map of a counting pass's per-ray counts
 // (trx_shade_heat_dev / trx_render_heat_image, k_heat).  Image passes after the walk: none reads scene data, but
 // each takes a launch slot of the scene like the attribute pass, so trx_scene_refit waits for them.
@@ -70,8 +71,9 @@ int check_image(uint32_t w, uint32_t h) {
 }
 
 // A launch slot of the scene for `stream`, then `launch`, then the slot's event: what orders the pass with trx_scene_refit.
+// (launch takes the slot: a pass with scratch of its own on the slot)
 template <typename Launch>
-int enqueue_image(trx_scene *s, hipStream_t stream, bool need_table, Launch launch) {
+int enqueue_image_slot(trx_scene *s, hipStream_t stream, bool need_table, Launch launch) {
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->mu);
     if (need_table && !s->image_thr) { // first shade on this scene: the code thresholds beside it on its device
@@ -85,9 +87,21 @@ int enqueue_image(trx_scene *s, hipStream_t stream, bool need_table, Launch laun
     if (int rc = acquire_slot(s, stream, slot)) return rc;
     slot->last_stream = stream;
     slot->last_use = ++s->launches;
-    if (int rc = launch()) return rc;
+    if (int rc = launch(*slot)) return rc;
     HIP_TRY(hipEventRecord(slot->done.get(), stream));
     slot->used = true;
+    return TRX_OK;
+}
+template <typename Launch>
+int enqueue_image(trx_scene *s, hipStream_t stream, bool need_table, Launch launch) {
+    return enqueue_image_slot(s, stream, need_table, [&](Slot &) -> int { return launch(); });
+}
+
+int check_value_filter(uint32_t n_levels, float depth_tol, float normal_cos) {
+    if (n_levels == 0 || n_levels > TRX_MAX_VALUE_FILTER_LEVELS)
+        return fail(TRX_ERR_INVALID, "n_levels %u outside 1..%d", n_levels, TRX_MAX_VALUE_FILTER_LEVELS);
+    if (!(depth_tol >= 0.0f)) return fail(TRX_ERR_INVALID, "depth_tol %g: must be >= 0 (+inf allowed)", (double)depth_tol);
+    if (normal_cos != normal_cos) return fail(TRX_ERR_INVALID, "normal_cos is NaN");
     return TRX_OK;
 }
 
@@ -224,6 +238,51 @@ int trx_shade_value_dev(trx_scene *s, const float *d_value, uint64_t n, uint8_t 
     return enqueue_shade(s, p, kShadeValue, n, (hipStream_t)stream);
 }
 
+int trx_value_filter_dev(trx_scene *s, uint32_t w, uint32_t h, const trx_hit *d_primary, const trx_hit_attr *d_attr, const float *d_in,
+                         const float *d_base, uint32_t n_levels, float depth_tol, float normal_cos, float *d_work, float *d_out,
+                         void *stream) {
+    if (int rc = check_value_filter(n_levels, depth_tol, normal_cos)) return rc;
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !d_primary || !d_in || !d_out) return fail(TRX_ERR_INVALID, "null argument");
+    if (n_levels >= 2 && !d_work) return fail(TRX_ERR_INVALID, "null d_work with n_levels %u", n_levels);
+    if (d_in == d_out) return fail(TRX_ERR_INVALID, "d_in is d_out: a level cannot run in place");
+    if (d_work && (d_work == d_in || d_work == d_out || d_work == d_base))
+        return fail(TRX_ERR_INVALID, "d_work is d_in, d_out or d_base");
+    const uint64_t n = (uint64_t)w * h;
+    // With d_base in d_out no level but the last may write d_out: the intermediate planes alternate between d_work and a
+    // plane of the slot's.  Otherwise between d_work and d_out, so that the last level lands in d_out.
+    const bool own_plane = d_base == d_out && n_levels >= 3;
+    return enqueue_image_slot(s, (hipStream_t)stream, false, [&](Slot &slot) -> int {
+        if (own_plane && slot.vf_plane.count() < n) {
+            // (the slot's previous kernel may still be reading the old plane)
+            if (slot.used) HIP_TRY(hipEventSynchronize(slot.done.get()));
+            HIP_TRY(slot.vf_plane.grow(n));
+        }
+        const float *src = d_in;
+        for (uint32_t j = 0; j < n_levels; j++) {
+            const bool last = j + 1 == n_levels;
+            float *dst = d_out;
+            if (!last) dst = own_plane ? ((j & 1u) ? slot.vf_plane.get() : d_work) : (((n_levels - 1u - j) & 1u) ? d_work : d_out);
+            AtrousParams p;
+            std::memset(&p, 0, sizeof(p));
+            p.primary = d_primary;
+            p.attr = d_attr;
+            p.in = src;
+            p.base = last ? d_base : nullptr;
+            p.out = dst;
+            p.width = w;
+            p.height = h;
+            p.spacing = 1u << j;
+            p.last = last ? 1u : 0u;
+            p.depth_tol = depth_tol;
+            p.normal_cos = normal_cos;
+            HIP_TRY(launch_atrous(p, (hipStream_t)stream));
+            src = dst;
+        }
+        return TRX_OK;
+    });
+}
+
 int trx_shade_heat_dev(trx_scene *s, const trx_ray_cost *d_cost, uint64_t n, uint32_t which, float scale, uint8_t *d_rgba,
                        void *stream) {
     if (int rc = check_heat(which, scale)) return rc;
@@ -358,13 +417,15 @@ int trx_render_image_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint
         });
 }
 
-// trx_render_image_lit (bounce_samples == 0) and trx_render_image_gi (bounce_samples >= 1: the indirect pass between the light
-// term and the shade, the term's values its base and its output)
+// trx_render_image_lit (bounce_samples == 0), trx_render_image_gi (bounce_samples >= 1: the indirect pass between the light
+// term and the shade, the term's values its base and its output) and trx_render_image_gi_filtered (filter_levels >= 1: the
+// indirect pass without a base into a plane of its own, the value filter over that plane with the term's values its base and
+// its output)
 static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
                       const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
                       float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
-                      float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint8_t *out_rgba,
-                      float *out_ms) {
+                      float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint32_t filter_levels,
+                      float bounce_depth_tol, float bounce_normal_cos, uint8_t *out_rgba, float *out_ms) {
     if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
     if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
@@ -381,12 +442,16 @@ static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
     const trx_shard whole{0, 1, 0, 0};
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
     HIP_TRY(hipSetDevice(s->device));
-    // the image scratch: the filter's terms, the image, the light term's values, then the lights' planes
-    HIP_TRY(s->scratch_img.grow(n * 12 + n * n_lights));
+    // the image scratch: the filter's terms, the image, the light term's values, with a value filter the indirect term and the
+    // filter's work plane, then the lights' planes
+    const uint64_t planes = filter_levels != 0 ? 5 : 3;
+    HIP_TRY(s->scratch_img.grow(n * 4 * planes + n * n_lights));
     auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
     auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
     auto d_value = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 8); };
-    auto d_lit = [&] { return s->scratch_img.get() + n * 12; };
+    auto d_indirect = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 12); };
+    auto d_work = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 16); };
+    auto d_lit = [&] { return s->scratch_img.get() + n * 4 * planes; };
     // (the AO counts go where trx_trace_ao_visibility puts them: n bytes of the second record buffer)
     auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
     return host_call(
@@ -410,9 +475,16 @@ static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
             rc = trx_light_term_dev(s, view, w, h, whole, lights, n_lights, light_samples, s->scratch_a.get(), s->scratch_attr.get(),
                                     d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
             if (rc) return rc;
-            if (bounce_samples != 0) {
+            if (bounce_samples != 0 && filter_levels == 0) {
                 rc = trx_trace_indirect_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples, bounce_eps,
                                             shadow_eps, bounce_albedo, s->scratch_a.get(), s->scratch_ia.get(), d_value(), d_value(), nullptr);
+                if (rc) return rc;
+            } else if (bounce_samples != 0) {
+                rc = trx_trace_indirect_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples, bounce_eps,
+                                            shadow_eps, bounce_albedo, s->scratch_a.get(), s->scratch_ia.get(), nullptr, d_indirect(), nullptr);
+                if (rc) return rc;
+                rc = trx_value_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), d_indirect(), d_value(), filter_levels,
+                                          bounce_depth_tol, bounce_normal_cos, d_work(), d_value(), nullptr);
                 if (rc) return rc;
             }
             return trx_shade_value_dev(s, d_value(), n, d_rgba(), nullptr);
@@ -428,7 +500,18 @@ int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_
                          float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                          float normal_cos, uint8_t *out_rgba, float *out_ms) {
     return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
-                      ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, out_rgba, out_ms);
+                      ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, 0u, 0.0f, 0.0f, out_rgba, out_ms);
+}
+
+// what trx_render_image_gi adds to the lit image's refusals (which come first, in their order)
+static int check_bounce(const trx_light *lights, uint32_t n_lights, uint32_t light_samples, uint32_t bounce_samples, float bounce_eps,
+                        float bounce_albedo) {
+    if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
+    if (bounce_samples == 0 || bounce_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "bounce_samples %u outside 1..%d", bounce_samples, TRX_MAX_AO_SAMPLES);
+    if (!(bounce_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "bounce_eps %g: must be >= 0", (double)bounce_eps);
+    if (!std::isfinite(bounce_albedo)) return fail(TRX_ERR_INVALID, "bounce_albedo %g is not finite", (double)bounce_albedo);
+    return TRX_OK;
 }
 
 int trx_render_image_gi(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
@@ -436,13 +519,26 @@ int trx_render_image_gi(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
                         float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                         float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint8_t *out_rgba,
                         float *out_ms) {
-    if (int rc = check_lights(lights, n_lights, light_samples)) return rc; // (the lit image's refusals come first, in its order)
-    if (bounce_samples == 0 || bounce_samples > TRX_MAX_AO_SAMPLES)
-        return fail(TRX_ERR_INVALID, "bounce_samples %u outside 1..%d", bounce_samples, TRX_MAX_AO_SAMPLES);
-    if (!(bounce_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "bounce_eps %g: must be >= 0", (double)bounce_eps);
-    if (!std::isfinite(bounce_albedo)) return fail(TRX_ERR_INVALID, "bounce_albedo %g is not finite", (double)bounce_albedo);
+    if (int rc = check_bounce(lights, n_lights, light_samples, bounce_samples, bounce_eps, bounce_albedo)) return rc;
     return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
-                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, out_rgba, out_ms);
+                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, 0u, 0.0f, 0.0f, out_rgba,
+                      out_ms);
+}
+
+int trx_render_image_gi_filtered(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                                 const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                                 float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius,
+                                 float depth_tol, float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo,
+                                 uint32_t bounce_filter_levels, float bounce_depth_tol, float bounce_normal_cos, uint8_t *out_rgba,
+                                 float *out_ms) {
+    if (int rc = check_bounce(lights, n_lights, light_samples, bounce_samples, bounce_eps, bounce_albedo)) return rc;
+    if (bounce_filter_levels > TRX_MAX_VALUE_FILTER_LEVELS)
+        return fail(TRX_ERR_INVALID, "bounce_filter_levels %u outside 0..%d", bounce_filter_levels, TRX_MAX_VALUE_FILTER_LEVELS);
+    if (bounce_filter_levels != 0)
+        if (int rc = check_value_filter(bounce_filter_levels, bounce_depth_tol, bounce_normal_cos)) return rc;
+    return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, bounce_filter_levels,
+                      bounce_depth_tol, bounce_normal_cos, out_rgba, out_ms);
 }
 
 } // extern "C"

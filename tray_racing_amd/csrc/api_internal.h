@@ -80,6 +80,9 @@ struct Slot {
     DevBuf<uint32_t> gi_inst;
     DevBuf<trx_hit_attr> gi_attr;
     DevBuf<float> gi_sum, gi_acc;
+    // trx_value_filter_dev on this slot's stream with d_base == d_out and three levels or more: the second intermediate plane,
+    // which cannot sit in d_out then (api_image.cpp)
+    DevBuf<float> vf_plane;
     bool used = false;
     bool pinned = false;               // a resident kernel (the ray service) runs on this slot: never recycled for another stream
     hipStream_t last_stream = nullptr; // stream of the last launch on this slot

@@ -66,6 +66,11 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // (trx_render_image_gi): the direct-light image plus one diffuse bounce of N samples per pixel
     int bounce_samples = -1; // -1: not given, everything stays as it is
     float bounce_albedo = -1.0f, bounce_eps = -1.0f; // (not given: 0.5, 0.01)
+    // --bounce-filter L [--bounce-filter-tol d] [--bounce-filter-cos c]: with --bounce-samples the bounce's term goes through L
+    // levels of the edge-aware value filter before it is added (trx_render_image_gi_filtered)
+    int bounce_filter = -1; // -1: not given, everything stays as it is
+    float bounce_filter_tol = 0.1f, bounce_filter_cos = 0.9f;
+    bool bounce_filter_opts = false; // one of the two tolerances was given
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -112,6 +117,9 @@ void usage() {
               "  [--bounce-samples 1..64] [--bounce-albedo a] [--bounce-eps e] (with --png --light: one diffuse bounce - N bounce rays\n"
               "   per pixel, the direct light at what they hit times the albedo (default 0.5), added to the direct-light image;\n"
               "   not together with --ao-stride or --profile-rt)\n"
+              "  [--bounce-filter 0..5] [--bounce-filter-tol d] [--bounce-filter-cos c] (with --bounce-samples: the bounce's term through\n"
+              "   L levels of the edge-aware a-trous filter - taps 1, 2, 4, .. pixels apart, kept where the depth is within d (default\n"
+              "   0.1) of the pixel's and the normals within c (default 0.9) - before it is added; 0: unfiltered)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -237,6 +245,17 @@ Options parse_args(int argc, char **argv) {
         } else if (a == "--bounce-eps") {
             o.bounce_eps = (float)std::atof(need(i));
             if (!(o.bounce_eps >= 0.0f)) die("--bounce-eps must be >= 0");
+        } else if (a == "--bounce-filter") {
+            o.bounce_filter = std::atoi(need(i));
+            if (o.bounce_filter < 0 || o.bounce_filter > TRX_MAX_VALUE_FILTER_LEVELS) die("--bounce-filter takes 0.." + std::to_string(TRX_MAX_VALUE_FILTER_LEVELS));
+        } else if (a == "--bounce-filter-tol") {
+            o.bounce_filter_tol = (float)std::atof(need(i));
+            o.bounce_filter_opts = true;
+            if (!(o.bounce_filter_tol >= 0.0f)) die("--bounce-filter-tol must be >= 0");
+        } else if (a == "--bounce-filter-cos") {
+            o.bounce_filter_cos = (float)std::atof(need(i));
+            o.bounce_filter_opts = true;
+            if (o.bounce_filter_cos != o.bounce_filter_cos) die("--bounce-filter-cos must be a number");
         }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
@@ -291,6 +310,8 @@ Options parse_args(int argc, char **argv) {
     if (o.bounce_samples < 0 && (o.bounce_albedo >= 0.0f || o.bounce_eps >= 0.0f)) die("--bounce-albedo and --bounce-eps go with --bounce-samples N");
     if (o.bounce_samples >= 0 && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--bounce-samples draws the GI image: not together with --ao-stride or --profile-rt");
     if (o.bounce_samples >= 0 && o.lights.empty()) die("--bounce-samples bounces the light of --light");
+    if (o.bounce_filter < 0 && o.bounce_filter_opts) die("--bounce-filter-tol and --bounce-filter-cos go with --bounce-filter L");
+    if (o.bounce_filter >= 0 && o.bounce_samples < 0) die("--bounce-filter filters the term of --bounce-samples N");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -359,7 +380,17 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
         const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
-        if (o.bounce_samples >= 0)
+        if (o.bounce_samples >= 0 && o.bounce_filter >= 0)
+            // ... and one diffuse bounce, filtered, on top of it
+            check(trx_render_image_gi_filtered(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                               o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
+                                               o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
+                                               radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
+                                               (uint32_t)o.bounce_samples, o.bounce_eps >= 0.0f ? o.bounce_eps : 0.01f,
+                                               o.bounce_albedo >= 0.0f ? o.bounce_albedo : 0.5f, (uint32_t)o.bounce_filter, o.bounce_filter_tol,
+                                               o.bounce_filter_cos, rgba.data(), &ms),
+                  "png frame");
+        else if (o.bounce_samples >= 0)
             // ... and one diffuse bounce on top of it (the GI image)
             check(trx_render_image_gi(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                       o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,

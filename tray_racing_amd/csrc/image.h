@@ -44,6 +44,28 @@ struct AoUpsampleParams {
 };
 hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream);
 
+// k_atrous (trx_value_filter_dev): one level of the a-trous filter at spacing s = 1 << level.  A level couples only pixels
+// of one residue class in y mod s (and in x mod s), so a workgroup of 256 lanes takes kAtrousTileW consecutive x of
+// kAtrousTileRows LATTICE rows y0 + k * s of one row class, and stages those rows, two lattice rows above and below and 2s
+// columns either side into LDS: (32 + 4s) x 12 cells, 432 at s = 1 and kAtrousMaxCells = 1152 at s = 16 - the footprint
+// grows linearly with s where a pixel-space tile with a halo of 2s would grow with its square.
+constexpr uint32_t kAtrousTileW = 32, kAtrousTileRows = 8;
+constexpr uint32_t kAtrousMaxLevels = TRX_MAX_VALUE_FILTER_LEVELS;
+constexpr uint32_t kAtrousMaxSpacing = 1u << (kAtrousMaxLevels - 1);                               // 16
+constexpr uint32_t kAtrousRows = kAtrousTileRows + 4;                                              // 12 staged lattice rows
+constexpr uint32_t kAtrousMaxCells = (kAtrousTileW + 4 * kAtrousMaxSpacing) * kAtrousRows;         // 1152
+struct AtrousParams {
+    const trx_hit *primary;   // whole image, y * width + x
+    const trx_hit_attr *attr; // or null: no normal test
+    const float *in;          // the level's input plane u
+    const float *base;        // last level only, or null; may be `out`
+    float *out;               // the level's output plane u' (never `in`)
+    uint32_t width, height, spacing;
+    uint32_t last;            // 1: the pass's last level - the base is added, a pixel without a surface gets its base
+    float depth_tol, normal_cos;
+};
+hipError_t launch_atrous(const AtrousParams &p, hipStream_t stream);
+
 // k_shade: one lane per record, 4 bytes {c, c, c, 255} written per record; c by an 8-step search of the 256 thresholds
 // (trx_image_code_table) each workgroup first copies into LDS.  kShadeValue (trx_shade_value_dev) launches k_value: the same
 // table, search and store over float values.

@@ -5,7 +5,8 @@
 //
 // Arithmetic contract (DESIGN.md "Numerics"): binary32, no contraction, IEEE divide, dot = (ax*bx + ay*by) + az*bz.  The
 // filter compares in float and sums in integers, the shade divides once and then only compares, so a host twin
-// (tests/image_twin.py) gives the same bits; the heat map is a fixed sequence of such operations (tests/heat_twin.py).
+// (tests/image_twin.py) gives the same bits; the heat map is a fixed sequence of such operations (tests/heat_twin.py), and so
+// is a level of the value filter over float planes (k_atrous, tests/value_filter_twin.py).
 #include "image.h"
 
 #pragma clang fp contract(off)
@@ -285,6 +286,101 @@ __global__ void __launch_bounds__(256) k_heat(const HeatParams P) {
     reinterpret_cast<uint32_t *>(P.rgba)[i] = px;
 }
 
+// One level of the value filter (trx_value_filter_dev; the rules are stated in include/trx.h): the 5 x 5 B3-spline kernel
+// with its taps s = P.spacing pixels apart, every tap under the AO filter's acceptance rule.  A level couples only pixels of
+// one residue class in y mod s (and x mod s), so the workgroup is not a pixel-space tile - its halo of 2s would be 32
+// pixels deep at s = 16 - but 32 consecutive x of 8 LATTICE rows y0 + k * s of one row class; lane l is pixel
+// (32 tx + (l & 31), y0 + (l >> 5) * s), a wave two lattice rows of 32 pixels.
+//   phase 1: those rows, two lattice rows above and below and 2s columns either side - (32 + 4s) x 12 cells - into LDS as
+// separate arrays (depth, value, three normal components), k_ao_filter's layout.  A cell is a run element of one image row, so
+// the global loads are whole runs of consecutive records at every level.  A cell outside the image or without a surface gets
+// the depth +inf - "no tap" - and loads nothing further.
+//   phase 2: every lane visits its 25 taps in the stated order out of LDS, cell (row + dy) * pitch + x + dx * s: per 32-lane
+// half, the unit ds_read_b32 banks over, 32 consecutive dwords of one row - conflict-free whatever the pitch and the spacing.
+// The sums are the rule's operations one by one (contraction is off in this file); a skipped tap leaves num and den as they
+// are.  The last level adds the pixel's base, read by the lane that then writes the value: d_base may be d_out.
+template <bool NORMALS>
+__global__ void __launch_bounds__(256) k_atrous(const AtrousParams P) {
+    __shared__ float s_t[kAtrousMaxCells];
+    __shared__ float s_v[kAtrousMaxCells];
+    __shared__ float s_n[NORMALS ? 3 * kAtrousMaxCells : 1];
+    const uint32_t s = P.spacing; // 1 .. kAtrousMaxSpacing (launch_atrous)
+    const uint32_t hw = kAtrousTileW + 4u * s, cells = hw * kAtrousRows; // <= kAtrousMaxCells
+    const uint32_t tiles_x = (P.width + kAtrousTileW - 1u) / kAtrousTileW;
+    const uint32_t classes = s < P.height ? s : P.height; // row classes that hold a row
+    const uint32_t rest = blockIdx.x / tiles_x, tx = blockIdx.x - rest * tiles_x;
+    const uint32_t grp = rest / classes, cls = rest - grp * classes;
+    const uint64_t y0 = (uint64_t)cls + (uint64_t)grp * (kAtrousTileRows * s);
+    if (y0 >= P.height) return; // (a class with fewer groups of rows than the fullest one: the whole workgroup leaves)
+    const int64_t x_first = (int64_t)(tx * kAtrousTileW) - (int64_t)(2u * s);
+    for (uint32_t c = threadIdx.x; c < cells; c += 256u) {
+        const uint32_t cy = c / hw, cx = c - cy * hw;
+        const int64_t gx = x_first + (int64_t)cx, gy = (int64_t)y0 + ((int64_t)cy - 2) * (int64_t)s;
+        float t = __builtin_inff(), v = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        if (gx >= 0 && gy >= 0 && gx < (int64_t)P.width && gy < (int64_t)P.height) {
+            const size_t i = (size_t)gy * P.width + (size_t)gx;
+            const trx_hit h = P.primary[i];
+            if (h.t < TRX_F32_MAX && h.prim != TRX_INVALID) {
+                t = h.t;
+                v = P.in[i];
+                if constexpr (NORMALS) {
+                    const float *n = P.attr[i].normal;
+                    nx = n[0]; ny = n[1]; nz = n[2];
+                }
+            }
+        }
+        s_t[c] = t;
+        s_v[c] = v;
+        if constexpr (NORMALS) {
+            s_n[c] = nx;
+            s_n[kAtrousMaxCells + c] = ny;
+            s_n[2u * kAtrousMaxCells + c] = nz;
+        }
+    }
+    __syncthreads();
+    const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
+    const uint32_t px = tx * kAtrousTileW + lx;
+    const uint64_t py = y0 + (uint64_t)ly * s;
+    if (px >= P.width || py >= P.height) return;
+    const size_t ip = (size_t)py * P.width + px;
+    const uint32_t c0 = (ly + 2u) * hw + lx + 2u * s;
+    const float tp = s_t[c0];
+    const bool with_base = P.last != 0u && P.base != nullptr;
+    if (!(tp < TRX_F32_MAX)) { // no surface: the plane's own bits - at the last level the base's - copied
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(with_base ? P.base : P.in);
+        const uint32_t bits = src[ip];
+        reinterpret_cast<uint32_t *>(P.out)[ip] = bits;
+        return;
+    }
+    const float tol = P.depth_tol * tp;
+    float npx = 0.0f, npy = 0.0f, npz = 0.0f;
+    if constexpr (NORMALS) {
+        npx = s_n[c0]; npy = s_n[kAtrousMaxCells + c0]; npz = s_n[2u * kAtrousMaxCells + c0];
+    }
+    float num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (uint32_t dy = 0; dy < 5u; dy++) {
+        const uint32_t row = (ly + dy) * hw + lx;
+#pragma unroll
+        for (uint32_t dx = 0; dx < 5u; dx++) {
+            constexpr uint32_t k[5] = {1u, 4u, 6u, 4u, 1u};
+            const float w = (float)(k[dy] * k[dx]);
+            const uint32_t c = row + dx * s;
+            const float tq = s_t[c];
+            bool ok = tq < TRX_F32_MAX && __builtin_fabsf(tq - tp) <= tol;
+            if constexpr (NORMALS)
+                ok = ok && (npx * s_n[c] + npy * s_n[kAtrousMaxCells + c]) + npz * s_n[2u * kAtrousMaxCells + c] >= P.normal_cos;
+            ok = ok || (dy == 2u && dx == 2u);
+            const float term = w * s_v[c];
+            num = ok ? num + term : num;
+            den = ok ? den + w : den;
+        }
+    }
+    float f = __fdiv_rn(num, den);
+    if (with_base) f = P.base[ip] + f;
+    P.out[ip] = f;
+}
+
 } // namespace
 
 hipError_t launch_heat(const HeatParams &p, hipStream_t stream) {
@@ -311,6 +407,20 @@ hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream) {
         return hipErrorInvalidValue;
     if (p.attr) hipLaunchKernelGGL(k_ao_upsample<true>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(k_ao_upsample<false>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_atrous(const AtrousParams &p, hipStream_t stream) {
+    // (what bounds the kernel's LDS indices: a power of two up to kAtrousMaxSpacing)
+    if (p.spacing == 0 || p.spacing > kAtrousMaxSpacing || (p.spacing & (p.spacing - 1u)) != 0 || p.in == p.out) return hipErrorInvalidValue;
+    if (p.width == 0 || p.height == 0) return hipSuccess;
+    // per tile column: every row class that holds a row, and in each as many groups of 8 lattice rows as the fullest class has
+    const uint64_t tiles_x = (p.width + kAtrousTileW - 1u) / kAtrousTileW, classes = p.spacing < p.height ? p.spacing : p.height;
+    const uint64_t lattice_rows = ((uint64_t)p.height + p.spacing - 1u) / p.spacing;
+    const uint64_t blocks = tiles_x * classes * ((lattice_rows + kAtrousTileRows - 1u) / kAtrousTileRows);
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (p.attr) hipLaunchKernelGGL(k_atrous<true>, dim3((uint32_t)blocks), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(k_atrous<false>, dim3((uint32_t)blocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

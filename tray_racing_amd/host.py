@@ -592,6 +592,22 @@ class Scene:
                                               bounce_samples, bounce_eps, bounce_albedo, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_image_gi_filtered(self, view, width, height, lights, bounce_samples, bounce_filter_levels, bounce_depth_tol=0.1,
+                                 bounce_normal_cos=0.9, bounce_eps=0.01, bounce_albedo=0.5, sem=L.SEM_HLSL, ray_mask=0, frame0=0,
+                                 light_samples=1, shadow_eps=0.01, ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"),
+                                 filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_gi_filtered - render_image_gi with the indirect term put
+        through bounce_filter_levels (0..5; 0: render_image_gi itself) levels of the value filter (value_filter_dev, with the
+        attribute pass's normals) before it is added to the light term; only the image crosses the bus."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_gi_filtered(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0,
+                                                       light_samples, shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius,
+                                                       depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo,
+                                                       bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
         """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
         of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
@@ -861,6 +877,15 @@ class Scene:
         L.check(self._lib.trx_ao_filter_dev(self._h, width, height, C.c_void_p(d_primary), C.c_void_p(d_attr),
                                             C.c_void_p(d_unoccluded), n_samples, radius, depth_tol, normal_cos,
                                             C.c_void_p(d_term), C.c_void_p(stream)))
+
+    def value_filter_dev(self, width, height, d_primary, d_in, d_out, n_levels, depth_tol=0.1, normal_cos=0.9, d_attr=0, d_base=0,
+                         d_work=0, stream=0):
+        """trx_value_filter_dev: n_levels (1..5) levels of the edge-aware a-trous filter over the float plane d_in into d_out,
+        taps 1, 2, 4, .. pixels apart, each accepted as in the AO filter; d_base's value (none without one; d_base may be d_out)
+        is added at surface pixels and copied elsewhere.  d_work: a plane of the caller's, needed from two levels on."""
+        L.check(self._lib.trx_value_filter_dev(self._h, width, height, C.c_void_p(d_primary), C.c_void_p(d_attr), C.c_void_p(d_in),
+                                               C.c_void_p(d_base), n_levels, depth_tol, normal_cos, C.c_void_p(d_work),
+                                               C.c_void_p(d_out), C.c_void_p(stream)))
 
     def ao_upsample_dev(self, width, height, stride, phase, d_primary, d_unoccluded_lo, d_term, n_samples, radius, depth_tol=0.02,
                         normal_cos=0.9, d_attr=0, stream=0):
