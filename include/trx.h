@@ -859,6 +859,74 @@ int trx_render_image_gi_filtered(trx_scene *scene, const trx_view *view, uint32_
                                  uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint32_t bounce_filter_levels,
                                  float bounce_depth_tol, float bounce_normal_cos, uint8_t *out_rgba, float *out_ms);
 
+/* ---- the sparse indirect term: one bounce pixel in every stride x stride block, upsampled edge-aware ---------------------------
+ * The indirect pass is the most expensive pass here, and most of it is the closest-hit walk over incoherent rays: the remedy
+ * is fewer rays.  This is the sparse visibility pass's form for the indirect term: trx_trace_indirect_sparse_dev traces the
+ * term over a low grid, trx_value_upsample_dev rebuilds a full-resolution plane from it under the filter's depth and normal
+ * rule, and trx_value_filter_dev may follow.
+ *
+ * THE SPARSE PASS.  Whole-image and image-layout, without a shard argument, like trx_trace_ao_visibility_sparse_dev, and
+ * with that call's grid: stride s is 1..TRX_MAX_AO_STRIDE, phase is 0..s*s-1 with px0 = phase % s, py0 = phase / s; the low
+ * grid is Wlo = ceil(width / s) by Hlo = ceil(height / s) cells; d_value_lo holds Wlo * Hlo floats at Y * Wlo + X, nothing
+ * beyond them is written; cell (X, Y) stands for the full-resolution pixel (X * s + px0, Y * s + py0).  d_primary and
+ * d_primary_inst are FULL-resolution image-layout records.
+ *  - A cell whose pixel lies outside the image, or whose pixel is not a surface pixel, gets +0.0f.
+ *  - Every other cell gets, bit for bit, what trx_trace_indirect_dev writes for that pixel with d_base == NULL under the same
+ *    arguments: the bounce ray is rule 1's for the full-resolution pixel coordinates in the full image, the rect light's
+ *    noise of rule 3 is hash_noise(px, py, ...) of the full-resolution pixel, not of the cell, and the sums are formed in
+ *    rule 4's and rule 5's order under any scratch cap.  Stride 1 is the dense pass without a base.
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): stride 0 or above the maximum,
+ * phase >= s*s, everything trx_trace_indirect_dev refuses, a null d_value_lo.  Scratch, chunking, stream and ordering are the
+ * dense pass's: the same launch slot's scratch ([tile][sample][64] over the 8 x 8 tiles of the low grid) under the same cap,
+ * counted once by trx_scene_device_bytes; a trx_scene_refit* called after this call has returned waits for every launch. */
+int trx_trace_indirect_sparse_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                  uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t ray_mask,
+                                  const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
+                                  float bounce_eps, float shadow_eps, float bounce_albedo, const trx_hit *d_primary,
+                                  const uint32_t *d_primary_inst, float *d_value_lo, void *stream);
+/* THE UPSAMPLE of a low-grid float plane.  d_primary, d_attr (may be NULL: no normal test), d_base (may be NULL) and d_out
+ * are full-resolution, whole-image, image-layout buffers; d_in_lo is a Wlo x Hlo plane of floats for the same width, height,
+ * stride s and phase.  Every operation is rounded once in binary32, no contraction, every division a single IEEE division.
+ *  - Surface pixels are the filter's: t < FLT_MAX && prim != 0xFFFFFFFF.
+ *  - The WINDOW of pixel p = (x, y) is the set of low cells (x / s + dx, y / s + dy) with |dx|, |dy| <= radius (integer
+ *    divisions; radius 0..TRX_MAX_VALUE_UPSAMPLE_RADIUS), clipped to the low grid: trx_ao_upsample_dev's window.
+ *  - The cells are visited for dy ascending and, inside that, dx ascending.  The weight of a cell is w = k[|dy|] * k[|dx|]
+ *    with k[d] = radius + 1 - d: an exact small integer as a float, at most 9.
+ *  - Cell q is a SURFACE CELL iff its pixel (X * s + px0, Y * s + py0) is inside the image and is a surface pixel.
+ *  - Cell q is ACCEPTED iff it is a surface cell, fabsf(t_q - t_p) <= depth_tol * t_p and - with d_attr -
+ *    (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z >= normal_cos, t_q and n_q the full-resolution records of q's pixel
+ *    (trx_ao_upsample_dev's statements).  The cell whose pixel is p itself is accepted unconditionally.
+ *  - num = 0.0f, den = 0.0f; for every accepted cell in the visit order: num = num + w * u[q]; den = den + w.  A cell that is
+ *    not accepted leaves both as they are: a NaN or an infinity at a rejected cell stays out.
+ *  - At least one cell accepted: F = num / den.  FALLBACK - none accepted but the window holds surface cells: the same two
+ *    sums over ALL surface cells of the window, in the same order with the same weights, then F = num / den.  EMPTY - no
+ *    surface cell in the window: F = +0.0f.
+ *  - A surface pixel gets base + F (one addition) with base = d_base[p], or F when d_base is NULL.  A pixel without a surface
+ *    gets d_base[p], its bits copied, or +0.0f without a base.  d_base may be d_out (every pixel's base is read before its
+ *    value is written).
+ * At stride 1 and radius 0 every surface pixel gets its own cell's value (u / 1.0f).
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): stride 0 or above TRX_MAX_AO_STRIDE,
+ * phase >= s*s, radius > TRX_MAX_VALUE_UPSAMPLE_RADIUS, depth_tol negative or NaN (+inf allowed), normal_cos NaN,
+ * width * height == 0 or beyond 2^31 - 1, a null scene, d_primary, d_in_lo or d_out, d_in_lo == d_out.
+ * Ordering: one launch on `stream`, taking a launch slot of the scene like the other image passes. */
+#define TRX_MAX_VALUE_UPSAMPLE_RADIUS 2
+int trx_value_upsample_dev(trx_scene *scene, uint32_t width, uint32_t height, uint32_t stride, uint32_t phase,
+                           const trx_hit *d_primary, const trx_hit_attr *d_attr, const float *d_in_lo, const float *d_base,
+                           uint32_t radius, float depth_tol, float normal_cos, float *d_out, void *stream);
+/* trx_render_image_gi_filtered with the indirect term traced sparsely: the lit chain up to the light term V,
+ * trx_trace_indirect_sparse_dev (bounce_stride, bounce_phase) into a low plane; with bounce_filter_levels == 0
+ * trx_value_upsample_dev (bounce_upsample_radius, bounce_depth_tol, bounce_normal_cos, the attribute pass's normals) with
+ * d_base = d_out = V; otherwise the upsample without a base into a plane I and trx_value_filter_dev over I with
+ * d_base = d_out = V; then the value shade; 4 bytes per pixel are copied back (out_rgba may be NULL).  The two tolerances are
+ * looked at in either case: the upsample uses them.  Every argument is validated before the first pass is enqueued. */
+int trx_render_image_gi_sparse(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                               uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                               uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                               float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos,
+                               uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint32_t bounce_filter_levels,
+                               float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
+                               uint32_t bounce_upsample_radius, uint8_t *out_rgba, float *out_ms);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL. */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,

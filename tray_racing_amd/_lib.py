@@ -34,6 +34,7 @@ MAX_AO_FILTER_RADIUS = 4
 MAX_AO_STRIDE = 4
 MAX_VALUE_FILTER_LEVELS = 5
 MAX_AO_UPSAMPLE_RADIUS = 2
+MAX_VALUE_UPSAMPLE_RADIUS = 2
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_RECT = 0, 1, 2
 MAX_LIGHTS = 8
 HEAT_NODES = 0
@@ -197,6 +198,11 @@ SIGNATURES = {
     "trx_value_filter_dev": (_i, [_P, _u32, _u32, _P, _P, _P, _P, _u32, _f, _f, _P, _P, _P]),
     "trx_render_image_gi_filtered": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32,
                                           _f, _f, _u32, _f, _f, _u32, _f, _f, _P, C.POINTER(_f)]),
+    "trx_trace_indirect_sparse_dev": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P,
+                                           _P, _P]),
+    "trx_value_upsample_dev": (_i, [_P, _u32, _u32, _u32, _u32, _P, _P, _P, _P, _u32, _f, _f, _P, _P]),
+    "trx_render_image_gi_sparse": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32,
+                                        _f, _f, _u32, _f, _f, _u32, _f, _f, _u32, _u32, _u32, _P, C.POINTER(_f)]),
     "trx_debug_indirect_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P,
                                        C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),

@@ -281,8 +281,9 @@ int bounce_geometry(TileGeom &geom, uint32_t w, uint32_t h, trx_shard shard, uin
 int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
                   const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps,
                   float albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base, float *d_value,
-                  hipStream_t stream, BouncePhases *phases) {
+                  hipStream_t stream, BouncePhases *phases, const SparseGrid *sparse = nullptr) {
     if (!s || !d_primary || !d_value) return fail(TRX_ERR_INVALID, "null argument");
+    if (sparse) if (int rc = check_sparse(sparse->stride, sparse->phase)) return rc;
     if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
@@ -292,6 +293,16 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     AoRaysParams g;
     uint32_t tiles = 0;
     if (int rc = ao_geometry(g, view, w, h, shard, tiles)) return rc;
+    if (sparse) {
+        // (visibility_impl's statement: the full image's geometry stays in g.geom and g.view, the tiles are the low grid's)
+        AoRaysParams lo;
+        const uint32_t st = sparse->stride;
+        if (int rc = ao_geometry(lo, view, (w + st - 1) / st, (h + st - 1) / st, shard, tiles)) return rc;
+        g.lo = lo.geom;
+        g.stride = st;
+        g.px0 = sparse->phase % st;
+        g.py0 = sparse->phase / st;
+    }
     if (int rc = need_inst(s, d_primary_inst)) return rc;
     if (tiles == 0) return TRX_OK;
     HIP_TRY(hipSetDevice(s->device));
@@ -359,6 +370,10 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     b.geom = g.geom;
     b.shadow_eps = shadow_eps;
     b.albedo = albedo;
+    b.stride = g.stride; // (0: the dense kernels)
+    b.px0 = g.px0;
+    b.py0 = g.py0;
+    b.lo = g.lo;
     // one rays launch on the pass's slot (the slot is this stream's once the first kernel of the chunk is recorded)
     auto walk = [&](TraceParams &p) -> int {
         SlotCounters *ctr = nullptr;
@@ -645,6 +660,15 @@ int trx_trace_indirect_dev(trx_scene *s, const trx_view *view, uint32_t w, uint3
                            const float *d_base, float *d_value, void *stream) {
     return indirect_impl(s, view, w, h, shard, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps, bounce_albedo,
                          d_primary, d_primary_inst, d_base, d_value, (hipStream_t)stream, nullptr);
+}
+
+int trx_trace_indirect_sparse_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t stride, uint32_t phase, uint32_t sem,
+                                  uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
+                                  float bounce_eps, float shadow_eps, float bounce_albedo, const trx_hit *d_primary,
+                                  const uint32_t *d_primary_inst, float *d_value_lo, void *stream) {
+    const SparseGrid grid{stride, phase};
+    return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
+                         bounce_albedo, d_primary, d_primary_inst, nullptr, d_value_lo, (hipStream_t)stream, nullptr, &grid);
 }
 
 // ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // api_image.cpp - the frame's image (include/trx.h, trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev /
 // trx_render_image*, trx_render_image_lit among them): the edge-aware filter over the AO visibility pass's counts, the edge-aware upsample of the sparse
 // pass's counts and the shading to RGBA8 (k_ao_filter, k_ao_upsample, k_shade, image.hip), the a-trous filter over float
-// planes (trx_value_filter_dev / trx_render_image_gi_filtered, k_atrous), and the table of
+// planes (trx_value_filter_dev / trx_render_image_gi_filtered, k_atrous), the edge-aware upsample of a low-grid float plane (trx_value_upsample_dev / trx_render_image_gi_sparse, k_plane_upsample), and the table of
 // code thresholds the shade searches instead of evaluating pow; the PROFILE_RT heat map of a counting pass's per-ray counts
 // (trx_shade_heat_dev / trx_render_heat_image, k_heat).  Image passes after the walk: none reads scene data, but
 // each takes a launch slot of the scene like the attribute pass, so trx_scene_refit waits for them.
@@ -100,6 +100,16 @@ int enqueue_image(trx_scene *s, hipStream_t stream, bool need_table, Launch laun
 int check_value_filter(uint32_t n_levels, float depth_tol, float normal_cos) {
     if (n_levels == 0 || n_levels > TRX_MAX_VALUE_FILTER_LEVELS)
         return fail(TRX_ERR_INVALID, "n_levels %u outside 1..%d", n_levels, TRX_MAX_VALUE_FILTER_LEVELS);
+    if (!(depth_tol >= 0.0f)) return fail(TRX_ERR_INVALID, "depth_tol %g: must be >= 0 (+inf allowed)", (double)depth_tol);
+    if (normal_cos != normal_cos) return fail(TRX_ERR_INVALID, "normal_cos is NaN");
+    return TRX_OK;
+}
+
+// what trx_value_upsample_dev refuses of its numbers (trx_render_image_gi_sparse asks too)
+int check_value_upsample(uint32_t stride, uint32_t phase, uint32_t radius, float depth_tol, float normal_cos) {
+    if (int rc = check_sparse(stride, phase, 0u)) return rc;
+    if (radius > TRX_MAX_VALUE_UPSAMPLE_RADIUS)
+        return fail(TRX_ERR_INVALID, "upsample radius %u beyond %d", radius, TRX_MAX_VALUE_UPSAMPLE_RADIUS);
     if (!(depth_tol >= 0.0f)) return fail(TRX_ERR_INVALID, "depth_tol %g: must be >= 0 (+inf allowed)", (double)depth_tol);
     if (normal_cos != normal_cos) return fail(TRX_ERR_INVALID, "normal_cos is NaN");
     return TRX_OK;
@@ -283,6 +293,36 @@ int trx_value_filter_dev(trx_scene *s, uint32_t w, uint32_t h, const trx_hit *d_
     });
 }
 
+int trx_value_upsample_dev(trx_scene *s, uint32_t w, uint32_t h, uint32_t stride, uint32_t phase, const trx_hit *d_primary,
+                           const trx_hit_attr *d_attr, const float *d_in_lo, const float *d_base, uint32_t radius, float depth_tol,
+                           float normal_cos, float *d_out, void *stream) {
+    if (int rc = check_value_upsample(stride, phase, radius, depth_tol, normal_cos)) return rc;
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !d_primary || !d_in_lo || !d_out) return fail(TRX_ERR_INVALID, "null argument");
+    if (d_in_lo == d_out) return fail(TRX_ERR_INVALID, "d_in_lo is d_out: the upsample cannot run in place");
+    PlaneUpsampleParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.primary = d_primary;
+    p.attr = d_attr;
+    p.in_lo = d_in_lo;
+    p.base = d_base;
+    p.out = d_out;
+    p.width = w;
+    p.height = h;
+    p.lo_width = (w + stride - 1u) / stride;
+    p.lo_height = (h + stride - 1u) / stride;
+    p.stride = stride;
+    p.px0 = phase % stride;
+    p.py0 = phase / stride;
+    p.radius = radius;
+    p.depth_tol = depth_tol;
+    p.normal_cos = normal_cos;
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        HIP_TRY(launch_plane_upsample(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
 int trx_shade_heat_dev(trx_scene *s, const trx_ray_cost *d_cost, uint64_t n, uint32_t which, float scale, uint8_t *d_rgba,
                        void *stream) {
     if (int rc = check_heat(which, scale)) return rc;
@@ -420,12 +460,14 @@ int trx_render_image_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint
 // trx_render_image_lit (bounce_samples == 0), trx_render_image_gi (bounce_samples >= 1: the indirect pass between the light
 // term and the shade, the term's values its base and its output) and trx_render_image_gi_filtered (filter_levels >= 1: the
 // indirect pass without a base into a plane of its own, the value filter over that plane with the term's values its base and
-// its output)
+// its output); trx_render_image_gi_sparse (bounce_stride >= 1: the sparse indirect pass into a low plane, then the upsample - with
+// the term's values its base and its output, or with filter levels without a base into the plane the filter then reads)
 static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
                       const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
                       float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                       float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint32_t filter_levels,
-                      float bounce_depth_tol, float bounce_normal_cos, uint8_t *out_rgba, float *out_ms) {
+                      float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
+                      uint32_t upsample_radius, uint8_t *out_rgba, float *out_ms) {
     if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
     if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
@@ -443,14 +485,15 @@ static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
     HIP_TRY(hipSetDevice(s->device));
     // the image scratch: the filter's terms, the image, the light term's values, with a value filter the indirect term and the
-    // filter's work plane, then the lights' planes
-    const uint64_t planes = filter_levels != 0 ? 5 : 3;
+    // filter's work plane, with a sparse indirect pass its low plane (at most one plane), then the lights' planes
+    const uint64_t planes = bounce_stride != 0 ? 6 : filter_levels != 0 ? 5 : 3;
     HIP_TRY(s->scratch_img.grow(n * 4 * planes + n * n_lights));
     auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
     auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
     auto d_value = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 8); };
     auto d_indirect = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 12); };
     auto d_work = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 16); };
+    auto d_low = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 20); };
     auto d_lit = [&] { return s->scratch_img.get() + n * 4 * planes; };
     // (the AO counts go where trx_trace_ao_visibility puts them: n bytes of the second record buffer)
     auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
@@ -475,7 +518,22 @@ static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
             rc = trx_light_term_dev(s, view, w, h, whole, lights, n_lights, light_samples, s->scratch_a.get(), s->scratch_attr.get(),
                                     d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
             if (rc) return rc;
-            if (bounce_samples != 0 && filter_levels == 0) {
+            if (bounce_samples != 0 && bounce_stride != 0) {
+                rc = trx_trace_indirect_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights, n_lights, frame0,
+                                                   bounce_samples, bounce_eps, shadow_eps, bounce_albedo, s->scratch_a.get(),
+                                                   s->scratch_ia.get(), d_low(), nullptr);
+                if (rc) return rc;
+                const bool filter = filter_levels != 0;
+                rc = trx_value_upsample_dev(s, w, h, bounce_stride, bounce_phase, s->scratch_a.get(), s->scratch_attr.get(), d_low(),
+                                            filter ? nullptr : d_value(), upsample_radius, bounce_depth_tol, bounce_normal_cos,
+                                            filter ? d_indirect() : d_value(), nullptr);
+                if (rc) return rc;
+                if (filter) {
+                    rc = trx_value_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), d_indirect(), d_value(), filter_levels,
+                                              bounce_depth_tol, bounce_normal_cos, d_work(), d_value(), nullptr);
+                    if (rc) return rc;
+                }
+            } else if (bounce_samples != 0 && filter_levels == 0) {
                 rc = trx_trace_indirect_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples, bounce_eps,
                                             shadow_eps, bounce_albedo, s->scratch_a.get(), s->scratch_ia.get(), d_value(), d_value(), nullptr);
                 if (rc) return rc;
@@ -500,7 +558,7 @@ int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_
                          float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                          float normal_cos, uint8_t *out_rgba, float *out_ms) {
     return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
-                      ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, 0u, 0.0f, 0.0f, out_rgba, out_ms);
+                      ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, 0u, 0.0f, 0.0f, 0u, 0u, 0u, out_rgba, out_ms);
 }
 
 // what trx_render_image_gi adds to the lit image's refusals (which come first, in their order)
@@ -521,8 +579,8 @@ int trx_render_image_gi(trx_scene *s, const trx_view *view, uint32_t w, uint32_t
                         float *out_ms) {
     if (int rc = check_bounce(lights, n_lights, light_samples, bounce_samples, bounce_eps, bounce_albedo)) return rc;
     return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
-                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, 0u, 0.0f, 0.0f, out_rgba,
-                      out_ms);
+                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, 0u, 0.0f, 0.0f, 0u, 0u, 0u,
+                      out_rgba, out_ms);
 }
 
 int trx_render_image_gi_filtered(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
@@ -538,7 +596,23 @@ int trx_render_image_gi_filtered(trx_scene *s, const trx_view *view, uint32_t w,
         if (int rc = check_value_filter(bounce_filter_levels, bounce_depth_tol, bounce_normal_cos)) return rc;
     return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
                       ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, bounce_filter_levels,
-                      bounce_depth_tol, bounce_normal_cos, out_rgba, out_ms);
+                      bounce_depth_tol, bounce_normal_cos, 0u, 0u, 0u, out_rgba, out_ms);
+}
+
+int trx_render_image_gi_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                               const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                               float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                               float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo,
+                               uint32_t bounce_filter_levels, float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride,
+                               uint32_t bounce_phase, uint32_t bounce_upsample_radius, uint8_t *out_rgba, float *out_ms) {
+    if (int rc = check_bounce(lights, n_lights, light_samples, bounce_samples, bounce_eps, bounce_albedo)) return rc;
+    if (bounce_filter_levels > TRX_MAX_VALUE_FILTER_LEVELS)
+        return fail(TRX_ERR_INVALID, "bounce_filter_levels %u outside 0..%d", bounce_filter_levels, TRX_MAX_VALUE_FILTER_LEVELS);
+    // (the upsample looks at the two tolerances whatever the levels)
+    if (int rc = check_value_upsample(bounce_stride, bounce_phase, bounce_upsample_radius, bounce_depth_tol, bounce_normal_cos)) return rc;
+    return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                      ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo, bounce_filter_levels,
+                      bounce_depth_tol, bounce_normal_cos, bounce_stride, bounce_phase, bounce_upsample_radius, out_rgba, out_ms);
 }
 
 } // extern "C"

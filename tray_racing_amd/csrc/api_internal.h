@@ -9,8 +9,8 @@
 //   api_attr.cpp     trx_hit_attributes_* / trx_trace_rays_attr: the hit-attribute post-pass (k_hit_attr, kernels.hip)
 //   api_ao.cpp       trx_ao_rays_dev / trx_trace_ao_visibility*: AO rays as explicit rays, any-hit walk, per-pixel counts;
 //                    trx_light_rays_dev / trx_trace_light_visibility_dev / trx_light_term_dev: the same chain per light, and the light term
-//                    trx_bounce_light_rays_dev / trx_trace_indirect_dev: one diffuse bounce - closest-hit bounce rays, their attributes, shadow rays from the bounce hits
-//   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
+//                    trx_bounce_light_rays_dev / trx_trace_indirect_dev / trx_trace_indirect_sparse_dev: one diffuse bounce (dense, or over a low grid) - closest-hit bounce rays, their attributes, shadow rays from the bounce hits
+//   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_value_filter_dev / trx_value_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H

@@ -71,6 +71,10 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     int bounce_filter = -1; // -1: not given, everything stays as it is
     float bounce_filter_tol = 0.1f, bounce_filter_cos = 0.9f;
     bool bounce_filter_opts = false; // one of the two tolerances was given
+    // --bounce-stride S [--bounce-phase P] [--bounce-upsample R]: with --bounce-samples the bounce's term is traced at one pixel
+    // in S x S and rebuilt by the edge-aware upsample (trx_render_image_gi_sparse; the filter's two tolerances are its own)
+    int bounce_stride = -1; // -1: not given, everything stays as it is
+    int bounce_phase = -1, bounce_upsample = -1; // (not given: phase 0, radius 1)
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -120,6 +124,9 @@ void usage() {
               "  [--bounce-filter 0..5] [--bounce-filter-tol d] [--bounce-filter-cos c] (with --bounce-samples: the bounce's term through\n"
               "   L levels of the edge-aware a-trous filter - taps 1, 2, 4, .. pixels apart, kept where the depth is within d (default\n"
               "   0.1) of the pixel's and the normals within c (default 0.9) - before it is added; 0: unfiltered)\n"
+              "  [--bounce-stride 1..4] [--bounce-phase P] [--bounce-upsample 0..2] (with --bounce-samples: the bounce rays of one pixel\n"
+              "   in every S x S block - pixel P = 0..S*S-1 of the block, default 0 - and the full-resolution term rebuilt from the\n"
+              "   cells of a (2R+1)^2 window, default R = 1, under --bounce-filter-tol / --bounce-filter-cos; before --bounce-filter)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -248,6 +255,16 @@ Options parse_args(int argc, char **argv) {
         } else if (a == "--bounce-filter") {
             o.bounce_filter = std::atoi(need(i));
             if (o.bounce_filter < 0 || o.bounce_filter > TRX_MAX_VALUE_FILTER_LEVELS) die("--bounce-filter takes 0.." + std::to_string(TRX_MAX_VALUE_FILTER_LEVELS));
+        } else if (a == "--bounce-stride") {
+            o.bounce_stride = std::atoi(need(i));
+            if (o.bounce_stride < 1 || o.bounce_stride > TRX_MAX_AO_STRIDE) die("--bounce-stride takes 1.." + std::to_string(TRX_MAX_AO_STRIDE));
+        } else if (a == "--bounce-phase") {
+            o.bounce_phase = std::atoi(need(i));
+            if (o.bounce_phase < 0) die("--bounce-phase takes 0..S*S-1 of --bounce-stride S");
+        } else if (a == "--bounce-upsample") {
+            o.bounce_upsample = std::atoi(need(i));
+            if (o.bounce_upsample < 0 || o.bounce_upsample > TRX_MAX_VALUE_UPSAMPLE_RADIUS)
+                die("--bounce-upsample takes 0.." + std::to_string(TRX_MAX_VALUE_UPSAMPLE_RADIUS));
         } else if (a == "--bounce-filter-tol") {
             o.bounce_filter_tol = (float)std::atof(need(i));
             o.bounce_filter_opts = true;
@@ -310,7 +327,10 @@ Options parse_args(int argc, char **argv) {
     if (o.bounce_samples < 0 && (o.bounce_albedo >= 0.0f || o.bounce_eps >= 0.0f)) die("--bounce-albedo and --bounce-eps go with --bounce-samples N");
     if (o.bounce_samples >= 0 && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--bounce-samples draws the GI image: not together with --ao-stride or --profile-rt");
     if (o.bounce_samples >= 0 && o.lights.empty()) die("--bounce-samples bounces the light of --light");
-    if (o.bounce_filter < 0 && o.bounce_filter_opts) die("--bounce-filter-tol and --bounce-filter-cos go with --bounce-filter L");
+    if (o.bounce_stride < 0 && (o.bounce_phase >= 0 || o.bounce_upsample >= 0)) die("--bounce-phase and --bounce-upsample go with --bounce-stride S");
+    if (o.bounce_stride >= 0 && o.bounce_samples < 0) die("--bounce-stride thins the rays of --bounce-samples N");
+    if (o.bounce_stride >= 0 && o.bounce_phase >= o.bounce_stride * o.bounce_stride) die("--bounce-phase takes 0..S*S-1 of --bounce-stride S");
+    if (o.bounce_filter < 0 && o.bounce_stride < 0 && o.bounce_filter_opts) die("--bounce-filter-tol and --bounce-filter-cos go with --bounce-filter L");
     if (o.bounce_filter >= 0 && o.bounce_samples < 0) die("--bounce-filter filters the term of --bounce-samples N");
     if (o.passes == 0) o.passes = 1;
     return o;
@@ -380,7 +400,19 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
         const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
-        if (o.bounce_samples >= 0 && o.bounce_filter >= 0)
+        if (o.bounce_samples >= 0 && o.bounce_stride >= 0)
+            // ... and one diffuse bounce traced at one pixel in stride x stride, upsampled (and filtered), on top of it
+            check(trx_render_image_gi_sparse(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                             o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
+                                             o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
+                                             radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
+                                             (uint32_t)o.bounce_samples, o.bounce_eps >= 0.0f ? o.bounce_eps : 0.01f,
+                                             o.bounce_albedo >= 0.0f ? o.bounce_albedo : 0.5f, o.bounce_filter >= 0 ? (uint32_t)o.bounce_filter : 0u,
+                                             o.bounce_filter_tol, o.bounce_filter_cos, (uint32_t)o.bounce_stride,
+                                             o.bounce_phase >= 0 ? (uint32_t)o.bounce_phase : 0u, o.bounce_upsample >= 0 ? (uint32_t)o.bounce_upsample : 1u,
+                                             rgba.data(), &ms),
+                  "png frame");
+        else if (o.bounce_samples >= 0 && o.bounce_filter >= 0)
             // ... and one diffuse bounce, filtered, on top of it
             check(trx_render_image_gi_filtered(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                                o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,

@@ -44,6 +44,23 @@ struct AoUpsampleParams {
 };
 hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream);
 
+// k_plane_upsample (trx_value_upsample_dev): k_ao_upsample's shape and window over a low grid of FLOATS - the sparse indirect
+// pass's values - with the weighted float sums of the header's rule in place of the integer counts.  The same tile, the same
+// cells in LDS (kUpsampleMaxCells: depth, value and, with normals, three components - 20 B or 8 B a cell).
+static_assert(TRX_MAX_VALUE_UPSAMPLE_RADIUS == TRX_MAX_AO_UPSAMPLE_RADIUS, "k_plane_upsample stages kUpsampleMaxCells cells");
+struct PlaneUpsampleParams {
+    const trx_hit *primary;   // whole FULL-resolution image, y * width + x
+    const trx_hit_attr *attr; // or null: no normal test
+    const float *in_lo;       // the low grid, Y * lo_width + X
+    const float *base;        // full resolution, or null; may be `out`
+    float *out;               // full resolution
+    uint32_t width, height, lo_width, lo_height;
+    uint32_t stride, px0, py0;
+    uint32_t radius;
+    float depth_tol, normal_cos;
+};
+hipError_t launch_plane_upsample(const PlaneUpsampleParams &p, hipStream_t stream);
+
 // k_atrous (trx_value_filter_dev): one level of the a-trous filter at spacing s = 1 << level.  A level couples only pixels
 // of one residue class in y mod s (and in x mod s), so a workgroup of 256 lanes takes kAtrousTileW consecutive x of
 // kAtrousTileRows LATTICE rows y0 + k * s of one row class, and stages those rows, two lattice rows above and below and 2s

@@ -6,7 +6,7 @@
 // Arithmetic contract (DESIGN.md "Numerics"): binary32, no contraction, IEEE divide, dot = (ax*bx + ay*by) + az*bz.  The
 // filter compares in float and sums in integers, the shade divides once and then only compares, so a host twin
 // (tests/image_twin.py) gives the same bits; the heat map is a fixed sequence of such operations (tests/heat_twin.py), and so
-// is a level of the value filter over float planes (k_atrous, tests/value_filter_twin.py).
+// is a level of the value filter over float planes (k_atrous, tests/value_filter_twin.py) and the upsample of a low-grid float plane (k_plane_upsample, tests/indirect_sparse_twin.py).
 #include "image.h"
 
 #pragma clang fp contract(off)
@@ -381,6 +381,116 @@ __global__ void __launch_bounds__(256) k_atrous(const AtrousParams P) {
     P.out[ip] = f;
 }
 
+// The edge-aware upsample of a low grid of floats (trx_value_upsample_dev; the rules are stated in include/trx.h): what
+// k_ao_upsample is to the sparse visibility pass's counts, for the sparse indirect pass's values.  Its shape, tile, cells
+// and window: one workgroup per 32 x 8 tile of full-resolution pixels, lane l is pixel (l & 31, l >> 5).
+//   phase 1: the low cells under the tile and a halo of r cells into LDS as separate arrays (depth, value, three normal
+// components).  A cell's depth and normal are the full-resolution records of its pixel (X s + px0, Y s + py0); its value is
+// the low grid's float.  A cell outside the low grid, whose pixel is outside the image, or without a surface gets the depth
+// +inf - "no cell" - and the value 0, and loads nothing further.  At most kUpsampleMaxCells cells: 8 640 B with normals,
+// 3 456 B without.
+//   phase 2: every lane reads its own pixel's depth and normal from memory (consecutive records) and walks the (2r + 1)^2
+// cells around cell (x / s, y / s) out of LDS in the stated order.  k_ao_upsample's reads, so its argument holds: a 32-lane
+// half is one row of pixels and reads, per window step, the dwords row * pitch + x / s + const - s neighbouring lanes name
+// the same dword (one broadcast), the distinct ones are at most 32 CONSECUTIVE dwords, and ds_read_b32 banks a half over
+// (address / 4) mod 32: conflict-free whatever the pitch (8 .. 36 dwords) and whatever s.
+// Two pairs of sums run side by side - over the accepted cells and over all surface cells (FALLBACK) - each the rule's
+// operations one by one (contraction is off in this file); a cell that does not count is a select that leaves the pair as it
+// is, so a NaN or an infinity there stays out.  The weights are positive, so den > 0 says that a cell was accepted.  The
+// lane reads its base, then writes its value: d_base may be d_out.
+template <bool NORMALS>
+__global__ void __launch_bounds__(256) k_plane_upsample(const PlaneUpsampleParams P) {
+    __shared__ float s_t[kUpsampleMaxCells];
+    __shared__ float s_v[kUpsampleMaxCells];
+    __shared__ float s_n[NORMALS ? 3 * kUpsampleMaxCells : 1];
+    const uint32_t r = P.radius, st = P.stride;
+    const uint32_t tiles_x = (P.width + kFilterTileW - 1u) / kFilterTileW;
+    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const uint32_t cx_first = (tx * kFilterTileW) / st, cy_first = (ty * kFilterTileH) / st;
+    const uint32_t hw = (tx * kFilterTileW + kFilterTileW - 1u) / st - cx_first + 1u + 2u * r;
+    const uint32_t hh = (ty * kFilterTileH + kFilterTileH - 1u) / st - cy_first + 1u + 2u * r;
+    const uint32_t cells = hw * hh; // <= kUpsampleMaxCells for st >= 1, r <= kUpsampleMaxRadius (image.h)
+    const int x0 = (int)cx_first - (int)r, y0 = (int)cy_first - (int)r;
+    for (uint32_t c = threadIdx.x; c < cells; c += 256u) {
+        const uint32_t cy = c / hw, cx = c - cy * hw;
+        const int X = x0 + (int)cx, Y = y0 + (int)cy;
+        float t = __builtin_inff(), v = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        if (X >= 0 && Y >= 0 && (uint32_t)X < P.lo_width && (uint32_t)Y < P.lo_height) {
+            const uint32_t gx = (uint32_t)X * st + P.px0, gy = (uint32_t)Y * st + P.py0;
+            if (gx < P.width && gy < P.height) {
+                const size_t i = (size_t)gy * P.width + gx;
+                const trx_hit h = P.primary[i];
+                if (h.t < TRX_F32_MAX && h.prim != TRX_INVALID) {
+                    t = h.t;
+                    v = P.in_lo[(size_t)Y * P.lo_width + (uint32_t)X];
+                    if constexpr (NORMALS) {
+                        const float *n = P.attr[i].normal;
+                        nx = n[0]; ny = n[1]; nz = n[2];
+                    }
+                }
+            }
+        }
+        s_t[c] = t;
+        s_v[c] = v;
+        if constexpr (NORMALS) {
+            s_n[c] = nx;
+            s_n[kUpsampleMaxCells + c] = ny;
+            s_n[2u * kUpsampleMaxCells + c] = nz;
+        }
+    }
+    __syncthreads();
+    const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
+    const uint32_t px = tx * kFilterTileW + lx, py = ty * kFilterTileH + ly;
+    if (px >= P.width || py >= P.height) return;
+    const size_t ip = (size_t)py * P.width + px;
+    const trx_hit hp = P.primary[ip];
+    if (!(hp.t < TRX_F32_MAX && hp.prim != TRX_INVALID)) { // no surface: the base's bits copied, +0 without a base
+        uint32_t bits = 0u;
+        if (P.base) bits = reinterpret_cast<const uint32_t *>(P.base)[ip];
+        reinterpret_cast<uint32_t *>(P.out)[ip] = bits;
+        return;
+    }
+    const float tp = hp.t, tol = P.depth_tol * tp;
+    float npx = 0.0f, npy = 0.0f, npz = 0.0f;
+    if constexpr (NORMALS) {
+        const float *n = P.attr[ip].normal;
+        npx = n[0]; npy = n[1]; npz = n[2];
+    }
+    // the window's first cell, and the cell whose pixel is p itself (none when p is not a pixel of this phase)
+    const uint32_t qx = px / st, qy = py / st;
+    const uint32_t wx = qx - cx_first, wy = qy - cy_first;
+    const uint32_t own = (px - qx * st == P.px0 && py - qy * st == P.py0) ? (wy + r) * hw + wx + r : 0xFFFFFFFFu;
+    float num = 0.0f, den = 0.0f, num_all = 0.0f, den_all = 0.0f;
+    for (uint32_t dy = 0; dy <= 2u * r; dy++) {
+        const uint32_t row = (wy + dy) * hw + wx;
+        const uint32_t ky = dy <= r ? dy + 1u : 2u * r + 1u - dy; // k[|dy - r|] = r + 1 - |dy - r|
+        for (uint32_t dx = 0; dx <= 2u * r; dx++) {
+            const uint32_t kx = dx <= r ? dx + 1u : 2u * r + 1u - dx;
+            const float w = (float)(ky * kx);
+            const uint32_t c = row + dx;
+            const float tq = s_t[c];
+            const bool surf = tq < TRX_F32_MAX;
+            bool ok = surf && __builtin_fabsf(tq - tp) <= tol;
+            if constexpr (NORMALS)
+                ok = ok && (npx * s_n[c] + npy * s_n[kUpsampleMaxCells + c]) + npz * s_n[2u * kUpsampleMaxCells + c] >= P.normal_cos;
+            ok = ok || c == own;
+            const float term = w * s_v[c];
+            num = ok ? num + term : num;
+            den = ok ? den + w : den;
+            num_all = surf ? num_all + term : num_all;
+            den_all = surf ? den_all + w : den_all;
+        }
+    }
+    // no cell accepted: every surface cell of the window (FALLBACK); none of those either: +0 (EMPTY)
+    if (!(den > 0.0f)) {
+        num = num_all;
+        den = den_all;
+    }
+    float f = den > 0.0f ? __fdiv_rn(num, den) : 0.0f;
+    if (P.base) f = P.base[ip] + f;
+    P.out[ip] = f;
+}
+
 } // namespace
 
 hipError_t launch_heat(const HeatParams &p, hipStream_t stream) {
@@ -407,6 +517,19 @@ hipError_t launch_ao_upsample(const AoUpsampleParams &p, hipStream_t stream) {
         return hipErrorInvalidValue;
     if (p.attr) hipLaunchKernelGGL(k_ao_upsample<true>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(k_ao_upsample<false>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_plane_upsample(const PlaneUpsampleParams &p, hipStream_t stream) {
+    const uint64_t tiles = (uint64_t)((p.width + kFilterTileW - 1u) / kFilterTileW) * ((p.height + kFilterTileH - 1u) / kFilterTileH);
+    if (tiles == 0) return hipSuccess;
+    // (what bounds the kernel's LDS indices and its reads of the low grid)
+    if (tiles > 0x7fffffffull || p.radius > kUpsampleMaxRadius || p.stride == 0 || p.stride > kUpsampleMaxStride || p.px0 >= p.stride ||
+        p.py0 >= p.stride || p.lo_width != (p.width + p.stride - 1u) / p.stride || p.lo_height != (p.height + p.stride - 1u) / p.stride ||
+        p.in_lo == p.out)
+        return hipErrorInvalidValue;
+    if (p.attr) hipLaunchKernelGGL(k_plane_upsample<true>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(k_plane_upsample<false>, dim3((uint32_t)tiles), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

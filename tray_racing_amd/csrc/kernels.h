@@ -303,6 +303,8 @@ hipError_t launch_light_term(const LightTermParams &p, hipStream_t stream);
 //   k_bounce_finish      one lane per pixel of the chunk's tiles: value[record] = base + (albedo * acc) / n_total, or base
 //                        where the primary record is no surface (base: base[record], 0 with a null pointer).  The running sum
 //                        sits in acc, not in value, so base may be value itself.
+// k_bounce_light_rays and k_bounce_finish have a SPARSE instantiation (below, `stride`); k_bounce_weight and k_bounce_gather
+// see the scratch alone and serve both forms.
 // scratch per (tile, sample): the bounce rays, hits, instance ids, attributes and sums beside the AO pass's rays and flags,
 // and the tile's 64 running sums (one set per tile: counted here per sample, which is at most what they take)
 constexpr uint32_t kBounceUnitBytes = kAoUnitBytes + 64u * (32u + 8u + 4u + 24u + 4u + 4u);
@@ -324,6 +326,12 @@ struct BounceParams {
     uint32_t seed0;               // the seed of the chunk's first sample: frame0 + light_index * 64 + sample
     float shadow_eps, albedo;
     trx_light light;
+    // sparse (trx_trace_indirect_sparse_dev; scratch layout, whole image; last: the fields above keep their offsets): the
+    // tiles are those of the LOW grid `lo`, as AoRaysParams describes them.  k_bounce_light_rays takes its noise at the cell's
+    // pixel (X * stride + px0, Y * stride + py0) of the full image `geom`; k_bounce_finish reads that pixel's primary record
+    // and writes value[Y * lo.width + X] - +0 for a cell whose pixel leaves the image.  The dense launches leave stride 0.
+    uint32_t stride, px0, py0;
+    TileGeom lo;
 };
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream);

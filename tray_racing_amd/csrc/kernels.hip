@@ -1185,15 +1185,28 @@ __device__ __forceinline__ bool bounce_hit(const BounceParams &P, uint32_t index
 // The shadow ray of every (tile, sample, pixel) from its bounce hit toward ONE light: k_light_rays with the primary hit
 // replaced by the bounce hit - the normal comes from the attribute record, so no triangle and no instance row is read.  A
 // streaming kernel: 32 B of bounce ray, 8 B of hit, 24 B of attributes read per ray, 32 B written; the light is launch-uniform.
+//   SPARSE (trx_trace_indirect_sparse_dev; scratch layout): the tile is one of the low grid, and the rect light's noise is
+// taken at the cell's pixel of the full image - k_ao_rays' mapping; everything else is the dense statement.  A cell whose
+// pixel leaves the image carries the inert bounce ray, so its coordinates are never looked at.
+template <bool SPARSE>
 __global__ void __launch_bounds__(256) k_bounce_light_rays(const BounceParams P) {
     const uint32_t item = blockIdx.x * 256u + threadIdx.x;
     if (item >= P.n_tiles * P.n_samples * 64u) return;
     const uint32_t unit = item >> 6, k = item & 63u;
     const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
     uint32_t px, py, rec;
-    const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
-    if (!inside && !P.scratch) return; // (no record is there)
-    const uint32_t index = P.scratch ? item : rec;
+    uint32_t index;
+    if constexpr (SPARSE) {
+        uint32_t cx, cy;
+        tile_pixel(P.lo, P.tile0 + lt, k, cx, cy, rec);
+        px = cx * P.stride + P.px0;
+        py = cy * P.stride + P.py0;
+        index = item;
+    } else {
+        const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+        if (!inside && !P.scratch) return; // (no record is there)
+        index = P.scratch ? item : rec;
+    }
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
     BounceHit B;
     if (bounce_hit(P, index, B)) { // (scratch layout: a lane outside the image reads the inert bounce ray k_ao_rays wrote there)
@@ -1275,10 +1288,27 @@ __global__ void __launch_bounds__(256) k_bounce_gather(const BounceParams P) {
 
 // One lane per pixel of the chunk's tiles: the pass's value.  base is read before value is written, by the same lane: they
 // may be one buffer.
+//   SPARSE: one lane per cell of the low grid's tiles, the value at the cell's place in the low grid (there is no base: the
+// dense statement with base = 0.0f); the primary record is that of the cell's pixel in the full image, and a cell whose
+// pixel leaves the image gets +0.
+template <bool SPARSE>
 __global__ void __launch_bounds__(256) k_bounce_finish(const BounceParams P) {
     const uint32_t item = blockIdx.x * 256u + threadIdx.x;
     if (item >= P.n_tiles * 64u) return;
     uint32_t px, py, rec;
+    if constexpr (SPARSE) {
+        uint32_t cell;
+        if (!tile_pixel(P.lo, P.tile0 + (item >> 6), item & 63u, px, py, cell)) return;
+        px = px * P.stride + P.px0;
+        py = py * P.stride + P.py0;
+        float out = 0.0f;
+        if (px < P.geom.width && py < P.geom.height) {
+            const trx_hit ph = P.primary[(size_t)py * P.geom.width + px];
+            if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) out = out + (P.albedo * P.acc[item]) / (float)P.n_total;
+        }
+        P.value[cell] = out;
+        return;
+    }
     if (!tile_pixel(P.geom, P.tile0 + (item >> 6), item & 63u, px, py, rec)) return;
     const trx_hit ph = P.primary[rec];
     float out = P.base ? P.base[rec] : 0.0f;
@@ -1288,11 +1318,25 @@ __global__ void __launch_bounds__(256) k_bounce_finish(const BounceParams P) {
 
 } // namespace
 
+// (the sparse form of the bounce kernels exists for the scratch layout of a whole image only: what bounds their cell -> pixel
+// mapping and k_bounce_finish's writes to the low grid)
+static bool bounce_sparse_ok(const BounceParams &p) {
+    return p.scratch && p.stride <= TRX_MAX_AO_STRIDE && p.px0 < p.stride && p.py0 < p.stride && p.lo.shard_count == 1u && !p.lo.compact &&
+           p.geom.shard_count == 1u && !p.geom.compact && p.lo.width == (p.geom.width + p.stride - 1u) / p.stride &&
+           p.lo.height == (p.geom.height + p.stride - 1u) / p.stride;
+}
+
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream) {
     const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
     if (n == 0) return hipSuccess;
     if (n > 0xffffff00ull || p.light.kind > TRX_LIGHT_RECT || (!p.scratch && p.n_samples != 1u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_bounce_light_rays, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    const dim3 grid((uint32_t)((n + 255u) / 256u));
+    if (p.stride) {
+        if (!bounce_sparse_ok(p)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_bounce_light_rays<true>, grid, dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(k_bounce_light_rays<false>, grid, dim3(256), 0, stream, p);
+    }
     return hipGetLastError();
 }
 
@@ -1314,7 +1358,13 @@ hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream) {
 hipError_t launch_bounce_finish(const BounceParams &p, hipStream_t stream) {
     if (p.n_tiles == 0) return hipSuccess;
     if (p.n_tiles > 0x3ffffffu || p.n_total == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_bounce_finish, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    const dim3 grid((p.n_tiles * 64u + 255u) / 256u);
+    if (p.stride) {
+        if (!bounce_sparse_ok(p) || p.base) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_bounce_finish<true>, grid, dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(k_bounce_finish<false>, grid, dim3(256), 0, stream, p);
+    }
     return hipGetLastError();
 }
 

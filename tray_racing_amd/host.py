@@ -608,6 +608,24 @@ class Scene:
                                                        bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_image_gi_sparse(self, view, width, height, lights, bounce_samples, bounce_stride, bounce_phase=0, bounce_upsample_radius=1,
+                               bounce_filter_levels=0, bounce_depth_tol=0.1, bounce_normal_cos=0.9, bounce_eps=0.01, bounce_albedo=0.5,
+                               sem=L.SEM_HLSL, ray_mask=0, frame0=0, light_samples=1, shadow_eps=0.01, ambient=0.0, ao_samples=0, ao_eps=0.01,
+                               ao_radius=float("inf"), filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_gi_sparse - render_image_gi_filtered with the indirect term
+        traced at one pixel of every bounce_stride x bounce_stride block (the pixel bounce_phase names;
+        trace_indirect_sparse_dev) and rebuilt at full resolution by the edge-aware upsample of bounce_upsample_radius low
+        cells (value_upsample_dev, with the attribute pass's normals) before the filter; only the image crosses the bus."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_gi_sparse(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0,
+                                                     light_samples, shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius,
+                                                     depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo,
+                                                     bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, bounce_stride,
+                                                     bounce_phase, bounce_upsample_radius, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
         """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
         of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
@@ -851,6 +869,27 @@ class Scene:
         L.check(self._lib.trx_trace_indirect_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask, arr, len(arr),
                                                  frame0, n_samples, bounce_eps, shadow_eps, bounce_albedo, C.c_void_p(d_primary),
                                                  C.c_void_p(d_primary_inst), C.c_void_p(d_base), C.c_void_p(d_value), C.c_void_p(stream)))
+
+    def trace_indirect_sparse_dev(self, view, width, height, stride, phase, lights, d_primary, d_value_lo, n_samples=1, sem=L.SEM_HLSL,
+                                  ray_mask=0, frame0=0, bounce_eps=0.01, shadow_eps=0.01, bounce_albedo=0.5, d_primary_inst=0, stream=0):
+        """trx_trace_indirect_sparse_dev: the indirect pass at pixel (X * stride + phase % stride, Y * stride + phase // stride)
+        of every cell (X, Y) of the ceil(width / stride) x ceil(height / stride) low grid, one float per cell at d_value_lo -
+        that pixel's value of trx_trace_indirect_dev without a base, +0 where the pixel leaves the image or has no surface.
+        d_primary / d_primary_inst are whole-image, image-layout, full-resolution records."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_sparse_dev(self._h, C.byref(view), width, height, stride, phase, sem, ray_mask, arr, len(arr),
+                                                        frame0, n_samples, bounce_eps, shadow_eps, bounce_albedo, C.c_void_p(d_primary),
+                                                        C.c_void_p(d_primary_inst), C.c_void_p(d_value_lo), C.c_void_p(stream)))
+
+    def value_upsample_dev(self, width, height, stride, phase, d_primary, d_in_lo, d_out, radius, depth_tol=0.1, normal_cos=0.9, d_attr=0,
+                           d_base=0, stream=0):
+        """trx_value_upsample_dev: one float per full-resolution pixel at d_out from a low-grid float plane - the weighted mean
+        (weights (radius + 1 - |dy|) * (radius + 1 - |dx|)) of the accepted low cells of the (2 * radius + 1)^2 window around
+        cell (x // stride, y // stride), accepted as in trx_ao_upsample_dev; of every surface cell of the window where none is
+        accepted; d_base's value (none without one; d_base may be d_out) is added at surface pixels and copied elsewhere."""
+        L.check(self._lib.trx_value_upsample_dev(self._h, width, height, stride, phase, C.c_void_p(d_primary), C.c_void_p(d_attr),
+                                                 C.c_void_p(d_in_lo), C.c_void_p(d_base), radius, depth_tol, normal_cos,
+                                                 C.c_void_p(d_out), C.c_void_p(stream)))
 
     def shade_value_dev(self, d_value, n, d_rgba, stream=0):
         """trx_shade_value_dev: n float values as RGBA8 through the code table (0 for negative or NaN, 255 from 1 upward)."""
