@@ -79,6 +79,7 @@ def load():
         "orc_trace_rays": (None, [SP, P, u64, u32, i, P, STP]),
         "orc_traverse_inst": (HitC, [SP, P, P, f, f, u32, STP, P]),
         "orc_ao_ray_inst": (i, [SP, VP, u32, u32, u32, u32, HitC, u32, u32, f, P, P]),
+        "orc_ao_rays": (None, [SP, VP, u32, u32, u32, f, f, i, P, P, P]),
         "orc_xform_point": (None, [P, P, P]),
         "orc_xform_dir": (None, [P, P, P]),
         "orc_trace_primary_inst": (None, [SP, VP, u32, u32, u32, u32, u32, i, P, P, STP]),
@@ -205,6 +206,18 @@ class Scene:
         load().orc_trace_ao_inst(C.byref(self.c), C.byref(view), w, h, shard[0], shard[1], sem, frame, ao_eps, threads,
                                  _ptr(primary), _ptr(primary_inst), _ptr(ao), _ptr(inst), C.byref(st))
         return ao, inst, st
+
+    def ao_rays(self, view, w, h, primary, primary_inst=None, frame=0, ao_eps=0.01, tmax=F32_MAX, threads=0):
+        """[w * h] rays in pixel order: orc_ao_ray_inst of every record for seed `frame` (taken mod 2^32), tmin 0 and `tmax`;
+        the inert ray (all words 0, tmax = -1) where the record is a miss."""
+        primary = np.ascontiguousarray(primary, dtype=HIT_DTYPE)
+        assert primary.shape[0] == w * h
+        inst = None if primary_inst is None else np.ascontiguousarray(primary_inst, dtype=np.uint32)
+        assert inst is None or inst.shape[0] == w * h
+        rays = np.zeros(w * h, dtype=RAY_DTYPE)
+        load().orc_ao_rays(C.byref(self.c), C.byref(view), w, h, int(frame) & 0xFFFFFFFF, ao_eps, tmax, threads, _ptr(primary),
+                           _ptr(inst) if inst is not None else None, _ptr(rays))
+        return rays
 
     def trace_rays_inst(self, rays, sem=SEM_HLSL, threads=0):
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)

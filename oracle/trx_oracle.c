@@ -869,6 +869,25 @@ void orc_trace_rays_inst(const orc_scene *s, const orc_ray *rays, uint64_t n, ui
     if (st) *st = total;
 }
 
+/* The AO ray of every record of a w x h image (pixel order) for one seed, as explicit rays: orc_ao_ray_inst per record,
+ * tmin 0 and the given tmax; the inert ray (all words 0, tmax = -1) where the record is a miss.  No second statement of
+ * the ray: a loop over the function above, for tests that need more rays than a loop of foreign calls can build. */
+void orc_ao_rays(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t frame, float ao_eps, float tmax,
+                 int threads, const orc_hit *primary, const uint32_t *primary_inst, orc_ray *rays) {
+    threads = pick_threads(threads);
+    const int64_t n = (int64_t)w * h;
+#pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64_t i = 0; i < n; i++) {
+        orc_ray r;
+        memset(&r, 0, sizeof(r));
+        r.tmax = -1.0f;
+        if (orc_ao_ray_inst(s, view, w, h, (uint32_t)(i % w), (uint32_t)(i / w), primary[i],
+                            primary_inst ? primary_inst[i] : INVALID, frame, ao_eps, r.origin, r.direction))
+            r.tmax = tmax;
+        rays[i] = r;
+    }
+}
+
 /* The reference's CPU frame, src/rt_cpu/rt_cpu.rs:35-92: per pixel primary ray,
  * and if it hit one AO ray, shade.  rgb may be NULL.  Returns wall seconds. */
 double orc_render_frame(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t sem,

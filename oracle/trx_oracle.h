@@ -124,6 +124,10 @@ orc_hit orc_traverse_inst(const orc_scene *s, const float o[3], const float d[3]
                           uint32_t sem, orc_stats *st, uint32_t *inst);
 int orc_ao_ray_inst(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t px, uint32_t py,
                     orc_hit primary, uint32_t primary_inst, uint32_t frame, float ao_eps, float o[3], float d[3]);
+/* orc_ao_ray_inst for every record of a w x h image in pixel order, as rays {o, tmin 0, d, tmax}; the inert ray (all words
+ * 0, tmax = -1) where the record is a miss.  primary_inst may be NULL. */
+void orc_ao_rays(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t frame, float ao_eps, float tmax,
+                 int threads, const orc_hit *primary, const uint32_t *primary_inst, orc_ray *rays);
 /* point / direction through a 3x4 transform with the operation order both sides use:
  * ((m0*x + m1*y) + m2*z) [+ t] per row */
 void orc_xform_point(const float m[12], const float p[3], float out[3]);

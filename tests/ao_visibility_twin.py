@@ -45,8 +45,9 @@ def record_map(w, h, shard=(0, 1, 0)):
 
 def ao_rays(orc, osc, oview, w, h, primary, primary_inst, frame, ao_eps, ao_radius):
     """([w * h] rays in pixel order, surface mask): the twin's ray of every pixel for seed `frame`; the inert ray where the
-    primary record is a miss."""
+    primary record is a miss.  Seeds are 32-bit words: `frame` is taken mod 2^32, as the device's frame0 + f wraps."""
     lib = orc.load()
+    frame = int(frame) & 0xFFFFFFFF
     rays = np.zeros(w * h, dtype=orc.RAY_DTYPE)
     rays["tmax"] = np.float32(-1.0)
     surface = np.zeros(w * h, dtype=bool)
