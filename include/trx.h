@@ -278,7 +278,9 @@ int trx_scene_get_instance_masks(const trx_scene *scene, uint8_t *out, uint32_t 
 /* Masked forms of trx_trace_rays_inst_dev, trx_trace_occluded_dev, trx_trace_primary_inst_dev and
  * trx_trace_ao_inst_dev: the same arguments and rules (d_inst / d_ao_inst may be NULL; the AO call needs d_primary_inst
  * on scenes with instance transforms) plus ray_mask.  The AO pass takes the records of a primary pass - usually the
- * masked one - as they are: pixels whose primary record is a miss get a miss record. */
+ * masked one - as they are: pixels whose primary record is a miss get a miss record.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_rays_masked_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, uint32_t semantics,
                               uint32_t ray_mask, trx_hit *d_hits, uint32_t *d_inst, void *stream);
 int trx_trace_occluded_masked_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, uint32_t semantics,
@@ -346,8 +348,8 @@ int trx_refit_nodes(const void *nodes, uint64_t n_nodes, const float *tri_verts,
  * out-of-range ray never changes another ray's record (it may send its wave through slower arithmetic: the literal
  * divisions), and it does not raise TRX_ERR_STACK_OVERFLOW: that error still means a tree deeper than 64 entries - or a
  * single ray that ran past the step cap of 2^22 trips, which only a whole-tree walker (below) over several million nodes
- * and triangles can reach.  The ids handed to the attribute, AO and filter passes are NOT covered: a `prim` or an
- * instance id must come from a trace call over the same scene.
+ * and triangles can reach.  The primary records and instance ids a caller hands to the passes after the trace: CALLER
+ * RECORDS, below.
  *   What the shader's arithmetic does with such rays, because its node test is max(near planes, 0.0001) <= min(far planes,
  * t) with a max / min that drop NaN operands (query.hlsl:237-300):
  *   - a negative tmin is accepted by the triangle test but no hit nearer than a box's clamped entry is ever looked for:
@@ -362,6 +364,34 @@ int trx_refit_nodes(const void *nodes, uint64_t n_nodes, const float *tri_verts,
  *     passes every box test and fails every triangle test: it reports a miss after visiting every node and testing every
  *     triangle of the scene.  Callers that cannot rule NaNs out should filter them: such a frame costs
  *     (nodes + triangles) per pixel.
+ *
+ * ---- CALLER RECORDS: the primary records and instance ids the later passes are handed ------------------------------
+ * Several *_dev passes take a frame of primary records (d_primary), and the instance ids beside them (d_primary_inst),
+ * from the caller and use the ids in them as indices into the scene's own tables.  Any bit pattern is accepted there as
+ * well - a buffer nobody initialised, the records of another scene, an image-layout buffer of which one shard was traced
+ * - and is never a fault: no address depends on a record's words.  The rule, stated once:
+ *   - A primary record is a SURFACE RECORD of a scene iff t < FLT_MAX and prim < n_tris, n_tris being the extent given to
+ *     trx_scene_create (0xFFFFFFFF is never below it: one unsigned comparison).  EVERY OTHER RECORD IS A MISS - NaN, +inf
+ *     and FLT_MAX in t, any prim at or past the table's end - and the pass writes for that pixel exactly what it writes
+ *     for a primary miss:
+ *       the AO passes (trx_trace_ao_dev, _ao_inst_dev, _ao_batch_dev, _ao_masked_dev): the miss record {+inf, 0xFFFFFFFF},
+ *         the instance id 0xFFFFFFFF;  trx_count_ao / trx_count_ao_per_ray: no ray - nothing counted, a zero trx_ray_cost;
+ *       the ray writers (trx_ao_rays_dev, trx_light_rays_dev): the inert ray;
+ *       the visibility passes (trx_trace_ao_visibility_dev, _sparse_dev, trx_trace_light_visibility_dev): TRX_AO_NO_SURFACE,
+ *         the light pass in every light's plane;
+ *       the indirect passes (trx_trace_indirect_dev, _sparse_dev): the base's bits (+0 without a base, and in the sparse form).
+ *     A surface record is used as it stands, whatever walk or scene it came from: t may be negative or 0, prim need not be
+ *     the triangle that pixel's primary ray hits.
+ *   - On a scene with instance transforms an instance id >= n_instances selects no row: the hit triangle's object-space
+ *     normal is used as it is - what 0xFFFFFFFF always meant.  Scenes without instance transforms never read the ids.
+ *   - The attribute pass has its own rule for ids outside the tables: the zero record (trx_hit_attributes_*, below).
+ *   - The passes that read no scene table - trx_ao_filter_dev, trx_ao_upsample_dev, trx_value_filter_dev,
+ *     trx_value_upsample_dev, trx_light_term_dev and the shade calls - decide "surface" by t < FLT_MAX and
+ *     prim != 0xFFFFFFFF: to them a record with a prim past the table is a surface pixel whose neighbours' terms it
+ *     receives.  A caller who mixes the two families over foreign records gets each family's rule, not a fault.
+ *   - No result changes for a record a trace call over the same scene wrote.
+ * tests/test_gpu_caller_records.py holds every pass above to this over ids at, just past and far past the tables' ends
+ * (tests/test_caller_records.py: the oracle and the twins).
  *
  * ---- camera ---------------------------------------------------------------
  * ViewUniform::from_camera (src/main.rs:602-616): proj_inv =
@@ -423,14 +453,18 @@ int trx_trace_primary_batch_dev(trx_scene *scene, const trx_view *views, uint32_
  * architectures pick other variants and may differ in the last bit), so on such a host the AO directions are the
  * reference CPU path's own.
  * Against a correctly rounded sin / cos (another C library) the AO hit's t moves in its last bits on a fraction of a
- * per cent of the rays. */
+ * per cent of the rays.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_ao_dev(trx_scene *scene, const trx_view *view, uint32_t width,
                      uint32_t height, trx_shard shard, uint32_t semantics, uint32_t frame,
                      float ao_eps, const trx_hit *d_primary, trx_hit *d_ao, void *stream);
 
 /* AO pass with instance ids: d_primary_inst (from trx_trace_primary_inst_dev) is REQUIRED when the scene has
  * instance transforms — the hit triangle's normal lives in object space and is taken to world space by the
- * transpose of the instance's world-to-object matrix; d_ao_inst may be NULL. */
+ * transpose of the instance's world-to-object matrix; d_ao_inst may be NULL.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_ao_inst_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
                           uint32_t semantics, uint32_t frame, float ao_eps, const trx_hit *d_primary,
                           const uint32_t *d_primary_inst, trx_hit *d_ao, uint32_t *d_ao_inst, void *stream);
@@ -450,7 +484,9 @@ int trx_trace_frame_dev(trx_scene *scene, const trx_view *view, uint32_t width, 
  * (src/rt_cpu/rt_cpu.rs:95-97, src/rt_gpu/rt_gpu_software.rs:285-288), so 4 spp are frames 0..3 - submitted together
  * they share one launch's start-up and, above all, ONE drain (the end of an incoherent pass, where every wave finishes
  * its last rays at falling occupancy: two thirds of a hairball-class pass).  The seeds of a tile go to the same XCD.
- * Results are identical to n_frames separate trx_trace_ao_inst_dev launches. */
+ * Results are identical to n_frames separate trx_trace_ao_inst_dev launches.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_ao_batch_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
                            uint32_t semantics, uint32_t frame0, uint32_t n_frames, float ao_eps,
                            const trx_hit *d_primary, const uint32_t *d_primary_inst, trx_hit *d_ao, uint32_t *d_ao_inst,
@@ -507,7 +543,9 @@ int trx_hit_attributes_primary_dev(trx_scene *scene, const trx_view *view, uint3
  * the AO pass walks to; anything else (0, negative, NaN) is TRX_ERR_INVALID.  A pixel whose primary record is a miss
  * (!(t < FLT_MAX) or prim == 0xFFFFFFFF) gets the INERT ray: every word 0 except tmax = -1.0f - no walk can commit a hit on
  * it (closest-hit and any-hit kernels alike start from min(tmax, FLT_MAX)).  d_primary_inst is REQUIRED on scenes with
- * instance transforms, as for trx_trace_ao_inst_dev: without it the call returns TRX_ERR_INVALID before anything is enqueued. */
+ * instance transforms, as for trx_trace_ao_inst_dev: without it the call returns TRX_ERR_INVALID before anything is enqueued.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_ao_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
                     uint32_t frame, float ao_eps, float ao_radius, const trx_hit *d_primary,
                     const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream);
@@ -523,7 +561,9 @@ int trx_ao_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint
  * previous launch), the any-hit rays launch of trx_trace_occluded_dev walks them, a reduce kernel adds the flags into the
  * counts; chunk after chunk until every tile and sample is done.
  * Ordering: as for the other trace launches - a trx_scene_refit* called after this call has returned waits for the pass,
- * which sees the old geometry in full.  A stack overflow latches as for every rays launch (trx_scene_check). */
+ * which sees the old geometry in full.  A stack overflow latches as for every rays launch (trx_scene_check).
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 #define TRX_MAX_AO_SAMPLES 64
 #define TRX_AO_NO_SURFACE 0xFFu
 int trx_trace_ao_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
@@ -544,7 +584,9 @@ int trx_trace_ao_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t
  * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): stride 0 or above the maximum,
  * phase >= s*s, and everything trx_trace_ao_visibility_dev refuses - a missing d_primary_inst on a scene with instance
  * transforms among it.  Scratch, chunking, stream and ordering are the dense pass's: the same launch slot's scratch
- * ([tile][sample][64] over the 8 x 8 tiles of the low grid) under the same cap. */
+ * ([tile][sample][64] over the 8 x 8 tiles of the low grid) under the same cap.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 #define TRX_MAX_AO_STRIDE 4
 int trx_trace_ao_visibility_sparse_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
                                        uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t frame0,
@@ -687,7 +729,9 @@ typedef struct trx_light {
  * ONE sample as explicit rays: one trx_ray per record, laid out by `shard` exactly as for trx_ao_rays_dev; records outside
  * the shard or the image are left untouched.  Refused (TRX_ERR_INVALID, nothing enqueued): what the pass below refuses of
  * a light, light_index >= TRX_MAX_LIGHTS, sample >= TRX_MAX_AO_SAMPLES, a bad shadow_eps, null buffers, a missing
- * d_primary_inst on a scene with instance transforms. */
+ * d_primary_inst on a scene with instance transforms.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_light_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
                        const trx_light *light, uint32_t light_index, uint32_t frame0, uint32_t sample, float shadow_eps,
                        const trx_hit *d_primary, const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream);
@@ -706,7 +750,9 @@ int trx_light_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, u
  * d_primary_inst on a scene with instance transforms.
  * Mechanics, stream and ordering are trx_trace_ao_visibility_dev's, once per light: the same launch slot's scratch
  * ([tile][sample][64]) under the same cap, the same chunk loops, no host synchronisation; a trx_scene_refit* called after
- * this call has returned waits for the pass. */
+ * this call has returned waits for the pass.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_light_visibility_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
                                    trx_shard shard, uint32_t semantics, uint32_t ray_mask, const trx_light *lights,
                                    uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float shadow_eps,
@@ -794,7 +840,9 @@ int trx_bounce_light_rays_dev(trx_scene *scene, uint32_t width, uint32_t height,
  * shares the AO pass's rays and flags and its cap (288 MiB per slot), is counted once by trx_scene_device_bytes and
  * released by trx_scene_destroy; growing it waits for the slot's previous launch.
  * Ordering: as for the other passes - a trx_scene_refit* called after this call has returned waits for every launch of the
- * pass, which sees the old geometry in full.  A stack overflow latches as for every rays launch (trx_scene_check). */
+ * pass, which sees the old geometry in full.  A stack overflow latches as for every rays launch (trx_scene_check).
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_indirect_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
                            uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
                            uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps, float bounce_albedo,
@@ -878,7 +926,9 @@ int trx_render_image_gi_filtered(trx_scene *scene, const trx_view *view, uint32_
  * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): stride 0 or above the maximum,
  * phase >= s*s, everything trx_trace_indirect_dev refuses, a null d_value_lo.  Scratch, chunking, stream and ordering are the
  * dense pass's: the same launch slot's scratch ([tile][sample][64] over the 8 x 8 tiles of the low grid) under the same cap,
- * counted once by trx_scene_device_bytes; a trx_scene_refit* called after this call has returned waits for every launch. */
+ * counted once by trx_scene_device_bytes; a trx_scene_refit* called after this call has returned waits for every launch.
+ * d_primary (and d_primary_inst) may hold any bit pattern: a record that is no surface record of this scene is a miss
+ * (CALLER RECORDS, above). */
 int trx_trace_indirect_sparse_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
                                   uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t ray_mask,
                                   const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
@@ -928,7 +978,8 @@ int trx_render_image_gi_sparse(trx_scene *scene, const trx_view *view, uint32_t 
                                uint32_t bounce_upsample_radius, uint8_t *out_rgba, float *out_ms);
 
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
- * Synchronous; d_hits may be NULL. */
+ * Synchronous; d_hits may be NULL.  trx_count_ao: d_primary may hold any bit pattern - a record that is no surface record
+ * of this scene is a miss, no ray and nothing counted (CALLER RECORDS, above). */
 int trx_count_primary(trx_scene *scene, const trx_view *view, uint32_t width,
                       uint32_t height, trx_shard shard, uint32_t semantics,
                       trx_hit *d_hits, trx_stats *stats);
@@ -952,6 +1003,8 @@ typedef struct trx_ray_cost {
     uint16_t n_node;
     uint16_t n_tri;
 } trx_ray_cost; /* 4 bytes */
+/* (trx_count_ao_per_ray: d_primary may hold any bit pattern - a record that is no surface record of this scene is a miss and
+ * gets {0, 0}: CALLER RECORDS, above.) */
 int trx_count_primary_per_ray(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
                               uint32_t semantics, trx_hit *d_hits, trx_ray_cost *d_cost, trx_stats *stats);
 int trx_count_ao_per_ray(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,

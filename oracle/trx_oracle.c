@@ -310,7 +310,7 @@ uint64_t orc_sincos_libm_mismatches(uint32_t lo_bits, uint32_t hi_bits, uint32_t
 }
 
 /* AO ray of src/rt_cpu/rt_cpu.rs:61-76 / src/rt_gpu/rt_gpu_software.hlsl:105-121.
- * Returns 0 when the primary ray missed. */
+ * Returns 0 when the primary record is a miss (trx_oracle.h: any record that is no surface record of the scene). */
 void orc_xform_point(const float m[12], const float p[3], float out[3]) {
     for (int r = 0; r < 3; r++) out[r] = ((m[4 * r] * p[0] + m[4 * r + 1] * p[1]) + m[4 * r + 2] * p[2]) + m[4 * r + 3];
 }
@@ -325,13 +325,15 @@ int orc_ao_ray(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h,
 
 int orc_ao_ray_inst(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t px, uint32_t py,
                     orc_hit primary, uint32_t primary_inst, uint32_t frame, float ao_eps, float o[3], float d[3]) {
-    if (!(primary.t < F32_MAX) || primary.prim == INVALID) return 0;
+    /* a surface record: t < FLT_MAX and prim inside the scene's triangle table (one unsigned comparison: INVALID is never
+     * below it).  Every other record a caller hands in is a miss - no address is formed from it. */
+    if (!(primary.t < F32_MAX) || !(primary.prim < s->n_tris)) return 0;
     float ro[3], rd[3];
     orc_primary_ray(view, w, h, px, py, ro, rd);
     const float *tri = s->tris + 9 * (uint64_t)primary.prim;
     float n[3];
     cross3(tri + 3, tri + 6, n); /* ng = e1 x e2, compute_normal() = ng.normalize() */
-    if (s->instance_w2o && primary_inst != INVALID) {
+    if (s->instance_w2o && primary_inst < s->n_instances) { /* an id outside the table selects no row */
         /* object-space normal -> world: transpose of world-to-object (= inverse transpose of object-to-world) */
         const float *m = s->instance_w2o + 12 * (uint64_t)primary_inst;
         float nw[3];

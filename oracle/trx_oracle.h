@@ -122,6 +122,11 @@ orc_hit orc_traverse(const orc_scene *s, const float o[3], const float d[3], flo
  * 0xFFFFFFFF for a miss / a scene without TLAS */
 orc_hit orc_traverse_inst(const orc_scene *s, const float o[3], const float d[3], float tmin, float tmax,
                           uint32_t sem, orc_stats *st, uint32_t *inst);
+/* the AO ray (o, d) of pixel (px, py) from its primary record; returns 0, writing nothing, where the record is a miss.
+ * `primary` and `primary_inst` are a caller's and may hold anything (include/trx.h, "CALLER RECORDS"): a record is a
+ * surface record iff t < FLT_MAX and prim < s->n_tris, every other record is a miss; with instance_w2o an id
+ * >= s->n_instances selects no row (the object-space normal is used as it is).  No address is formed from a value
+ * outside the tables. */
 int orc_ao_ray_inst(const orc_scene *s, const orc_view *view, uint32_t w, uint32_t h, uint32_t px, uint32_t py,
                     orc_hit primary, uint32_t primary_inst, uint32_t frame, float ao_eps, float o[3], float d[3]);
 /* orc_ao_ray_inst for every record of a w x h image in pixel order, as rays {o, tmin 0, d, tmax}; the inert ray (all words

@@ -6,6 +6,11 @@ pixel's primary record; the ray is orc_ray{o, tmin 0, d, tmax} with tmax = the A
 of its samples (seeds frame0 .. frame0 + n_samples - 1) that are NOT occluded; a pixel whose primary record is a miss
 carries the inert ray (all words 0, tmax = -1) and the count NO_SURFACE.
 
+CALLER RECORDS (include/trx.h): the pass takes its records from the caller.  A record is a surface record of the scene iff
+t < FLT_MAX and prim < n_tris; every other record - whatever its words hold - is a miss.  On a transformed scene an
+instance id >= n_instances selects no row: the object-space normal is used as it is.  `surface_records` is that rule here;
+`orc_ao_ray_inst` states it a second time, and `ao_rays` asserts that the two agree on every record.
+
 Thresholding the closest-hit AO record's t against the radius is NOT the definition: at t == radius the tie rule of the
 semantics word decides, and a walk with a shorter tmax culls node boxes the long walk enters.
 
@@ -26,6 +31,11 @@ def stored_tmax(ao_radius):
     r = np.float32(ao_radius)
     assert r > 0
     return F32_MAX if np.isinf(r) else r
+
+
+def surface_records(primary, n_tris):
+    """The caller-record rule: [n] bool, t < FLT_MAX and prim < n_tris (unsigned: 0xFFFFFFFF is never below it)."""
+    return (primary["t"] < F32_MAX) & (primary["prim"].astype(np.uint64) < np.uint64(n_tris))
 
 
 def record_map(w, h, shard=(0, 1, 0)):
@@ -55,11 +65,14 @@ def ao_rays(orc, osc, oview, w, h, primary, primary_inst, frame, ao_eps, ao_radi
     po, pd = o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)
     tmax = stored_tmax(ao_radius)
     sc, vw = C.byref(osc.c), C.byref(oview)
-    for i in np.flatnonzero((primary["t"] < F32_MAX) & (primary["prim"] != INVALID)):
+    rule = surface_records(primary, int(osc.c.n_tris))
+    for i in np.flatnonzero(primary["t"] < F32_MAX):                   # (the oracle decides on prim for itself)
         inst = int(primary_inst[i]) if primary_inst is not None else INVALID
         ok = lib.orc_ao_ray_inst(sc, vw, w, h, int(i % w), int(i // w), orc.HitC(float(primary["t"][i]), int(primary["prim"][i])),
                                  inst, int(frame), float(ao_eps), po, pd)
-        assert ok == 1
+        assert ok == int(rule[i]), "the oracle and the twin disagree on record %d" % i
+        if not ok:
+            continue
         rays["origin"][i] = o
         rays["direction"][i] = d
         rays["tmax"][i] = tmax

@@ -13,18 +13,20 @@ base + F, any other pixel its base's bits (+0 without a base)."""
 import numpy as np
 
 from ao_sparse_twin import ACCEPTED, EMPTY, FALLBACK, NOT_SURFACE, cell_pixels, lo_size, phase_xy
+from ao_visibility_twin import surface_records
 from image_twin import surface
 
 MAX_RADIUS = 2
 f32 = np.float32
 
 
-def sparse_values(dense_values_without_base, primary, w, h, stride, phase):
+def sparse_values(dense_values_without_base, primary, w, h, stride, phase, n_tris=None):
     """[Wlo * Hlo] float32: the dense pass's values [w * h] (no base) at the cells' pixels, +0 where the pixel is outside the
-    image or no surface pixel."""
+    image or no surface pixel.  n_tris: the scene's triangle count - the pass reads the scene's tables, so a caller's record
+    with prim >= n_tris is no surface pixel (light_twin.surface); None: records the library wrote itself."""
     gx, gy, inside = cell_pixels(w, h, stride, phase)
     dense = np.asarray(dense_values_without_base, dtype=np.float32).reshape(h, w)
-    surf = surface(primary).reshape(h, w)
+    surf = (surface(primary) if n_tris is None else surface_records(primary, n_tris)).reshape(h, w)
     out = np.zeros(gx.shape, dtype=np.float32)
     take = inside.copy()
     take[inside] = surf[gy[inside], gx[inside]]

@@ -122,8 +122,9 @@ def sample_sum(orc, w, h, b_rays, b_hits, b_attr, lights, frame0, sample, shadow
     return s
 
 
-def term(sums, primary, bounce_albedo, base=None):
-    """Rule 5: [w * h] float32 from the samples' sums [n_samples, w * h] (ascending)."""
+def term(sums, primary, bounce_albedo, base=None, n_tris=None):
+    """Rule 5: [w * h] float32 from the samples' sums [n_samples, w * h] (ascending).  n_tris: the scene's triangle count -
+    a caller's record with prim >= n_tris is no surface pixel (LT.surface); None: every prim but 0xFFFFFFFF is one."""
     n_samples = len(sums)
     A = np.zeros(primary.shape[0], dtype=np.float32)
     with np.errstate(invalid="ignore", over="ignore"):
@@ -131,7 +132,8 @@ def term(sums, primary, bounce_albedo, base=None):
             A = (A + s).astype(np.float32)
         b = np.zeros(primary.shape[0], dtype=np.float32) if base is None else np.asarray(base, dtype=np.float32)
         out = (b + (f32(bounce_albedo) * A) / f32(n_samples)).astype(np.float32)
-    return np.where(LT.surface(primary), out, b).astype(np.float32)
+    bits = np.where(LT.surface(primary, n_tris), out.view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+    return bits.astype(np.uint32).view(np.float32)                 # (a pixel without a surface: its base's bits copied)
 
 
 def oracle_occluded(osc, sem):
@@ -168,4 +170,4 @@ def indirect(orc, osc, oview, w, h, primary, primary_inst, recs, w2o, lights, fr
                 return occ
             stats.append((bounce_surface(rays, hits), seen))
         sums.append(sample_sum(orc, w, h, rays, hits, attr, lights, frame0, f, shadow_eps, occluded))
-    return term(sums, primary, bounce_albedo, base)
+    return term(sums, primary, bounce_albedo, base, n_tris=recs.shape[0])

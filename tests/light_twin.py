@@ -7,10 +7,13 @@ point (the oracle's `orc_hash_noise` for a rect light), the direction, the reach
 statements restated one binary32 operation at a time.
 Visibility.  The rays go through `OracleScene.trace_rays`; a ray is occluded when the answer's prim is not 0xFFFFFFFF.  A
 masked pass walks `inst_mask_twin.oracle_twin` of the visibility vector (masks & ray_mask) != 0.
-Term and shade.  The header's order of operations in float32; `image_twin` supplies the code table shade."""
+Term and shade.  The header's order of operations in float32; `image_twin` supplies the code table shade.
+Caller records (include/trx.h).  The rays and the planes take the scene's rule: a surface record has t < FLT_MAX and
+prim < n_tris (`surface(primary, n_tris)`), an instance id >= n_instances selects no row.  The light term reads no scene
+table and keeps prim != 0xFFFFFFFF (`surface(primary)`)."""
 import numpy as np
 
-from ao_visibility_twin import THREADS
+from ao_visibility_twin import THREADS, surface_records
 from hit_attr_twin import hit_attrs, primary_dirs, primary_origins
 from image_twin import _rgba
 
@@ -47,8 +50,11 @@ def _dot3(a, b):
     return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 
 
-def surface(primary):
-    return (primary["t"] < F32_MAX) & (primary["prim"] != INVALID)
+def surface(primary, n_tris=None):
+    """n_tris None: the rule of the passes that read no scene table; else the caller-record rule of those that do."""
+    if n_tris is None:
+        return (primary["t"] < F32_MAX) & (primary["prim"] != INVALID)
+    return surface_records(primary, n_tris)
 
 
 def hash_noise(orc, px, py, seed):
@@ -67,11 +73,15 @@ def directional(light):
 def frame_geometry(view, w, h, primary, primary_inst, recs, w2o=None):
     """(indices of the surface pixels, their px, py, d [n, 3], flipped unit normal n [n, 3], t [n]) for whole-image records in
     pixel order.  recs: hit_attr_twin.tri_records; w2o: [n_instances, 12] rows of a transformed scene (else None)."""
-    idx = np.flatnonzero(surface(primary))
+    idx = np.flatnonzero(surface(primary, recs.shape[0]))
     px, py = idx % w, idx // w
     d = primary_dirs(view, w, h, px, py)
     inst = None if w2o is None else np.asarray(primary_inst, dtype=np.uint32)[idx]
     n = hit_attrs(recs, primary_origins(view, idx.size), d, primary["prim"][idx], inst=inst, w2o=w2o)["normal"]
+    if w2o is not None:
+        # an id outside the table selects no row: the unit object-space normal (the attribute pass's own rule zeroes it)
+        no_row = np.flatnonzero(inst >= w2o.shape[0])
+        n[no_row] = hit_attrs(recs, primary_origins(view, no_row.size), d[no_row], primary["prim"][idx][no_row])["normal"]
     return idx, px, py, d, flip(n, d), np.asarray(primary["t"], dtype=np.float32)[idx]
 
 
@@ -122,7 +132,8 @@ def light_rays(orc, view, w, h, geometry, light, light_index, frame0, sample, sh
 def visibility_planes(orc, osc, view, w, h, geometry, primary, lights, frame0, n_samples, shadow_eps, sem):
     """[n_lights, w * h] uint8 in pixel order: per light the samples cast and not occluded, NO_SURFACE without a surface.
     osc: the oracle scene the shadow rays walk (a masked pass: inst_mask_twin.oracle_twin of the visible instances)."""
-    surf = surface(primary)
+    surf = np.zeros(w * h, dtype=bool)
+    surf[geometry[0]] = True                                        # (frame_geometry's surface pixels: the scene's rule)
     planes = np.full((len(lights), w * h), NO_SURFACE, dtype=np.uint8)
     for k, light in enumerate(lights):
         planes[k][surf] = 0

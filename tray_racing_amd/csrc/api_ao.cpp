@@ -108,6 +108,8 @@ int visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, 
     g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
     g.primary = d_primary;
     g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull); // (kernels.h, surface_record)
+    g.n_inst = s->n_inst;
     g.rays = slot->ao_rays.get();
     g.flags = slot->ao_flags.get();
     g.counts = d_unoccluded;
@@ -160,6 +162,8 @@ void light_scene(LightRaysParams &g, const trx_scene *s, const trx_hit *d_primar
     g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
     g.primary = d_primary;
     g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull); // (kernels.h, surface_record)
+    g.n_inst = s->n_inst;
 }
 
 // visibility_impl's sibling: its chunk loops and slot bookkeeping statement for statement, per light, with k_light_rays /
@@ -339,6 +343,8 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     g.inst_xform = xf ? s->inst_xform.get() : nullptr;
     g.primary = d_primary;
     g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull); // (kernels.h, surface_record)
+    g.n_inst = s->n_inst;
     g.rays = slot->gi_rays.get();
     g.scratch = 1u;
     g.ao_eps = bounce_eps;
@@ -363,6 +369,7 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     b.sum = slot->gi_sum.get();
     b.acc = slot->gi_acc.get();
     b.primary = d_primary;
+    b.n_tris = g.n_tris;
     b.base = d_base;
     b.value = d_value;
     b.scratch = 1u;
@@ -481,6 +488,8 @@ int trx_ao_rays_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, 
     g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
     g.primary = d_primary;
     g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull); // (kernels.h, surface_record)
+    g.n_inst = s->n_inst;
     g.rays = d_rays;
     g.n_tiles = tiles;
     g.n_samples = 1u;

@@ -160,7 +160,7 @@ int enqueue_locked(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool co
         p.tune = tune ? (uint32_t)strtoul(tune, nullptr, 0) : 0u;
     }
 #endif
-    p.n_tris = (uint32_t)s->n_tris;
+    p.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull); // (also what a caller's record may index: kernels.h, surface_record)
     p.n_nodes = (uint32_t)s->n_nodes;
     {   // (kernels.hip, div_uniform)
         auto rcp32 = [](uint32_t d) -> uint32_t { return d <= 1u ? 0xffffffffu : (uint32_t)((1ull << 32) / d); };
@@ -307,6 +307,7 @@ int enqueue_locked(trx_scene *s, TraceParams &p, int mode, uint32_t sem, bool co
     TraceParamsTlas kp;
     static_cast<TraceParams &>(kp) = p;
     kp.inst_mask = inst_mask;
+    kp.n_inst = s->n_inst; // (the AO refill: which caller's instance ids select a row of inst_xform)
     HIP_TRY(launch_trace(kp, mode, s->tlas, sem, count, pipe, grid, stream));
     HIP_TRY(hipEventRecord(slot.done.get(), stream));
     slot.used = true;

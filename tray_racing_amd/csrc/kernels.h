@@ -189,10 +189,19 @@ struct TraceParams {
 // (inst_mask[k] & ray_mask) != 0.  Null: every instance is entered (the unmasked calls, and masked calls on a scene without
 // a table).  The single-level kernels take TraceParams alone: ray_mask sits in what was its tail padding, so TraceParams
 // keeps its 1536 bytes and the single-level kernels' arguments - the hidden ones behind them included - keep their offsets.
+// n_inst, the extent of inst_xform, sits here for the same reason: only a two-level AO pass over instance rows reads it.
 struct TraceParamsTlas : TraceParams {
     const uint8_t *inst_mask;
+    uint32_t n_inst; // rows of inst_xform (the AO refill reads it with them, and only there: instance_row below)
 };
 static_assert(sizeof(TraceParams) == 1536, "TraceParams grew: every single-level kernel's hidden arguments would move");
+
+// Caller records (include/trx.h, "CALLER RECORDS"): the passes that take primary records from the caller index the scene's
+// triangle table with a record's prim and its instance rows with the id beside it.  This is the one statement of which
+// records and ids may: a SURFACE record has t < FLT_MAX and prim < n_tris (0xFFFFFFFF is never below it), every other record
+// is a miss; an id >= n_inst selects no row.  One unsigned comparison each - no address is formed from a value that fails it.
+__host__ __device__ inline bool surface_record(const trx_hit &h, uint32_t n_tris) { return h.t < 3.402823466e+38f && h.prim < n_tris; }
+__host__ __device__ inline bool instance_row(uint32_t inst, uint32_t n_inst) { return inst < n_inst; }
 
 // The image geometry of a tile-ordered pass as the small kernels take it: the fields of TraceParams of the same names.
 struct TileGeom {
@@ -246,6 +255,7 @@ struct AoRaysParams {
     ViewDev view;
     uint32_t stride, px0, py0;    // sparse: 1..TRX_MAX_AO_STRIDE and the phase's pixel in the stride x stride block (dense: 0)
     TileGeom lo;                  // sparse: the low grid (whole image, image layout)
+    uint32_t n_tris, n_inst;      // the extents of tris and inst_xform: what a caller's record may index (surface_record; last: the fields above keep their offsets)
 };
 hipError_t launch_ao_rays(const AoRaysParams &p, hipStream_t stream);
 hipError_t launch_ao_reduce(const AoRaysParams &p, hipStream_t stream);
@@ -270,6 +280,7 @@ struct LightRaysParams {
     float shadow_eps;
     ViewDev view;
     trx_light light;
+    uint32_t n_tris, n_inst;      // the extents of tris and inst_xform: what a caller's record may index (surface_record; last, as in AoRaysParams)
 };
 hipError_t launch_light_rays(const LightRaysParams &p, hipStream_t stream);
 hipError_t launch_light_reduce(const LightRaysParams &p, hipStream_t stream);
@@ -332,6 +343,7 @@ struct BounceParams {
     // and writes value[Y * lo.width + X] - +0 for a cell whose pixel leaves the image.  The dense launches leave stride 0.
     uint32_t stride, px0, py0;
     TileGeom lo;
+    uint32_t n_tris;              // k_bounce_finish: the scene's triangle extent (surface_record: the surface as k_ao_rays decided it)
 };
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream);

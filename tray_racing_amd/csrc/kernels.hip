@@ -967,14 +967,14 @@ __global__ void __launch_bounds__(256) k_ao_rays(const AoRaysParams P) {
     ph.t = __builtin_inff();
     ph.prim = TRX_INVALID;
     if (inside) ph = P.primary[rec];
-    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
+    if (surface_record(ph, P.n_tris)) { // (kernels.h: a caller's record that fails it is a miss - the inert ray)
         float dx, dy, dz;
         primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
         const float4 *tp = P.tris + (size_t)ph.prim * 3;
         float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
         if (P.inst_xform) {
             const uint32_t pi = P.primary_inst[rec];
-            if (pi != TRX_INVALID) {
+            if (instance_row(pi, P.n_inst)) {
                 const float4 *m = P.inst_xform + (size_t)pi * 3;
                 const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
                 nx = w.x; ny = w.y; nz = w.z;
@@ -1035,14 +1035,14 @@ __global__ void __launch_bounds__(256) k_light_rays(const LightRaysParams P) {
     ph.t = __builtin_inff();
     ph.prim = TRX_INVALID;
     if (inside) ph = P.primary[rec];
-    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
+    if (surface_record(ph, P.n_tris)) { // (kernels.h: a caller's record that fails it is a miss - the inert ray)
         float dx, dy, dz;
         primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
         const float4 *tp = P.tris + (size_t)ph.prim * 3;
         float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
         if (P.inst_xform) {
             const uint32_t pi = P.primary_inst[rec];
-            if (pi != TRX_INVALID) {
+            if (instance_row(pi, P.n_inst)) {
                 const float4 *m = P.inst_xform + (size_t)pi * 3;
                 const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
                 nx = w.x; ny = w.y; nz = w.z;
@@ -1096,7 +1096,7 @@ __global__ void __launch_bounds__(256) k_light_reduce(const LightRaysParams P) {
     uint32_t px, py, rec;
     if (!tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec)) return;
     const trx_hit ph = P.primary[rec];
-    const bool surface = ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID;
+    const bool surface = surface_record(ph, P.n_tris); // (as k_light_rays decided it)
     const uint32_t base = lt * P.n_samples * 64u + k;
     uint32_t n = 0u;
     for (uint32_t s = 0; s < P.n_samples; s++)
@@ -1287,7 +1287,8 @@ __global__ void __launch_bounds__(256) k_bounce_gather(const BounceParams P) {
 }
 
 // One lane per pixel of the chunk's tiles: the pass's value.  base is read before value is written, by the same lane: they
-// may be one buffer.
+// may be one buffer.  The surface is k_ao_rays' (kernels.h, surface_record): a caller's record that got the inert bounce
+// ray keeps its base bit for bit.
 //   SPARSE: one lane per cell of the low grid's tiles, the value at the cell's place in the low grid (there is no base: the
 // dense statement with base = 0.0f); the primary record is that of the cell's pixel in the full image, and a cell whose
 // pixel leaves the image gets +0.
@@ -1304,7 +1305,7 @@ __global__ void __launch_bounds__(256) k_bounce_finish(const BounceParams P) {
         float out = 0.0f;
         if (px < P.geom.width && py < P.geom.height) {
             const trx_hit ph = P.primary[(size_t)py * P.geom.width + px];
-            if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) out = out + (P.albedo * P.acc[item]) / (float)P.n_total;
+            if (surface_record(ph, P.n_tris)) out = out + (P.albedo * P.acc[item]) / (float)P.n_total;
         }
         P.value[cell] = out;
         return;
@@ -1312,7 +1313,7 @@ __global__ void __launch_bounds__(256) k_bounce_finish(const BounceParams P) {
     if (!tile_pixel(P.geom, P.tile0 + (item >> 6), item & 63u, px, py, rec)) return;
     const trx_hit ph = P.primary[rec];
     float out = P.base ? P.base[rec] : 0.0f;
-    if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) out = out + (P.albedo * P.acc[item]) / (float)P.n_total;
+    if (surface_record(ph, P.n_tris)) out = out + (P.albedo * P.acc[item]) / (float)P.n_total;
     P.value[rec] = out;
 }
 

@@ -215,17 +215,22 @@
                             } else {
                                 ph = R.primary[out_index - frame_base];
                             }
-                            if (ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID) {
+                            // a caller's record: whatever fails kernels.h's surface_record is a miss, no address is formed from it
+                            // (a fused frame's record is its own walk's: a hit's prim comes from node bytes that were validated)
+                            if (kFused ? ph.t < TRX_F32_MAX && ph.prim != TRX_INVALID : surface_record(ph, R.n_tris)) {
                                 // normal of the hit triangle, flipped toward the viewer
                                 const float4 *tp = P.tris + (size_t)ph.prim * 3;
                                 float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
-                                if (TLAS && R.inst_xform) {
-                                    // object-space normal -> world: transpose of world-to-object
-                                    const uint32_t pi = kFused ? hit_inst : R.primary_inst[out_index - frame_base];
-                                    if (pi != TRX_INVALID) {
-                                        const float4 *m = R.inst_xform + (size_t)pi * 3;
-                                        const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
-                                        nx = w.x; ny = w.y; nz = w.z;
+                                if constexpr (TLAS) {
+                                    if (R.inst_xform) {
+                                        // object-space normal -> world: transpose of world-to-object
+                                        const uint32_t pi = kFused ? hit_inst : R.primary_inst[out_index - frame_base];
+                                        // (n_inst: behind TraceParams in the two-level kernels' block, which R is here)
+                                        if (instance_row(pi, static_cast<const TraceParamsTlas &>(R).n_inst)) {
+                                            const float4 *m = R.inst_xform + (size_t)pi * 3;
+                                            const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
+                                            nx = w.x; ny = w.y; nz = w.z;
+                                        }
                                     }
                                 }
                                 TRX_AO_RAY(nx, ny, nz, dx, dy, dz, ph.t, view.eye, R.ao_eps, px, py, seed, r.ox, r.oy, r.oz)
