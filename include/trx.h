@@ -313,7 +313,10 @@ int trx_trace_occluded_masked(trx_scene *scene, const trx_ray *rays, uint64_t n_
  * It keeps imask, child_base_idx, primitive_base_idx, child_meta, the bytes of empty slots, the instance table and the
  * entry nodes.  So a refit with the vertices (and transforms) a scene was built from returns its nodes byte for byte for
  * single-level builds without pre-splitting (trx_set_build_split(0), the default), trx_flat_build TLAS builds without
- * re-braiding (trx_set_build_rebraid(0)) and trx_flat_build_instanced scenes.  Pre-split and re-braided scenes get boxes
+ * re-braiding (trx_set_build_rebraid(0)) and trx_flat_build_instanced scenes.  That holds for signed zeros too: a box
+ * minimum over +0 and -0 keeps whichever the fold met first, and the builder folds in merge order where the refit folds in
+ * slot order, so builder and refit both write a frame origin that is zero as +0 (never -0), whichever zero the box kept.
+ * Pre-split and re-braided scenes get boxes
  * that bound everything they must but are not the build's bytes (a split reference gets its whole triangle's box, an
  * entry subtree its exact box instead of the decoded, outward-rounded one).  The tree was built for the old geometry:
  * walks cost more as the geometry moves away from it, and when to rebuild is the caller's decision.

@@ -291,14 +291,18 @@ def test_refused_refit_leaves_the_scene_unchanged(trx):
     sc.close()
 
 
-def test_bistro_class_refit_time(trx):
+def test_bistro_class_refit_time(trx, orc):
     """BASELINE.json configs[2]'s stand-in (3.9 M triangles): a loose sanity bound on the device refit, not the target
-    (tools/gpu_refit.py measures it)."""
+    (tools/gpu_refit.py measures it) - and the only size at which the grid-stride loops of k_refit_tris (8192 x 256 threads)
+    and k_refit_stats (1024 x 256) wrap, so the result is checked too: the nodes against the host twin, the launch words
+    against a created scene's, and - there is no read-back of the triangle records - rays aimed only at records the second
+    pass of k_refit_tris wrote against the oracle."""
     import torch
     v, c = trx.gen_scene("bistro", 0, 1)
     flat = trx.flat_build_preset_device(v, c, device=0)
     sc = trx.Scene(flat)
-    d = torch.from_numpy(_deformations(flat, 1)[0][1]).cuda()
+    moved = _deformations(flat, 1)[0][1]
+    d = torch.from_numpy(moved).cuda()
     sc.refit(d)                                                       # schedule derived on the first refit
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ms = []
@@ -309,4 +313,25 @@ def test_bistro_class_refit_time(trx):
         t1.synchronize()
         ms.append(t0.elapsed_time(t1))
     assert min(ms) < 5.0, ms
+    assert flat.n_tris > 8192 * 256 and flat.n_nodes > 1024 * 256
+    nodes = sc.read_nodes()
+    assert np.array_equal(nodes, trx.refit_nodes(flat, moved))
+    got, want = sc.info(), _created_info(trx, flat, nodes, moved)
+    assert got["exp_exact"] == want["exp_exact"] and got["scene_diag"] == want["scene_diag"], (got, want)
+    rng = np.random.default_rng(21)
+    tri = moved[rng.integers(8192 * 256, flat.n_tris, size=4000)].astype(np.float64).reshape(-1, 3, 3)
+    target = (tri * rng.dirichlet([1, 1, 1], size=4000)[:, :, None]).sum(1)
+    lo, hi = moved.reshape(-1, 3).min(0).astype(np.float64), moved.reshape(-1, 3).max(0).astype(np.float64)
+    origin = rng.uniform(lo - 0.3 * (hi - lo), hi + 0.3 * (hi - lo), size=(4000, 3))
+    rays = np.zeros(4000, dtype=trx.RAY_DTYPE)
+    rays["origin"] = origin.astype(np.float32)
+    rays["direction"] = ((target - origin) / np.linalg.norm(target - origin, axis=1, keepdims=True)).astype(np.float32)
+    rays["tmax"] = 3.4028234663852886e38
+    osc = orc.Scene(nodes, moved)
+    for sem in (0, 3):
+        hits, _ = sc.trace_rays(rays, sem=sem)
+        want_hits, _ = osc.trace_rays(rays, sem=sem)
+        assert_hits_equal(hits, want_hits, "rays at records of the second pass, sem %d" % sem)
+        second = (want_hits["prim"] >= 8192 * 256) & (want_hits["prim"] < flat.n_tris)
+        assert second.sum() > 400      # (the other rays stop at nearer geometry)
     sc.close()

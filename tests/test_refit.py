@@ -6,8 +6,7 @@ import numpy as np
 import pytest
 
 from helpers import aimed_rays, bits, instanced_scene, random_affine, random_rays, w2o_rows
-
-EMPTY_META = 0
+from refit_twin import _topology_kept
 
 
 @pytest.fixture()
@@ -21,20 +20,6 @@ def build_knobs(trx):
 def _flat(trx, name, n, tlas=False, seed=1):
     verts, counts = trx.gen_scene(name, n, seed)
     return trx.flat_build(verts, counts, use_tlas=tlas), counts
-
-
-def _topology_kept(old, new):
-    """imask, child_base_idx, primitive_base_idx, child_meta and the bytes of empty slots are the build's."""
-    old = np.ascontiguousarray(old, dtype=np.uint32).reshape(-1, 20)
-    new = np.ascontiguousarray(new, dtype=np.uint32).reshape(-1, 20)
-    assert np.array_equal(old[:, 3] >> 24, new[:, 3] >> 24)          # imask
-    assert np.array_equal(old[:, 4:8], new[:, 4:8])                   # bases + child_meta
-    ob, nb = old.view(np.uint8).reshape(-1, 80), new.view(np.uint8).reshape(-1, 80)
-    meta = ob[:, 24:32]
-    for plane in range(6):                                            # min_x, max_x, min_y, max_y, min_z, max_z
-        q = slice(32 + 8 * plane, 40 + 8 * plane)
-        empty = meta == EMPTY_META
-        assert np.array_equal(ob[:, q][empty], nb[:, q][empty])
 
 
 def _hits_match_brute_force(orc, osc, rays, what):

@@ -300,6 +300,12 @@ TRX_HD inline void assign_slots(const Aabb &box, BoxAt child_box_at, int count, 
 }
 
 // ---- node encoding (embree/src/bvh_embree_to_cwbvh.rs:85-186) -----------------------------------------------------------
+// Origin of one axis of a node's frame: the box minimum, a zero minimum always as +0.  Which zero a box minimum keeps
+// depends on the order its contents were folded in (rf_min keeps the first of equals), and the builders fold in merge
+// order where the refit folds in slot order; the bytes must not.  -0 would also cost the scene the exact shortcut of
+// origins that are +0 or 2^-36 <= |p| <= 2^59 (trx_scene_create, exp_exact == 2) for nothing.
+TRX_HD inline float frame_origin(float mn) { return mn == 0.0f ? 0.0f : mn; }
+
 // Quantisation step of one axis of a node whose box spans [mn, mx].
 TRX_HD inline float quant_step(float mn, float mx) {
     // the smallest power of two >= x = max(extent, 1e-20) / 255, read off x's bits (what frexp / ldexp give: ldexp(1, k) for

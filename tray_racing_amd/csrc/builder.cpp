@@ -1519,7 +1519,7 @@ struct Collapser {
         std::memset(&node, 0, sizeof(node));
         float e[3];
         for (int k = 0; k < 3; k++) {
-            node.p[k] = nd.box.mn[k];
+            node.p[k] = frame_origin(nd.box.mn[k]);
             e[k] = quant_step(nd.box.mn[k], nd.box.mx[k]);
             node.e[k] = (uint8_t)(rf_bits(e[k]) >> 23);
         }

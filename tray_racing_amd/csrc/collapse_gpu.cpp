@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k8_encode(const Node2 *nodes, const Re
     float e[3], p[3];
     uint32_t ebyte[3];
     for (int k = 0; k < 3; k++) {
-        p[k] = nd.box.mn[k];
+        p[k] = frame_origin(nd.box.mn[k]);
         e[k] = quant_step(nd.box.mn[k], nd.box.mx[k]);
         ebyte[k] = (__float_as_uint(e[k]) >> 23) & 0xffu;
     }

@@ -4,12 +4,14 @@
 // The per-node work is ONE __host__ __device__ function (refit_node) that the host twin (api_refit.cpp) and the device
 // kernels (refit_gpu.cpp) both call, so that the two produce the same bytes.  Where it does what the builder does it calls
 // the builder's own rules (build_rules.h), which is why a refit with the build's own inputs returns the build's bytes
-// (tests/test_refit.py):
+// (tests/test_refit.py, tests/test_refit_twin.py) - for signed zeros too, although the refit folds a node's box over its
+// children in slot order and the builder in merge order, so that a minimum over +0 and -0 may keep the other zero:
+// frame_origin writes a zero origin as +0 on both sides.
 //   triangle record  convert_tris for TRX_TRI_VERTS_36 (api.cpp): e1 = v0 - v1, e2 = v2 - v0, ng = e1 x e2
 //   leaf box         min / max over the three vertices of every triangle of the slot, the first of equal ones as grow_pt
 //                    keeps it (builder, api_build.cpp refs.box)
 //   inner box        the union of the boxes of the child node's own children (the f32 box array below, never the bytes)
-//   encoding         quant_step and quant_planes, as Collapser::emit (builder.cpp) and k8_encode (collapse_gpu.cpp)
+//   encoding         frame_origin, quant_step and quant_planes, as Collapser::emit (builder.cpp) and k8_encode (collapse_gpu.cpp)
 //   TLAS leaf box    the refit box of BLAS node instance_offsets[k] + entry[k]; with instance transforms it goes through
 //                    instance_world_box, as in trx_flat_build_instanced
 #pragma once
@@ -119,7 +121,7 @@ TRX_HD inline void refit_node(const RefitCtx &c, uint32_t i) {
     float p[3], e[3];
     uint32_t ebyte[3];
     for (int a = 0; a < 3; a++) {
-        p[a] = nb.mn[a];
+        p[a] = frame_origin(nb.mn[a]);
         e[a] = quant_step(nb.mn[a], nb.mx[a]);
         ebyte[a] = (rf_bits(e[a]) >> 23) & 0xffu;
     }
