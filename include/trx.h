@@ -980,6 +980,116 @@ int trx_render_image_gi_sparse(trx_scene *scene, const trx_view *view, uint32_t 
                                float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
                                uint32_t bounce_upsample_radius, uint8_t *out_rgba, float *out_ms);
 
+/* ---- materials and the colour image: per-triangle albedo and emission, the RGB bounce, compose, the RGB shade --------------------
+ * Everything above is scalar.  What a bounce exists to carry is the colour of the surface it left: this section gives a scene
+ * a material table keyed by trx_hit.prim, carries it through the indirect pass as three planes, and composes and shades a
+ * colour image.  Purely additive: every call above computes what it computed.  Lights stay scalar (white).
+ *
+ * A material is a diffuse albedo and an emission, linear RGB.  tri_material[i] is the material of triangle i of the buffer
+ * handed to trx_scene_create - `prim` order; a caller with a trx_flat applies tri_source.  On a two-level scene the instances
+ * of a BLAS share its triangles' materials.
+ * trx_scene_set_materials validates on the host before anything is copied and refuses with TRX_ERR_INVALID: a null pointer,
+ * n_materials outside 1..TRX_MAX_MATERIALS, n_tris different from the scene's, any index >= n_materials, any albedo or
+ * emission component that is negative or not finite.  Every index is checked here, so no kernel reads past the material
+ * table.  Both tables are owned like the instance mask table: counted by trx_scene_device_bytes (24 B per material, 2 B per
+ * triangle), kept by a refit, released by trx_scene_destroy; a second call replaces them after waiting for the scene's
+ * launches in flight, which see the old tables in full; a refused call leaves the old tables in force.
+ * trx_scene_get_materials: *inout_n_materials holds the capacity of out_materials on entry and the table's size on return;
+ * refused on a scene without materials, with a capacity below the size, or with n_tris different from the scene's.
+ * Every colour entry point below is refused with TRX_ERR_INVALID on a scene without materials. */
+typedef struct trx_material {
+    float albedo[3];
+    float emission[3];
+} trx_material; /* 24 B */
+#define TRX_MAX_MATERIALS 65536u
+int trx_scene_set_materials(trx_scene *scene, const trx_material *materials, uint32_t n_materials,
+                            const uint16_t *tri_material, uint64_t n_tris);
+int trx_scene_get_materials(const trx_scene *scene, trx_material *out_materials, uint32_t *inout_n_materials,
+                            uint16_t *out_tri_material, uint64_t n_tris);
+
+/* THE RGB INDIRECT TERM.  trx_trace_indirect_dev with the launch-wide bounce_albedo replaced by the material of the triangle
+ * every bounce ray hits.  Rules 1 to 4 of "indirect light" hold unchanged: bounce ray, bounce hit, secondary shadow rays and
+ * s_f are bit for bit those of trx_trace_indirect_dev.  In rule 5's place:
+ *  5c. Every operation is rounded once in binary32, no contraction.  A_c = 0.0f for c = 0 (R), 1 (G), 2 (B).  For f
+ *      ascending: if bounce f has a surface (rule 2), m = tri_material[bounce_hit_f.prim] and for each c
+ *      A_c = A_c + (albedo_c(m) * s_f + emission_c(m)) - one multiplication and two additions, in that association; a bounce
+ *      without a surface leaves A_c as it is.  out_c = A_c / (float)n_samples, a single IEEE division.  A record that is no
+ *      surface record gets +0.0f in all three planes; a record outside the shard or the image is untouched.  The order holds
+ *      under any scratch cap.  Emission is two-sided: there is no facing test.
+ * d_value_rgb holds three planes of floats, plane c at c * records, each laid out by `shard` like d_primary; records follows
+ * trx_trace_light_visibility_dev's plane rule (width * height in image layout, trx_shard_tiles() * 64 in TRX_LAYOUT_SHARD).
+ * There is no base and no bounce_albedo.  The sparse form is trx_trace_indirect_sparse_dev's statement: its grid and phase,
+ * plane c at c * Wlo * Hlo, every cell bit for bit the dense value of its full-resolution pixel, +0 in all three planes for a
+ * cell whose pixel leaves the image or is no surface pixel; stride 1 is the dense pass in image layout.
+ * Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it was): everything the grey pass refuses, a
+ * scene without materials, a null output.  Mechanics, scratch, cap, stream and ordering are the grey pass's; the running sums
+ * are three per tile pixel.  An emissive triangle is seen by bounce rays (and directly, below); it is no sampled light. */
+int trx_trace_indirect_rgb_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                               uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
+                               uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps,
+                               const trx_hit *d_primary, const uint32_t *d_primary_inst, float *d_value_rgb, void *stream);
+int trx_trace_indirect_rgb_sparse_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                      uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t ray_mask,
+                                      const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
+                                      float bounce_eps, float shadow_eps, const trx_hit *d_primary,
+                                      const uint32_t *d_primary_inst, float *d_value_rgb_lo, void *stream);
+
+/* COMPOSE AND SHADE.  Both are elementwise over n_records records in any layout; planes lie at c * n_records.
+ * trx_material_compose_dev: a record with t < FLT_MAX, prim != 0xFFFFFFFF and prim < n_tris has m = tri_material[prim] and
+ * colour_c = emission_c(m) + albedo_c(m) * (E + I_c) with E = d_direct[r] (trx_light_term_dev's scalar plane, AO-scaled ambient
+ * included) and I_c = d_indirect_rgb[c * n_records + r]: the inner addition, then the multiplication, then the addition, each
+ * rounded once in binary32.  With d_indirect_rgb == NULL it is emission_c(m) + albedo_c(m) * E.  Any other record is
+ * background: +0.0f in all three planes (CALLER RECORDS, above).  d_colour_rgb may be d_indirect_rgb: each lane reads before
+ * it writes.  The primary albedo multiplies here, after any filter: trx_value_upsample_dev and trx_value_filter_dev run on the
+ * demodulated I_c, one call per plane - why the layout is planar.  Refused (TRX_ERR_INVALID): a null scene, d_primary,
+ * d_direct or d_colour_rgb, n_records == 0 or beyond 2^31 - 1, a scene without materials.
+ * trx_shade_rgb_dev: {code(R), code(G), code(B), 255} per record, code derived exactly as trx_shade_value_dev derives it - the
+ * same threshold table, 0 for negative or NaN, 255 for >= 1.  Refusals as for the other shades, and n_records beyond 2^31 - 1 (it
+ * needs no materials). */
+int trx_material_compose_dev(trx_scene *scene, const trx_hit *d_primary, const float *d_direct, const float *d_indirect_rgb,
+                             uint64_t n_records, float *d_colour_rgb, void *stream);
+int trx_shade_rgb_dev(trx_scene *scene, const float *d_colour_rgb, uint64_t n_records, uint8_t *d_rgba, void *stream);
+
+/* trx_render_image_gi_sparse in colour (synchronous): the lit chain up to the light term V; with bounce_samples == 0 the
+ * compose without an indirect term; otherwise the RGB indirect pass - trx_trace_indirect_rgb_dev at bounce_stride 1,
+ * trx_trace_indirect_rgb_sparse_dev (bounce_stride, bounce_phase) above it - then per plane trx_value_upsample_dev without a
+ * base when bounce_stride > 1 and trx_value_filter_dev without a base when bounce_filter_levels >= 1; then
+ * trx_material_compose_dev with V and trx_shade_rgb_dev; 4 bytes per pixel are copied back (out_rgba may be NULL).
+ * bounce_stride is 1..TRX_MAX_AO_STRIDE; the tolerances are looked at when a step uses them.  Every argument is validated
+ * before the first pass is enqueued; refused on a scene without materials. */
+int trx_render_image_colour(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                            uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                            uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                            float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos,
+                            uint32_t bounce_samples, float bounce_eps, uint32_t bounce_filter_levels, float bounce_depth_tol,
+                            float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
+                            uint32_t bounce_upsample_radius, uint8_t *out_rgba, float *out_ms);
+
+/* Materials of the generated scenes (trx_gen_scene), for the mesh as generated: verts (n_tris x 9 floats) and object_counts
+ * (n_objects triangle counts) as trx_gen_scene returned them.  *out_materials (n entries at *out_n_materials) and
+ * *out_tri_material (n_tris indices, in the order of verts) are trx_free'd by the caller.
+ *  "cornell": material 0 albedo (0.8, 0.8, 0.8); material 1 albedo (0.8, 0, 0) for every triangle whose three x are all
+ *  exactly -1.0f (the left wall); material 2 albedo (0, 0.8, 0) for all x exactly +1.0f (the right wall); material 3 albedo 0,
+ *  emission (4, 4, 4) for the triangles of the last object (the light quad); material 0 for the rest.
+ *  Any other name: six materials, emission 0, albedo palette = {(.8,.8,.8), (.8,.4,.3), (.3,.6,.8), (.5,.7,.3), (.8,.7,.4),
+ *  (.6,.5,.7)}; every triangle of object j gets material j % 6.
+ * Refused (TRX_ERR_INVALID): null arguments, object counts that do not sum to n_tris. */
+int trx_standin_materials(const char *name, const float *verts, uint64_t n_tris, const uint64_t *object_counts,
+                          uint32_t n_objects, trx_material **out_materials, uint32_t *out_n_materials,
+                          uint16_t **out_tri_material);
+
+/* trx_load_model with the model's materials: the same verts and object counts, byte for byte, plus a material table and
+ * tri_material in that triangle order (all four trx_free'd by the caller).  Material 0 always exists and is the default: albedo
+ * (0.8, 0.8, 0.8), emission 0.  OBJ: every `mtllib` file is read from the OBJ's directory; its `newmtl` entries follow in file
+ * order; `Kd` gives the albedo (a missing Kd: 0.8 each), `Ke` the emission (a missing Ke: 0); nothing else of a material is
+ * read.  `usemtl` names are looked up once the whole OBJ is read (the first material of a name wins).  Material 0 goes to:
+ * faces before any usemtl, an unknown name, everything when the mtl file is missing, every triangle of a JSON model.  A
+ * quad's two triangles share a material.  Refused with TRX_ERR_INVALID: a negative or non-finite Kd or Ke (or one that is not
+ * three numbers), more than 65535 named materials, null arguments; TRX_ERR_IO: an unreadable model, as trx_load_model. */
+int trx_load_model_materials(const char *path, float **out_verts, uint64_t *out_n_tris, uint64_t **out_object_counts,
+                             uint32_t *out_n_objects, trx_material **out_materials, uint32_t *out_n_materials,
+                             uint16_t **out_tri_material);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL.  trx_count_ao: d_primary may hold any bit pattern - a record that is no surface record
  * of this scene is a miss, no ray and nothing counted (CALLER RECORDS, above). */

@@ -37,6 +37,7 @@ MAX_AO_UPSAMPLE_RADIUS = 2
 MAX_VALUE_UPSAMPLE_RADIUS = 2
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_RECT = 0, 1, 2
 MAX_LIGHTS = 8
+MAX_MATERIALS = 65536
 HEAT_NODES = 0
 HEAT_TRIS = 1
 HEAT_SCALE_NODES = 0.002
@@ -80,6 +81,11 @@ class Light(C.Structure):
     scalar intensity; 64 bytes, _pad must be 0."""
     _fields_ = [("kind", C.c_uint32), ("position", C.c_float * 3), ("edge1", C.c_float * 3), ("edge2", C.c_float * 3),
                 ("intensity", C.c_float), ("_pad", C.c_uint32 * 5)]
+
+
+class Material(C.Structure):
+    """trx_material: a diffuse albedo and an emission, linear RGB; 24 bytes."""
+    _fields_ = [("albedo", C.c_float * 3), ("emission", C.c_float * 3)]
 
 
 class RayCost(C.Structure):
@@ -203,6 +209,18 @@ SIGNATURES = {
     "trx_value_upsample_dev": (_i, [_P, _u32, _u32, _u32, _u32, _P, _P, _P, _P, _u32, _f, _f, _P, _P]),
     "trx_render_image_gi_sparse": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32,
                                         _f, _f, _u32, _f, _f, _u32, _f, _f, _u32, _u32, _u32, _P, C.POINTER(_f)]),
+    "trx_scene_set_materials": (_i, [_P, _P, _u32, _P, _u64]),
+    "trx_scene_get_materials": (_i, [_P, _P, C.POINTER(_u32), _P, _u64]),
+    "trx_trace_indirect_rgb_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _P, _P, _P, _P]),
+    "trx_trace_indirect_rgb_sparse_dev": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _P, _P,
+                                               _P, _P]),
+    "trx_material_compose_dev": (_i, [_P, _P, _P, _P, _u64, _P, _P]),
+    "trx_shade_rgb_dev": (_i, [_P, _P, _u64, _P, _P]),
+    "trx_render_image_colour": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32, _f, _f,
+                                     _u32, _f, _u32, _f, _f, _u32, _u32, _u32, _P, C.POINTER(_f)]),
+    "trx_standin_materials": (_i, [C.c_char_p, _P, _u64, _P, _u32, C.POINTER(_P), C.POINTER(_u32), C.POINTER(_P)]),
+    "trx_load_model_materials": (_i, [C.c_char_p, C.POINTER(C.POINTER(_f)), C.POINTER(_u64), C.POINTER(C.POINTER(_u64)), C.POINTER(_u32),
+                                      C.POINTER(_P), C.POINTER(_u32), C.POINTER(_P)]),
     "trx_debug_indirect_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P,
                                        C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),

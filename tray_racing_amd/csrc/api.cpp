@@ -294,6 +294,8 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     // launch slots claimed so far: stack spill areas and tile-order lists
     std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
     bytes += s->inst_mask.count(); // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
+    // the material table and the triangles' indices (trx_scene_set_materials; swapped under mu)
+    bytes += s->materials.count() * sizeof(trx_material) + s->tri_material.count() * sizeof(uint16_t);
     bytes += s->image_thr.count() * sizeof(float); // the shade's code thresholds (api_image.cpp)
     for (const Slot &sl : s->slots) {
         bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
@@ -481,6 +483,80 @@ int trx_scene_set_instance_masks(trx_scene *s, const uint8_t *masks, uint32_t n)
     }
     if (retire(old, e) != hipSuccess) // (the old table is kept rather than freed under a kernel that may still read it)
         return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    return TRX_OK;
+}
+
+// Materials (include/trx.h, "materials"): read by the colour passes under s->mu, like the instance mask table.
+int trx_scene_set_materials(trx_scene *s, const trx_material *materials, uint32_t n_materials, const uint16_t *tri_material,
+                            uint64_t n_tris) {
+    if (!s || !materials || !tri_material) return fail(TRX_ERR_INVALID, "null argument");
+    if (n_materials == 0 || n_materials > TRX_MAX_MATERIALS)
+        return fail(TRX_ERR_INVALID, "n_materials %u outside 1..%u", n_materials, TRX_MAX_MATERIALS);
+    if (n_tris != s->n_tris)
+        return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
+    for (uint32_t m = 0; m < n_materials; m++)
+        for (int c = 0; c < 3; c++) {
+            const float a = materials[m].albedo[c], e = materials[m].emission[c];
+            if (!std::isfinite(a) || a < 0.0f) return fail(TRX_ERR_INVALID, "material %u: albedo %g is negative or not finite", m, (double)a);
+            if (!std::isfinite(e) || e < 0.0f) return fail(TRX_ERR_INVALID, "material %u: emission %g is negative or not finite", m, (double)e);
+        }
+    for (uint64_t i = 0; i < n_tris; i++)
+        if (tri_material[i] >= n_materials)
+            return fail(TRX_ERR_INVALID, "triangle %llu: material index %u of %u materials", (unsigned long long)i, (unsigned)tri_material[i], n_materials);
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<trx_material> host_mat;
+    std::vector<uint16_t> host_idx;
+    try {
+        host_mat.assign(materials, materials + n_materials);
+        host_idx.assign(tri_material, tri_material + n_tris);
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "host allocation failed");
+    }
+    DevBuf<trx_material> fresh_mat;
+    DevBuf<uint16_t> fresh_idx;
+    HIP_TRY(fresh_mat.alloc(n_materials));
+    HIP_TRY(fresh_idx.alloc(std::max<uint64_t>(n_tris, 1)));
+    // (uploaded from the validated host copies: what the kernels index is what was checked)
+    hipError_t e = hipMemcpy(fresh_mat.get(), host_mat.data(), (size_t)n_materials * sizeof(trx_material), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_tris) e = hipMemcpy(fresh_idx.get(), host_idx.data(), (size_t)n_tris * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the materials failed: %s", hipGetErrorString(e));
+    // Swapped under the launch mutex (the colour passes read the pointers there); the old tables are freed once every launch
+    // slot's last kernel has finished - trx_scene_set_instance_masks' statement: a pass enqueued before this call uses the
+    // old tables in full.
+    DevBuf<trx_material> old_mat;
+    DevBuf<uint16_t> old_idx;
+    e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        old_mat = std::move(s->materials);
+        old_idx = std::move(s->tri_material);
+        s->materials = std::move(fresh_mat);
+        s->tri_material = std::move(fresh_idx);
+        s->h_materials.swap(host_mat);
+        s->h_tri_material.swap(host_idx);
+        if (old_mat)
+            for (Slot &sl : s->slots)
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
+    }
+    (void)retire(old_idx, e);
+    if (retire(old_mat, e) != hipSuccess) // (the old tables are kept rather than freed under a kernel that may still read them)
+        return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    return TRX_OK;
+}
+
+int trx_scene_get_materials(const trx_scene *s, trx_material *out_materials, uint32_t *inout_n_materials, uint16_t *out_tri_material,
+                            uint64_t n_tris) {
+    if (!s || !out_materials || !inout_n_materials || !out_tri_material) return fail(TRX_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
+    if (s->h_materials.empty()) return fail(TRX_ERR_INVALID, "the scene has no materials (trx_scene_set_materials)");
+    if (n_tris != s->n_tris)
+        return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
+    if (*inout_n_materials < s->h_materials.size())
+        return fail(TRX_ERR_INVALID, "room for %u materials, the scene has %zu", *inout_n_materials, s->h_materials.size());
+    std::memcpy(out_materials, s->h_materials.data(), s->h_materials.size() * sizeof(trx_material));
+    if (n_tris) std::memcpy(out_tri_material, s->h_tri_material.data(), (size_t)n_tris * sizeof(uint16_t));
+    *inout_n_materials = (uint32_t)s->h_materials.size();
     return TRX_OK;
 }
 

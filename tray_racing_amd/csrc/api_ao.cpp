@@ -282,11 +282,19 @@ int bounce_geometry(TileGeom &geom, uint32_t w, uint32_t h, trx_shard shard, uin
 // rays launch with p.ray_mask, k_bounce_weight; k_bounce_gather adds the chunk's sums to the tiles' running sums, and after a
 // tile chunk's last samples k_bounce_finish writes the values.  Sample chunks ascend inside a tile chunk, lights ascend inside
 // a sample chunk: every float sum is formed in the header's order whatever the cap.
+//   colour (trx_trace_indirect_rgb_dev / _rgb_sparse_dev, rule 5c): the same launches up to the weights; the gather and the
+// finish are k_bounce_gather_rgb and k_bounce_finish_rgb (BounceParams::materials), the running sums three per tile pixel,
+// d_value three planes; albedo and d_base are not looked at.  The tables are read under s->mu, where
+// trx_scene_set_materials swaps them, and every launch of the pass is recorded on the slot before the lock is released.
 int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
                   const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps,
                   float albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base, float *d_value,
-                  hipStream_t stream, BouncePhases *phases, const SparseGrid *sparse = nullptr) {
+                  hipStream_t stream, BouncePhases *phases, const SparseGrid *sparse = nullptr, bool colour = false) {
     if (!s || !d_primary || !d_value) return fail(TRX_ERR_INVALID, "null argument");
+    if (colour) { // (a table once set is only ever replaced: what holds here holds under the pass's lock below)
+        std::lock_guard<std::mutex> lock(s->mu);
+        if (!s->materials) return fail(TRX_ERR_INVALID, "the scene has no materials (trx_scene_set_materials)");
+    }
     if (sparse) if (int rc = check_sparse(sparse->stride, sparse->phase)) return rc;
     if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
@@ -308,6 +316,9 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
         g.py0 = sparse->phase / st;
     }
     if (int rc = need_inst(s, d_primary_inst)) return rc;
+    // (colour: floats per plane of d_value - the light visibility pass's plane rule, the low grid's cells in the sparse form)
+    const uint64_t plane = sparse ? (uint64_t)g.lo.width * g.lo.height : g.geom.compact ? (uint64_t)tiles * 64u : (uint64_t)w * h;
+    if (colour && plane > 0x7fffffffull) return fail(TRX_ERR_INVALID, "image %ux%u", w, h);
     if (tiles == 0) return TRX_OK;
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->mu);
@@ -317,7 +328,7 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / kBounceUnitBytes, 1), 1ull << 24);
     const uint32_t tile_chunk = (uint32_t)std::min<uint64_t>(tiles, units);
     const uint32_t sample_chunk = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(units / tile_chunk, 1));
-    const uint64_t rays = (uint64_t)tile_chunk * sample_chunk * 64, pixels = (uint64_t)tile_chunk * 64;
+    const uint64_t rays = (uint64_t)tile_chunk * sample_chunk * 64, pixels = (uint64_t)tile_chunk * 64 * (colour ? 3 : 1);
     if (slot->ao_rays.count() < rays || slot->gi_rays.count() < rays || slot->gi_acc.count() < pixels) {
         // (the slot's previous kernel may still be walking the old scratch)
         if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
@@ -381,6 +392,11 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     b.px0 = g.px0;
     b.py0 = g.py0;
     b.lo = g.lo;
+    if (colour) {
+        b.materials = s->materials.get();
+        b.tri_material = s->tri_material.get();
+        b.plane = (uint32_t)plane;
+    }
     // one rays launch on the pass's slot (the slot is this stream's once the first kernel of the chunk is recorded)
     auto walk = [&](TraceParams &p) -> int {
         SlotCounters *ctr = nullptr;
@@ -678,6 +694,24 @@ int trx_trace_indirect_sparse_dev(trx_scene *s, const trx_view *view, uint32_t w
     const SparseGrid grid{stride, phase};
     return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
                          bounce_albedo, d_primary, d_primary_inst, nullptr, d_value_lo, (hipStream_t)stream, nullptr, &grid);
+}
+
+// ---- the RGB indirect term (include/trx.h, "materials", rule 5c) -----------------------------------------------------------------
+
+int trx_trace_indirect_rgb_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
+                               const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps,
+                               float shadow_eps, const trx_hit *d_primary, const uint32_t *d_primary_inst, float *d_value_rgb, void *stream) {
+    return indirect_impl(s, view, w, h, shard, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps, 1.0f, d_primary,
+                         d_primary_inst, nullptr, d_value_rgb, (hipStream_t)stream, nullptr, nullptr, true);
+}
+
+int trx_trace_indirect_rgb_sparse_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t stride, uint32_t phase,
+                                      uint32_t sem, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                                      uint32_t n_samples, float bounce_eps, float shadow_eps, const trx_hit *d_primary,
+                                      const uint32_t *d_primary_inst, float *d_value_rgb_lo, void *stream) {
+    const SparseGrid grid{stride, phase};
+    return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
+                         1.0f, d_primary, d_primary_inst, nullptr, d_value_rgb_lo, (hipStream_t)stream, nullptr, &grid, true);
 }
 
 // ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------

@@ -652,6 +652,54 @@ int trx_gen_scene(const char *name, uint64_t n_tris, uint64_t seed, float **out_
     return export_mesh(verts, objects, out_verts, out_n, out_counts, out_nobj);
 }
 
+// Materials of the generated scenes (include/trx.h, trx_standin_materials): decided from the mesh as generated - the Cornell
+// walls by their x, its light quad and every other scene's palette by object.
+int trx_standin_materials(const char *name, const float *verts, uint64_t n_tris, const uint64_t *object_counts, uint32_t n_objects,
+                          trx_material **out_materials, uint32_t *out_n_materials, uint16_t **out_tri_material) {
+    if (!name || (!verts && n_tris) || (!object_counts && n_objects) || !out_materials || !out_n_materials || !out_tri_material)
+        return fail(TRX_ERR_INVALID, "null argument");
+    uint64_t sum = 0;
+    for (uint32_t j = 0; j < n_objects; j++) {
+        if (object_counts[j] > n_tris - sum) return fail(TRX_ERR_INVALID, "the object counts exceed %llu triangles", (unsigned long long)n_tris);
+        sum += object_counts[j];
+    }
+    if (sum != n_tris) return fail(TRX_ERR_INVALID, "the object counts sum to %llu of %llu triangles", (unsigned long long)sum, (unsigned long long)n_tris);
+    static const float palette[6][3] = {{.8f, .8f, .8f}, {.8f, .4f, .3f}, {.3f, .6f, .8f}, {.5f, .7f, .3f}, {.8f, .7f, .4f}, {.6f, .5f, .7f}};
+    const bool cornell = std::strcmp(name, "cornell") == 0;
+    const uint32_t n_mat = cornell ? 4u : 6u;
+    trx_material *mat = static_cast<trx_material *>(std::calloc(n_mat, sizeof(trx_material)));
+    uint16_t *idx = static_cast<uint16_t *>(std::calloc(std::max<uint64_t>(n_tris, 1), sizeof(uint16_t)));
+    if (!mat || !idx) {
+        std::free(mat);
+        std::free(idx);
+        return fail(TRX_ERR_OOM, "host allocation failed");
+    }
+    if (cornell) {
+        for (int c = 0; c < 3; c++) {
+            mat[0].albedo[c] = 0.8f;
+            mat[3].emission[c] = 4.0f;
+        }
+        mat[1].albedo[0] = 0.8f;
+        mat[2].albedo[1] = 0.8f;
+        const uint64_t light0 = n_objects ? n_tris - object_counts[n_objects - 1] : n_tris;
+        for (uint64_t i = 0; i < n_tris; i++) {
+            const float *v = verts + i * 9;
+            if (i >= light0) idx[i] = 3;
+            else if (v[0] == -1.0f && v[3] == -1.0f && v[6] == -1.0f) idx[i] = 1;
+            else if (v[0] == 1.0f && v[3] == 1.0f && v[6] == 1.0f) idx[i] = 2;
+        }
+    } else {
+        for (uint32_t m = 0; m < 6; m++) std::memcpy(mat[m].albedo, palette[m], sizeof(palette[m]));
+        uint64_t i = 0;
+        for (uint32_t j = 0; j < n_objects; j++)
+            for (uint64_t k = 0; k < object_counts[j]; k++) idx[i++] = (uint16_t)(j % 6u);
+    }
+    *out_materials = mat;
+    *out_n_materials = n_mat;
+    *out_tri_material = idx;
+    return TRX_OK;
+}
+
 int trx_scene_camera(const char *name, float eye[3], float look_at[3], float *fov) {
     if (!name || !eye || !look_at || !fov) return fail(TRX_ERR_INVALID, "null argument");
     if (!scene_camera(name, eye, look_at, fov)) return fail(TRX_ERR_INVALID, "unknown scene '%s'", name);
@@ -668,6 +716,43 @@ int trx_load_model(const char *path, float **out_verts, uint64_t *out_n, uint64_
         return fail(TRX_ERR_OOM, "out of memory loading '%s'", path);
     }
     return export_mesh(verts, objects, out_verts, out_n, out_counts, out_nobj);
+}
+
+// trx_load_model with the model's materials (include/trx.h): the mesh comes out of the same loader call path, so verts and
+// counts are trx_load_model's byte for byte.
+int trx_load_model_materials(const char *path, float **out_verts, uint64_t *out_n, uint64_t **out_counts, uint32_t *out_nobj,
+                             trx_material **out_materials, uint32_t *out_n_materials, uint16_t **out_tri_material) {
+    if (!path || !out_verts || !out_n || !out_materials || !out_n_materials || !out_tri_material) return fail(TRX_ERR_INVALID, "null argument");
+    std::vector<float> verts;
+    std::vector<uint64_t> objects;
+    ModelMaterials mm;
+    try {
+        if (!load_model_materials(path, verts, objects, mm)) {
+            if (!mm.error.empty()) return fail(TRX_ERR_INVALID, "%s: %s", path, mm.error.c_str());
+            return fail(TRX_ERR_IO, "Error while loading model file \"%s\"", path);
+        }
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "out of memory loading '%s'", path);
+    }
+    static_assert(sizeof(trx_material) == 6 * sizeof(float), "the loader's table is 6 floats per material");
+    trx_material *mat = static_cast<trx_material *>(std::malloc(std::max<size_t>(mm.table.size() * sizeof(float), 4)));
+    uint16_t *idx = static_cast<uint16_t *>(std::malloc(std::max<size_t>(mm.tri.size() * sizeof(uint16_t), 4)));
+    if (!mat || !idx) {
+        std::free(mat);
+        std::free(idx);
+        return fail(TRX_ERR_OOM, "host allocation failed");
+    }
+    std::memcpy(mat, mm.table.data(), mm.table.size() * sizeof(float));
+    if (!mm.tri.empty()) std::memcpy(idx, mm.tri.data(), mm.tri.size() * sizeof(uint16_t));
+    if (int rc = export_mesh(verts, objects, out_verts, out_n, out_counts, out_nobj)) {
+        std::free(mat);
+        std::free(idx);
+        return rc;
+    }
+    *out_materials = mat;
+    *out_n_materials = (uint32_t)(mm.table.size() / 6);
+    *out_tri_material = idx;
+    return TRX_OK;
 }
 
 int trx_load_scene(const char *path, float **out_verts, uint64_t *out_n, uint64_t **out_counts, uint32_t *out_nobj, float eye[3],

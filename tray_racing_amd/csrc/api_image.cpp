@@ -615,4 +615,164 @@ int trx_render_image_gi_sparse(trx_scene *s, const trx_view *view, uint32_t w, u
                       bounce_depth_tol, bounce_normal_cos, bounce_stride, bounce_phase, bounce_upsample_radius, out_rgba, out_ms);
 }
 
+// ---- the colour image (include/trx.h, "materials") ---------------------------------------------------------------------------------
+
+// (the scene's tables are swapped under s->mu and, once set, only ever replaced: what holds here holds when the pass reads them)
+static int need_materials(trx_scene *s) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->materials) return fail(TRX_ERR_INVALID, "the scene has no materials (trx_scene_set_materials)");
+    return TRX_OK;
+}
+
+int trx_material_compose_dev(trx_scene *s, const trx_hit *d_primary, const float *d_direct, const float *d_indirect_rgb, uint64_t n,
+                             float *d_colour_rgb, void *stream) {
+    if (!s || !d_primary || !d_direct || !d_colour_rgb) return fail(TRX_ERR_INVALID, "null argument");
+    if (n == 0 || n > 0x7fffffffull) return fail(TRX_ERR_INVALID, "n_records %llu outside 1..2^31 - 1", (unsigned long long)n);
+    if (int rc = need_materials(s)) return rc;
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        ComposeParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.primary = d_primary;
+        p.direct = d_direct;
+        p.indirect = d_indirect_rgb;
+        p.out = d_colour_rgb;
+        p.materials = s->materials.get(); // (under s->mu: enqueue_image holds it)
+        p.tri_material = s->tri_material.get();
+        p.n_items = (uint32_t)n;
+        p.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull);
+        HIP_TRY(launch_compose(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
+int trx_shade_rgb_dev(trx_scene *s, const float *d_colour_rgb, uint64_t n, uint8_t *d_rgba, void *stream) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    if (n == 0) return TRX_OK;
+    if (!d_colour_rgb || !d_rgba) return fail(TRX_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_rgba) & 3u) return fail(TRX_ERR_INVALID, "d_rgba is not 4-byte aligned");
+    if (n > 0x7fffffffull) return fail(TRX_ERR_INVALID, "n_records %llu beyond 2^31 - 1", (unsigned long long)n);
+    return enqueue_image(s, (hipStream_t)stream, true, [&]() -> int {
+        ShadeRgbParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.thr = s->image_thr.get();
+        p.colour = d_colour_rgb;
+        p.rgba = d_rgba;
+        p.n_items = (uint32_t)n;
+        HIP_TRY(launch_shade_rgb(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
+int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                            const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                            float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                            float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
+                            float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
+                            uint8_t *out_rgba, float *out_ms) {
+    // render_lit's refusals in its order, then the bounce's, the filter's and the upsample's where those steps run
+    if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
+    if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
+    if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
+    if (!std::isfinite(ambient)) return fail(TRX_ERR_INVALID, "ambient %g is not finite", (double)ambient);
+    if (ao_samples > TRX_MAX_AO_SAMPLES) return fail(TRX_ERR_INVALID, "ao_samples %u outside 0..%d", ao_samples, TRX_MAX_AO_SAMPLES);
+    if (ao_samples != 0) {
+        if (!(ao_radius > 0.0f)) return fail(TRX_ERR_INVALID, "ao_radius %g: must be > 0 (+inf allowed)", (double)ao_radius);
+        if (int rc = check_filter(filter_radius, depth_tol, normal_cos)) return rc;
+    }
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (int rc = check_image(w, h)) return rc;
+    if (!s || !view) return fail(TRX_ERR_INVALID, "null argument");
+    if (bounce_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "bounce_samples %u outside 0..%d", bounce_samples, TRX_MAX_AO_SAMPLES);
+    const bool sparse = bounce_samples != 0 && bounce_stride > 1u, filter = bounce_samples != 0 && filter_levels != 0;
+    if (bounce_samples != 0) {
+        if (!(bounce_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "bounce_eps %g: must be >= 0", (double)bounce_eps);
+        if (filter_levels > TRX_MAX_VALUE_FILTER_LEVELS)
+            return fail(TRX_ERR_INVALID, "bounce_filter_levels %u outside 0..%d", filter_levels, TRX_MAX_VALUE_FILTER_LEVELS);
+        if (filter)
+            if (int rc = check_value_filter(filter_levels, bounce_depth_tol, bounce_normal_cos)) return rc;
+        if (int rc = check_sparse(bounce_stride, bounce_phase, 0u)) return rc;
+        if (sparse)
+            if (int rc = check_value_upsample(bounce_stride, bounce_phase, upsample_radius, bounce_depth_tol, bounce_normal_cos)) return rc;
+    }
+    if (int rc = need_materials(s)) return rc;
+    const uint64_t n = (uint64_t)w * h;
+    const trx_shard whole{0, 1, 0, 0};
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
+    HIP_TRY(hipSetDevice(s->device));
+    // the image scratch: the AO filter's terms, the image, the light term's values, two sets of three planes (the indirect
+    // term's steps alternate between them: a low grid holds at most n cells), the value filter's work plane, the lights' planes
+    HIP_TRY(s->scratch_img.grow(n * 4 * 10 + n * n_lights));
+    auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
+    auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
+    auto d_value = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 8); };
+    auto d_a = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 12); };
+    auto d_b = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 24); };
+    auto d_work = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 36); };
+    auto d_lit = [&] { return s->scratch_img.get() + n * 40; };
+    auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
+    return host_call(
+        s, n, nullptr, 0, n, out_ms,
+        [&] {
+            int rc = trx_trace_primary_inst_dev(s, view, w, h, whole, sem, s->scratch_a.get(), s->scratch_ia.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
+            if (rc) return rc;
+            rc = trx_trace_light_visibility_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps,
+                                                s->scratch_a.get(), s->scratch_ia.get(), d_lit(), nullptr);
+            if (rc) return rc;
+            if (ao_samples != 0) {
+                rc = trx_trace_ao_visibility_dev(s, view, w, h, whole, sem, frame0, ao_samples, ao_eps, ao_radius, s->scratch_a.get(),
+                                                 s->scratch_ia.get(), d_counts(), nullptr);
+                if (rc) return rc;
+                rc = trx_ao_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), d_counts(), ao_samples, filter_radius, depth_tol,
+                                       normal_cos, d_term(), nullptr);
+                if (rc) return rc;
+            }
+            rc = trx_light_term_dev(s, view, w, h, whole, lights, n_lights, light_samples, s->scratch_a.get(), s->scratch_attr.get(),
+                                    d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
+            if (rc) return rc;
+            float *planes = nullptr; // the indirect term's three full-resolution planes, or none
+            if (bounce_samples != 0) {
+                float *other = d_b();
+                planes = d_a();
+                if (sparse) {
+                    rc = trx_trace_indirect_rgb_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights, n_lights, frame0,
+                                                           bounce_samples, bounce_eps, shadow_eps, s->scratch_a.get(), s->scratch_ia.get(),
+                                                           planes, nullptr);
+                    if (rc) return rc;
+                    const uint64_t n_lo = (uint64_t)((w + bounce_stride - 1u) / bounce_stride) * ((h + bounce_stride - 1u) / bounce_stride);
+                    for (uint64_t c = 0; c < 3; c++) {
+                        rc = trx_value_upsample_dev(s, w, h, bounce_stride, bounce_phase, s->scratch_a.get(), s->scratch_attr.get(),
+                                                    planes + c * n_lo, nullptr, upsample_radius, bounce_depth_tol, bounce_normal_cos,
+                                                    other + c * n, nullptr);
+                        if (rc) return rc;
+                    }
+                    std::swap(planes, other);
+                } else {
+                    rc = trx_trace_indirect_rgb_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples, bounce_eps,
+                                                    shadow_eps, s->scratch_a.get(), s->scratch_ia.get(), planes, nullptr);
+                    if (rc) return rc;
+                }
+                if (filter) {
+                    for (uint64_t c = 0; c < 3; c++) {
+                        rc = trx_value_filter_dev(s, w, h, s->scratch_a.get(), s->scratch_attr.get(), planes + c * n, nullptr, filter_levels,
+                                                  bounce_depth_tol, bounce_normal_cos, d_work(), other + c * n, nullptr);
+                        if (rc) return rc;
+                    }
+                    std::swap(planes, other);
+                }
+            }
+            // (the colour lands in the planes the indirect term ends in - the compose may run in place - or in the first set)
+            float *colour = planes ? planes : d_a();
+            rc = trx_material_compose_dev(s, s->scratch_a.get(), d_value(), planes, n, colour, nullptr);
+            if (rc) return rc;
+            return trx_shade_rgb_dev(s, colour, n, d_rgba(), nullptr);
+        },
+        [&]() -> int {
+            if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));
+            return TRX_OK;
+        });
+}
+
 } // extern "C"

@@ -11,6 +11,8 @@
 //                    trx_light_rays_dev / trx_trace_light_visibility_dev / trx_light_term_dev: the same chain per light, and the light term
 //                    trx_bounce_light_rays_dev / trx_trace_indirect_dev / trx_trace_indirect_sparse_dev: one diffuse bounce (dense, or over a low grid) - closest-hit bounce rays, their attributes, shadow rays from the bounce hits
 //   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_value_filter_dev / trx_value_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
+//   materials        (include/trx.h, "materials") trx_scene_set_materials / _get_materials in api.cpp; trx_trace_indirect_rgb_dev / _rgb_sparse_dev: the indirect pass's colour mode in api_ao.cpp;
+//                    trx_material_compose_dev / trx_shade_rgb_dev / trx_render_image_colour in api_image.cpp; trx_standin_materials / trx_load_model_materials in api_build.cpp (the OBJ/MTL reading itself in scenes.cpp)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -214,6 +216,13 @@ struct trx_scene {
     // calls only; host copy and device table, empty = every instance 0xFF
     std::vector<uint8_t> h_inst_mask;
     trxapi::DevBuf<uint8_t> inst_mask;
+    // materials (trx_scene_set_materials): the table and one index per triangle in `prim` order, every index validated
+    // against the table on upload; host copies and device tables, swapped together under mu; empty = no materials (the
+    // colour entry points are refused)
+    std::vector<trx_material> h_materials;
+    std::vector<uint16_t> h_tri_material;
+    trxapi::DevBuf<trx_material> materials;
+    trxapi::DevBuf<uint16_t> tri_material;
     // the frame's image (api_image.cpp): the shade's 256 code thresholds on the scene's device (first shade; under mu), and
     // trx_render_image's scratch - the filter's terms, then the RGBA8 image (under host_mu)
     trxapi::DevBuf<float> image_thr;

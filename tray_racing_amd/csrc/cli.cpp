@@ -75,6 +75,9 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // in S x S and rebuilt by the edge-aware upsample (trx_render_image_gi_sparse; the filter's two tolerances are its own)
     int bounce_stride = -1; // -1: not given, everything stays as it is
     int bounce_phase = -1, bounce_upsample = -1; // (not given: phase 0, radius 1)
+    // --colour: with --png --light the image is the colour image (trx_render_image_colour) - the scene gets a material table, the
+    // mtl files' for -i <file.obj>, the stand-in table for standin:<name>, and every --bounce-*, --ao-* and --light option applies
+    bool colour = false;
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -127,6 +130,9 @@ void usage() {
               "  [--bounce-stride 1..4] [--bounce-phase P] [--bounce-upsample 0..2] (with --bounce-samples: the bounce rays of one pixel\n"
               "   in every S x S block - pixel P = 0..S*S-1 of the block, default 0 - and the full-resolution term rebuilt from the\n"
               "   cells of a (2R+1)^2 window, default R = 1, under --bounce-filter-tol / --bounce-filter-cos; before --bounce-filter)\n"
+              "  [--colour] (with --png --light: the colour image - per-triangle albedo and emission from the mtl files of\n"
+              "   -i <file.obj> or the stand-in table of standin:<name>; the bounce carries the colour of what it hit; not together\n"
+              "   with --bounce-albedo)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -274,6 +280,9 @@ Options parse_args(int argc, char **argv) {
             o.bounce_filter_opts = true;
             if (o.bounce_filter_cos != o.bounce_filter_cos) die("--bounce-filter-cos must be a number");
         }
+        else if (a == "--colour") {
+            o.colour = true;
+        }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
             if (m == "nodes") o.profile_rt = (int)TRX_HEAT_NODES;
@@ -332,6 +341,8 @@ Options parse_args(int argc, char **argv) {
     if (o.bounce_stride >= 0 && o.bounce_phase >= o.bounce_stride * o.bounce_stride) die("--bounce-phase takes 0..S*S-1 of --bounce-stride S");
     if (o.bounce_filter < 0 && o.bounce_stride < 0 && o.bounce_filter_opts) die("--bounce-filter-tol and --bounce-filter-cos go with --bounce-filter L");
     if (o.bounce_filter >= 0 && o.bounce_samples < 0) die("--bounce-filter filters the term of --bounce-samples N");
+    if (o.colour && o.lights.empty()) die("--colour colours the image of --light");
+    if (o.colour && o.bounce_albedo >= 0.0f) die("--colour takes the albedo of the materials: not together with --bounce-albedo");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -400,7 +411,18 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
         const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
-        if (o.bounce_samples >= 0 && o.bounce_stride >= 0)
+        if (o.colour)
+            // the colour image: the same chain, the bounce's term in three planes, composed with the scene's materials
+            check(trx_render_image_colour(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                          o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
+                                          o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
+                                          radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
+                                          o.bounce_samples >= 0 ? (uint32_t)o.bounce_samples : 0u, o.bounce_eps >= 0.0f ? o.bounce_eps : 0.01f,
+                                          o.bounce_filter >= 0 ? (uint32_t)o.bounce_filter : 0u, o.bounce_filter_tol, o.bounce_filter_cos,
+                                          o.bounce_stride >= 0 ? (uint32_t)o.bounce_stride : 1u, o.bounce_phase >= 0 ? (uint32_t)o.bounce_phase : 0u,
+                                          o.bounce_upsample >= 0 ? (uint32_t)o.bounce_upsample : 1u, rgba.data(), &ms),
+                  "png frame");
+        else if (o.bounce_samples >= 0 && o.bounce_stride >= 0)
             // ... and one diffuse bounce traced at one pixel in stride x stride, upsampled (and filtered), on top of it
             check(trx_render_image_gi_sparse(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                              o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
@@ -499,12 +521,39 @@ Stats render_input(const Options &o, const std::string &input) {
     uint64_t n_tris = 0, *counts = nullptr;
     uint32_t n_objects = 0;
     Camera cam;
+    // --colour: the materials in the order of verts (permuted by tri_source once the scene is built)
+    trx_material *materials = nullptr;
+    uint32_t n_materials = 0;
+    uint16_t *tri_material = nullptr;
+    const bool obj = input.size() > 4 && input.compare(input.size() - 4, 4, ".obj") == 0;
     if (input == "demoscene" || input.rfind("standin:", 0) == 0) {
         const std::string name = input == "demoscene" ? "demoscene" : input.substr(8);
         st.name = name;
         check(trx_gen_scene(name.c_str(), 0, 1, &verts, &n_tris, &counts, &n_objects), "scene");
         check(trx_scene_camera(name.c_str(), cam.eye, cam.look_at, &cam.fov), "camera");
+        if (o.colour) check(trx_standin_materials(name.c_str(), verts, n_tris, counts, n_objects, &materials, &n_materials, &tri_material), "materials");
+    } else if (obj) {
+        // a model file on its own, with the materials of its mtl files: seen from +z, a box diagonal away from the box's centre
+        size_t k = input.find_last_of('/');
+        st.name = input.substr(k == std::string::npos ? 0 : k + 1);
+        st.name.erase(st.name.size() - 4);
+        check(trx_load_model_materials(input.c_str(), &verts, &n_tris, &counts, &n_objects, &materials, &n_materials, &tri_material), "model");
+        float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+        for (uint64_t i = 0; i < n_tris * 3; i++)
+            for (int c = 0; c < 3; c++) {
+                const float x = verts[i * 3 + c];
+                if (i == 0 || x < lo[c]) lo[c] = x;
+                if (i == 0 || x > hi[c]) hi[c] = x;
+            }
+        float diag = 0;
+        for (int c = 0; c < 3; c++) {
+            cam.look_at[c] = cam.eye[c] = 0.5f * (lo[c] + hi[c]);
+            diag += (hi[c] - lo[c]) * (hi[c] - lo[c]);
+        }
+        cam.eye[2] += std::sqrt(diag) > 0.0f ? std::sqrt(diag) : 1.0f;
+        cam.fov = 60.0f;
     } else {
+        if (o.colour) die("--colour takes the materials of -i <file.obj> or of standin:<name>");
         size_t k = input.find_last_of('/');
         st.name = input.substr(k == std::string::npos ? 0 : k + 1);
         k = st.name.find_last_of('.');
@@ -549,6 +598,8 @@ Stats render_input(const Options &o, const std::string &input) {
         trx_flat_destroy(flat);
         trx_free(verts);
         trx_free(counts);
+        trx_free(materials);
+        trx_free(tri_material);
         return st;
     }
 
@@ -561,6 +612,11 @@ Stats render_input(const Options &o, const std::string &input) {
     // BLAS would walk that BLAS k times (same hits, many more node visits)
     if (flat->instance_entry_nodes && flat->n_instances)
         check(trx_scene_set_instance_entry_nodes(scene, flat->instance_entry_nodes, flat->n_instances), "instance entry nodes");
+    if (o.colour) { // the table in `prim` order: record i of the scene is triangle tri_source[i] of the mesh
+        std::vector<uint16_t> by_prim(flat->n_tris);
+        for (uint64_t i = 0; i < flat->n_tris; i++) by_prim[i] = flat->tri_source[i] < n_tris ? tri_material[flat->tri_source[i]] : 0;
+        check(trx_scene_set_materials(scene, materials, n_materials, by_prim.data(), flat->n_tris), "materials");
+    }
     trx_view view;
     check(trx_view_from_camera(cam.eye, cam.look_at, cam.fov, (float)o.width, (float)o.height, &view), "camera");
 
@@ -606,6 +662,8 @@ Stats render_input(const Options &o, const std::string &input) {
     trx_flat_destroy(flat);
     trx_free(verts);
     trx_free(counts);
+    trx_free(materials);
+    trx_free(tri_material);
     return st;
 }
 

@@ -100,6 +100,31 @@ struct ShadeParams {
 };
 hipError_t launch_shade(const ShadeParams &p, int mode, hipStream_t stream);
 
+// The colour image (include/trx.h, "materials"): both kernels are elementwise over n_items records, planes at c * n_items.
+//   k_compose    (trx_material_compose_dev) one lane per record: 8 B of primary record, the u16 index and 24 B of material for
+//                a surface record of the scene (prim < n_tris; every index was validated on upload), 4 B of the direct plane
+//                and 12 B of the indirect planes (none with a null pointer) read, 12 B written: emission + albedo * (E + I_c),
+//                +0 for any other record.  Every lane reads before it writes: out may be indirect.
+//   k_rgb_shade  (trx_shade_rgb_dev) one lane per record: 12 B read, {code(R), code(G), code(B), 255} written, each code by
+//                k_value's 8-step search - in the table where it lies in device memory (1 KiB, cache-resident), not in LDS.
+struct ComposeParams {
+    const trx_hit *primary;
+    const float *direct;
+    const float *indirect;         // three planes, or null
+    float *out;                    // three planes
+    const trx_material *materials;
+    const uint16_t *tri_material;
+    uint32_t n_items, n_tris;
+};
+hipError_t launch_compose(const ComposeParams &p, hipStream_t stream);
+struct ShadeRgbParams {
+    const float *thr;   // 256 floats, device memory
+    const float *colour; // three planes
+    uint8_t *rgba;
+    uint32_t n_items;
+};
+hipError_t launch_shade_rgb(const ShadeRgbParams &p, hipStream_t stream);
+
 // k_heat: the PROFILE_RT heat map (trx_shade_heat_dev) - one lane per record, 4 bytes of per-ray counts read, 4 bytes
 // {r, g, b, 255} written.  No table in LDS, no pow: the colour is arithmetic on the count.
 struct HeatParams {

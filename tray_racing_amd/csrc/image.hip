@@ -491,7 +491,66 @@ __global__ void __launch_bounds__(256) k_plane_upsample(const PlaneUpsampleParam
     P.out[ip] = f;
 }
 
+// The colour compose (trx_material_compose_dev; include/trx.h, "materials"): one lane per record, planes at c * n_items.  A
+// record with t < FLT_MAX and prim < n_tris (which rules 0xFFFFFFFF out) is a surface record of the scene, its index into the
+// material table was validated on upload; any other record - a caller's too - reads neither table and is background.  All of a
+// lane's reads come before its writes, so out may be the indirect planes.  A streaming kernel: no scratch, no LDS.
+__global__ void __launch_bounds__(256) k_compose(const ComposeParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    const size_t n = P.n_items;
+    const trx_hit ph = P.primary[i];
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (ph.t < TRX_F32_MAX && ph.prim < P.n_tris) {
+        const float2 *mp = reinterpret_cast<const float2 *>(P.materials + P.tri_material[ph.prim]);
+        const float2 m0 = mp[0], m1 = mp[1], m2 = mp[2]; // {albedo r, g}, {albedo b, emission r}, {emission g, b}
+        const float E = P.direct[i];
+        float Ir = E, Ig = E, Ib = E;
+        if (P.indirect) {
+            Ir = E + P.indirect[i];
+            Ig = E + P.indirect[n + i];
+            Ib = E + P.indirect[2u * n + i];
+        }
+        r = m1.y + m0.x * Ir;
+        g = m2.x + m0.y * Ig;
+        b = m2.y + m1.x * Ib;
+    }
+    P.out[i] = r;
+    P.out[n + i] = g;
+    P.out[2u * n + i] = b;
+}
+
+// The colour shade (trx_shade_rgb_dev): k_value's code, three times per record.  The 1 KiB table is searched where it lies:
+// every wave reads the same few lines of it, which stay in cache, and the kernel takes no LDS.
+__device__ __forceinline__ uint32_t colour_code(const float *thr, float col) {
+    uint32_t c = 0u;
+#pragma unroll
+    for (uint32_t step = 128u; step != 0u; step >>= 1) c += col >= thr[c + step] ? step : 0u;
+    return c;
+}
+__global__ void __launch_bounds__(256) k_rgb_shade(const ShadeRgbParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    const size_t n = P.n_items;
+    const uint32_t r = colour_code(P.thr, P.colour[i]), g = colour_code(P.thr, P.colour[n + i]), b = colour_code(P.thr, P.colour[2u * n + i]);
+    reinterpret_cast<uint32_t *>(P.rgba)[i] = r | g << 8 | b << 16 | 0xFF000000u; // {r, g, b, 255}
+}
+
 } // namespace
+
+hipError_t launch_compose(const ComposeParams &p, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    if (!p.primary || !p.direct || !p.out || !p.materials || !p.tri_material) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_compose, dim3((p.n_items + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_rgb(const ShadeRgbParams &p, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    if (!p.thr || !p.colour || !p.rgba) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rgb_shade, dim3((p.n_items + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_heat(const HeatParams &p, hipStream_t stream) {
     if (p.n_items == 0) return hipSuccess;

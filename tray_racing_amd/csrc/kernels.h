@@ -344,6 +344,17 @@ struct BounceParams {
     uint32_t stride, px0, py0;
     TileGeom lo;
     uint32_t n_tris;              // k_bounce_finish: the scene's triangle extent (surface_record: the surface as k_ao_rays decided it)
+    // colour (trx_trace_indirect_rgb_dev / _rgb_sparse_dev; include/trx.h, rule 5c; last again: the fields above keep their
+    // offsets): with `materials` set launch_bounce_gather and launch_bounce_finish run k_bounce_gather_rgb and
+    // k_bounce_finish_rgb.  acc then holds three planes of n_tiles * 64 running sums (plane c at c * n_tiles * 64), value three
+    // planes of `plane` floats (plane c at c * plane); base and albedo are not read.
+    //   k_bounce_gather_rgb  one lane per pixel of the chunk's tiles: per sample of the chunk, where the bounce has a surface
+    //                        (the ray's tmax, the hit), m = tri_material[hit.prim] and A_c = A_c + (albedo_c(m) * s + emission_c(m)).
+    //   k_bounce_finish_rgb  one lane per pixel (SPARSE: cell) of the chunk's tiles: value[c * plane + record] = A_c / n_total,
+    //                        +0 where the primary record is no surface.
+    const trx_material *materials; // the scene's table, or null: the grey kernels
+    const uint16_t *tri_material;  // n_tris indices into it, every one validated on upload
+    uint32_t plane;                // floats per plane of value
 };
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream);

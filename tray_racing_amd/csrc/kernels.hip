@@ -1317,6 +1317,72 @@ __global__ void __launch_bounds__(256) k_bounce_finish(const BounceParams P) {
     P.value[rec] = out;
 }
 
+// k_bounce_gather in colour (include/trx.h, rule 5c): one lane per pixel of the chunk's tiles, three running sums per lane
+// (plane c of acc at c * n_tiles * 64).  Per sample the wave's 64 lanes read 64 consecutive floats of sum, 64 consecutive hits
+// and the tmax word of 64 consecutive bounce rays; the u16 index and the 24 B material are gathers into tables of at most
+// 1.5 MiB that stay in cache.  A bounce without a surface (bounce_hit's test) adds nothing.  hit.prim is the walk's own answer
+// and every index of tri_material was checked against the table on upload: the prim < n_tris test is surface_record's, for a
+// scratch that holds anything else.  A streaming kernel: no scratch, no LDS.
+__global__ void __launch_bounds__(256) k_bounce_gather_rgb(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lanes = P.n_tiles * 64u;
+    if (item >= lanes) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    const uint32_t from = lt * P.n_samples * 64u + k;
+    float Ar = 0.0f, Ag = 0.0f, Ab = 0.0f;
+    if (!P.first) {
+        Ar = P.acc[item];
+        Ag = P.acc[lanes + item];
+        Ab = P.acc[2u * lanes + item];
+    }
+    for (uint32_t s = 0; s < P.n_samples; s++) {
+        const uint32_t index = from + s * 64u;
+        const float sf = P.sum[index];
+        const float tmax = P.bounce_rays[index].tmax;
+        const trx_hit bh = P.bounce_hits[index];
+        if (tmax < 0.0f || !surface_record(bh, P.n_tris)) continue;
+        const float2 *mp = reinterpret_cast<const float2 *>(P.materials + P.tri_material[bh.prim]);
+        const float2 m0 = mp[0], m1 = mp[1], m2 = mp[2]; // {albedo r, g}, {albedo b, emission r}, {emission g, b}
+        Ar = Ar + (m0.x * sf + m1.y);
+        Ag = Ag + (m0.y * sf + m2.x);
+        Ab = Ab + (m1.x * sf + m2.y);
+    }
+    P.acc[item] = Ar;
+    P.acc[lanes + item] = Ag;
+    P.acc[2u * lanes + item] = Ab;
+}
+
+// k_bounce_finish in colour: three planes of `plane` floats, out_c = A_c / n_total at a surface record (k_bounce_finish's
+// surface and cell -> pixel mapping), +0 elsewhere; there is no base.
+template <int SPARSE> // (an int: tests select the grey kernels' sparse instantiations by the bool's mangling)
+__global__ void __launch_bounds__(256) k_bounce_finish_rgb(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lanes = P.n_tiles * 64u;
+    if (item >= lanes) return;
+    uint32_t px, py, rec;
+    bool surf;
+    if constexpr (SPARSE) {
+        if (!tile_pixel(P.lo, P.tile0 + (item >> 6), item & 63u, px, py, rec)) return;
+        px = px * P.stride + P.px0;
+        py = py * P.stride + P.py0;
+        surf = px < P.geom.width && py < P.geom.height && surface_record(P.primary[(size_t)py * P.geom.width + px], P.n_tris);
+    } else {
+        if (!tile_pixel(P.geom, P.tile0 + (item >> 6), item & 63u, px, py, rec)) return;
+        surf = surface_record(P.primary[rec], P.n_tris);
+    }
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (surf) {
+        const float n = (float)P.n_total;
+        r = P.acc[item] / n;
+        g = P.acc[lanes + item] / n;
+        b = P.acc[2u * lanes + item] / n;
+    }
+    if (rec >= P.plane) return; // (never: the launch checked the planes against the geometry)
+    P.value[rec] = r;
+    P.value[(size_t)P.plane + rec] = g;
+    P.value[2u * (size_t)P.plane + rec] = b;
+}
+
 } // namespace
 
 // (the sparse form of the bounce kernels exists for the scratch layout of a whole image only: what bounds their cell -> pixel
@@ -1352,6 +1418,11 @@ hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream) {
 hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream) {
     if (p.n_tiles == 0) return hipSuccess;
     if (p.n_tiles > 0x3ffffffu) return hipErrorInvalidValue;
+    if (p.materials) {
+        if (!p.tri_material || !p.scratch) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_bounce_gather_rgb, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_bounce_gather, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
@@ -1360,6 +1431,19 @@ hipError_t launch_bounce_finish(const BounceParams &p, hipStream_t stream) {
     if (p.n_tiles == 0) return hipSuccess;
     if (p.n_tiles > 0x3ffffffu || p.n_total == 0u) return hipErrorInvalidValue;
     const dim3 grid((p.n_tiles * 64u + 255u) / 256u);
+    if (p.materials) {
+        // (the three planes hold every record the kernel can form: k_bounce_finish_rgb writes nothing at or past `plane`)
+        if (p.base) return hipErrorInvalidValue;
+        if (p.stride) {
+            if (!bounce_sparse_ok(p) || (uint64_t)p.plane != (uint64_t)p.lo.width * p.lo.height) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(k_bounce_finish_rgb<1>, grid, dim3(256), 0, stream, p);
+        } else {
+            const uint64_t need = p.geom.compact ? ((uint64_t)p.tile0 + p.n_tiles) * 64u : (uint64_t)p.geom.width * p.geom.height;
+            if (p.plane < need) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(k_bounce_finish_rgb<0>, grid, dim3(256), 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.stride) {
         if (!bounce_sparse_ok(p) || p.base) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_bounce_finish<true>, grid, dim3(256), 0, stream, p);

@@ -703,9 +703,61 @@ bool scene_camera(const std::string &name, float eye[3], float look_at[3], float
 
 // ---- load_meshs (src/main.rs:494-561) ---------------------------------------------
 namespace {
-bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects) {
+// the rest of a line after its keyword, without surrounding blanks and the line end
+std::string line_rest(const char *p) {
+    std::string s(p);
+    const size_t a = s.find_first_not_of(" \t"), b = s.find_last_not_of(" \t\r\n");
+    return a == std::string::npos ? std::string() : s.substr(a, b - a + 1);
+}
+
+// One mtl file into names / table (6 floats per material: Kd, a missing one 0.8 each; Ke, a missing one 0).  A file that cannot
+// be opened adds nothing.  false (mm.error set): a negative or non-finite Kd or Ke, more than 65535 named materials.
+bool load_mtl(const std::string &path, std::vector<std::string> &names, ModelMaterials &mm) {
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) return true;
+    char line[4096];
+    bool ok = true, open = false;
+    while (ok && std::fgets(line, sizeof(line), f)) {
+        const char *p = line;
+        while (*p == ' ' || *p == '\t') p++;
+        if (std::strncmp(p, "newmtl", 6) == 0 && (p[6] == ' ' || p[6] == '\t')) {
+            if (names.size() >= 65535) {
+                mm.error = "more than 65535 named materials";
+                ok = false;
+                break;
+            }
+            names.push_back(line_rest(p + 6));
+            const float fresh[6] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.0f};
+            mm.table.insert(mm.table.end(), fresh, fresh + 6);
+            open = true;
+        } else if (open && (p[0] == 'K') && (p[1] == 'd' || p[1] == 'e') && (p[2] == ' ' || p[2] == '\t')) {
+            float c[3] = {0, 0, 0};
+            const int got = std::sscanf(p + 2, "%f %f %f", &c[0], &c[1], &c[2]);
+            for (int k = 0; k < 3; k++)
+                if (got != 3 || !std::isfinite(c[k]) || c[k] < 0.0f) {
+                    mm.error = std::string("material '") + names.back() + "': " + (p[1] == 'd' ? "Kd" : "Ke") + " is negative, not finite or not three numbers";
+                    ok = false;
+                }
+            if (ok) std::memcpy(&mm.table[mm.table.size() - 6 + (p[1] == 'd' ? 0 : 3)], c, sizeof(c));
+        }
+    }
+    std::fclose(f);
+    return ok;
+}
+
+// mm (optional): the materials of trx_load_model_materials - `mtllib` files are read from the OBJ's directory as they are
+// named, `usemtl` names are looked up once the whole file is read (the first material of a name wins; an unknown name, and
+// faces before any usemtl, get material 0, the default).  The mesh is the same with and without it.
+bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials *mm = nullptr) {
     FILE *f = std::fopen(path.c_str(), "rb");
     if (!f) return false;
+    std::vector<std::string> names, uses; // the mtl files' materials in file order; the names given to usemtl
+    std::vector<uint32_t> tri_use;        // per triangle: 0 = before any usemtl, else 1 + index into uses
+    uint32_t use = 0;
+    if (mm) {
+        const float fresh[6] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.0f};
+        mm->table.assign(fresh, fresh + 6);
+    }
     std::vector<float> pos;
     uint64_t open_start = 0;
     bool any_object = false;
@@ -725,6 +777,16 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
         } else if (line[0] == 'o' && (line[1] == ' ' || line[1] == '\t')) {
             if (any_object || verts.size() / 9 > open_start) close_object();
             any_object = true;
+        } else if (mm && std::strncmp(line, "mtllib", 6) == 0 && (line[6] == ' ' || line[6] == '\t')) {
+            const size_t slash = path.find_last_of('/');
+            const std::string dir = slash == std::string::npos ? std::string() : path.substr(0, slash + 1);
+            if (!load_mtl(dir + line_rest(line + 6), names, *mm)) {
+                std::fclose(f);
+                return false;
+            }
+        } else if (mm && std::strncmp(line, "usemtl", 6) == 0 && (line[6] == ' ' || line[6] == '\t')) {
+            uses.push_back(line_rest(line + 6));
+            use = (uint32_t)uses.size();
         } else if (line[0] == 'f' && (line[1] == ' ' || line[1] == '\t')) {
             long idx[4];
             int n = 0;
@@ -749,6 +811,7 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
                     verts.push_back(pos[3 * i + 1]);
                     verts.push_back(pos[3 * i + 2]);
                 }
+                if (mm) tri_use.push_back(use);
             };
             // the reference reads vertices 0,1,2 and, for quads only, 0,2,3 (src/main.rs:536-553)
             if (n >= 3) push(idx[0], idx[1], idx[2]);
@@ -758,6 +821,17 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
     std::fclose(f);
     close_object();
     if (objects.empty()) objects.push_back(0);
+    if (mm) {
+        std::vector<uint16_t> of_use(uses.size() + 1, 0);
+        for (size_t u = 0; u < uses.size(); u++)
+            for (size_t m = 0; m < names.size(); m++)
+                if (names[m] == uses[u]) {
+                    of_use[u + 1] = (uint16_t)(m + 1);
+                    break;
+                }
+        mm->tri.resize(tri_use.size());
+        for (size_t i = 0; i < tri_use.size(); i++) mm->tri[i] = of_use[tri_use[i]];
+    }
     return true;
 }
 
@@ -809,6 +883,19 @@ bool load_model(const std::string &path, std::vector<float> &verts, std::vector<
         path.substr(path.rfind('.')).find("json") != std::string::npos)
         return load_json(path, verts, objects);
     return load_obj(path, verts, objects);
+}
+
+bool load_model_materials(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials &mm) {
+    mm = ModelMaterials();
+    if (path.find("json") != std::string::npos && path.rfind('.') != std::string::npos &&
+        path.substr(path.rfind('.')).find("json") != std::string::npos) {
+        if (!load_json(path, verts, objects)) return false;
+        const float fresh[6] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.0f};
+        mm.table.assign(fresh, fresh + 6);
+        mm.tri.assign(verts.size() / 9, 0);
+        return true;
+    }
+    return load_obj(path, verts, objects, &mm);
 }
 
 // The subset of RON the reference's scene files use (assets/scenes/*.ron): model_path, camera(eye, look_at, fov,

@@ -10,6 +10,15 @@ bool gen_scene(const std::string &name, uint64_t n_tris, uint64_t seed, std::vec
                std::vector<uint64_t> &objects);
 bool scene_camera(const std::string &name, float eye[3], float look_at[3], float *fov_deg);
 bool load_model(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects);
+// load_model with the model's materials (trx_load_model_materials): the same verts and objects, a table of 6 floats per
+// material (albedo, emission; material 0 the default 0.8 / 0, then the mtl files' newmtl entries in file order) and one index
+// per triangle in the order of verts.  false with `error` set: a mtl file the loader refuses; false without: unreadable.
+struct ModelMaterials {
+    std::vector<float> table;
+    std::vector<uint16_t> tri;
+    std::string error;
+};
+bool load_model_materials(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials &mm);
 // A scene file of the reference (assets/scenes/*.ron: model_path, camera(eye, look_at, fov)): the model's path resolved by
 // the reference's rule (src/main.rs:271-284) and the camera.  false = unreadable or not such a file.
 bool parse_scene_ron(const std::string &path, std::string &model_path, float eye[3], float look_at[3], float *fov_deg);

@@ -20,6 +20,8 @@ HIT_ATTR_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("_
 # trx_ao_term: the edge-aware AO filter's output per pixel
 AO_TERM_DTYPE = np.dtype([("unoccluded", "<u2"), ("samples", "<u2")])
 RAY_COST_DTYPE = np.dtype([("n_node", "<u2"), ("n_tri", "<u2")])
+# trx_material: diffuse albedo and emission, linear RGB
+MATERIAL_DTYPE = np.dtype([("albedo", "<f4", 3), ("emission", "<f4", 3)])
 MISS_PRIM = 0xFFFFFFFF
 
 
@@ -47,6 +49,22 @@ def gen_scene(name, n_tris=0, seed=1):
     return _take_mesh(vp, n, cp, nobj)
 
 
+def standin_materials(name, verts, counts):
+    """(materials [n] MATERIAL_DTYPE, tri_material [n_tris] uint16): trx_standin_materials - the materials of a generated
+    scene for the mesh gen_scene returned (cornell: grey, red left wall, green right wall, emissive light quad; any other
+    name: a palette of six albedos by object).  tri_material is in the order of verts."""
+    lib = L.load()
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 9)
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    mp, ip, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
+    L.check(lib.trx_standin_materials(name.encode(), _ptr(v), v.shape[0], _ptr(c), c.size, C.byref(mp), C.byref(n), C.byref(ip)))
+    mats = np.frombuffer(C.string_at(mp.value, n.value * MATERIAL_DTYPE.itemsize), dtype=MATERIAL_DTYPE).copy()
+    idx = np.frombuffer(C.string_at(ip.value, v.shape[0] * 2), dtype=np.uint16).copy()
+    lib.trx_free(mp)
+    lib.trx_free(ip)
+    return mats, idx
+
+
 def load_meshs(path):
     """load_meshs (src/main.rs:494-561): OBJ or JSON -> (verts [n,9], triangles per object)."""
     lib = L.load()
@@ -54,6 +72,24 @@ def load_meshs(path):
     n, nobj = C.c_uint64(), C.c_uint32()
     L.check(lib.trx_load_model(str(path).encode(), C.byref(vp), C.byref(n), C.byref(cp), C.byref(nobj)))
     return _take_mesh(vp, n, cp, nobj)
+
+
+def load_model_materials(path):
+    """(verts [n,9], triangles per object, materials [m] MATERIAL_DTYPE, tri_material [n] uint16): trx_load_model_materials -
+    load_meshs' mesh with the materials of the OBJ's mtl files (Kd: albedo, Ke: emission; material 0 is the default 0.8 / 0 and
+    goes to faces without a known usemtl, and to every triangle of a JSON model)."""
+    lib = L.load()
+    vp, cp = C.POINTER(C.c_float)(), C.POINTER(C.c_uint64)()
+    n, nobj, nmat = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    mp, ip = C.c_void_p(), C.c_void_p()
+    L.check(lib.trx_load_model_materials(str(path).encode(), C.byref(vp), C.byref(n), C.byref(cp), C.byref(nobj), C.byref(mp), C.byref(nmat),
+                                         C.byref(ip)))
+    mats = np.frombuffer(C.string_at(mp.value, nmat.value * MATERIAL_DTYPE.itemsize), dtype=MATERIAL_DTYPE).copy()
+    idx = np.frombuffer(C.string_at(ip.value, n.value * 2), dtype=np.uint16).copy()
+    lib.trx_free(mp)
+    lib.trx_free(ip)
+    verts, counts = _take_mesh(vp, n, cp, nobj)
+    return verts, counts, mats, idx
 
 
 def load_scene(path):
@@ -373,6 +409,24 @@ class Scene:
         L.check(self._lib.trx_scene_get_instance_masks(self._h, _ptr(out), out.size))
         return out
 
+    def set_materials(self, materials, tri_material):
+        """trx_scene_set_materials: the material table ([n] MATERIAL_DTYPE, or [n, 6] floats: albedo rgb, emission rgb) and
+        one uint16 index per triangle in `prim` order (the order of flat.tri_verts; a table in mesh order goes through
+        flat.tri_source).  Validated on the host; replaces an earlier table after the scene's launches in flight."""
+        m = np.ascontiguousarray(materials)
+        if m.dtype != MATERIAL_DTYPE:
+            m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 6)
+        idx = np.ascontiguousarray(tri_material, dtype=np.uint16).reshape(-1)
+        L.check(self._lib.trx_scene_set_materials(self._h, _ptr(m), m.shape[0], _ptr(idx), idx.size))
+
+    def get_materials(self):
+        """(materials [n] MATERIAL_DTYPE, tri_material [n_tris] uint16) as set; refused on a scene without materials."""
+        mats = np.zeros(L.MAX_MATERIALS, dtype=MATERIAL_DTYPE)
+        idx = np.zeros(self.flat.tri_verts.shape[0], dtype=np.uint16)
+        n = C.c_uint32(mats.size)
+        L.check(self._lib.trx_scene_get_materials(self._h, _ptr(mats), C.byref(n), _ptr(idx), idx.size))
+        return mats[:n.value].copy(), idx
+
     def refit(self, tri_verts):
         """New vertices for every triangle record, in record order ([n_tris, 9] f32; record_order_verts maps object-order
         vertices): trx_scene_refit for a numpy array, trx_scene_refit_dev on torch.cuda.current_stream() for a tensor on
@@ -624,6 +678,23 @@ class Scene:
                                                      depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_albedo,
                                                      bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, bounce_stride,
                                                      bounce_phase, bounce_upsample_radius, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
+    def render_image_colour(self, view, width, height, lights, bounce_samples=0, bounce_stride=1, bounce_phase=0, bounce_upsample_radius=1,
+                            bounce_filter_levels=0, bounce_depth_tol=0.1, bounce_normal_cos=0.9, bounce_eps=0.01, sem=L.SEM_HLSL, ray_mask=0,
+                            frame0=0, light_samples=1, shadow_eps=0.01, ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"),
+                            filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_colour - render_image_gi_sparse in colour on a scene with
+        materials: the lit chain up to the light term, the RGB indirect pass (trace_indirect_rgb_dev at bounce_stride 1,
+        trace_indirect_rgb_sparse_dev above it; none with bounce_samples 0), per plane the upsample (bounce_stride > 1) and
+        the value filter (bounce_filter_levels >= 1), material_compose_dev and shade_rgb_dev; only the image crosses the bus."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_colour(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0, light_samples,
+                                                  shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius, depth_tol, normal_cos,
+                                                  bounce_samples, bounce_eps, bounce_filter_levels, bounce_depth_tol, bounce_normal_cos,
+                                                  bounce_stride, bounce_phase, bounce_upsample_radius, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
@@ -880,6 +951,36 @@ class Scene:
         L.check(self._lib.trx_trace_indirect_sparse_dev(self._h, C.byref(view), width, height, stride, phase, sem, ray_mask, arr, len(arr),
                                                         frame0, n_samples, bounce_eps, shadow_eps, bounce_albedo, C.c_void_p(d_primary),
                                                         C.c_void_p(d_primary_inst), C.c_void_p(d_value_lo), C.c_void_p(stream)))
+
+    def trace_indirect_rgb_dev(self, view, width, height, lights, d_primary, d_value_rgb, n_samples=1, sem=L.SEM_HLSL, ray_mask=0, frame0=0,
+                               bounce_eps=0.01, shadow_eps=0.01, d_primary_inst=0, shard=(0, 1), stream=0):
+        """trx_trace_indirect_rgb_dev: trace_indirect_dev with the material of the triangle every bounce ray hits in
+        bounce_albedo's place - three planes of floats at d_value_rgb (plane c at c * records, records as for
+        trace_light_visibility_dev's planes): per sample albedo * s + emission summed, over n_samples; +0 without a surface."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_rgb_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask, arr, len(arr),
+                                                     frame0, n_samples, bounce_eps, shadow_eps, C.c_void_p(d_primary),
+                                                     C.c_void_p(d_primary_inst), C.c_void_p(d_value_rgb), C.c_void_p(stream)))
+
+    def trace_indirect_rgb_sparse_dev(self, view, width, height, stride, phase, lights, d_primary, d_value_rgb_lo, n_samples=1,
+                                      sem=L.SEM_HLSL, ray_mask=0, frame0=0, bounce_eps=0.01, shadow_eps=0.01, d_primary_inst=0, stream=0):
+        """trx_trace_indirect_rgb_sparse_dev: trace_indirect_sparse_dev's grid in colour - three low planes at d_value_rgb_lo
+        (plane c at c * Wlo * Hlo), every cell its full-resolution pixel's value of trace_indirect_rgb_dev."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_rgb_sparse_dev(self._h, C.byref(view), width, height, stride, phase, sem, ray_mask, arr,
+                                                            len(arr), frame0, n_samples, bounce_eps, shadow_eps, C.c_void_p(d_primary),
+                                                            C.c_void_p(d_primary_inst), C.c_void_p(d_value_rgb_lo), C.c_void_p(stream)))
+
+    def material_compose_dev(self, d_primary, d_direct, n, d_colour_rgb, d_indirect_rgb=0, stream=0):
+        """trx_material_compose_dev: three planes of n floats at d_colour_rgb - emission + albedo * (direct + indirect_c) of the
+        primary record's material (indirect 0 without d_indirect_rgb, which may be d_colour_rgb); +0 where the record is no
+        surface record of the scene."""
+        L.check(self._lib.trx_material_compose_dev(self._h, C.c_void_p(d_primary), C.c_void_p(d_direct), C.c_void_p(d_indirect_rgb), n,
+                                                   C.c_void_p(d_colour_rgb), C.c_void_p(stream)))
+
+    def shade_rgb_dev(self, d_colour_rgb, n, d_rgba, stream=0):
+        """trx_shade_rgb_dev: three planes of n floats as RGBA8, every channel through shade_value_dev's code table."""
+        L.check(self._lib.trx_shade_rgb_dev(self._h, C.c_void_p(d_colour_rgb), n, C.c_void_p(d_rgba), C.c_void_p(stream)))
 
     def value_upsample_dev(self, width, height, stride, phase, d_primary, d_in_lo, d_out, radius, depth_tol=0.1, normal_cos=0.9, d_attr=0,
                            d_base=0, stream=0):
