@@ -1090,6 +1090,122 @@ int trx_load_model_materials(const char *path, float **out_verts, uint64_t *out_
                              uint32_t *out_n_objects, trx_material **out_materials, uint32_t *out_n_materials,
                              uint16_t **out_tri_material);
 
+/* ---- emitters: emissive triangles sampled as lights at primary and bounce hits ---------------------------------------------------
+ * Above, an emissive triangle lights the scene only when a cosine-distributed bounce ray happens to hit it.  This section
+ * samples the emitters directly (next-event estimation): a device-built table of the scene's emissive triangles, a pass that
+ * casts one shadow ray per sample toward a point on a selected emitter from every primary hit, and a mode of the RGB indirect
+ * pass that does the same from every bounce hit.  Purely additive: every call above computes what it computed.
+ *
+ * THE EMITTER TABLE.  An emitter is one (instance, triangle) pair whose material has any emission component > 0.  On a
+ * single-level scene the emitters are the emissive triangles in `prim` order (instance id 0xFFFFFFFF); on a two-level scene
+ * every TLAS primitive k, ascending, crossed with the emissive triangles reachable from its entry node (its BLAS), ascending
+ * by `prim`.  trx_scene_build_emitters needs materials, finds the pairs on the host and refuses with TRX_ERR_INVALID when there
+ * are none or more than TRX_MAX_EMITTERS; *out_n (may be NULL) receives the count.  The device then writes one 64-byte record
+ * per emitter from the scene's own 48-byte triangle records {v0, e1, e2, cross(e1, e2)}.  That record stores e1 = v0 - v1
+ * (and e2 = v2 - v0), so the emitter's first edge is E1 = -e1 (the sign flipped, nothing rounded) = v1 - v0 and E2 = e2:
+ * V0 + b1 * E1 + b2 * E2 with b1, b2 >= 0, b1 + b2 <= 1 lies in the triangle.  Where the scene has instance transforms, with
+ * m the instance's object-to-world matrix as trx_scene_set_instance_transforms took it (m[c * 4 + r]), a point p becomes
+ *   P_r = ((m[r] * p.x + m[4 + r] * p.y) + m[8 + r] * p.z) + m[12 + r]
+ * and an edge e becomes (m[r] * e.x + m[4 + r] * e.y) + m[8 + r] * e.z, r = 0, 1, 2: every operation rounded once in binary32,
+ * no contraction; without transforms the record's values are taken as they are.  NG = cross(E1, E2) of the world-space
+ * edges: NG.x = E1.y * E2.z - E1.z * E2.y and cyclic, two products and one subtraction, each rounded once.
+ *   record (16 floats): V0.x V0.y V0.z kinv | E1.x E1.y E1.z material | E2.x E2.y E2.z prim | NG.x NG.y NG.z instance
+ *   (material, prim, instance: the uint32 as the bit pattern of the float lane).
+ * The host reads the records back and builds the selection table in binary64, in index order, with Le = the emission of the
+ * record's material:  w_j = sqrt(NG.x^2 + NG.y^2 + NG.z^2) * (Le_r + Le_g + Le_b),  W = sum of w_j,
+ *   p_j = 0.5 * w_j / W + 0.5 / n   (p_j = 1 / n when W == 0),
+ *   P_j = (float)p_j,  kinv_j = (float)(1.0 / (3.14159265358979323846 * (double)P_j)),
+ *   c_i = (float)(p_0 + ... + p_i) for i = 0 .. n - 2 (a dense array; none for n == 1).
+ * The defensive half keeps every p_j >= 0.5 / n: no weight can overflow, a zero-area emitter is harmless.
+ * SELECTION for u0 in [0, 1]: j = the number of i in 0 .. n - 2 with c_i <= u0.  The device finds it by bisection (at most 20
+ * steps); there is no clamp, no special case for u0 == 1.0f (which the hash does produce) and none for n == 1.
+ * Ownership is that of the material tables: counted by trx_scene_device_bytes (64 B per emitter and 4 B per c_i, at least one),
+ * released by trx_scene_destroy, replaced by a second build under the launch mutex after the scene's launches in flight.
+ * STALENESS.  The table holds world-space geometry and material indices: a later trx_scene_set_materials, trx_scene_refit*,
+ * trx_scene_set_instance_transforms or trx_scene_set_instance_entry_nodes marks it stale, and every emitter entry point then
+ * refuses with TRX_ERR_INVALID until trx_scene_build_emitters has run again (a flag on the host; no kernel of those calls changed).
+ * trx_scene_get_emitters: *inout_n holds the capacity of out_records in emitters on entry (out_c then has room for capacity - 1
+ * floats) and the table's size on return; refused without a table, with a stale one, or with too little room. */
+#define TRX_MAX_EMITTERS (1u << 20)
+int trx_scene_build_emitters(trx_scene *scene, uint32_t *out_n);
+int trx_scene_get_emitters(const trx_scene *scene, float *out_records, uint32_t *inout_n, float *out_c);
+
+/* THE EMITTER LIGHT PASS at primary hits.  For pixel (px, py) and sample f in 0 .. n_samples - 1 (n_samples in
+ * 1..TRX_MAX_AO_SAMPLES); every operation rounded once in binary32, no contraction; dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *  E1. Surface pixel, flipped unit normal n and origin o are THE SHADOW RAY's statements with shadow_eps - the caller-record
+ *      rule and the required d_primary_inst on a scene with instance transforms included.  Any other pixel gets the inert ray.
+ *  E2. se = frame0 + 2048u + f;  u0 = hash_noise(px, py, se), u1 = hash_noise(px, py, se + 1024u),
+ *      u2 = hash_noise(px, py, se + 4096u).  (AO and bounce rays use frame0 + f and + 1024; rect lights stay below frame0 + 1600.)
+ *  E3. j is selected by u0.  su = sqrtf(u1), b1 = su * (1.0f - u2), b2 = su * u2, y[i] = (V0[i] + b1 * E1[i]) + b2 * E2[i].
+ *  E4. v = y - o, q = dot3(v, v), dist = sqrtf(q), inv = 1.0f / dist, l = v * inv; tmin = 0, tmax = dist - dist * emitter_eps
+ *      (emitter_eps finite, in [0, 1): it stops the ray short of the emitter's own triangle); c = dot3(n, l),
+ *      a = 0.5f * fabsf(dot3(NG, l)) (emission is two-sided, as in rule 5c; cos x area needs no normalisation),
+ *      wgeo = ((c * a) / q) * kinv_j.  The ray is CAST iff c > 0.0f && wgeo > 0.0f && wgeo < +inf; otherwise the sample gets
+ *      the inert ray and contributes nothing (NaN, a light at the hit point, a zero-area or edge-on emitter).
+ *  E5. A_c = 0.0f; for f ascending, if the ray was cast and is NOT occluded (trx_trace_occluded_dev's answer, or
+ *      trx_trace_occluded_masked_dev's with ray_mask 1..255): A_c = A_c + wgeo_f * emission_c(material of emitter j_f).
+ *      out_c = base_c + A_c / (float)n_samples at a surface record, base_c elsewhere; base_c = d_base_rgb[c * records + r], +0.0f
+ *      with d_base_rgb == NULL.  d_base_rgb may be d_out_rgb: each lane reads before it writes.  A record outside the shard or
+ *      the image is untouched.  The order holds under any scratch cap.
+ * The 1 / pi inside kinv makes the pass estimate what rule 5c's "+ emission_c(m)" term estimates over cosine-distributed bounce
+ * rays: the mean of emission_c over the hemisphere, cosine-weighted.
+ * trx_emitter_rays_dev writes one sample's rays, one per record of `shard`, like trx_light_rays_dev (sample in
+ * 0..TRX_MAX_AO_SAMPLES - 1).  trx_trace_emitter_light_dev is the pass: three planes at c * records by
+ * trx_trace_light_visibility_dev's plane rule; its mechanics too - the stream's launch slot, [tile][sample][64] scratch under
+ * the same cap, no host synchronisation.  Refused with TRX_ERR_INVALID before anything is enqueued (the output left as it
+ * was): a null scene, d_primary or output, n_samples or sample out of range, unknown semantics bits, ray_mask > 255, a
+ * negative or NaN shadow_eps, an emitter_eps outside [0, 1), a missing d_primary_inst on a transformed scene, a scene without
+ * an emitter table or with a stale one. */
+int trx_emitter_rays_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                         uint32_t frame0, uint32_t sample, float shadow_eps, float emitter_eps, const trx_hit *d_primary,
+                         const uint32_t *d_primary_inst, trx_ray *d_rays, void *stream);
+int trx_trace_emitter_light_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                                uint32_t semantics, uint32_t ray_mask, uint32_t frame0, uint32_t n_samples, float shadow_eps,
+                                float emitter_eps, const trx_hit *d_primary, const uint32_t *d_primary_inst,
+                                const float *d_base_rgb, float *d_out_rgb, void *stream);
+
+/* EMITTERS AT BOUNCE HITS.  trx_trace_indirect_rgb_dev with one more argument, emitter_eps; n_lights may be 0 (lights may
+ * then be NULL).  Rules 1 to 4 are unchanged - bounce ray, bounce hit, the lights' shadow rays and s_f are bit for bit the
+ * existing pass's; with 0 lights s_f = +0.0f.  For every bounce with a surface, rules E2 to E4 then apply with the primary hit
+ * replaced by the bounce hit: d is the bounce ray's direction, n the flipped attr.normal of rule 3, o[i] = Q[i] - d[i] *
+ * shadow_eps, the seed se = frame0 + 8192u + f hashed at the pixel of the full-resolution image (as the rect noise is); the
+ * any-hit launch is masked when ray_mask != 0.  In rule 5c's place:
+ *  5e. For f ascending, where bounce f has a surface: m = tri_material[bounce_hit_f.prim], X_c = wgeo_f * emission_c(emitter
+ *      j_f) if that ray was cast and is not occluded, else +0.0f, and A_c = A_c + albedo_c(m) * (s_f + X_c) - the inner
+ *      addition, then the product, then the outer addition.  There is no "+ emission_c(m)" term: light that reaches the
+ *      primary hit straight from an emitter belongs to trx_trace_emitter_light_dev, and counting it here too would count it
+ *      twice.  out_c = A_c / (float)n_samples.
+ * The sparse form is trx_trace_indirect_rgb_sparse_dev's statement: each cell is bit for bit the dense value of its pixel.
+ * Refusals: everything trx_trace_indirect_rgb_dev refuses except n_lights == 0, and what the emitter pass refuses of
+ * emitter_eps and the table. */
+int trx_trace_indirect_rgb_emitters_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                        trx_shard shard, uint32_t semantics, uint32_t ray_mask, const trx_light *lights,
+                                        uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps,
+                                        float shadow_eps, float emitter_eps, const trx_hit *d_primary,
+                                        const uint32_t *d_primary_inst, float *d_value_rgb, void *stream);
+int trx_trace_indirect_rgb_emitters_sparse_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                               uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t ray_mask,
+                                               const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                                               uint32_t n_samples, float bounce_eps, float shadow_eps, float emitter_eps,
+                                               const trx_hit *d_primary, const uint32_t *d_primary_inst,
+                                               float *d_value_rgb_lo, void *stream);
+
+/* trx_render_image_colour with the emitters sampled (synchronous): trx_render_image_colour's arguments plus emitter_samples
+ * (1..TRX_MAX_AO_SAMPLES) and emitter_eps; n_lights may be 0.  The chain: the lit chain up to V - with no lights V is the
+ * AO-scaled ambient alone, what trx_light_term_dev gives for one light of intensity 0; with bounce_samples >= 1 the
+ * emitter-mode indirect pass, dense or sparse, then upsample and filter per plane as in trx_render_image_colour; then
+ * trx_trace_emitter_light_dev at full resolution, dense and unfiltered (direct shadows stay sharp), with the filtered planes
+ * as both base and output (no base with bounce_samples == 0); then trx_material_compose_dev and trx_shade_rgb_dev.  It builds
+ * the emitter table first if the scene has none, or a stale one. */
+int trx_render_image_colour_emitters(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                     uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
+                                     uint32_t frame0, uint32_t light_samples, float shadow_eps, float ambient,
+                                     uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                                     float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t bounce_filter_levels,
+                                     float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride,
+                                     uint32_t bounce_phase, uint32_t bounce_upsample_radius, uint32_t emitter_samples,
+                                     float emitter_eps, uint8_t *out_rgba, float *out_ms);
+
 /* Counting variant (PROFILE_RT): same traversal, also accumulates trx_stats.
  * Synchronous; d_hits may be NULL.  trx_count_ao: d_primary may hold any bit pattern - a record that is no surface record
  * of this scene is a miss, no ray and nothing counted (CALLER RECORDS, above). */

@@ -133,6 +133,11 @@ typedef struct trx_schedule_state {
 int trx_debug_schedule_state(trx_scene *scene, void *stream, uint32_t kind, trx_schedule_state *out, uint32_t *out_order,
                              uint32_t max_tiles);
 
+/* Emitters (include/trx.h, "emitters"): the device's selection function over n caller-given u0 values (device memory), one
+ * uint32 j per value at d_j; on the null stream, synchronous.  It holds the search to the counting rule at every c_i itself,
+ * not only at the values the hash happens to reach.  Refused like every emitter entry point (no table, a stale one). */
+int trx_debug_emitter_select(trx_scene *scene, const float *d_u0, uint64_t n, uint32_t *d_j);
+
 /* Kernel variant selection (tuning aid; 0 = default).  Returns the previous
  * value.  Variants compute identical results. */
 uint32_t trx_set_kernel_variant(uint32_t variant);

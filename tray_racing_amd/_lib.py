@@ -38,6 +38,7 @@ MAX_VALUE_UPSAMPLE_RADIUS = 2
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_RECT = 0, 1, 2
 MAX_LIGHTS = 8
 MAX_MATERIALS = 65536
+MAX_EMITTERS = 1 << 20
 HEAT_NODES = 0
 HEAT_TRIS = 1
 HEAT_SCALE_NODES = 0.002
@@ -221,6 +222,17 @@ SIGNATURES = {
     "trx_standin_materials": (_i, [C.c_char_p, _P, _u64, _P, _u32, C.POINTER(_P), C.POINTER(_u32), C.POINTER(_P)]),
     "trx_load_model_materials": (_i, [C.c_char_p, C.POINTER(C.POINTER(_f)), C.POINTER(_u64), C.POINTER(C.POINTER(_u64)), C.POINTER(_u32),
                                       C.POINTER(_P), C.POINTER(_u32), C.POINTER(_P)]),
+    "trx_scene_build_emitters": (_i, [_P, C.POINTER(_u32)]),
+    "trx_scene_get_emitters": (_i, [_P, _P, C.POINTER(_u32), _P]),
+    "trx_emitter_rays_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _f, _f, _P, _P, _P, _P]),
+    "trx_trace_emitter_light_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _u32, _u32, _f, _f, _P, _P, _P, _P, _P]),
+    "trx_trace_indirect_rgb_emitters_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P,
+                                                 _P, _P]),
+    "trx_trace_indirect_rgb_emitters_sparse_dev": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f,
+                                                        _f, _P, _P, _P, _P]),
+    "trx_render_image_colour_emitters": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32,
+                                              _f, _f, _u32, _f, _u32, _f, _f, _u32, _u32, _u32, _u32, _f, _P, C.POINTER(_f)]),
+    "trx_debug_emitter_select": (_i, [_P, _P, _u64, _P]),
     "trx_debug_indirect_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P,
                                        C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),

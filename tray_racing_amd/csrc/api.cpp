@@ -296,6 +296,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     bytes += s->inst_mask.count(); // the instance mask table (trx_scene_set_instance_masks; swapped under mu)
     // the material table and the triangles' indices (trx_scene_set_materials; swapped under mu)
     bytes += s->materials.count() * sizeof(trx_material) + s->tri_material.count() * sizeof(uint16_t);
+    bytes += s->emitters.count() * sizeof(float4) + s->emitter_cdf.count() * sizeof(float); // the emitter table (trx_scene_build_emitters; swapped under mu)
     bytes += s->image_thr.count() * sizeof(float); // the shade's code thresholds (api_image.cpp)
     for (const Slot &sl : s->slots) {
         bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
@@ -303,6 +304,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
         // the indirect pass's scratch (api_ao.cpp)
         bytes += sl.gi_rays.count() * sizeof(trx_ray) + sl.gi_hits.count() * sizeof(trx_hit) + sl.gi_inst.count() * sizeof(uint32_t) +
                  sl.gi_attr.count() * sizeof(trx_hit_attr) + (sl.gi_sum.count() + sl.gi_acc.count()) * sizeof(float);
+        bytes += (sl.em_wgeo.count() + sl.em_acc.count()) * sizeof(float) + sl.em_pick.count() * sizeof(uint32_t); // the emitter passes' scratch
         bytes += sl.vf_plane.count() * sizeof(float); // the value filter's plane of an aliased base (api_image.cpp)
         for (const auto &o : sl.order) bytes += o.lists.count() * sizeof(uint32_t);
     }
@@ -378,6 +380,7 @@ int trx_scene_set_instance_entry_nodes(trx_scene *s, const uint32_t *entry_nodes
         s->inst_entry = std::move(fresh);
         s->h_inst_entry.swap(host_copy); // (no-throw: device and host copies change together)
         s->inst_entry_version++;
+        s->emitters_stale = true; // (an instance's triangles are those reachable from its entry node)
         forget_tile_orders(s);
     }
     HIP_TRY(retire(old, hipDeviceSynchronize()));
@@ -399,6 +402,7 @@ int trx_scene_set_instance_transforms(trx_scene *s, const float *object_to_world
             std::lock_guard<std::mutex> lock(s->mu);
             old = std::move(s->inst_xform);
             s->inst_xform = std::move(fresh);
+            s->emitters_stale = true; // (the emitter table holds world-space geometry)
             forget_tile_orders(s);
         }
         HIP_TRY(retire(old, hipDeviceSynchronize()));
@@ -535,6 +539,7 @@ int trx_scene_set_materials(trx_scene *s, const trx_material *materials, uint32_
         s->tri_material = std::move(fresh_idx);
         s->h_materials.swap(host_mat);
         s->h_tri_material.swap(host_idx);
+        s->emitters_stale = true; // (the emitter table was chosen by, and indexes, the old materials)
         if (old_mat)
             for (Slot &sl : s->slots)
                 if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());

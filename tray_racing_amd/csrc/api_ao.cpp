@@ -250,6 +250,111 @@ int light_visibility_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32
     return TRX_OK;
 }
 
+// ---- the emitter light pass at primary hits (include/trx.h, "emitters", rules E1-E5) --------------------------------------------
+
+void emitter_scene(EmitterParams &g, const trx_scene *s, const trx_hit *d_primary, const uint32_t *d_primary_inst) {
+    g.tris = s->tris.get();
+    g.inst_xform = s->tlas ? s->inst_xform.get() : nullptr;
+    g.primary = d_primary;
+    g.primary_inst = g.inst_xform ? d_primary_inst : nullptr;
+    g.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull); // (kernels.h, surface_record)
+    g.n_inst = s->n_inst;
+    g.emitters = s->emitters.get();
+    g.cdf = s->emitter_cdf.get();
+    g.n_emitters = s->n_emitters;
+}
+
+// light_visibility_impl's sibling with the emitter table for the light: its chunk loops and slot bookkeeping, k_emitter_rays
+// and k_emitter_gather_rgb around the rays launch; the running sums of a tile chunk sit in the slot's em_acc between its
+// sample chunks, and the gather of the last one writes the planes (base read first: it may be the output).
+int emitter_light_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
+                       uint32_t frame0, uint32_t n_samples, float shadow_eps, float emitter_eps, const trx_hit *d_primary,
+                       const uint32_t *d_primary_inst, const float *d_base, float *d_out, hipStream_t stream) {
+    if (!s || !d_primary || !d_out) return fail(TRX_ERR_INVALID, "null argument");
+    if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
+        return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
+    if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
+    if (int rc = check_eps(shadow_eps)) return rc;
+    if (int rc = check_emitter_eps(emitter_eps)) return rc;
+    AoRaysParams geom;
+    uint32_t tiles = 0;
+    if (int rc = ao_geometry(geom, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    const uint64_t records = geom.geom.compact ? (uint64_t)tiles * 64u : (uint64_t)w * h;
+    if (records > 0x7fffffffull) return fail(TRX_ERR_INVALID, "image %ux%u", w, h);
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = need_emitters(s)) return rc;
+    if (tiles == 0) return TRX_OK;
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, stream, slot)) return rc;
+    EmitterParams g;
+    std::memset(&g, 0, sizeof(g));
+    g.geom = geom.geom;
+    g.view = geom.view;
+    emitter_scene(g, s, d_primary, d_primary_inst);
+    g.materials = s->materials.get();
+    g.scratch = 1u;
+    g.shadow_eps = shadow_eps;
+    g.emitter_eps = emitter_eps;
+    g.n_total = n_samples;
+    g.base = d_base;
+    g.value = d_out;
+    g.plane = (uint32_t)records;
+    // chunks: as many tiles as the scratch holds, and for them as many samples as it holds (a unit of its own: kEmitterUnitBytes)
+    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / kEmitterUnitBytes, 1), 1ull << 24);
+    const uint32_t tile_chunk = (uint32_t)std::min<uint64_t>(tiles, units);
+    const uint32_t sample_chunk = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(units / tile_chunk, 1));
+    const uint64_t rays = (uint64_t)tile_chunk * sample_chunk * 64, pixels = (uint64_t)tile_chunk * 64 * 3;
+    if (slot->ao_rays.count() < rays || slot->em_wgeo.count() < rays || slot->em_pick.count() < rays || slot->em_acc.count() < pixels) {
+        // (the slot's previous kernel may still be walking the old scratch)
+        if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
+        if (slot->ao_rays.count() < rays) {
+            slot->ao_flags.reset();
+            HIP_TRY(slot->ao_rays.alloc(rays));
+            HIP_TRY(slot->ao_flags.alloc(rays));
+        }
+        HIP_TRY(slot->em_wgeo.grow(rays));
+        HIP_TRY(slot->em_pick.grow(rays));
+        HIP_TRY(slot->em_acc.grow(pixels));
+    }
+    g.rays = slot->ao_rays.get();
+    g.flags = slot->ao_flags.get();
+    g.wgeo = slot->em_wgeo.get();
+    g.pick = slot->em_pick.get();
+    g.acc = slot->em_acc.get();
+    for (uint32_t tile0 = 0; tile0 < tiles; tile0 += tile_chunk) {
+        for (uint32_t s0 = 0; s0 < n_samples; s0 += sample_chunk) {
+            g.tile0 = tile0;
+            g.n_tiles = std::min(tile_chunk, tiles - tile0);
+            g.n_samples = std::min(sample_chunk, n_samples - s0);
+            g.seed0 = frame0 + 2048u + s0;
+            g.first = s0 == 0 ? 1u : 0u;
+            g.last = s0 + g.n_samples == n_samples ? 1u : 0u;
+            HIP_TRY(launch_emitter_rays(g, stream));
+            // (from here on the slot is this stream's: the rays launch below finds it by its stream)
+            slot->last_stream = stream;
+            slot->last_use = ++s->launches;
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+            slot->used = true;
+            TraceParams p;
+            std::memset(&p, 0, sizeof(p));
+            p.rays = g.rays;
+            p.out = reinterpret_cast<trx_hit *>(slot->ao_flags.get());
+            p.any_hit = 1u;
+            p.ray_mask = ray_mask; // (0: the unmasked launch; enqueue_locked hands a masked one the scene's table)
+            p.n_items = g.n_tiles * g.n_samples * 64u;
+            SlotCounters *ctr = nullptr;
+            if (int rc = enqueue_locked(s, p, kModeRays, sem, false, stream, &ctr)) return rc;
+            if (ctr != slot->ctr.get()) return fail(TRX_ERR_INVALID, "internal: the rays launch left the pass's launch slot");
+            HIP_TRY(launch_emitter_gather(g, stream));
+            HIP_TRY(hipEventRecord(slot->done.get(), stream));
+        }
+    }
+    return TRX_OK;
+}
+
 // ---- one-bounce indirect light (include/trx.h, "indirect light") ----------------------------------------------------------------
 
 // hipEvents around the launches of the indirect pass (trx_debug_indirect_phases): every mark but a chunk's first ends an
@@ -286,17 +391,27 @@ int bounce_geometry(TileGeom &geom, uint32_t w, uint32_t h, trx_shard shard, uin
 // finish are k_bounce_gather_rgb and k_bounce_finish_rgb (BounceParams::materials), the running sums three per tile pixel,
 // d_value three planes; albedo and d_base are not looked at.  The tables are read under s->mu, where
 // trx_scene_set_materials swaps them, and every launch of the pass is recorded on the slot before the lock is released.
+//   emitters (trx_trace_indirect_rgb_emitters_dev / _sparse_dev, rule 5e; emitter_eps set): the colour mode with one more step
+// per chunk after the lights - k_bounce_emitter_rays, the any-hit rays launch with p.ray_mask - and
+// k_bounce_emitter_gather for the gather; wgeo and j of every ray sit in the slot's em_wgeo / em_pick, 8 bytes per ray
+// that this mode alone adds to its chunking unit; n_lights may be 0.  The other modes' launches and accounting are untouched.
 int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
                   const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps,
                   float albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base, float *d_value,
-                  hipStream_t stream, BouncePhases *phases, const SparseGrid *sparse = nullptr, bool colour = false) {
+                  hipStream_t stream, BouncePhases *phases, const SparseGrid *sparse = nullptr, bool colour = false,
+                  const float *emitter_eps = nullptr) {
     if (!s || !d_primary || !d_value) return fail(TRX_ERR_INVALID, "null argument");
     if (colour) { // (a table once set is only ever replaced: what holds here holds under the pass's lock below)
         std::lock_guard<std::mutex> lock(s->mu);
         if (!s->materials) return fail(TRX_ERR_INVALID, "the scene has no materials (trx_scene_set_materials)");
+        if (emitter_eps) if (int rc = need_emitters(s)) return rc; // (asked again under the pass's lock: a table can go stale)
     }
+    if (emitter_eps) if (int rc = check_emitter_eps(*emitter_eps)) return rc;
     if (sparse) if (int rc = check_sparse(sparse->stride, sparse->phase)) return rc;
-    if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
+    if (emitter_eps && n_lights == 0) { // (the emitter mode alone runs without a light: what check_lights asks of the samples)
+        if (n_samples == 0 || n_samples > TRX_MAX_AO_SAMPLES)
+            return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", n_samples, TRX_MAX_AO_SAMPLES);
+    } else if (int rc = check_lights(lights, n_lights, n_samples)) return rc;
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
     if (!(bounce_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "bounce_eps %g: must be >= 0", (double)bounce_eps);
@@ -323,12 +438,21 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->mu);
     Slot *slot = nullptr;
+    if (emitter_eps) if (int rc = need_emitters(s)) return rc;
     if (int rc = acquire_slot(s, stream, slot)) return rc;
-    // chunks: as many tiles as the scratch holds, and for them as many samples as it holds (a unit of its own: kBounceUnitBytes)
-    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / kBounceUnitBytes, 1), 1ull << 24);
+    // chunks: as many tiles as the scratch holds, and for them as many samples as it holds (a unit of its own: kBounceUnitBytes,
+    // in the emitter mode with the 8 bytes per ray of wgeo and j)
+    const uint64_t unit_bytes = emitter_eps ? kBounceUnitBytes + 64u * 8u : kBounceUnitBytes;
+    const uint64_t units = std::min<uint64_t>(std::max<uint64_t>(g_ao_scratch_cap.load(std::memory_order_relaxed) / unit_bytes, 1), 1ull << 24);
     const uint32_t tile_chunk = (uint32_t)std::min<uint64_t>(tiles, units);
     const uint32_t sample_chunk = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(units / tile_chunk, 1));
     const uint64_t rays = (uint64_t)tile_chunk * sample_chunk * 64, pixels = (uint64_t)tile_chunk * 64 * (colour ? 3 : 1);
+    if (emitter_eps && (slot->em_wgeo.count() < rays || slot->em_pick.count() < rays)) {
+        // (the slot's previous kernel may still be reading the old scratch)
+        if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
+        HIP_TRY(slot->em_wgeo.grow(rays));
+        HIP_TRY(slot->em_pick.grow(rays));
+    }
     if (slot->ao_rays.count() < rays || slot->gi_rays.count() < rays || slot->gi_acc.count() < pixels) {
         // (the slot's previous kernel may still be walking the old scratch)
         if (slot->used) HIP_TRY(hipEventSynchronize(slot->done.get()));
@@ -397,6 +521,15 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
         b.tri_material = s->tri_material.get();
         b.plane = (uint32_t)plane;
     }
+    if (emitter_eps) {
+        b.emitters = s->emitters.get();
+        b.cdf = s->emitter_cdf.get();
+        b.n_emitters = s->n_emitters;
+        b.wgeo = slot->em_wgeo.get();
+        b.pick = slot->em_pick.get();
+        b.has_lights = n_lights ? 1u : 0u;
+        b.emitter_eps = *emitter_eps;
+    }
     // one rays launch on the pass's slot (the slot is this stream's once the first kernel of the chunk is recorded)
     auto walk = [&](TraceParams &p) -> int {
         SlotCounters *ctr = nullptr;
@@ -451,6 +584,20 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
                 HIP_TRY(launch_bounce_weight(b, stream));
                 HIP_TRY(hipEventRecord(slot->done.get(), stream));
                 if (phases) if (int rc = phases->mark(stream, kPhWeightGather)) return rc;
+            }
+            if (emitter_eps) {
+                // rule 5e's step: the shadow rays from the bounce hits toward the emitters their noise selects, walked like a light's
+                b.seed0 = frame0 + 8192u + s0;
+                HIP_TRY(launch_bounce_emitter_rays(b, stream));
+                HIP_TRY(hipEventRecord(slot->done.get(), stream));
+                TraceParams p;
+                std::memset(&p, 0, sizeof(p));
+                p.rays = slot->ao_rays.get();
+                p.out = reinterpret_cast<trx_hit *>(slot->ao_flags.get());
+                p.any_hit = 1u;
+                p.ray_mask = ray_mask;
+                p.n_items = n_rays;
+                if (int rc = walk(p)) return rc;
             }
             b.first = s0 == 0 ? 1u : 0u;
             HIP_TRY(launch_bounce_gather(b, stream));
@@ -712,6 +859,69 @@ int trx_trace_indirect_rgb_sparse_dev(trx_scene *s, const trx_view *view, uint32
     const SparseGrid grid{stride, phase};
     return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
                          1.0f, d_primary, d_primary_inst, nullptr, d_value_rgb_lo, (hipStream_t)stream, nullptr, &grid, true);
+}
+
+// ---- emitters (include/trx.h, "emitters") ---------------------------------------------------------------------------------------
+
+int trx_emitter_rays_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t frame0, uint32_t sample,
+                         float shadow_eps, float emitter_eps, const trx_hit *d_primary, const uint32_t *d_primary_inst, trx_ray *d_rays,
+                         void *stream) {
+    if (!s || !d_primary || !d_rays) return fail(TRX_ERR_INVALID, "null argument");
+    if (sample >= TRX_MAX_AO_SAMPLES) return fail(TRX_ERR_INVALID, "sample %u outside 0..%d", sample, TRX_MAX_AO_SAMPLES - 1);
+    if (int rc = check_eps(shadow_eps)) return rc;
+    if (int rc = check_emitter_eps(emitter_eps)) return rc;
+    AoRaysParams geom;
+    uint32_t tiles = 0;
+    if (int rc = ao_geometry(geom, view, w, h, shard, tiles)) return rc;
+    if (int rc = need_inst(s, d_primary_inst)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = need_emitters(s)) return rc;
+    if (tiles == 0) return TRX_OK;
+    Slot *slot = nullptr;
+    if (int rc = acquire_slot(s, (hipStream_t)stream, slot)) return rc;
+    EmitterParams g;
+    std::memset(&g, 0, sizeof(g));
+    g.geom = geom.geom;
+    g.view = geom.view;
+    emitter_scene(g, s, d_primary, d_primary_inst);
+    g.rays = d_rays;
+    g.n_tiles = tiles;
+    g.n_samples = 1u;
+    g.seed0 = frame0 + 2048u + sample;
+    g.shadow_eps = shadow_eps;
+    g.emitter_eps = emitter_eps;
+    slot->last_stream = (hipStream_t)stream;
+    slot->last_use = ++s->launches;
+    HIP_TRY(launch_emitter_rays(g, (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(slot->done.get(), (hipStream_t)stream));
+    slot->used = true;
+    return TRX_OK;
+}
+
+int trx_trace_emitter_light_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem, uint32_t ray_mask,
+                                uint32_t frame0, uint32_t n_samples, float shadow_eps, float emitter_eps, const trx_hit *d_primary,
+                                const uint32_t *d_primary_inst, const float *d_base_rgb, float *d_out_rgb, void *stream) {
+    return emitter_light_impl(s, view, w, h, shard, sem, ray_mask, frame0, n_samples, shadow_eps, emitter_eps, d_primary, d_primary_inst,
+                              d_base_rgb, d_out_rgb, (hipStream_t)stream);
+}
+
+int trx_trace_indirect_rgb_emitters_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t sem,
+                                        uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
+                                        float bounce_eps, float shadow_eps, float emitter_eps, const trx_hit *d_primary,
+                                        const uint32_t *d_primary_inst, float *d_value_rgb, void *stream) {
+    return indirect_impl(s, view, w, h, shard, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps, 1.0f, d_primary,
+                         d_primary_inst, nullptr, d_value_rgb, (hipStream_t)stream, nullptr, nullptr, true, &emitter_eps);
+}
+
+int trx_trace_indirect_rgb_emitters_sparse_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t stride, uint32_t phase,
+                                               uint32_t sem, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                                               uint32_t n_samples, float bounce_eps, float shadow_eps, float emitter_eps,
+                                               const trx_hit *d_primary, const uint32_t *d_primary_inst, float *d_value_rgb_lo,
+                                               void *stream) {
+    const SparseGrid grid{stride, phase};
+    return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
+                         1.0f, d_primary, d_primary_inst, nullptr, d_value_rgb_lo, (hipStream_t)stream, nullptr, &grid, true, &emitter_eps);
 }
 
 // ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------

@@ -663,14 +663,25 @@ int trx_shade_rgb_dev(trx_scene *s, const float *d_colour_rgb, uint64_t n, uint8
     });
 }
 
-int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
-                            const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
-                            float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
-                            float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
-                            float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
-                            uint8_t *out_rgba, float *out_ms) {
+} // extern "C"
+
+// trx_render_image_colour (emitter_eps null) and trx_render_image_colour_emitters (include/trx.h, "emitters": emitter_eps set -
+// n_lights may be 0, the indirect pass runs in its emitter mode, and the emitter light pass adds to the planes the indirect
+// term ends in before the compose)
+static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                         const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                         float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                         float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
+                         float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
+                         uint32_t emitter_samples, const float *emitter_eps, uint8_t *out_rgba, float *out_ms) {
     // render_lit's refusals in its order, then the bounce's, the filter's and the upsample's where those steps run
-    if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
+    // (no light at all - the emitter form alone: V is what the light term gives for this one light of intensity 0)
+    const trx_light none{TRX_LIGHT_DIRECTIONAL, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f, {0u, 0u}};
+    const bool unlit = emitter_eps && n_lights == 0;
+    if (unlit) {
+        if (light_samples == 0 || light_samples > TRX_MAX_AO_SAMPLES)
+            return fail(TRX_ERR_INVALID, "n_samples %u outside 1..%d", light_samples, TRX_MAX_AO_SAMPLES);
+    } else if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
     if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
     if (!std::isfinite(ambient)) return fail(TRX_ERR_INVALID, "ambient %g is not finite", (double)ambient);
@@ -695,14 +706,27 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
         if (sparse)
             if (int rc = check_value_upsample(bounce_stride, bounce_phase, upsample_radius, bounce_depth_tol, bounce_normal_cos)) return rc;
     }
+    if (emitter_eps) {
+        if (emitter_samples == 0 || emitter_samples > TRX_MAX_AO_SAMPLES)
+            return fail(TRX_ERR_INVALID, "emitter_samples %u outside 1..%d", emitter_samples, TRX_MAX_AO_SAMPLES);
+        if (int rc = check_emitter_eps(*emitter_eps)) return rc;
+    }
     if (int rc = need_materials(s)) return rc;
     const uint64_t n = (uint64_t)w * h;
     const trx_shard whole{0, 1, 0, 0};
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
     HIP_TRY(hipSetDevice(s->device));
+    if (emitter_eps) { // (no table yet, or a stale one: built here; every call that stales it holds host_mu)
+        bool build;
+        {
+            std::lock_guard<std::mutex> lock(s->mu);
+            build = s->n_emitters == 0 || s->emitters_stale;
+        }
+        if (build) if (int rc = trx_scene_build_emitters(s, nullptr)) return rc;
+    }
     // the image scratch: the AO filter's terms, the image, the light term's values, two sets of three planes (the indirect
     // term's steps alternate between them: a low grid holds at most n cells), the value filter's work plane, the lights' planes
-    HIP_TRY(s->scratch_img.grow(n * 4 * 10 + n * n_lights));
+    HIP_TRY(s->scratch_img.grow(n * 4 * 10 + n * (unlit ? 1u : n_lights)));
     auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
     auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
     auto d_value = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 8); };
@@ -718,8 +742,9 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
             if (rc) return rc;
             rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
             if (rc) return rc;
-            rc = trx_trace_light_visibility_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps,
-                                                s->scratch_a.get(), s->scratch_ia.get(), d_lit(), nullptr);
+            if (unlit) HIP_TRY(hipMemsetAsync(d_lit(), 0, n, nullptr)); // (a light of intensity 0 adds +0 whatever its plane counts)
+            else rc = trx_trace_light_visibility_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps,
+                                                     s->scratch_a.get(), s->scratch_ia.get(), d_lit(), nullptr);
             if (rc) return rc;
             if (ao_samples != 0) {
                 rc = trx_trace_ao_visibility_dev(s, view, w, h, whole, sem, frame0, ao_samples, ao_eps, ao_radius, s->scratch_a.get(),
@@ -729,17 +754,20 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
                                        normal_cos, d_term(), nullptr);
                 if (rc) return rc;
             }
-            rc = trx_light_term_dev(s, view, w, h, whole, lights, n_lights, light_samples, s->scratch_a.get(), s->scratch_attr.get(),
-                                    d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
+            rc = trx_light_term_dev(s, view, w, h, whole, unlit ? &none : lights, unlit ? 1u : n_lights, light_samples, s->scratch_a.get(),
+                                    s->scratch_attr.get(), d_lit(), ao_samples != 0 ? d_term() : nullptr, ambient, d_value(), nullptr);
             if (rc) return rc;
             float *planes = nullptr; // the indirect term's three full-resolution planes, or none
             if (bounce_samples != 0) {
                 float *other = d_b();
                 planes = d_a();
                 if (sparse) {
-                    rc = trx_trace_indirect_rgb_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights, n_lights, frame0,
-                                                           bounce_samples, bounce_eps, shadow_eps, s->scratch_a.get(), s->scratch_ia.get(),
-                                                           planes, nullptr);
+                    rc = emitter_eps ? trx_trace_indirect_rgb_emitters_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights,
+                                                                                  n_lights, frame0, bounce_samples, bounce_eps, shadow_eps,
+                                                                                  *emitter_eps, s->scratch_a.get(), s->scratch_ia.get(), planes, nullptr)
+                                     : trx_trace_indirect_rgb_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights, n_lights,
+                                                                         frame0, bounce_samples, bounce_eps, shadow_eps, s->scratch_a.get(),
+                                                                         s->scratch_ia.get(), planes, nullptr);
                     if (rc) return rc;
                     const uint64_t n_lo = (uint64_t)((w + bounce_stride - 1u) / bounce_stride) * ((h + bounce_stride - 1u) / bounce_stride);
                     for (uint64_t c = 0; c < 3; c++) {
@@ -750,8 +778,11 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
                     }
                     std::swap(planes, other);
                 } else {
-                    rc = trx_trace_indirect_rgb_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples, bounce_eps,
-                                                    shadow_eps, s->scratch_a.get(), s->scratch_ia.get(), planes, nullptr);
+                    rc = emitter_eps ? trx_trace_indirect_rgb_emitters_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples,
+                                                                           bounce_eps, shadow_eps, *emitter_eps, s->scratch_a.get(),
+                                                                           s->scratch_ia.get(), planes, nullptr)
+                                     : trx_trace_indirect_rgb_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples,
+                                                                  bounce_eps, shadow_eps, s->scratch_a.get(), s->scratch_ia.get(), planes, nullptr);
                     if (rc) return rc;
                 }
                 if (filter) {
@@ -765,6 +796,12 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
             }
             // (the colour lands in the planes the indirect term ends in - the compose may run in place - or in the first set)
             float *colour = planes ? planes : d_a();
+            if (emitter_eps) { // the emitter light pass at full resolution, unfiltered: the planes so far its base and its output
+                rc = trx_trace_emitter_light_dev(s, view, w, h, whole, sem, ray_mask, frame0, emitter_samples, shadow_eps, *emitter_eps,
+                                                 s->scratch_a.get(), s->scratch_ia.get(), planes, colour, nullptr);
+                if (rc) return rc;
+                planes = colour;
+            }
             rc = trx_material_compose_dev(s, s->scratch_a.get(), d_value(), planes, n, colour, nullptr);
             if (rc) return rc;
             return trx_shade_rgb_dev(s, colour, n, d_rgba(), nullptr);
@@ -773,6 +810,31 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
             if (out_rgba) HIP_TRY(hipMemcpy(out_rgba, d_rgba(), n * 4, hipMemcpyDeviceToHost));
             return TRX_OK;
         });
+}
+
+extern "C" {
+
+int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                            const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                            float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                            float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
+                            float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
+                            uint8_t *out_rgba, float *out_ms) {
+    return render_colour(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                         ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, filter_levels, bounce_depth_tol,
+                         bounce_normal_cos, bounce_stride, bounce_phase, upsample_radius, 0u, nullptr, out_rgba, out_ms);
+}
+
+int trx_render_image_colour_emitters(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                                     const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                                     float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius,
+                                     float depth_tol, float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels,
+                                     float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
+                                     uint32_t upsample_radius, uint32_t emitter_samples, float emitter_eps, uint8_t *out_rgba,
+                                     float *out_ms) {
+    return render_colour(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                         ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, filter_levels, bounce_depth_tol,
+                         bounce_normal_cos, bounce_stride, bounce_phase, upsample_radius, emitter_samples, &emitter_eps, out_rgba, out_ms);
 }
 
 } // extern "C"

@@ -13,6 +13,8 @@
 //   api_image.cpp    trx_ao_filter_dev / trx_ao_upsample_dev / trx_value_filter_dev / trx_value_upsample_dev / trx_shade_*_dev / trx_render_image* / trx_render_heat_image: the image passes after the walk (image.hip)
 //   materials        (include/trx.h, "materials") trx_scene_set_materials / _get_materials in api.cpp; trx_trace_indirect_rgb_dev / _rgb_sparse_dev: the indirect pass's colour mode in api_ao.cpp;
 //                    trx_material_compose_dev / trx_shade_rgb_dev / trx_render_image_colour in api_image.cpp; trx_standin_materials / trx_load_model_materials in api_build.cpp (the OBJ/MTL reading itself in scenes.cpp)
+//   emitters         (include/trx.h, "emitters") trx_scene_build_emitters / _get_emitters / trx_debug_emitter_select in api_emitters.cpp; trx_emitter_rays_dev / trx_trace_emitter_light_dev and the
+//                    indirect pass's emitter mode (trx_trace_indirect_rgb_emitters_dev / _sparse_dev) in api_ao.cpp; trx_render_image_colour_emitters in api_image.cpp
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -82,6 +84,11 @@ struct Slot {
     DevBuf<uint32_t> gi_inst;
     DevBuf<trx_hit_attr> gi_attr;
     DevBuf<float> gi_sum, gi_acc;
+    // the emitter passes on this slot's stream (api_emitters.cpp; the indirect pass's emitter mode in api_ao.cpp): per
+    // (tile, sample, pixel) of a chunk the sample's geometric weight and its emitter; per pixel of the chunk's tiles the
+    // primary pass's three running sums
+    DevBuf<float> em_wgeo, em_acc;
+    DevBuf<uint32_t> em_pick;
     // trx_value_filter_dev on this slot's stream with d_base == d_out and three levels or more: the second intermediate plane,
     // which cannot sit in d_out then (api_image.cpp)
     DevBuf<float> vf_plane;
@@ -223,6 +230,14 @@ struct trx_scene {
     std::vector<uint16_t> h_tri_material;
     trxapi::DevBuf<trx_material> materials;
     trxapi::DevBuf<uint16_t> tri_material;
+    // emitters (trx_scene_build_emitters, api_emitters.cpp): the world-space records (four float4 each) and the n - 1
+    // cumulative selection probabilities, host copies and device tables, swapped together under mu; stale once the
+    // materials, the triangles or the instances changed under them (every emitter entry point then refuses)
+    std::vector<float> h_emitters, h_emitter_cdf;
+    trxapi::DevBuf<float4> emitters;
+    trxapi::DevBuf<float> emitter_cdf;
+    uint32_t n_emitters = 0;
+    bool emitters_stale = false;
     // the frame's image (api_image.cpp): the shade's 256 code thresholds on the scene's device (first shade; under mu), and
     // trx_render_image's scratch - the filter's terms, then the RGBA8 image (under host_mu)
     trxapi::DevBuf<float> image_thr;
@@ -264,6 +279,10 @@ int trace_rays_impl(trx_scene *s, const trx_ray *d_rays, uint64_t n, uint32_t se
 
 // what the direct-light entry points refuse of their lights and sample count (api_ao.cpp)
 int check_lights(const trx_light *lights, uint32_t n_lights, uint32_t n_samples);
+
+// what every emitter entry point refuses of the scene's emitter table (api_emitters.cpp; s->mu held) and of emitter_eps
+int need_emitters(const trx_scene *s);
+int check_emitter_eps(float emitter_eps);
 
 // ---- the synchronous host-buffer entry points (api_trace.cpp, api_attr.cpp) ----
 // ev0, what `run` enqueues on the null stream, ev1; waits for ev1 and puts the elapsed time into *ms (may be null)

@@ -249,6 +249,7 @@ int scene_refit(trx_scene *s, const float *d_verts, const float *h_verts, uint64
         if (hipMemcpyAsync(r.o2w.get(), s->inst_o2w.data(), (size_t)s->n_inst * 64, hipMemcpyHostToDevice, stream) != hipSuccess)
             return release(fail(TRX_ERR_NO_DEVICE, "refit: upload failed"));
     }
+    s->emitters_stale = true; // (the emitter table holds the old triangles in world space: a host flag, no launch changes)
     bool ok = refit_launch_tris(d_verts, n_tris, s->tris.get(), stream);
     RefitCtx ctx;
     ctx.nodes = s->nodes.get();

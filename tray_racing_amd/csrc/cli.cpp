@@ -78,6 +78,11 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // --colour: with --png --light the image is the colour image (trx_render_image_colour) - the scene gets a material table, the
     // mtl files' for -i <file.obj>, the stand-in table for standin:<name>, and every --bounce-*, --ao-* and --light option applies
     bool colour = false;
+    // --emitters N [--emitter-eps e]: with --png --colour the image is trx_render_image_colour_emitters' - the scene's emissive
+    // triangles sampled as lights, N shadow rays per pixel toward them (and one per bounce ray), each stopped e of its length
+    // short of the emitter; --light becomes optional
+    int emitters = -1;
+    float emitter_eps = -1.0f;
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -133,6 +138,9 @@ void usage() {
               "  [--colour] (with --png --light: the colour image - per-triangle albedo and emission from the mtl files of\n"
               "   -i <file.obj> or the stand-in table of standin:<name>; the bounce carries the colour of what it hit; not together\n"
               "   with --bounce-albedo)\n"
+              "  [--emitters 1..64] [--emitter-eps e] (with --png --colour: the emissive triangles sampled as lights - N shadow rays per\n"
+              "   pixel and one per bounce ray toward points on them, each stopped e (default 0.001) of its length short of the\n"
+              "   emitter; --light becomes optional)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -282,6 +290,12 @@ Options parse_args(int argc, char **argv) {
         }
         else if (a == "--colour") {
             o.colour = true;
+        } else if (a == "--emitters") {
+            o.emitters = std::atoi(need(i));
+            if (o.emitters < 1 || o.emitters > TRX_MAX_AO_SAMPLES) die("--emitters takes 1.." + std::to_string(TRX_MAX_AO_SAMPLES));
+        } else if (a == "--emitter-eps") {
+            o.emitter_eps = (float)std::atof(need(i));
+            if (!(o.emitter_eps >= 0.0f && o.emitter_eps < 1.0f)) die("--emitter-eps takes a number in [0, 1)");
         }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
@@ -329,19 +343,23 @@ Options parse_args(int argc, char **argv) {
     if (o.ao_stride >= 0 && o.ao_phase >= o.ao_stride * o.ao_stride) die("--ao-phase takes 0..S*S-1 of --ao-stride S");
     if (o.profile_rt >= 0 && (o.ao_samples != 0 || o.ao_filter >= 0)) die("--profile-rt draws the heat map: not together with --ao-samples or --ao-filter");
     if (o.profile_rt < 0 && o.profile_rt_scale >= 0.0f) die("--profile-rt-scale scales the heat map of --profile-rt nodes|tris");
-    if (o.lights.empty() && (o.light_samples >= 0 || o.light_mask >= 0 || o.shadow_eps >= 0.0f || o.ambient >= 0.0f))
+    if (o.emitters < 0 && o.emitter_eps >= 0.0f) die("--emitter-eps goes with --emitters N");
+    if (o.emitters >= 0 && !o.colour) die("--emitters samples the emissive materials of --colour");
+    if (o.emitters >= 0 && !o.png) die("--emitters lights the image of --png");
+    if (o.emitters >= 0 && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--emitters draws the colour image: not together with --ao-stride or --profile-rt");
+    if (o.lights.empty() && o.emitters < 0 && (o.light_samples >= 0 || o.light_mask >= 0 || o.shadow_eps >= 0.0f || o.ambient >= 0.0f))
         die("--light-samples, --light-mask, --shadow-eps and --ambient go with --light");
     if (!o.lights.empty() && !o.png) die("--light lights the image of --png");
     if (!o.lights.empty() && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--light draws the direct-light image: not together with --ao-stride or --profile-rt");
     if (o.bounce_samples < 0 && (o.bounce_albedo >= 0.0f || o.bounce_eps >= 0.0f)) die("--bounce-albedo and --bounce-eps go with --bounce-samples N");
     if (o.bounce_samples >= 0 && (o.ao_stride >= 0 || o.profile_rt >= 0)) die("--bounce-samples draws the GI image: not together with --ao-stride or --profile-rt");
-    if (o.bounce_samples >= 0 && o.lights.empty()) die("--bounce-samples bounces the light of --light");
+    if (o.bounce_samples >= 0 && o.lights.empty() && o.emitters < 0) die("--bounce-samples bounces the light of --light");
     if (o.bounce_stride < 0 && (o.bounce_phase >= 0 || o.bounce_upsample >= 0)) die("--bounce-phase and --bounce-upsample go with --bounce-stride S");
     if (o.bounce_stride >= 0 && o.bounce_samples < 0) die("--bounce-stride thins the rays of --bounce-samples N");
     if (o.bounce_stride >= 0 && o.bounce_phase >= o.bounce_stride * o.bounce_stride) die("--bounce-phase takes 0..S*S-1 of --bounce-stride S");
     if (o.bounce_filter < 0 && o.bounce_stride < 0 && o.bounce_filter_opts) die("--bounce-filter-tol and --bounce-filter-cos go with --bounce-filter L");
     if (o.bounce_filter >= 0 && o.bounce_samples < 0) die("--bounce-filter filters the term of --bounce-samples N");
-    if (o.colour && o.lights.empty()) die("--colour colours the image of --light");
+    if (o.colour && o.lights.empty() && o.emitters < 0) die("--colour colours the image of --light");
     if (o.colour && o.bounce_albedo >= 0.0f) die("--colour takes the albedo of the materials: not together with --bounce-albedo");
     if (o.passes == 0) o.passes = 1;
     return o;
@@ -406,12 +424,25 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
                         (double)st.n_node / (double)std::max<uint64_t>(st.n_rays, 1), (double)st.n_tri / (double)std::max<uint64_t>(st.n_rays, 1));
         return;
     }
-    if (!o.lights.empty()) {
+    if (!o.lights.empty() || o.emitters >= 0) {
         // the direct-light image, made on the device: shadow rays, the light term, the value shade; 4 bytes per pixel back
         const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
         const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
-        if (o.colour)
+        if (o.colour && o.emitters >= 0)
+            // the colour image with the emissive triangles sampled as lights; there may be no --light at all
+            check(trx_render_image_colour_emitters(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                                   o.lights.empty() ? nullptr : o.lights.data(), (uint32_t)o.lights.size(), frame_count,
+                                                   o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u, o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f,
+                                                   o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f, radius,
+                                                   o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
+                                                   o.bounce_samples >= 0 ? (uint32_t)o.bounce_samples : 0u, o.bounce_eps >= 0.0f ? o.bounce_eps : 0.01f,
+                                                   o.bounce_filter >= 0 ? (uint32_t)o.bounce_filter : 0u, o.bounce_filter_tol, o.bounce_filter_cos,
+                                                   o.bounce_stride >= 0 ? (uint32_t)o.bounce_stride : 1u, o.bounce_phase >= 0 ? (uint32_t)o.bounce_phase : 0u,
+                                                   o.bounce_upsample >= 0 ? (uint32_t)o.bounce_upsample : 1u, (uint32_t)o.emitters,
+                                                   o.emitter_eps >= 0.0f ? o.emitter_eps : 0.001f, rgba.data(), &ms),
+                  "png frame");
+        else if (o.colour)
             // the colour image: the same chain, the bounce's term in three planes, composed with the scene's materials
             check(trx_render_image_colour(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                           o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,

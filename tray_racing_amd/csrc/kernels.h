@@ -355,11 +355,88 @@ struct BounceParams {
     const trx_material *materials; // the scene's table, or null: the grey kernels
     const uint16_t *tri_material;  // n_tris indices into it, every one validated on upload
     uint32_t plane;                // floats per plane of value
+    // emitters (trx_trace_indirect_rgb_emitters_dev / _sparse_dev; include/trx.h, rule 5e; last once more: the fields above
+    // keep their offsets): with `emitters` set launch_bounce_emitter_rays runs k_bounce_emitter_rays after the chunk's lights
+    // and launch_bounce_gather runs k_bounce_emitter_gather in k_bounce_gather_rgb's place.
+    //   k_bounce_emitter_rays         one lane per (tile, sample, pixel): rules E2-E4 at the bounce hit (seed0 = frame0 + 8192 +
+    //                                 the chunk's first sample) - the shadow ray at rays[index], wgeo (+0 where no ray was
+    //                                 cast) at wgeo[index], the emitter at pick[index].
+    //   k_bounce_emitter_gather  k_bounce_gather_rgb with rule 5e for 5c: s is sum[index] (+0 with has_lights == 0: no
+    //                                 weight kernel wrote it), X_c = wgeo * emission_c(emitter) where wgeo > 0 and flags == 0.
+    const float4 *emitters;        // the scene's emitter table (EmitterParams), or null: every other mode
+    const float *cdf;
+    float *wgeo;
+    uint32_t *pick;
+    uint32_t n_emitters, has_lights;
+    float emitter_eps;
 };
+hipError_t launch_bounce_emitter_rays(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_weight(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_finish(const BounceParams &p, hipStream_t stream);
+
+// Emissive triangles as sampled lights (include/trx.h, "emitters").  The emitter table: four float4 per emitter, world space -
+//   [0] V0.xyz, kinv    [1] E1.xyz, material index    [2] E2.xyz, prim    [3] NG.xyz, instance id (0xFFFFFFFF: single level)
+// (the three indices as the bit patterns of the w lanes) - and the dense array c of n - 1 cumulative selection probabilities.
+//   k_emitter_build   one lane per emitter: the (instance, prim) pair's 48-byte scene record, through the instance's
+//                     object-to-world matrix (16 floats, column-major, as the refit takes them) where o2w is set; kinv is
+//                     written as +0 - the host fills it in once it has the areas.
+//   k_emitter_select  one lane per u0: emitter_select over caller-given values (trx_debug_emitter_select).
+struct EmitterBuildParams {
+    const float4 *tris;
+    const float *o2w;              // or null: no instance transforms
+    const uint2 *pairs;            // {instance id, prim} per emitter
+    const uint16_t *tri_material;
+    float4 *out;
+    uint32_t n, n_tris, n_inst;    // the extents of pairs, tris and o2w (a pair outside them writes a zero record)
+};
+hipError_t launch_emitter_build(const EmitterBuildParams &p, hipStream_t stream);
+struct EmitterSelectParams {
+    const float *cdf;
+    const float *u0;
+    uint32_t *j;
+    uint32_t n_emitters, n;
+};
+hipError_t launch_emitter_select(const EmitterSelectParams &p, hipStream_t stream);
+
+// The emitter light pass at primary hits (trx_emitter_rays_dev / trx_trace_emitter_light_dev): the light visibility pass's
+// shape with one "light", the table.  k_emitter_rays writes the shadow rays of rules E1-E4 - record layout or scratch layout
+// exactly as AoRaysParams describes them, one lane per (tile, sample, pixel) - and, in scratch layout, wgeo (+0 where no ray
+// was cast) and the selected emitter j beside them; the any-hit rays launch walks them; k_emitter_gather_rgb adds
+// wgeo * emission_c(emitter j) of the samples that were cast and not occluded to three running sums per tile pixel (acc,
+// plane c at c * n_tiles * 64; set for the first samples of the tiles), samples ascending, and with `last` writes
+// value[c * plane + record] = base + A_c / n_total (base where the primary record is no surface; base read before value is
+// written, by the same lane: they may be one buffer) instead of storing the sums.
+// scratch per (tile, sample): rays, flags, wgeo and j, and the tile's 3 x 64 running sums (counted per sample, as in kBounceUnitBytes)
+constexpr uint32_t kEmitterUnitBytes = kAoUnitBytes + 64u * (4u + 4u + 12u);
+struct EmitterParams {
+    const float4 *tris;
+    const float4 *inst_xform;     // world-to-object rows per instance, or null (no instance transforms)
+    const trx_hit *primary;
+    const uint32_t *primary_inst; // read only with inst_xform
+    trx_ray *rays;
+    const uint8_t *flags;         // k_emitter_gather_rgb: the occlusion flags of the scratch rays
+    const float4 *emitters;
+    const float *cdf;
+    const trx_material *materials;
+    float *wgeo;                  // scratch layout only (null in record layout)
+    uint32_t *pick;
+    float *acc;
+    const float *base;            // three planes like value, or null
+    float *value;
+    uint32_t tile0, n_tiles, n_samples, scratch;
+    uint32_t first, last;         // k_emitter_gather_rgb: the first / the last samples of these tiles
+    uint32_t n_total;             // the pass's n_samples
+    TileGeom geom;
+    uint32_t seed0;               // the seed of the chunk's first sample: frame0 + 2048 + sample
+    float shadow_eps, emitter_eps;
+    ViewDev view;
+    uint32_t n_emitters, plane;   // floats per plane of value and base
+    uint32_t n_tris, n_inst;      // the extents of tris and inst_xform: what a caller's record may index (surface_record)
+};
+hipError_t launch_emitter_rays(const EmitterParams &p, hipStream_t stream);
+hipError_t launch_emitter_gather(const EmitterParams &p, hipStream_t stream);
 
 // Resident waves the persistent kernel should be launched with on `device`.
 int trace_grid_size(int device, int mode, bool tlas, uint32_t sem, bool count);

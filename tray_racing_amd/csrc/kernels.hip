@@ -1383,6 +1383,282 @@ __global__ void __launch_bounds__(256) k_bounce_finish_rgb(const BounceParams P)
     P.value[2u * (size_t)P.plane + rec] = b;
 }
 
+// Emissive triangles as sampled lights (include/trx.h, "emitters"; kernels.h, EmitterBuildParams / EmitterParams).
+// One lane per emitter: the world-space record of the (instance, prim) pair from the scene's own triangle record - V0,
+// E1 = -e1 (the record stores v0 - v1), E2 = e2 - points and edges through the instance's object-to-world matrix in the
+// header's association, NG = cross(E1, E2) of the world-space edges.  kinv is the host's to fill in.  64 B written per lane.
+__global__ void __launch_bounds__(256) k_emitter_build(const EmitterBuildParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n) return;
+    const uint2 pr = P.pairs[i];
+    float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e1 = v0, e2 = v0, ng = v0;
+    if (pr.y < P.n_tris && (!P.o2w || pr.x < P.n_inst)) { // (the host formed every pair from the scene's own tables)
+        const float4 *tp = P.tris + (size_t)pr.y * 3;
+        const float4 a = tp[0], b = tp[1], c = tp[2];
+        float px = a.x, py = a.y, pz = a.z;
+        float ax = -b.x, ay = -b.y, az = -b.z;
+        float bx = c.x, by = c.y, bz = c.z;
+        if (P.o2w) {
+            const float *m = P.o2w + (size_t)pr.x * 16; // m[c * 4 + r]
+            const float wx = ((m[0] * px + m[4] * py) + m[8] * pz) + m[12];
+            const float wy = ((m[1] * px + m[5] * py) + m[9] * pz) + m[13];
+            const float wz = ((m[2] * px + m[6] * py) + m[10] * pz) + m[14];
+            px = wx; py = wy; pz = wz;
+            const float ux = (m[0] * ax + m[4] * ay) + m[8] * az;
+            const float uy = (m[1] * ax + m[5] * ay) + m[9] * az;
+            const float uz = (m[2] * ax + m[6] * ay) + m[10] * az;
+            ax = ux; ay = uy; az = uz;
+            const float tx = (m[0] * bx + m[4] * by) + m[8] * bz;
+            const float ty = (m[1] * bx + m[5] * by) + m[9] * bz;
+            const float tz = (m[2] * bx + m[6] * by) + m[10] * bz;
+            bx = tx; by = ty; bz = tz;
+        }
+        v0 = make_float4(px, py, pz, 0.0f);
+        e1 = make_float4(ax, ay, az, __uint_as_float((uint32_t)P.tri_material[pr.y]));
+        e2 = make_float4(bx, by, bz, __uint_as_float(pr.y));
+        ng = make_float4(ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx, __uint_as_float(pr.x));
+    }
+    float4 *out = P.out + (size_t)i * 4;
+    out[0] = v0;
+    out[1] = e1;
+    out[2] = e2;
+    out[3] = ng;
+}
+
+// Selection (include/trx.h): j = the number of i in 0 .. n - 2 with c[i] <= u0, found by bisection over the non-decreasing c
+// - at most 20 steps for TRX_MAX_EMITTERS, no step at all for one emitter; no clamp, no special value of u0 (a NaN reaches
+// no c[i]: emitter 0).  The result is below n whatever u0 is.
+__device__ __forceinline__ uint32_t emitter_select(const float *cdf, uint32_t n_emitters, float u0) {
+    uint32_t lo = 0u, hi = n_emitters - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (cdf[mid] <= u0) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) k_emitter_select(const EmitterSelectParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n) return;
+    P.j[i] = emitter_select(P.cdf, P.n_emitters, P.u0[i]);
+}
+
+// Rules E2 to E4 for one sample at the point o with the flipped normal n: the emitter, the point on it, the shadow ray (a, b:
+// left as they are - the inert ray - where no ray is cast) and the geometric weight; false (wgeo untouched) where the sample
+// contributes nothing.  One 64-byte gather into the table per lane, and the search.
+__device__ __forceinline__ bool emitter_sample(const float4 *emitters, const float *cdf, uint32_t n_emitters, uint32_t px, uint32_t py,
+                                               uint32_t se, float emitter_eps, float ox, float oy, float oz, float nx, float ny, float nz,
+                                               float4 &a, float4 &b, float &wgeo, uint32_t &j) {
+    const float u0 = hash_noise(px, py, se);
+    const float u1 = hash_noise(px, py, se + 1024u);
+    const float u2 = hash_noise(px, py, se + 4096u);
+    j = emitter_select(cdf, n_emitters, u0);
+    const float4 *ep = emitters + (size_t)j * 4;
+    const float4 V0 = ep[0], E1 = ep[1], E2 = ep[2], NG = ep[3];
+    const float su = sqrtf(u1);
+    const float b1 = su * (1.0f - u2);
+    const float b2 = su * u2;
+    const float yx = (V0.x + b1 * E1.x) + b2 * E2.x;
+    const float yy = (V0.y + b1 * E1.y) + b2 * E2.y;
+    const float yz = (V0.z + b1 * E1.z) + b2 * E2.z;
+    const float vx = yx - ox, vy = yy - oy, vz = yz - oz;
+    const float q = dot3(vx, vy, vz, vx, vy, vz);
+    const float dist = sqrtf(q);
+    const float inv = 1.0f / dist;
+    const float lx = vx * inv, ly = vy * inv, lz = vz * inv;
+    const float tmax = dist - dist * emitter_eps;
+    const float c = dot3(nx, ny, nz, lx, ly, lz);
+    const float ar = 0.5f * fabsf(dot3(NG.x, NG.y, NG.z, lx, ly, lz));
+    const float wg = ((c * ar) / q) * V0.w;
+    if (!(c > 0.0f && wg > 0.0f && wg < __builtin_inff())) return false; // (NaN fails: a light at the hit point, a zero-area or edge-on emitter)
+    a.x = ox; a.y = oy; a.z = oz;
+    b = make_float4(lx, ly, lz, tmax);
+    wgeo = wg;
+    return true;
+}
+
+// The shadow ray of every (tile, sample, pixel) toward the emitter its noise selects: k_light_rays up to the origin - the
+// addressing, the primary direction, the flipped normal, o with shadow_eps (rule E1 is THE SHADOW RAY's statement) - then
+// emitter_sample.  In scratch layout wgeo (+0 where the inert ray went) and j go beside the ray.  A streaming kernel like
+// k_light_rays, plus the 64-byte table gather and the search; 32 (+ 8) B written.
+__global__ void __launch_bounds__(256) k_emitter_rays(const EmitterParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * P.n_samples * 64u) return;
+    const uint32_t unit = item >> 6, k = item & 63u;
+    const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
+    uint32_t px, py, rec;
+    const bool inside = tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+    if (!inside && !P.scratch) return; // (the trace writes no record for it either)
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    float wgeo = 0.0f;
+    uint32_t j = 0u;
+    trx_hit ph;
+    ph.t = __builtin_inff();
+    ph.prim = TRX_INVALID;
+    if (inside) ph = P.primary[rec];
+    if (surface_record(ph, P.n_tris)) { // (kernels.h: a caller's record that fails it is a miss - the inert ray)
+        float dx, dy, dz;
+        primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
+        const float4 *tp = P.tris + (size_t)ph.prim * 3;
+        float nx = tp[0].w, ny = tp[1].w, nz = tp[2].w; // cross(e1, e2)
+        if (P.inst_xform) {
+            const uint32_t pi = P.primary_inst[rec];
+            if (instance_row(pi, P.n_inst)) {
+                const float4 *m = P.inst_xform + (size_t)pi * 3;
+                const float3 w = normal_to_world(m[0], m[1], m[2], nx, ny, nz);
+                nx = w.x; ny = w.y; nz = w.z;
+            }
+        }
+        const float ninv = 1.0f / sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+        nx *= ninv; ny *= ninv; nz *= ninv;
+        const float nd = (nx * -dx + ny * -dy) + nz * -dz;
+        const float sg = copysignf(1.0f, nd);
+        nx *= sg; ny *= sg; nz *= sg;
+        const float ox = (P.view.eye[0] + dx * ph.t) - dx * P.shadow_eps;
+        const float oy = (P.view.eye[1] + dy * ph.t) - dy * P.shadow_eps;
+        const float oz = (P.view.eye[2] + dz * ph.t) - dz * P.shadow_eps;
+        emitter_sample(P.emitters, P.cdf, P.n_emitters, px, py, P.seed0 + sample, P.emitter_eps, ox, oy, oz, nx, ny, nz, a, b, wgeo, j);
+    }
+    const uint32_t index = P.scratch ? item : rec;
+    float4 *out = reinterpret_cast<float4 *>(P.rays + index);
+    out[0] = a;
+    out[1] = b;
+    if (P.wgeo) {
+        P.wgeo[index] = wgeo;
+        P.pick[index] = j;
+    }
+}
+
+// One lane per pixel of the chunk's tiles (rule E5): three running sums (k_bounce_gather_rgb's layout of acc), samples
+// ascending - wgeo * emission_c of the emitter's material where the ray was cast (wgeo > 0) and is not occluded.  Per sample
+// the wave reads 64 consecutive floats, indices and flags; the emitter's material index and the 12 B of emission are gathers
+// into tables that stay in cache.  With `last` the sums are not stored: the lane writes the pass's value, base read first.
+__global__ void __launch_bounds__(256) k_emitter_gather_rgb(const EmitterParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lanes = P.n_tiles * 64u;
+    if (item >= lanes) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    const uint32_t from = lt * P.n_samples * 64u + k;
+    float Ar = 0.0f, Ag = 0.0f, Ab = 0.0f;
+    if (!P.first) {
+        Ar = P.acc[item];
+        Ag = P.acc[lanes + item];
+        Ab = P.acc[2u * lanes + item];
+    }
+    for (uint32_t s = 0; s < P.n_samples; s++) {
+        const uint32_t index = from + s * 64u;
+        const float wg = P.wgeo[index];
+        const uint32_t j = P.pick[index];
+        if (!(wg > 0.0f) || P.flags[index] != 0u || j >= P.n_emitters) continue;
+        const uint32_t m = __float_as_uint(P.emitters[(size_t)j * 4 + 1].w);
+        const trx_material *mp = P.materials + m;
+        Ar = Ar + wg * mp->emission[0];
+        Ag = Ag + wg * mp->emission[1];
+        Ab = Ab + wg * mp->emission[2];
+    }
+    if (!P.last) {
+        P.acc[item] = Ar;
+        P.acc[lanes + item] = Ag;
+        P.acc[2u * lanes + item] = Ab;
+        return;
+    }
+    uint32_t px, py, rec;
+    if (!tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec)) return;
+    if (rec >= P.plane) return; // (never: the launch checked the planes against the geometry)
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (P.base) {
+        r = P.base[rec];
+        g = P.base[(size_t)P.plane + rec];
+        b = P.base[2u * (size_t)P.plane + rec];
+    }
+    if (surface_record(P.primary[rec], P.n_tris)) {
+        const float n = (float)P.n_total;
+        r = r + Ar / n;
+        g = g + Ag / n;
+        b = b + Ab / n;
+    }
+    P.value[rec] = r;
+    P.value[(size_t)P.plane + rec] = g;
+    P.value[2u * (size_t)P.plane + rec] = b;
+}
+
+// Emitters at bounce hits (rule 5e): k_bounce_light_rays with the light replaced by emitter_sample at the bounce hit - its
+// addressing, its sparse instantiation (the noise at the cell's pixel of the full image), o = Q - d * shadow_eps, the
+// attribute normal flipped against d.  Scratch layout only: wgeo and j go beside the ray.
+template <int SPARSE>
+__global__ void __launch_bounds__(256) k_bounce_emitter_rays(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_tiles * P.n_samples * 64u) return;
+    const uint32_t unit = item >> 6, k = item & 63u;
+    const uint32_t lt = unit / P.n_samples, sample = unit - lt * P.n_samples;
+    uint32_t px, py, rec;
+    if constexpr (SPARSE) {
+        uint32_t cx, cy;
+        tile_pixel(P.lo, P.tile0 + lt, k, cx, cy, rec);
+        px = cx * P.stride + P.px0;
+        py = cy * P.stride + P.py0;
+    } else {
+        tile_pixel(P.geom, P.tile0 + lt, k, px, py, rec);
+    }
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    float wgeo = 0.0f;
+    uint32_t j = 0u;
+    BounceHit B;
+    if (bounce_hit(P, item, B)) { // (a lane outside the image reads the inert bounce ray k_ao_rays wrote there)
+        const float ox = B.qx - B.dx * P.shadow_eps;
+        const float oy = B.qy - B.dy * P.shadow_eps;
+        const float oz = B.qz - B.dz * P.shadow_eps;
+        emitter_sample(P.emitters, P.cdf, P.n_emitters, px, py, P.seed0 + sample, P.emitter_eps, ox, oy, oz, B.nx, B.ny, B.nz, a, b, wgeo, j);
+    }
+    float4 *out = reinterpret_cast<float4 *>(P.rays + item);
+    out[0] = a;
+    out[1] = b;
+    P.wgeo[item] = wgeo;
+    P.pick[item] = j;
+}
+
+// k_bounce_gather_rgb under rule 5e: A_c = A_c + albedo_c(m) * (s + X_c), X_c = wgeo * emission_c(emitter) where that ray was
+// cast and is not occluded (flags holds the emitter rays' answers: the lights' were consumed by k_bounce_weight), else +0;
+// the bounce triangle's own emission is not added.
+__global__ void __launch_bounds__(256) k_bounce_emitter_gather(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lanes = P.n_tiles * 64u;
+    if (item >= lanes) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    const uint32_t from = lt * P.n_samples * 64u + k;
+    float Ar = 0.0f, Ag = 0.0f, Ab = 0.0f;
+    if (!P.first) {
+        Ar = P.acc[item];
+        Ag = P.acc[lanes + item];
+        Ab = P.acc[2u * lanes + item];
+    }
+    for (uint32_t s = 0; s < P.n_samples; s++) {
+        const uint32_t index = from + s * 64u;
+        const float sf = P.has_lights ? P.sum[index] : 0.0f;
+        const float tmax = P.bounce_rays[index].tmax;
+        const trx_hit bh = P.bounce_hits[index];
+        if (tmax < 0.0f || !surface_record(bh, P.n_tris)) continue;
+        const float2 *mp = reinterpret_cast<const float2 *>(P.materials + P.tri_material[bh.prim]);
+        const float2 m0 = mp[0], m1 = mp[1]; // {albedo r, g}, {albedo b, emission r}
+        float Xr = 0.0f, Xg = 0.0f, Xb = 0.0f;
+        const float wg = P.wgeo[index];
+        const uint32_t j = P.pick[index];
+        if (wg > 0.0f && P.flags[index] == 0u && j < P.n_emitters) {
+            const trx_material *ep = P.materials + __float_as_uint(P.emitters[(size_t)j * 4 + 1].w);
+            Xr = wg * ep->emission[0];
+            Xg = wg * ep->emission[1];
+            Xb = wg * ep->emission[2];
+        }
+        Ar = Ar + m0.x * (sf + Xr);
+        Ag = Ag + m0.y * (sf + Xg);
+        Ab = Ab + m1.x * (sf + Xb);
+    }
+    P.acc[item] = Ar;
+    P.acc[lanes + item] = Ag;
+    P.acc[2u * lanes + item] = Ab;
+}
+
 } // namespace
 
 // (the sparse form of the bounce kernels exists for the scratch layout of a whole image only: what bounds their cell -> pixel
@@ -1391,6 +1667,64 @@ static bool bounce_sparse_ok(const BounceParams &p) {
     return p.scratch && p.stride <= TRX_MAX_AO_STRIDE && p.px0 < p.stride && p.py0 < p.stride && p.lo.shard_count == 1u && !p.lo.compact &&
            p.geom.shard_count == 1u && !p.geom.compact && p.lo.width == (p.geom.width + p.stride - 1u) / p.stride &&
            p.lo.height == (p.geom.height + p.stride - 1u) / p.stride;
+}
+
+// (the emitter mode of the bounce kernels: the table, its search array, a count the search cannot leave, and the scratch beside the rays)
+static bool bounce_emitters_ok(const BounceParams &p) {
+    return p.scratch && p.emitters && p.cdf && p.wgeo && p.pick && p.materials && p.n_emitters >= 1u && p.n_emitters <= TRX_MAX_EMITTERS;
+}
+
+hipError_t launch_bounce_emitter_rays(const BounceParams &p, hipStream_t stream) {
+    const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
+    if (n == 0) return hipSuccess;
+    if (n > 0xffffff00ull || !bounce_emitters_ok(p)) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((n + 255u) / 256u));
+    if (p.stride) {
+        if (!bounce_sparse_ok(p)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_bounce_emitter_rays<1>, grid, dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(k_bounce_emitter_rays<0>, grid, dim3(256), 0, stream, p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_emitter_build(const EmitterBuildParams &p, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    if (p.n > TRX_MAX_EMITTERS || !p.tris || !p.pairs || !p.tri_material || !p.out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_emitter_build, dim3((p.n + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_emitter_select(const EmitterSelectParams &p, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    if (p.n > 0xffffff00u || !p.cdf || !p.u0 || !p.j || p.n_emitters < 1u || p.n_emitters > TRX_MAX_EMITTERS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_emitter_select, dim3((p.n + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+static bool emitter_params_ok(const EmitterParams &p) {
+    return p.emitters && p.cdf && p.n_emitters >= 1u && p.n_emitters <= TRX_MAX_EMITTERS;
+}
+
+hipError_t launch_emitter_rays(const EmitterParams &p, hipStream_t stream) {
+    const uint64_t n = (uint64_t)p.n_tiles * p.n_samples * 64u;
+    if (n == 0) return hipSuccess;
+    if (n > 0xffffff00ull || !emitter_params_ok(p) || (!p.scratch && p.n_samples != 1u) || (p.wgeo && (!p.pick || !p.scratch))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_emitter_rays, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_emitter_gather(const EmitterParams &p, hipStream_t stream) {
+    if (p.n_tiles == 0) return hipSuccess;
+    if (p.n_tiles > 0x3ffffffu || !emitter_params_ok(p) || !p.materials || !p.wgeo || !p.pick || !p.acc || !p.scratch || p.n_total == 0u)
+        return hipErrorInvalidValue;
+    if (p.last) {
+        // (the three planes hold every record the kernel can form: k_emitter_gather_rgb writes nothing at or past `plane`)
+        const uint64_t need = p.geom.compact ? ((uint64_t)p.tile0 + p.n_tiles) * 64u : (uint64_t)p.geom.width * p.geom.height;
+        if (!p.value || p.plane < need) return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(k_emitter_gather_rgb, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream) {
@@ -1420,6 +1754,11 @@ hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream) {
     if (p.n_tiles > 0x3ffffffu) return hipErrorInvalidValue;
     if (p.materials) {
         if (!p.tri_material || !p.scratch) return hipErrorInvalidValue;
+        if (p.emitters) {
+            if (!bounce_emitters_ok(p)) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(k_bounce_emitter_gather, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL(k_bounce_gather_rgb, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
         return hipGetLastError();
     }

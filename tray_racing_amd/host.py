@@ -697,6 +697,26 @@ class Scene:
                                                   bounce_stride, bounce_phase, bounce_upsample_radius, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
+    def render_image_colour_emitters(self, view, width, height, lights=(), emitter_samples=4, emitter_eps=0.001, bounce_samples=0,
+                                     bounce_stride=1, bounce_phase=0, bounce_upsample_radius=1, bounce_filter_levels=0, bounce_depth_tol=0.1,
+                                     bounce_normal_cos=0.9, bounce_eps=0.01, sem=L.SEM_HLSL, ray_mask=0, frame0=0, light_samples=1,
+                                     shadow_eps=0.01, ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"), filter_radius=0,
+                                     depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_colour_emitters - render_image_colour with the scene's
+        emissive triangles sampled as lights: the indirect pass in its emitter mode, then trace_emitter_light_dev at full
+        resolution over the (filtered) planes, then compose and shade.  `lights` may be empty; the emitter table is built if
+        the scene has none or a stale one."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_colour_emitters(self._h, C.byref(view), width, height, sem, ray_mask, arr if len(arr) else None,
+                                                           len(arr), frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps, ao_radius,
+                                                           filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps,
+                                                           bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, bounce_stride,
+                                                           bounce_phase, bounce_upsample_radius, emitter_samples, emitter_eps, _ptr(rgba),
+                                                           C.byref(ms)))
+        return rgba, ms.value
+
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
         """(uint8 image [height, width, 4], Stats): trx_render_heat_image - the counted primary pass and the PROFILE_RT heat map
         of its per-ray counts (which: L.HEAT_NODES or L.HEAT_TRIS; scale None: the reference's, 0.002 / 0.01); only the image
@@ -970,6 +990,70 @@ class Scene:
         L.check(self._lib.trx_trace_indirect_rgb_sparse_dev(self._h, C.byref(view), width, height, stride, phase, sem, ray_mask, arr,
                                                             len(arr), frame0, n_samples, bounce_eps, shadow_eps, C.c_void_p(d_primary),
                                                             C.c_void_p(d_primary_inst), C.c_void_p(d_value_rgb_lo), C.c_void_p(stream)))
+
+    # emitters (include/trx.h, "emitters") ---------------------------------------------
+    def build_emitters(self):
+        """trx_scene_build_emitters: the table of the scene's emissive (instance, triangle) pairs, built on the device from
+        the scene's own triangle records; returns the number of emitters.  Needs materials; stale after set_materials, a
+        refit or an instance change, until it is built again."""
+        n = C.c_uint32()
+        L.check(self._lib.trx_scene_build_emitters(self._h, C.byref(n)))
+        return n.value
+
+    def get_emitters(self):
+        """(records [n, 16] float32 - V0 kinv | E1 material | E2 prim | NG instance, the three indices as bit patterns -,
+        c [n - 1] float32: the cumulative selection probabilities)."""
+        rec = np.zeros((L.MAX_EMITTERS, 16), dtype=np.float32)
+        c = np.zeros(L.MAX_EMITTERS, dtype=np.float32)
+        n = C.c_uint32(L.MAX_EMITTERS)
+        L.check(self._lib.trx_scene_get_emitters(self._h, _ptr(rec), C.byref(n), _ptr(c)))
+        return rec[:n.value].copy(), c[:n.value - 1].copy()
+
+    def debug_emitter_select(self, d_u0, n, d_j):
+        """trx_debug_emitter_select: the device's selection function over n float32 u0 values at d_u0, one uint32 j each at
+        d_j (synchronous)."""
+        L.check(self._lib.trx_debug_emitter_select(self._h, C.c_void_p(d_u0), n, C.c_void_p(d_j)))
+
+    def emitter_rays_dev(self, view, width, height, d_primary, d_rays, frame0=0, sample=0, shadow_eps=0.01, emitter_eps=0.001,
+                         d_primary_inst=0, shard=(0, 1), stream=0):
+        """trx_emitter_rays_dev: one sample's shadow rays toward the emitters its noise selects (seed frame0 + 2048 + sample),
+        one per record laid out like the hit buffers of `shard`; the inert ray where nothing is cast."""
+        L.check(self._lib.trx_emitter_rays_dev(self._h, C.byref(view), width, height, L.Shard(*shard), frame0, sample, shadow_eps,
+                                               emitter_eps, C.c_void_p(d_primary), C.c_void_p(d_primary_inst), C.c_void_p(d_rays),
+                                               C.c_void_p(stream)))
+
+    def trace_emitter_light_dev(self, view, width, height, d_primary, d_out_rgb, n_samples=1, sem=L.SEM_HLSL, ray_mask=0, frame0=0,
+                                shadow_eps=0.01, emitter_eps=0.001, d_primary_inst=0, d_base_rgb=0, shard=(0, 1), stream=0):
+        """trx_trace_emitter_light_dev: three planes of floats at d_out_rgb (plane c at c * records) - d_base_rgb's value (0
+        without one; it may be d_out_rgb) plus the mean over n_samples of wgeo * emission of the emitters whose shadow ray
+        was cast and not occluded."""
+        L.check(self._lib.trx_trace_emitter_light_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask, frame0,
+                                                      n_samples, shadow_eps, emitter_eps, C.c_void_p(d_primary),
+                                                      C.c_void_p(d_primary_inst), C.c_void_p(d_base_rgb), C.c_void_p(d_out_rgb),
+                                                      C.c_void_p(stream)))
+
+    def trace_indirect_rgb_emitters_dev(self, view, width, height, lights, d_primary, d_value_rgb, n_samples=1, sem=L.SEM_HLSL, ray_mask=0,
+                                        frame0=0, bounce_eps=0.01, shadow_eps=0.01, emitter_eps=0.001, d_primary_inst=0, shard=(0, 1),
+                                        stream=0):
+        """trx_trace_indirect_rgb_emitters_dev: trace_indirect_rgb_dev with the emitters sampled from every bounce hit (rule
+        5e) in place of the bounce triangle's own emission; `lights` may be empty."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_rgb_emitters_dev(self._h, C.byref(view), width, height, L.Shard(*shard), sem, ray_mask,
+                                                              arr if len(arr) else None, len(arr), frame0, n_samples, bounce_eps, shadow_eps,
+                                                              emitter_eps, C.c_void_p(d_primary), C.c_void_p(d_primary_inst),
+                                                              C.c_void_p(d_value_rgb), C.c_void_p(stream)))
+
+    def trace_indirect_rgb_emitters_sparse_dev(self, view, width, height, stride, phase, lights, d_primary, d_value_rgb_lo, n_samples=1,
+                                               sem=L.SEM_HLSL, ray_mask=0, frame0=0, bounce_eps=0.01, shadow_eps=0.01, emitter_eps=0.001,
+                                               d_primary_inst=0, stream=0):
+        """trx_trace_indirect_rgb_emitters_sparse_dev: trace_indirect_rgb_sparse_dev's grid, every cell its full-resolution
+        pixel's value of trace_indirect_rgb_emitters_dev."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_rgb_emitters_sparse_dev(self._h, C.byref(view), width, height, stride, phase, sem, ray_mask,
+                                                                     arr if len(arr) else None, len(arr), frame0, n_samples, bounce_eps,
+                                                                     shadow_eps, emitter_eps, C.c_void_p(d_primary),
+                                                                     C.c_void_p(d_primary_inst), C.c_void_p(d_value_rgb_lo),
+                                                                     C.c_void_p(stream)))
 
     def material_compose_dev(self, d_primary, d_direct, n, d_colour_rgb, d_indirect_rgb=0, stream=0):
         """trx_material_compose_dev: three planes of n floats at d_colour_rgb - emission + albedo * (direct + indirect_c) of the
