@@ -396,6 +396,36 @@ int trx_refit_nodes(const void *nodes, uint64_t n_nodes, const float *tri_verts,
  * tests/test_gpu_caller_records.py holds every pass above to this over ids at, just past and far past the tables' ends
  * (tests/test_caller_records.py: the oracle and the twins).
  *
+ * ---- SCENE SCALE: what a scene's size does to the passes after the trace ------------------------------------------
+ * Multiply a scene by 2^k about the camera's eye (the eye at the origin) and every length the caller passes by 2^k too -
+ * light positions and rect edges, shadow_eps, ao_eps, ao_radius, bounce_eps, a caller record's t.  That is the same
+ * computation with every exponent shifted, so as long as nothing under- or overflows every output is an EXACT IMAGE of
+ * the unit-scale one: barycentrics, normals, ray directions, cast decisions, wgeo, kinv, c, the selected emitters and the
+ * 8-bit counts and filtered terms are the same bits; ray origins, tmax (not FLT_MAX, not the inert ray's -1), t and an
+ * emitter record's V0, E1, E2 are multiplied by 2^k, its NG by 2^2k; the light term of point and rect lights by 2^-2k (a
+ * directional light's and the ambient part are unchanged).  tests/test_scale.py computes the table ("scene
+ * scale") on the twins; tests/test_gpu_scale.py holds the device to its own unit-scale output under it, and to the twins.
+ * On the Cornell stand-in (triangle edges 0.0032 .. 1.34) every output above is exact for k = -20 .. +30: edges of about
+ * 3e-9 .. 1.4e9.
+ *   THE NORMAL LEAVES FIRST.  u and v of a carried record stay exact far beyond that range (k = -50 .. +62 on both test scenes); the unit normal does
+ * not, because its intermediate dot(ng, ng), ng = cross(e1, e2), scales with the FOURTH power of the edge length: it is
+ * a denormal below about 1.2e-38 (|ng|, twice the triangle's area, below 1.1e-19: edges of a few 1e-10) and +inf above
+ * 3.4e38 (|ng| above 1.8e19: edges of a few 1e9).  On the stand-in the first normals lose bits at k = -26 (its smallest
+ * edges at 4.8e-11), every dot(ng, ng) is a denormal at k = -32, the first normals are non-finite at k = -35 and all of
+ * them from k = -38 on (1 / sqrtf(0) = +inf times ng: infinite and NaN components); upward the first normals are all-zero
+ * at k = +33 (1 / sqrtf(+inf) = 0) and all of them at k = +48, until ng itself overflows (k = +68: NaN again).  The
+ * arithmetic is the reference shader's and is not widened.  What the consumers then write, pinned by the same tests:
+ *   - an all-zero normal faces nothing: trx_light_rays_dev, trx_bounce_light_rays_dev and trx_emitter_rays_dev write the
+ *     inert ray, the light term keeps its ambient part alone, wgeo is +0, and no neighbour passes the filters' and
+ *     upsamples' normal test (0 >= normal_cos fails): a pixel's filtered term is its own.  trx_ao_rays_dev still casts, along
+ *     a finite direction;
+ *   - a normal with NaN components fails every comparison likewise - the inert ray, +0, no accepted neighbour - and the AO
+ *     ray's direction is NaN (such a ray hits nothing: "what the trace calls accept");
+ *   - a normal that is infinite without a NaN component can pass a facing test: an ordinary shadow ray is cast and a
+ *     directional light's term is +inf.  A caller who scales a scene that far has to expect +inf in the value plane.
+ *   A PRIMARY WALK FINDS NOTHING once the whole scene is nearer than the node test's 0.0001 clamp (above): the stand-in at
+ * k = -20 is all misses, while caller records carried to that scale are still served exactly.
+ *
  * ---- camera ---------------------------------------------------------------
  * ViewUniform::from_camera (src/main.rs:602-616): proj_inv =
  * inverse(perspective_infinite_reverse_rh(fov_deg->rad, w/h, 0.01)),
