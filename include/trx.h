@@ -323,6 +323,8 @@ int trx_trace_occluded_masked(trx_scene *scene, const trx_ray *rays, uint64_t n_
  *
  * Moving instances: trx_scene_set_instance_transforms, then a refit (with the unchanged vertices) - the TLAS boxes then
  * bound the moved instances.  A vertex refit of a two-level scene refits its TLAS too.
+ * Vertex normals (trx_scene_set_vertex_normals, below) are kept as they are: they are not recomputed from the new vertices, so a
+ * caller whose refit changed the shape of the mesh sets the normals again.
  * Refused with TRX_ERR_INVALID, the scene left unchanged: a count other than the scene's triangle count, a null pointer,
  * a non-finite coordinate, a scene created from TRX_TRI_F16_24.
  * Ordering: every launch enqueued on the scene before the call sees the old geometry in full, every launch enqueued
@@ -1301,6 +1303,100 @@ int trx_shade_heat_dev(trx_scene *scene, const trx_ray_cost *d_cost, uint64_t n_
  * trx_stats.  Every argument is validated before the first pass. */
 int trx_render_heat_image(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
                           uint32_t which, float scale, uint8_t *out_rgba, trx_stats *out_stats);
+
+/* ---- vertex normals and the shading normal: smooth normals for the light term and the edge-aware filters ---------------------------
+ * Every pass above shades with the geometric normal of the committed triangle (trx_hit_attr.normal), so a tessellated curved
+ * surface comes out faceted and its facet edges fail the filters' normal test in the middle of a smooth surface.  This section
+ * gives a scene a table of vertex normals keyed by trx_hit.prim and a pass that rewrites the normal of attribute records from
+ * it; trx_light_term_dev, trx_ao_filter_dev, trx_ao_upsample_dev, trx_value_filter_dev and trx_value_upsample_dev take the
+ * rewritten buffer as they take any attribute buffer.  Purely additive: every call above computes what it computed.  Ray
+ * origins, bounce directions and the facing of shadow rays stay geometric - every ray-generating pass derives its normal from
+ * the triangle itself - which is what keeps an offset origin on the lit side of its own triangle.
+ *
+ * THE TABLE.  normals holds nine floats per triangle: the object-space normals of vertices 0, 1 and 2 of triangle i of the
+ * buffer handed to trx_scene_create - `prim` order; a caller with a trx_flat applies tri_source, as for tri_material.  On a
+ * two-level scene the instances of a BLAS share its triangles' normals.  trx_scene_set_vertex_normals validates on the host
+ * before anything is copied and refuses with TRX_ERR_INVALID: n_tris different from the scene's, any component that is not
+ * finite.  Zero and unnormalised vectors are legal: the rule below handles them.  normals == NULL or n_tris == 0 removes the
+ * table.  On the device the table is three float4 per triangle (w = +0).  It is owned like the material table: counted by
+ * trx_scene_device_bytes at 48 B per triangle, released by trx_scene_destroy; a second call replaces it after waiting for the
+ * scene's launches in flight, which see the old table in full; a refused call leaves the old table in force.  A refit KEEPS
+ * the table as it is: a caller whose refit changed the shape of the mesh sets the normals again.
+ * trx_scene_get_vertex_normals returns the caller's floats bit for bit; refused on a scene without a table or with n_tris
+ * different from the scene's. */
+int trx_scene_set_vertex_normals(trx_scene *scene, const float *normals, uint64_t n_tris);
+int trx_scene_get_vertex_normals(const trx_scene *scene, float *out_normals, uint64_t n_tris);
+
+/* THE SHADING NORMAL of a record.  Every operation is rounded once in binary32, no contraction;
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  In: the record's hit (t, prim), its instance id on a scene with instance
+ * transforms, its trx_hit_attr A - u, v and the world unit geometric normal g = A.normal - and the world ray direction d:
+ * primary_dir of the pixel as given (the primary form), or the ray's direction words as stored (the rays form); no
+ * zero-direction fix is applied, as in the light term.
+ *  N1. A record with prim >= n_tris, or with an instance id >= n_instances on a scene with instance transforms, is out of
+ *      range: it reads no table and out = A bit for bit (CALLER RECORDS, above; t is not looked at, as in the attribute pass).
+ *  N2. Otherwise, with n0, n1, n2 the triangle's vertex normals: w = (1.0f - u) - v and, per component c,
+ *      m[c] = (w*n0[c] + u*n1[c]) + v*n2[c].  On a scene with instance transforms m goes to world space exactly as the
+ *      attribute pass takes the geometric normal there: with r0, r1, r2 the instance's world-to-object rows,
+ *      m' = ((r0.x*m.x + r1.x*m.y) + r2.x*m.z, (r0.y*m.x + r1.y*m.y) + r2.y*m.z, (r0.z*m.x + r1.z*m.y) + r2.z*m.z).
+ *  N3. q = dot3(m, m);  s = m * (1.0f / sqrtf(q)) (an IEEE square root, an IEEE division, three multiplications);
+ *      c = dot3(s, g);  s = s * copysignf(1.0f, c).
+ *  N4. a = (g.x*-d.x + g.y*-d.y) + g.z*-d.z and b = (s.x*-d.x + s.y*-d.y) + s.z*-d.z - the light term's argument of its flip.
+ *  N5. The record is ADOPTED iff q > 0.0f and q < +inf and c == c and ((a > 0.0f and b > 0.0f) or (a < 0.0f and b < 0.0f)).
+ *      An adopted record gets out = {A.u, A.v, s, _pad = 0}; any other record gets out = A bit for bit.
+ * What N5's last condition buys: the light term's flip copysignf(1, .) is the same for s as for g, so a smooth normal never
+ * lights the back of a silhouette triangle.  Zero, NaN-producing and overflowing vertex normals fall back to the geometric
+ * normal, and so does a record whose A carries a NaN.
+ * Layouts and untouched records are those of trx_hit_attributes_*_dev: the primary form takes d_hits / d_inst / d_attr /
+ * d_out laid out by `shard`; in image layout the records of pixels outside the shard are left untouched, and so are a compact
+ * tile's pixels outside the image.  d_out may be d_attr: each lane reads its record before it writes it.  The rays form
+ * reads the direction words of d_rays alone.  Refused with TRX_ERR_INVALID before anything is enqueued, the output left as it
+ * was: a scene without a vertex-normal table, a null buffer, a missing d_inst on a scene with instance transforms, everything
+ * the attribute calls refuse of image and shard.  The launches take a launch slot as the attribute pass does: a refit or a
+ * table swap called afterwards waits for the pass, which sees the old tables in full. */
+int trx_shading_normals_primary_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                                    const trx_hit *d_hits, const uint32_t *d_inst, const trx_hit_attr *d_attr,
+                                    trx_hit_attr *d_out, void *stream);
+int trx_shading_normals_rays_dev(trx_scene *scene, const trx_ray *d_rays, uint64_t n_rays, const trx_hit *d_hits,
+                                 const uint32_t *d_inst, const trx_hit_attr *d_attr, trx_hit_attr *d_out, void *stream);
+
+/* trx_render_image_lit and trx_render_image_colour with the shading-normal pass inserted right after the attribute pass
+ * (synchronous): the shading attributes take the attribute buffer's place in the light term and in every filter and upsample
+ * call; every ray-generating pass keeps its own geometric normals.  Arguments, validation and order are the plain forms';
+ * refused in addition on a scene without a vertex-normal table.  With an all-zero table every record falls back and the image
+ * is the plain form's byte for byte. */
+int trx_render_image_lit_smooth(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                                uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                                uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                                float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos, uint8_t *out_rgba,
+                                float *out_ms);
+int trx_render_image_colour_smooth(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height,
+                                   uint32_t semantics, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
+                                   uint32_t frame0, uint32_t light_samples, float shadow_eps, float ambient,
+                                   uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                                   float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t bounce_filter_levels,
+                                   float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride,
+                                   uint32_t bounce_phase, uint32_t bounce_upsample_radius, uint8_t *out_rgba, float *out_ms);
+
+/* Vertex normals from the mesh alone (host): verts holds n_tris x 9 floats, out_normals receives n_tris x 9.  Every operation
+ * in binary64, rounded once, no contraction; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  The face vector of a triangle is
+ * F = cross(v1 - v0, v2 - v0), its unit face vector F / sqrt(dot(F, F)) per component.  A face whose sqrt(dot(F, F)) is zero or
+ * not finite contributes nowhere and its own corners get +0 (which THE SHADING NORMAL turns into the geometric normal).  For
+ * every other corner, S = the sum, in ascending triangle index, of the face vectors F of this triangle and of every other
+ * contributing triangle that has a corner at the bitwise-same position (-0.0 taken as +0.0) and whose unit face vector has a
+ * dot product >= crease_cos with this triangle's; the corner gets (float)(S[c] / sqrt(dot(S, S))), or +0 when that square
+ * root is zero or not finite.  The weights are the faces' areas.  Welding is over the whole buffer.  crease_cos = 1 gives
+ * flat normals up to coplanar neighbours, -1 welds everything.  Refused (TRX_ERR_INVALID): null arguments, crease_cos
+ * outside [-1, 1] or NaN, more than 2^32 / 3 triangles. */
+int trx_compute_vertex_normals(const float *verts, uint64_t n_tris, float crease_cos, float *out_normals);
+
+/* trx_load_model with the model's vertex normals: the same verts and object counts, byte for byte, plus nine floats per
+ * triangle in that triangle order (all trx_free'd by the caller).  OBJ: `vn` records are read; the third index of a face
+ * corner's v/vt/vn or v//vn names one, relative to the `vn` records read so far when negative.  A corner with no normal index,
+ * or with one out of range at that point of the file, gets +0.  A quad's two triangles take corners 0,1,2 and 0,2,3, as for
+ * positions.  A JSON model gets +0 everywhere.  *out_has_normals is 1 when any corner got a `vn`, else 0.  Refused with
+ * TRX_ERR_INVALID: a `vn` with a component that is not finite, null arguments; TRX_ERR_IO: an unreadable model. */
+int trx_load_model_normals(const char *path, float **out_verts, uint64_t *out_n_tris, uint64_t **out_object_counts,
+                           uint32_t *out_n_objects, float **out_normals, uint32_t *out_has_normals);
 
 /* Status of the most recent trace on this scene (stack overflow is detected
  * in-kernel and latched in device memory).  Synchronises `stream`. */

@@ -233,6 +233,17 @@ SIGNATURES = {
     "trx_render_image_colour_emitters": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32,
                                               _f, _f, _u32, _f, _u32, _f, _f, _u32, _u32, _u32, _u32, _f, _P, C.POINTER(_f)]),
     "trx_debug_emitter_select": (_i, [_P, _P, _u64, _P]),
+    "trx_scene_set_vertex_normals": (_i, [_P, _P, _u64]),
+    "trx_scene_get_vertex_normals": (_i, [_P, _P, _u64]),
+    "trx_shading_normals_primary_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _P, _P, _P, _P, _P]),
+    "trx_shading_normals_rays_dev": (_i, [_P, _P, _u64, _P, _P, _P, _P, _P]),
+    "trx_render_image_lit_smooth": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32, _f,
+                                         _f, _P, C.POINTER(_f)]),
+    "trx_render_image_colour_smooth": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32, _f,
+                                            _f, _u32, _f, _u32, _f, _f, _u32, _u32, _u32, _P, C.POINTER(_f)]),
+    "trx_compute_vertex_normals": (_i, [_P, _u64, _f, _P]),
+    "trx_load_model_normals": (_i, [C.c_char_p, C.POINTER(C.POINTER(_f)), C.POINTER(_u64), C.POINTER(C.POINTER(_u64)), C.POINTER(_u32),
+                                    C.POINTER(C.POINTER(_f)), C.POINTER(_u32)]),
     "trx_debug_indirect_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P,
                                        C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),

@@ -297,6 +297,7 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     // the material table and the triangles' indices (trx_scene_set_materials; swapped under mu)
     bytes += s->materials.count() * sizeof(trx_material) + s->tri_material.count() * sizeof(uint16_t);
     bytes += s->emitters.count() * sizeof(float4) + s->emitter_cdf.count() * sizeof(float); // the emitter table (trx_scene_build_emitters; swapped under mu)
+    bytes += s->vertex_normals.count() * sizeof(float4); // the vertex normals, 48 B per triangle (trx_scene_set_vertex_normals; swapped under mu)
     bytes += s->image_thr.count() * sizeof(float); // the shade's code thresholds (api_image.cpp)
     for (const Slot &sl : s->slots) {
         bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
@@ -562,6 +563,65 @@ int trx_scene_get_materials(const trx_scene *s, trx_material *out_materials, uin
     std::memcpy(out_materials, s->h_materials.data(), s->h_materials.size() * sizeof(trx_material));
     if (n_tris) std::memcpy(out_tri_material, s->h_tri_material.data(), (size_t)n_tris * sizeof(uint16_t));
     *inout_n_materials = (uint32_t)s->h_materials.size();
+    return TRX_OK;
+}
+
+// Vertex normals (include/trx.h, "vertex normals"): read by the shading-normal pass under s->mu, owned like the materials.
+int trx_scene_set_vertex_normals(trx_scene *s, const float *normals, uint64_t n_tris) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    const bool remove = !normals || n_tris == 0;
+    if (!remove) {
+        if (n_tris != s->n_tris)
+            return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
+        for (uint64_t i = 0; i < n_tris * 9; i++)
+            if (!std::isfinite(normals[i]))
+                return fail(TRX_ERR_INVALID, "triangle %llu: vertex normal component %g is not finite", (unsigned long long)(i / 9), (double)normals[i]);
+    }
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<float> host_copy;
+    DevBuf<float4> fresh;
+    if (!remove) {
+        std::vector<float> padded; // three float4 per triangle, w = +0
+        try {
+            host_copy.assign(normals, normals + n_tris * 9);
+            padded.assign((size_t)n_tris * 12, 0.0f);
+        } catch (const std::exception &) {
+            return fail(TRX_ERR_OOM, "host allocation failed");
+        }
+        for (uint64_t i = 0; i < n_tris * 3; i++)
+            for (int c = 0; c < 3; c++) padded[i * 4 + c] = host_copy[i * 3 + c];
+        HIP_TRY(fresh.alloc(n_tris * 3));
+        // (uploaded from the validated host copy)
+        const hipError_t e = hipMemcpy(fresh.get(), padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the vertex normals failed: %s", hipGetErrorString(e));
+    }
+    // Swapped under the launch mutex (the shading-normal pass reads the pointer there); the old table is freed once every
+    // launch slot's last kernel has finished - trx_scene_set_instance_masks' statement: a pass enqueued before this call uses
+    // the old table in full.
+    DevBuf<float4> old;
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        old = std::move(s->vertex_normals);
+        s->vertex_normals = std::move(fresh);
+        s->h_vertex_normals.swap(host_copy);
+        if (old)
+            for (Slot &sl : s->slots)
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
+    }
+    if (retire(old, e) != hipSuccess) // (the old table is kept rather than freed under a kernel that may still read it)
+        return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    return TRX_OK;
+}
+
+int trx_scene_get_vertex_normals(const trx_scene *s, float *out_normals, uint64_t n_tris) {
+    if (!s || !out_normals) return fail(TRX_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
+    if (!s->vertex_normals) return fail(TRX_ERR_INVALID, "the scene has no vertex normals (trx_scene_set_vertex_normals)");
+    if (n_tris != s->n_tris)
+        return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
+    if (n_tris) std::memcpy(out_normals, s->h_vertex_normals.data(), (size_t)n_tris * 9 * sizeof(float));
     return TRX_OK;
 }
 

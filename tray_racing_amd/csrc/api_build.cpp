@@ -755,6 +755,45 @@ int trx_load_model_materials(const char *path, float **out_verts, uint64_t *out_
     return TRX_OK;
 }
 
+// trx_load_model with the model's vertex normals (include/trx.h): the same loader call path again.
+int trx_load_model_normals(const char *path, float **out_verts, uint64_t *out_n, uint64_t **out_counts, uint32_t *out_nobj,
+                           float **out_normals, uint32_t *out_has_normals) {
+    if (!path || !out_verts || !out_n || !out_normals || !out_has_normals) return fail(TRX_ERR_INVALID, "null argument");
+    std::vector<float> verts;
+    std::vector<uint64_t> objects;
+    ModelNormals mn;
+    try {
+        if (!load_model_normals(path, verts, objects, mn)) {
+            if (!mn.error.empty()) return fail(TRX_ERR_INVALID, "%s: %s", path, mn.error.c_str());
+            return fail(TRX_ERR_IO, "Error while loading model file \"%s\"", path);
+        }
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "out of memory loading '%s'", path);
+    }
+    float *nrm = static_cast<float *>(std::malloc(std::max<size_t>(mn.normals.size() * sizeof(float), 4)));
+    if (!nrm) return fail(TRX_ERR_OOM, "host allocation failed");
+    if (!mn.normals.empty()) std::memcpy(nrm, mn.normals.data(), mn.normals.size() * sizeof(float));
+    if (int rc = export_mesh(verts, objects, out_verts, out_n, out_counts, out_nobj)) {
+        std::free(nrm);
+        return rc;
+    }
+    *out_normals = nrm;
+    *out_has_normals = mn.any ? 1u : 0u;
+    return TRX_OK;
+}
+
+int trx_compute_vertex_normals(const float *verts, uint64_t n_tris, float crease_cos, float *out_normals) {
+    if ((!verts || !out_normals) && n_tris) return fail(TRX_ERR_INVALID, "null argument");
+    if (!(crease_cos >= -1.0f && crease_cos <= 1.0f)) return fail(TRX_ERR_INVALID, "crease_cos %g outside [-1, 1]", (double)crease_cos);
+    if (n_tris > 0x55555555ull) return fail(TRX_ERR_INVALID, "n_tris %llu: more corners than 32 bits index", (unsigned long long)n_tris);
+    try {
+        compute_vertex_normals(verts, n_tris, (double)crease_cos, out_normals);
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "host allocation failed");
+    }
+    return TRX_OK;
+}
+
 int trx_load_scene(const char *path, float **out_verts, uint64_t *out_n, uint64_t **out_counts, uint32_t *out_nobj, float eye[3],
                    float look_at[3], float *fov_deg) {
     if (!path || !out_verts || !out_n || !eye || !look_at || !fov_deg) return fail(TRX_ERR_INVALID, "null argument");

@@ -461,13 +461,22 @@ int trx_render_image_sparse(trx_scene *s, const trx_view *view, uint32_t w, uint
 // term and the shade, the term's values its base and its output) and trx_render_image_gi_filtered (filter_levels >= 1: the
 // indirect pass without a base into a plane of its own, the value filter over that plane with the term's values its base and
 // its output); trx_render_image_gi_sparse (bounce_stride >= 1: the sparse indirect pass into a low plane, then the upsample - with
-// the term's values its base and its output, or with filter levels without a base into the plane the filter then reads)
+// the term's values its base and its output, or with filter levels without a base into the plane the filter then reads).
+// smooth (trx_render_image_lit_smooth): the shading-normal pass right after the attribute pass, in place - the light term, the
+// filters and the upsample then read the shading attributes; the ray-generating passes take no attribute buffer.
+// (the table is swapped under s->mu; a removal between this check and the pass makes the pass itself refuse)
+static int need_vertex_normals(trx_scene *s) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->vertex_normals) return fail(TRX_ERR_INVALID, "the scene has no vertex normals (trx_scene_set_vertex_normals)");
+    return TRX_OK;
+}
+
 static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
                       const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
                       float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                       float normal_cos, uint32_t bounce_samples, float bounce_eps, float bounce_albedo, uint32_t filter_levels,
                       float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
-                      uint32_t upsample_radius, uint8_t *out_rgba, float *out_ms) {
+                      uint32_t upsample_radius, uint8_t *out_rgba, float *out_ms, bool smooth = false) {
     if (int rc = check_lights(lights, n_lights, light_samples)) return rc;
     if (ray_mask > 0xffu) return fail(TRX_ERR_INVALID, "ray_mask 0x%x outside 0..255", ray_mask);
     if (!(shadow_eps >= 0.0f)) return fail(TRX_ERR_INVALID, "shadow_eps %g: must be >= 0", (double)shadow_eps);
@@ -480,6 +489,8 @@ static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
     if (sem & ~7u) return fail(TRX_ERR_INVALID, "unknown semantics bits 0x%x", sem);
     if (int rc = check_image(w, h)) return rc;
     if (!s || !view) return fail(TRX_ERR_INVALID, "null argument");
+    if (smooth)
+        if (int rc = need_vertex_normals(s)) return rc;
     const uint64_t n = (uint64_t)w * h;
     const trx_shard whole{0, 1, 0, 0};
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
@@ -504,6 +515,11 @@ static int render_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h
             if (rc) return rc;
             rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
             if (rc) return rc;
+            if (smooth) {
+                rc = trx_shading_normals_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(),
+                                                     s->scratch_attr.get(), nullptr);
+                if (rc) return rc;
+            }
             rc = trx_trace_light_visibility_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps,
                                                 s->scratch_a.get(), s->scratch_ia.get(), d_lit(), nullptr);
             if (rc) return rc;
@@ -559,6 +575,14 @@ int trx_render_image_lit(trx_scene *s, const trx_view *view, uint32_t w, uint32_
                          float normal_cos, uint8_t *out_rgba, float *out_ms) {
     return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
                       ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, 0u, 0.0f, 0.0f, 0u, 0u, 0u, out_rgba, out_ms);
+}
+
+int trx_render_image_lit_smooth(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                                const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                                float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                                float normal_cos, uint8_t *out_rgba, float *out_ms) {
+    return render_lit(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                      ao_radius, filter_radius, depth_tol, normal_cos, 0u, 0.0f, 0.0f, 0u, 0.0f, 0.0f, 0u, 0u, 0u, out_rgba, out_ms, true);
 }
 
 // what trx_render_image_gi adds to the lit image's refusals (which come first, in their order)
@@ -667,13 +691,13 @@ int trx_shade_rgb_dev(trx_scene *s, const float *d_colour_rgb, uint64_t n, uint8
 
 // trx_render_image_colour (emitter_eps null) and trx_render_image_colour_emitters (include/trx.h, "emitters": emitter_eps set -
 // n_lights may be 0, the indirect pass runs in its emitter mode, and the emitter light pass adds to the planes the indirect
-// term ends in before the compose)
+// term ends in before the compose); smooth (trx_render_image_colour_smooth): render_lit's statement of it
 static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
                          const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
                          float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                          float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
                          float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
-                         uint32_t emitter_samples, const float *emitter_eps, uint8_t *out_rgba, float *out_ms) {
+                         uint32_t emitter_samples, const float *emitter_eps, uint8_t *out_rgba, float *out_ms, bool smooth = false) {
     // render_lit's refusals in its order, then the bounce's, the filter's and the upsample's where those steps run
     // (no light at all - the emitter form alone: V is what the light term gives for this one light of intensity 0)
     const trx_light none{TRX_LIGHT_DIRECTIONAL, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f, {0u, 0u}};
@@ -712,6 +736,8 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
         if (int rc = check_emitter_eps(*emitter_eps)) return rc;
     }
     if (int rc = need_materials(s)) return rc;
+    if (smooth)
+        if (int rc = need_vertex_normals(s)) return rc;
     const uint64_t n = (uint64_t)w * h;
     const trx_shard whole{0, 1, 0, 0};
     std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (host_call takes it again: the image scratch is under it too)
@@ -742,6 +768,11 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
             if (rc) return rc;
             rc = trx_hit_attributes_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(), nullptr);
             if (rc) return rc;
+            if (smooth) {
+                rc = trx_shading_normals_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(),
+                                                     s->scratch_attr.get(), nullptr);
+                if (rc) return rc;
+            }
             if (unlit) HIP_TRY(hipMemsetAsync(d_lit(), 0, n, nullptr)); // (a light of intensity 0 adds +0 whatever its plane counts)
             else rc = trx_trace_light_visibility_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps,
                                                      s->scratch_a.get(), s->scratch_ia.get(), d_lit(), nullptr);
@@ -823,6 +854,17 @@ int trx_render_image_colour(trx_scene *s, const trx_view *view, uint32_t w, uint
     return render_colour(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
                          ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, filter_levels, bounce_depth_tol,
                          bounce_normal_cos, bounce_stride, bounce_phase, upsample_radius, 0u, nullptr, out_rgba, out_ms);
+}
+
+int trx_render_image_colour_smooth(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                                   const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                                   float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
+                                   float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
+                                   float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
+                                   uint8_t *out_rgba, float *out_ms) {
+    return render_colour(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                         ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, filter_levels, bounce_depth_tol,
+                         bounce_normal_cos, bounce_stride, bounce_phase, upsample_radius, 0u, nullptr, out_rgba, out_ms, true);
 }
 
 int trx_render_image_colour_emitters(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,

@@ -15,6 +15,8 @@
 //                    trx_material_compose_dev / trx_shade_rgb_dev / trx_render_image_colour in api_image.cpp; trx_standin_materials / trx_load_model_materials in api_build.cpp (the OBJ/MTL reading itself in scenes.cpp)
 //   emitters         (include/trx.h, "emitters") trx_scene_build_emitters / _get_emitters / trx_debug_emitter_select in api_emitters.cpp; trx_emitter_rays_dev / trx_trace_emitter_light_dev and the
 //                    indirect pass's emitter mode (trx_trace_indirect_rgb_emitters_dev / _sparse_dev) in api_ao.cpp; trx_render_image_colour_emitters in api_image.cpp
+//   vertex normals   (include/trx.h, "vertex normals") trx_scene_set_vertex_normals / _get_vertex_normals in api.cpp; trx_shading_normals_primary_dev / _rays_dev (k_shading_normal, kernels.hip) in api_attr.cpp;
+//                    trx_render_image_lit_smooth / _colour_smooth in api_image.cpp; trx_compute_vertex_normals / trx_load_model_normals in api_build.cpp (the welding and the OBJ `vn` reading in scenes.cpp)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -242,6 +244,11 @@ struct trx_scene {
     // trx_render_image's scratch - the filter's terms, then the RGBA8 image (under host_mu)
     trxapi::DevBuf<float> image_thr;
     trxapi::DevBuf<uint8_t> scratch_img;
+    // vertex normals (trx_scene_set_vertex_normals): the caller's nine floats per triangle in `prim` order and the device
+    // table of three float4 per triangle (w = +0), swapped together under mu; empty = no table (the shading-normal entry
+    // points are refused)
+    std::vector<float> h_vertex_normals;
+    trxapi::DevBuf<float4> vertex_normals;
 };
 
 struct trx_bvh {

@@ -83,6 +83,11 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // short of the emitter; --light becomes optional
     int emitters = -1;
     float emitter_eps = -1.0f;
+    // --smooth [--smooth-crease DEG]: with --png --light (the direct-light image) or with --colour the light term and the filters
+    // shade with interpolated vertex normals (trx_render_image_lit_smooth / _colour_smooth) - the OBJ's `vn` records where the
+    // file has any, else normals computed from the mesh, welded across edges flatter than DEG degrees (default 45)
+    bool smooth = false;
+    float smooth_crease = -1.0f; // (not given: 45)
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -141,6 +146,10 @@ void usage() {
               "  [--emitters 1..64] [--emitter-eps e] (with --png --colour: the emissive triangles sampled as lights - N shadow rays per\n"
               "   pixel and one per bounce ray toward points on them, each stopped e (default 0.001) of its length short of the\n"
               "   emitter; --light becomes optional)\n"
+              "  [--smooth] [--smooth-crease DEG] (with --png --light or with --colour: shade with interpolated vertex normals - the\n"
+              "   `vn` records of -i <file.obj> where it has any, else computed from the mesh, corners welded across edges flatter\n"
+              "   than DEG degrees, default 45; rays still start from the geometric normal; not together with --bounce-samples\n"
+              "   without --colour, --emitters, --profile-rt or --benchmark)\n"
               "stand-in names: cornell demoscene kitchen bistro hairball san_miguel (seeded procedural scenes)");
 }
 
@@ -297,6 +306,12 @@ Options parse_args(int argc, char **argv) {
             o.emitter_eps = (float)std::atof(need(i));
             if (!(o.emitter_eps >= 0.0f && o.emitter_eps < 1.0f)) die("--emitter-eps takes a number in [0, 1)");
         }
+        else if (a == "--smooth") {
+            o.smooth = true;
+        } else if (a == "--smooth-crease") {
+            o.smooth_crease = (float)std::atof(need(i));
+            if (!(o.smooth_crease >= 0.0f && o.smooth_crease <= 180.0f)) die("--smooth-crease takes an angle of 0..180 degrees");
+        }
         else if (a == "--profile-rt") {
             const std::string m = need(i);
             if (m == "nodes") o.profile_rt = (int)TRX_HEAT_NODES;
@@ -361,6 +376,12 @@ Options parse_args(int argc, char **argv) {
     if (o.bounce_filter >= 0 && o.bounce_samples < 0) die("--bounce-filter filters the term of --bounce-samples N");
     if (o.colour && o.lights.empty() && o.emitters < 0) die("--colour colours the image of --light");
     if (o.colour && o.bounce_albedo >= 0.0f) die("--colour takes the albedo of the materials: not together with --bounce-albedo");
+    if (!o.smooth && o.smooth_crease >= 0.0f) die("--smooth-crease goes with --smooth");
+    if (o.smooth && o.benchmark) die("--smooth shades the image of --png: not together with --benchmark");
+    if (o.smooth && o.profile_rt >= 0) die("--smooth shades the lit image: not together with --profile-rt");
+    if (o.smooth && o.emitters >= 0) die("--smooth shades the image of --light or --colour: not together with --emitters");
+    if (o.smooth && o.bounce_samples >= 0 && !o.colour) die("--smooth shades the direct-light image or the colour image: not together with the grey --bounce-samples image");
+    if (o.smooth && (!o.png || o.lights.empty())) die("--smooth shades the image of --png --light or of --colour");
     if (o.passes == 0) o.passes = 1;
     return o;
 }
@@ -444,7 +465,7 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
                   "png frame");
         else if (o.colour)
             // the colour image: the same chain, the bounce's term in three planes, composed with the scene's materials
-            check(trx_render_image_colour(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+            check((o.smooth ? trx_render_image_colour_smooth : trx_render_image_colour)(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                           o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
                                           o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
                                           radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
@@ -485,7 +506,7 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
                                       o.bounce_albedo >= 0.0f ? o.bounce_albedo : 0.5f, rgba.data(), &ms),
                   "png frame");
         else
-            check(trx_render_image_lit(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+            check((o.smooth ? trx_render_image_lit_smooth : trx_render_image_lit)(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                        o.lights.data(), (uint32_t)o.lights.size(), frame_count, o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u,
                                        o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f, o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f,
                                        radius, o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos, rgba.data(), &ms),
@@ -556,6 +577,9 @@ Stats render_input(const Options &o, const std::string &input) {
     trx_material *materials = nullptr;
     uint32_t n_materials = 0;
     uint16_t *tri_material = nullptr;
+    // --smooth: the vertex normals in the order of verts (permuted like the materials)
+    float *normals = nullptr;
+    uint32_t has_vn = 0;
     const bool obj = input.size() > 4 && input.compare(input.size() - 4, 4, ".obj") == 0;
     if (input == "demoscene" || input.rfind("standin:", 0) == 0) {
         const std::string name = input == "demoscene" ? "demoscene" : input.substr(8);
@@ -569,6 +593,15 @@ Stats render_input(const Options &o, const std::string &input) {
         st.name = input.substr(k == std::string::npos ? 0 : k + 1);
         st.name.erase(st.name.size() - 4);
         check(trx_load_model_materials(input.c_str(), &verts, &n_tris, &counts, &n_objects, &materials, &n_materials, &tri_material), "model");
+        if (o.smooth) { // (the same mesh again, byte for byte, with its `vn` records)
+            float *v2 = nullptr;
+            uint64_t n2 = 0, *c2 = nullptr;
+            uint32_t o2 = 0;
+            check(trx_load_model_normals(input.c_str(), &v2, &n2, &c2, &o2, &normals, &has_vn), "model normals");
+            trx_free(v2);
+            trx_free(c2);
+            if (n2 != n_tris) die("model normals: the model changed while it was read");
+        }
         float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
         for (uint64_t i = 0; i < n_tris * 3; i++)
             for (int c = 0; c < 3; c++) {
@@ -591,6 +624,13 @@ Stats render_input(const Options &o, const std::string &input) {
         if (k != std::string::npos) st.name.erase(k);
         // scene file + model through the library's loader (src/main.rs:259-298: "Failed to load config" / the model's error)
         check(trx_load_scene(input.c_str(), &verts, &n_tris, &counts, &n_objects, cam.eye, cam.look_at, &cam.fov), "scene");
+    }
+    if (o.smooth && !has_vn) { // no usable `vn` (always so for a generated scene): computed from the mesh
+        trx_free(normals);
+        normals = static_cast<float *>(std::malloc(std::max<size_t>((size_t)n_tris * 9 * sizeof(float), 4)));
+        if (!normals) die("out of memory");
+        const double deg = o.smooth_crease >= 0.0f ? (double)o.smooth_crease : 45.0;
+        check(trx_compute_vertex_normals(verts, n_tris, (float)std::cos(deg * 3.14159265358979323846 / 180.0), normals), "vertex normals");
     }
     const bool tlas = o.tlas && !o.flatten_blas; // src/main.rs:300-308
     if (o.verbose) std::printf("%u objects \"%s\"\ntriangles %llu\n", n_objects, st.name.c_str(), (unsigned long long)n_tris);
@@ -631,6 +671,7 @@ Stats render_input(const Options &o, const std::string &input) {
         trx_free(counts);
         trx_free(materials);
         trx_free(tri_material);
+        trx_free(normals);
         return st;
     }
 
@@ -647,6 +688,12 @@ Stats render_input(const Options &o, const std::string &input) {
         std::vector<uint16_t> by_prim(flat->n_tris);
         for (uint64_t i = 0; i < flat->n_tris; i++) by_prim[i] = flat->tri_source[i] < n_tris ? tri_material[flat->tri_source[i]] : 0;
         check(trx_scene_set_materials(scene, materials, n_materials, by_prim.data(), flat->n_tris), "materials");
+    }
+    if (o.smooth) { // the normals in `prim` order, like the materials
+        std::vector<float> by_prim((size_t)flat->n_tris * 9, 0.0f);
+        for (uint64_t i = 0; i < flat->n_tris; i++)
+            if (flat->tri_source[i] < n_tris) std::memcpy(&by_prim[i * 9], normals + (size_t)flat->tri_source[i] * 9, 9 * sizeof(float));
+        check(trx_scene_set_vertex_normals(scene, by_prim.data(), flat->n_tris), "vertex normals");
     }
     trx_view view;
     check(trx_view_from_camera(cam.eye, cam.look_at, cam.fov, (float)o.width, (float)o.height, &view), "camera");
@@ -695,6 +742,7 @@ Stats render_input(const Options &o, const std::string &input) {
     trx_free(counts);
     trx_free(materials);
     trx_free(tri_material);
+    trx_free(normals);
     return st;
 }
 

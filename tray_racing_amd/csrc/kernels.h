@@ -225,6 +225,23 @@ struct HitAttrParams {
 };
 hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream);
 
+// The shading normal (k_shading_normal, trx_shading_normals_*): one lane per record, indexed exactly as HitAttrParams'
+// records are; `normals` holds three float4 per triangle (the vertex normals of vertices 0, 1, 2, w = +0), n_tris of them.
+struct ShadingNormalParams {
+    const float4 *normals;
+    const float4 *inst_xform; // world-to-object rows per instance, or null (no instance transforms)
+    const trx_ray *rays;      // kAttrRays (the direction words alone are read)
+    const trx_hit *hits;
+    const uint32_t *inst;     // instance id per record (read only with inst_xform)
+    const trx_hit_attr *attr;
+    trx_hit_attr *out;        // may be attr
+    uint32_t n_items;         // kAttrRays: records; kAttrPrimary: the shard's tiles * 64, in tile order
+    uint32_t n_tris, n_inst;
+    TileGeom geom;            // kAttrPrimary
+    ViewDev view;
+};
+hipError_t launch_shading_normal(const ShadingNormalParams &p, int mode, hipStream_t stream);
+
 // AO visibility (trx_ao_rays_dev / trx_trace_ao_visibility_dev): k_ao_rays writes the AO pass's rays as explicit rays, the
 // any-hit rays launch walks them, k_ao_reduce adds the flags into per-pixel counts.  One lane per (tile, sample, pixel).
 //   record layout (scratch == 0, one sample): rays[record], records laid out by the shard like the hit buffers; pixels

@@ -935,6 +935,71 @@ __global__ void __launch_bounds__(256) k_hit_attr(const HitAttrParams P) {
     P.out[rec] = out;
 }
 
+// The shading normal (include/trx.h, "THE SHADING NORMAL"; kernels.h, ShadingNormalParams): one lane per record, no
+// traversal.  The record's attribute record comes back with its geometric normal replaced by the interpolated vertex normal
+// where the header's rule adopts it, and bit for bit as it was everywhere else - an out-of-range prim or instance id
+// included, which reads no table (CALLER RECORDS; t is not looked at, as in k_hit_attr).  The ray direction is the light
+// term's: primary_dir of the pixel, or the ray's direction words, no zero-direction fix.  A gather: 8 B of hit, 4 B of
+// instance id, 24 B of attributes, 48 B of normals (and 48 B of rows) per record, 24 B written; primary frames in the tile
+// order of the trace, like k_hit_attr.  Each lane reads its record before it writes it: out may be attr.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_shading_normal(const ShadingNormalParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= P.n_items) return;
+    uint32_t rec = item;
+    float dx, dy, dz;
+    if constexpr (MODE == kAttrPrimary) {
+        uint32_t px, py;
+        if (!tile_pixel(P.geom, item >> 6, item & 63u, px, py, rec)) return;
+        primary_dir(P.view, P.geom.width, P.geom.height, px, py, dx, dy, dz);
+    } else {
+        const float4 b = reinterpret_cast<const float4 *>(P.rays + item)[1];
+        dx = b.x; dy = b.y; dz = b.z;
+    }
+    const uint32_t prim = P.hits[rec].prim;
+    trx_hit_attr A = P.attr[rec];
+    float4 r0 = make_float4(1.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0;
+    bool ok = prim < P.n_tris;
+    if (P.inst_xform) {
+        const uint32_t inst = P.inst[rec];
+        ok = ok && inst < P.n_inst;
+        if (ok) {
+            const float4 *m = P.inst_xform + (size_t)inst * 3;
+            r0 = m[0]; r1 = m[1]; r2 = m[2];
+        }
+    }
+    if (ok) {
+        const float4 *np = P.normals + (size_t)prim * 3;
+        const float4 n0 = np[0], n1 = np[1], n2 = np[2];
+        const float u = A.u, v = A.v;
+        const float gx = A.normal[0], gy = A.normal[1], gz = A.normal[2];
+        const float w = (1.0f - u) - v;
+        float mx = (w * n0.x + u * n1.x) + v * n2.x;
+        float my = (w * n0.y + u * n1.y) + v * n2.y;
+        float mz = (w * n0.z + u * n1.z) + v * n2.z;
+        if (P.inst_xform) {
+            const float3 t = normal_to_world(r0, r1, r2, mx, my, mz);
+            mx = t.x; my = t.y; mz = t.z;
+        }
+        const float q = dot3(mx, my, mz, mx, my, mz);
+        const float inv = 1.0f / sqrtf(q);
+        float sx = mx * inv, sy = my * inv, sz = mz * inv;
+        const float c = dot3(sx, sy, sz, gx, gy, gz);
+        const float sg = copysignf(1.0f, c);
+        sx *= sg; sy *= sg; sz *= sg;
+        const float a = (gx * -dx + gy * -dy) + gz * -dz;
+        const float b = (sx * -dx + sy * -dy) + sz * -dz;
+        // adopted only where the light term's flip is the same for s as for g (false for a NaN on either side)
+        if (q > 0.0f && q < __builtin_inff() && c == c && ((a > 0.0f && b > 0.0f) || (a < 0.0f && b < 0.0f))) {
+            A.normal[0] = sx;
+            A.normal[1] = sy;
+            A.normal[2] = sz;
+            A._pad = 0u;
+        }
+    }
+    P.out[rec] = A;
+}
+
 // AO visibility (include/trx.h, trx_ao_rays_dev / trx_trace_ao_visibility_dev; kernels.h, AoRaysParams).
 // The AO ray of every (tile, sample, pixel) as an explicit ray: what the refill of k_trace<kModeAo> builds for that pixel
 // and seed (trace_refill.inc) through the same statements - primary_dir, normal_to_world, TRX_AO_RAY - with tmin = 0 and
@@ -1843,6 +1908,14 @@ hipError_t launch_hit_attr(const HitAttrParams &p, int mode, hipStream_t stream)
     const dim3 grid((p.n_items + 255u) / 256u), block(256);
     if (mode == kAttrPrimary) hipLaunchKernelGGL(k_hit_attr<kAttrPrimary>, grid, block, 0, stream, p);
     else hipLaunchKernelGGL(k_hit_attr<kAttrRays>, grid, block, 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_shading_normal(const ShadingNormalParams &p, int mode, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    const dim3 grid((p.n_items + 255u) / 256u), block(256);
+    if (mode == kAttrPrimary) hipLaunchKernelGGL(k_shading_normal<kAttrPrimary>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(k_shading_normal<kAttrRays>, grid, block, 0, stream, p);
     return hipGetLastError();
 }
 

@@ -748,7 +748,11 @@ bool load_mtl(const std::string &path, std::vector<std::string> &names, ModelMat
 // mm (optional): the materials of trx_load_model_materials - `mtllib` files are read from the OBJ's directory as they are
 // named, `usemtl` names are looked up once the whole file is read (the first material of a name wins; an unknown name, and
 // faces before any usemtl, get material 0, the default).  The mesh is the same with and without it.
-bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials *mm = nullptr) {
+// mn (optional): the vertex normals of trx_load_model_normals - `vn` records, and the third index of a face corner's
+// v/vt/vn or v//vn (relative when negative, against the `vn` records read so far); a corner without one, or with one out of
+// range, gets +0.  The mesh is the same with and without it.
+bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials *mm = nullptr,
+              ModelNormals *mn = nullptr) {
     FILE *f = std::fopen(path.c_str(), "rb");
     if (!f) return false;
     std::vector<std::string> names, uses; // the mtl files' materials in file order; the names given to usemtl
@@ -758,7 +762,7 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
         const float fresh[6] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.0f};
         mm->table.assign(fresh, fresh + 6);
     }
-    std::vector<float> pos;
+    std::vector<float> pos, nrm;
     uint64_t open_start = 0;
     bool any_object = false;
     auto close_object = [&]() {
@@ -774,6 +778,17 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
             pos.push_back(x);
             pos.push_back(y);
             pos.push_back(z);
+        } else if (mn && line[0] == 'v' && line[1] == 'n' && (line[2] == ' ' || line[2] == '\t')) {
+            float x = 0, y = 0, z = 0;
+            std::sscanf(line + 3, "%f %f %f", &x, &y, &z);
+            if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) {
+                mn->error = "vn record " + std::to_string(nrm.size() / 3 + 1) + " is not finite";
+                std::fclose(f);
+                return false;
+            }
+            nrm.push_back(x);
+            nrm.push_back(y);
+            nrm.push_back(z);
         } else if (line[0] == 'o' && (line[1] == ' ' || line[1] == '\t')) {
             if (any_object || verts.size() / 9 > open_start) close_object();
             any_object = true;
@@ -788,7 +803,7 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
             uses.push_back(line_rest(line + 6));
             use = (uint32_t)uses.size();
         } else if (line[0] == 'f' && (line[1] == ' ' || line[1] == '\t')) {
-            long idx[4];
+            long idx[4], nidx[4] = {-1, -1, -1, -1}; // (nidx: the corner's `vn`, -1 = none)
             int n = 0;
             char *p = line + 2;
             for (;;) { // n counts every vertex of the polygon; the first four are kept
@@ -801,9 +816,22 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
                 if (n < 4) idx[n] = v - 1;
                 n++;
                 p = end;
+                if (mn && n <= 4 && *p == '/') { // v/vt/vn or v//vn: the third index
+                    const char *q = p + 1;
+                    while (*q && *q != '/' && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;
+                    if (*q == '/') {
+                        char *nend;
+                        long vn = std::strtol(q + 1, &nend, 10);
+                        if (nend != q + 1) {
+                            if (vn < 0) vn = (long)(nrm.size() / 3) + vn + 1; // relative index
+                            nidx[n - 1] = vn - 1;
+                        }
+                    }
+                }
                 while (*p && *p != ' ' && *p != '\t' && *p != '\n' && *p != '\r') p++; // skip /vt/vn
             }
-            auto push = [&](long a, long b, long c) {
+            auto push = [&](int ka, int kb, int kc) {
+                const long a = idx[ka], b = idx[kb], c = idx[kc];
                 long np = (long)(pos.size() / 3);
                 if (a < 0 || b < 0 || c < 0 || a >= np || b >= np || c >= np) return;
                 for (long i : {a, b, c}) {
@@ -812,10 +840,17 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
                     verts.push_back(pos[3 * i + 2]);
                 }
                 if (mm) tri_use.push_back(use);
+                if (mn)
+                    for (int k : {ka, kb, kc}) {
+                        const long i = nidx[k];
+                        const bool have = i >= 0 && i < (long)(nrm.size() / 3);
+                        mn->any = mn->any || have;
+                        for (int j = 0; j < 3; j++) mn->normals.push_back(have ? nrm[3 * i + j] : 0.0f);
+                    }
             };
             // the reference reads vertices 0,1,2 and, for quads only, 0,2,3 (src/main.rs:536-553)
-            if (n >= 3) push(idx[0], idx[1], idx[2]);
-            if (n == 4) push(idx[0], idx[2], idx[3]);
+            if (n >= 3) push(0, 1, 2);
+            if (n == 4) push(0, 2, 3);
         }
     }
     std::fclose(f);
@@ -896,6 +931,104 @@ bool load_model_materials(const std::string &path, std::vector<float> &verts, st
         return true;
     }
     return load_obj(path, verts, objects, &mm);
+}
+
+bool load_model_normals(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelNormals &mn) {
+    mn = ModelNormals();
+    if (path.find("json") != std::string::npos && path.rfind('.') != std::string::npos &&
+        path.substr(path.rfind('.')).find("json") != std::string::npos) {
+        if (!load_json(path, verts, objects)) return false;
+        mn.normals.assign(verts.size(), 0.0f);
+        return true;
+    }
+    return load_obj(path, verts, objects, nullptr, &mn);
+}
+
+// Vertex normals from the mesh alone (include/trx.h, trx_compute_vertex_normals).  Every operation in binary64, rounded
+// once, no contraction (this file's flags); dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+void compute_vertex_normals(const float *verts, uint64_t n_tris, double crease_cos, float *out) {
+    struct V3 {
+        double x, y, z;
+    };
+    auto dot = [](const V3 &a, const V3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
+    // face vectors cross(v1 - v0, v2 - v0) and their unit vectors; len == 0 marks a face that contributes nowhere
+    std::vector<V3> face(n_tris), unit(n_tris);
+    std::vector<uint8_t> valid(n_tris);
+    for (uint64_t t = 0; t < n_tris; t++) {
+        const float *v = verts + 9 * t;
+        const V3 e1{(double)v[3] - (double)v[0], (double)v[4] - (double)v[1], (double)v[5] - (double)v[2]};
+        const V3 e2{(double)v[6] - (double)v[0], (double)v[7] - (double)v[1], (double)v[8] - (double)v[2]};
+        const V3 f{e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x};
+        const double len = std::sqrt(dot(f, f));
+        valid[t] = std::isfinite(len) && len > 0.0;
+        face[t] = f;
+        unit[t] = valid[t] ? V3{f.x / len, f.y / len, f.z / len} : V3{0.0, 0.0, 0.0};
+    }
+    // welding: one id per distinct position (bitwise, -0.0 taken as +0.0) among the corners of the valid faces, through an
+    // open-addressing table keyed by a hash of the position bits
+    const uint64_t n_corners = n_tris * 3;
+    uint64_t cap = 16;
+    while (cap < n_corners * 2) cap *= 2;
+    const uint32_t kEmpty = 0xffffffffu;
+    std::vector<uint32_t> table(cap, kEmpty); // -> the first corner seen at the position
+    std::vector<uint32_t> vid(n_corners, kEmpty), first_corner;
+    auto key = [&](uint64_t corner, uint32_t k[3]) {
+        for (int j = 0; j < 3; j++) {
+            std::memcpy(&k[j], verts + 3 * corner + j, 4);
+            if (k[j] == 0x80000000u) k[j] = 0u;
+        }
+    };
+    for (uint64_t c = 0; c < n_corners; c++) {
+        if (!valid[c / 3]) continue;
+        uint32_t k[3], o[3];
+        key(c, k);
+        uint64_t h = ((uint64_t)k[0] * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)k[1] * 0xC2B2AE3D27D4EB4Full) ^ ((uint64_t)k[2] * 0x165667B19E3779F9ull);
+        h ^= h >> 29;
+        for (uint64_t slot = h & (cap - 1);; slot = (slot + 1) & (cap - 1)) {
+            if (table[slot] == kEmpty) {
+                table[slot] = (uint32_t)first_corner.size();
+                vid[c] = (uint32_t)first_corner.size();
+                first_corner.push_back((uint32_t)c);
+                break;
+            }
+            key(first_corner[table[slot]], o);
+            if (o[0] == k[0] && o[1] == k[1] && o[2] == k[2]) {
+                vid[c] = table[slot];
+                break;
+            }
+        }
+    }
+    // the triangles at every position, ascending (a valid face has three distinct positions: listed once)
+    const uint64_t n_vid = first_corner.size();
+    std::vector<uint64_t> start(n_vid + 1, 0);
+    for (uint64_t c = 0; c < n_corners; c++)
+        if (vid[c] != kEmpty) start[vid[c] + 1]++;
+    for (uint64_t i = 0; i < n_vid; i++) start[i + 1] += start[i];
+    std::vector<uint32_t> list(start[n_vid]);
+    {
+        std::vector<uint64_t> fill(start.begin(), start.end() - 1);
+        for (uint64_t c = 0; c < n_corners; c++)
+            if (vid[c] != kEmpty) list[fill[vid[c]]++] = (uint32_t)(c / 3);
+    }
+    for (uint64_t c = 0; c < n_corners; c++) {
+        float *o = out + 3 * c;
+        o[0] = o[1] = o[2] = 0.0f;
+        const uint64_t t = c / 3;
+        if (!valid[t]) continue;
+        V3 sum{0.0, 0.0, 0.0};
+        for (uint64_t i = start[vid[c]]; i < start[vid[c] + 1]; i++) {
+            const uint32_t t2 = list[i];
+            if (t2 != t && !(dot(unit[t2], unit[t]) >= crease_cos)) continue;
+            sum.x += face[t2].x;
+            sum.y += face[t2].y;
+            sum.z += face[t2].z;
+        }
+        const double len = std::sqrt(dot(sum, sum));
+        if (!(std::isfinite(len) && len > 0.0)) continue;
+        o[0] = (float)(sum.x / len);
+        o[1] = (float)(sum.y / len);
+        o[2] = (float)(sum.z / len);
+    }
 }
 
 // The subset of RON the reference's scene files use (assets/scenes/*.ron): model_path, camera(eye, look_at, fov,

@@ -19,6 +19,17 @@ struct ModelMaterials {
     std::string error;
 };
 bool load_model_materials(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials &mm);
+// load_model with the model's vertex normals (trx_load_model_normals): the same verts and objects, nine floats per triangle
+// in the order of verts (an OBJ corner's `vn`, +0 where it names none or one out of range; all +0 for a JSON model) and
+// whether any corner got one.  false with `error` set: a `vn` the loader refuses; false without: unreadable.
+struct ModelNormals {
+    std::vector<float> normals;
+    bool any = false;
+    std::string error;
+};
+bool load_model_normals(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelNormals &mn);
+// Vertex normals from the mesh alone (include/trx.h, trx_compute_vertex_normals): nine floats per triangle into out.
+void compute_vertex_normals(const float *verts, uint64_t n_tris, double crease_cos, float *out);
 // A scene file of the reference (assets/scenes/*.ron: model_path, camera(eye, look_at, fov)): the model's path resolved by
 // the reference's rule (src/main.rs:271-284) and the camera.  false = unreadable or not such a file.
 bool parse_scene_ron(const std::string &path, std::string &model_path, float eye[3], float look_at[3], float *fov_deg);

@@ -92,6 +92,30 @@ def load_model_materials(path):
     return verts, counts, mats, idx
 
 
+def load_model_normals(path):
+    """(verts [n,9], triangles per object, normals [n,9] f32, has_normals): trx_load_model_normals - load_meshs' mesh with
+    the OBJ's `vn` record of every corner (v/vt/vn, v//vn; +0 for a corner that names none or one out of range, and for every
+    corner of a JSON model); has_normals says whether any corner got one."""
+    lib = L.load()
+    vp, cp, np_ = C.POINTER(C.c_float)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_float)()
+    n, nobj, has = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    L.check(lib.trx_load_model_normals(str(path).encode(), C.byref(vp), C.byref(n), C.byref(cp), C.byref(nobj), C.byref(np_), C.byref(has)))
+    normals = np.ctypeslib.as_array(np_, shape=(max(n.value, 1), 9))[: n.value].copy()
+    lib.trx_free(C.cast(np_, C.c_void_p))
+    verts, counts = _take_mesh(vp, n, cp, nobj)
+    return verts, counts, normals, bool(has.value)
+
+
+def compute_vertex_normals(verts, crease_cos=0.70710678):
+    """[n,9] f32: trx_compute_vertex_normals - per corner the area-weighted sum, normalised, of the face vectors of the
+    triangles that share the corner's position (bitwise, -0.0 as +0.0) and lie within the crease angle of the corner's own
+    triangle (unit face vectors' dot product >= crease_cos); +0 for the corners of a degenerate triangle."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 9)
+    out = np.zeros_like(v)
+    L.check(L.load().trx_compute_vertex_normals(_ptr(v), v.shape[0], crease_cos, _ptr(out)))
+    return out
+
+
 def load_scene(path):
     """A scene file of the reference (assets/scenes/*.ron) as src/main.rs:259-298 reads it: (verts [n,9], triangles per
     object, eye, look_at, fov) - trx_load_scene."""
@@ -427,6 +451,22 @@ class Scene:
         L.check(self._lib.trx_scene_get_materials(self._h, _ptr(mats), C.byref(n), _ptr(idx), idx.size))
         return mats[:n.value].copy(), idx
 
+    def set_vertex_normals(self, normals):
+        """trx_scene_set_vertex_normals: nine floats per triangle ([n_tris, 9] f32: the object-space normals of vertices 0, 1,
+        2) in `prim` order (the order of flat.tri_verts; normals in mesh order go through flat.tri_source); None removes the
+        table.  Validated on the host; replaces an earlier table after the scene's launches in flight.  A refit keeps it."""
+        if normals is None:
+            L.check(self._lib.trx_scene_set_vertex_normals(self._h, None, 0))
+            return
+        nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 9)
+        L.check(self._lib.trx_scene_set_vertex_normals(self._h, _ptr(nr), nr.shape[0]))
+
+    def get_vertex_normals(self):
+        """[n_tris, 9] f32 as set, bit for bit; refused on a scene without a table."""
+        out = np.zeros((self.flat.tri_verts.shape[0], 9), dtype=np.float32)
+        L.check(self._lib.trx_scene_get_vertex_normals(self._h, _ptr(out), out.shape[0]))
+        return out
+
     def refit(self, tri_verts):
         """New vertices for every triangle record, in record order ([n_tris, 9] f32; record_order_verts maps object-order
         vertices): trx_scene_refit for a numpy array, trx_scene_refit_dev on torch.cuda.current_stream() for a tensor on
@@ -695,6 +735,36 @@ class Scene:
                                                   shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius, depth_tol, normal_cos,
                                                   bounce_samples, bounce_eps, bounce_filter_levels, bounce_depth_tol, bounce_normal_cos,
                                                   bounce_stride, bounce_phase, bounce_upsample_radius, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
+    def render_image_lit_smooth(self, view, width, height, lights, sem=L.SEM_HLSL, ray_mask=0, frame0=0, light_samples=1, shadow_eps=0.01,
+                                ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"), filter_radius=0, depth_tol=0.02,
+                                normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_lit_smooth - render_image_lit with the shading-normal pass
+        after the attribute pass: the light term and the AO filter read the interpolated vertex normals (set_vertex_normals),
+        every ray is still built from the geometric normal."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_lit_smooth(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0,
+                                                      light_samples, shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius,
+                                                      depth_tol, normal_cos, _ptr(rgba), C.byref(ms)))
+        return rgba, ms.value
+
+    def render_image_colour_smooth(self, view, width, height, lights, bounce_samples=0, bounce_stride=1, bounce_phase=0,
+                                   bounce_upsample_radius=1, bounce_filter_levels=0, bounce_depth_tol=0.1, bounce_normal_cos=0.9,
+                                   bounce_eps=0.01, sem=L.SEM_HLSL, ray_mask=0, frame0=0, light_samples=1, shadow_eps=0.01, ambient=0.0,
+                                   ao_samples=0, ao_eps=0.01, ao_radius=float("inf"), filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_colour_smooth - render_image_colour with the shading-normal
+        pass after the attribute pass (the light term, the filters and the upsample read the interpolated vertex normals)."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_colour_smooth(self._h, C.byref(view), width, height, sem, ray_mask, arr, len(arr), frame0,
+                                                         light_samples, shadow_eps, ambient, ao_samples, ao_eps, ao_radius, filter_radius,
+                                                         depth_tol, normal_cos, bounce_samples, bounce_eps, bounce_filter_levels,
+                                                         bounce_depth_tol, bounce_normal_cos, bounce_stride, bounce_phase,
+                                                         bounce_upsample_radius, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
     def render_image_colour_emitters(self, view, width, height, lights=(), emitter_samples=4, emitter_eps=0.001, bounce_samples=0,
@@ -1092,6 +1162,19 @@ class Scene:
         L.check(self._lib.trx_hit_attributes_primary_dev(self._h, C.byref(view), width, height, L.Shard(*shard),
                                                          C.c_void_p(d_hits), C.c_void_p(d_inst), C.c_void_p(d_attr),
                                                          C.c_void_p(stream)))
+
+    def shading_normals_rays(self, d_rays, n, d_hits, d_attr, d_out, d_inst=0, stream=0):
+        """trx_shading_normals_rays_dev: the n attribute records d_attr (device pointers throughout) with their normal replaced
+        by the interpolated vertex normal where the header's rule adopts it, at d_out (may be d_attr); d_inst as for the
+        attribute pass.  Refused on a scene without vertex normals."""
+        L.check(self._lib.trx_shading_normals_rays_dev(self._h, C.c_void_p(d_rays), n, C.c_void_p(d_hits), C.c_void_p(d_inst),
+                                                       C.c_void_p(d_attr), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def shading_normals_primary(self, view, width, height, d_hits, d_attr, d_out, d_inst=0, shard=(0, 1), stream=0):
+        """trx_shading_normals_primary_dev: the same for a primary frame's records, laid out as the trace wrote them
+        (shard = (index, count) or (index, count, layout))."""
+        L.check(self._lib.trx_shading_normals_primary_dev(self._h, C.byref(view), width, height, L.Shard(*shard), C.c_void_p(d_hits),
+                                                          C.c_void_p(d_inst), C.c_void_p(d_attr), C.c_void_p(d_out), C.c_void_p(stream)))
 
     def ao_filter_dev(self, width, height, d_primary, d_unoccluded, d_term, n_samples, radius, depth_tol=0.02, normal_cos=0.9,
                       d_attr=0, stream=0):
