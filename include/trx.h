@@ -1025,7 +1025,9 @@ int trx_render_image_gi_sparse(trx_scene *scene, const trx_view *view, uint32_t 
  * emission component that is negative or not finite.  Every index is checked here, so no kernel reads past the material
  * table.  Both tables are owned like the instance mask table: counted by trx_scene_device_bytes (24 B per material, 2 B per
  * triangle), kept by a refit, released by trx_scene_destroy; a second call replaces them after waiting for the scene's
- * launches in flight, which see the old tables in full; a refused call leaves the old tables in force.
+ * launches in flight, which see the old tables in full; a refused call leaves the old tables in force.  A call whose
+ * n_materials differs from the table it replaces also drops the scene's texture set (trx_scene_set_textures, below), which is
+ * keyed by material.
  * trx_scene_get_materials: *inout_n_materials holds the capacity of out_materials on entry and the table's size on return;
  * refused on a scene without materials, with a capacity below the size, or with n_tris different from the scene's.
  * Every colour entry point below is refused with TRX_ERR_INVALID on a scene without materials. */
@@ -1397,6 +1399,162 @@ int trx_compute_vertex_normals(const float *verts, uint64_t n_tris, float crease
  * TRX_ERR_INVALID: a `vn` with a component that is not finite, null arguments; TRX_ERR_IO: an unreadable model. */
 int trx_load_model_normals(const char *path, float **out_verts, uint64_t *out_n_tris, uint64_t **out_object_counts,
                            uint32_t *out_n_objects, float **out_normals, uint32_t *out_has_normals);
+
+/* ---- texture coordinates and albedo textures: the surface's colour from an image ------------------------------------------------------
+ * Above, a triangle's albedo is its material's, flat.  This section gives a scene a table of texture coordinates keyed by
+ * trx_hit.prim, a set of RGBA8 textures keyed by material, a pass that writes the albedo of every hit record - the material's,
+ * times the texture sampled at the hit's interpolated coordinates - and a compose that reads that albedo in place of the
+ * material's.  Purely additive: every call above computes what it computed, with or without these tables on the scene.
+ *
+ * THE TEXCOORD TABLE.  uvs holds six floats per triangle, (s0, t0, s1, t1, s2, t2): the coordinates of vertices 0, 1 and 2 of
+ * triangle i of the scene's own order - the `prim` a hit record carries.  They are object-space: the instances of a BLAS share
+ * them, and neither a view nor an instance id is needed to use them.  Any float is legal, non-finite ones included: THE TEXTURED
+ * ALBEDO below handles them.  uvs == NULL or n_tris == 0 removes the table.  24 B per triangle on the device, counted by
+ * trx_scene_device_bytes.  Owned exactly like the vertex normals: the swap waits for every launch slot's last kernel, so a pass
+ * enqueued before the call uses the old table in full; trx_scene_refit keeps the table; it goes with the scene.
+ * trx_scene_get_texcoords returns the caller's floats bit for bit.  Refused (TRX_ERR_INVALID): a null scene, n_tris different
+ * from the scene's; the getter also on a scene without a table, and with a null output. */
+int trx_scene_set_texcoords(trx_scene *scene, const float *uvs, uint64_t n_tris);
+int trx_scene_get_texcoords(const trx_scene *scene, float *out_uvs, uint64_t n_tris);
+
+/* THE TEXTURE SET.  descs names n_textures textures; texels is one array of n_texels RGBA8 words (R in the low byte, then G, B,
+ * A), the textures back to back in descriptor order, each row-major, row 0 being the row at t = 0 (a loader of top-down image
+ * files flips the rows).  material_texture[m] is the texture of material m, or TRX_NO_TEXTURE.  Everything is validated on the
+ * host before anything is copied, so that no kernel needs a bound on an index (as with tri_material).  Refused
+ * (TRX_ERR_INVALID), the old set left in force: null arguments; a scene without materials; n_materials different from the
+ * scene's; an index >= n_textures that is not TRX_NO_TEXTURE; a width or height outside 1..TRX_MAX_TEXTURE_SIZE; n_textures
+ * outside 1..TRX_MAX_TEXTURES; n_texels different from the sum of width * height, or >= 2^31; an unknown format or filter.
+ * On the device: a 16-byte descriptor per texture {offset of its first texel, width, height, format | filter << 8}, the texel
+ * words, the per-material index and the 256 floats of trx_texture_srgb_table - all counted by trx_scene_device_bytes.  Owned
+ * like the materials (swap under the launch mutex, the old set freed after every launch slot's last kernel, kept by a refit).
+ * The set is keyed by material: a later trx_scene_set_materials with a different n_materials drops it (one with the same
+ * count keeps it).  trx_scene_remove_textures drops it.  trx_scene_get_textures returns what was set, bit for bit:
+ * *inout_n_textures, *inout_n_texels and *inout_n_materials hold the capacities of the three arrays on entry and the counts on
+ * return; refused on a scene without a set, with null arguments or with too little room (the counts are still returned). */
+typedef struct trx_texture_desc {
+    uint32_t width, height;
+    uint32_t format; /* TRX_TEX_RGBA8_UNORM / TRX_TEX_RGBA8_SRGB */
+    uint32_t filter; /* TRX_TEX_NEAREST / TRX_TEX_BILINEAR */
+} trx_texture_desc;
+#define TRX_TEX_RGBA8_UNORM 0u
+#define TRX_TEX_RGBA8_SRGB 1u
+#define TRX_TEX_NEAREST 0u
+#define TRX_TEX_BILINEAR 1u
+#define TRX_NO_TEXTURE 0xFFFFFFFFu
+#define TRX_MAX_TEXTURE_SIZE 8192u
+#define TRX_MAX_TEXTURES 65535u
+int trx_scene_set_textures(trx_scene *scene, const trx_texture_desc *descs, uint32_t n_textures, const uint32_t *texels,
+                           uint64_t n_texels, const uint32_t *material_texture, uint32_t n_materials);
+int trx_scene_get_textures(const trx_scene *scene, trx_texture_desc *out_descs, uint32_t *inout_n_textures, uint32_t *out_texels,
+                           uint64_t *inout_n_texels, uint32_t *out_material_texture, uint32_t *inout_n_materials);
+int trx_scene_remove_textures(trx_scene *scene);
+
+/* The sRGB decode table: out[c] for c = 0..255, with x = c / 255 in binary64, is x / 12.92 for x <= 0.04045 and
+ * pow((x + 0.055) / 1.055, 2.4) otherwise, computed in binary64 and rounded once to float. */
+void trx_texture_srgb_table(float out[256]);
+
+/* THE TEXTURED ALBEDO.  Every operation is rounded once in binary32, no contraction.
+ *  Which records.  A record is a surface record if t < FLT_MAX, prim != 0xFFFFFFFF and prim < n_tris.  Any other record is
+ *  background: +0.0f in all three planes.  For a surface record m = tri_material[prim], T = material_texture[m], and
+ *  A_c = albedo_c(m) exactly when the scene has no texcoord table, no texture set, or T is TRX_NO_TEXTURE.
+ *  Interpolation and wrap.  Otherwise, with u, v of the record's trx_hit_attr and (s0, t0, s1, t1, s2, t2) of triangle prim:
+ *  w = (1.0f - u) - v, s = (w * s0 + u * s1) + v * s2 and t = (w * t0 + u * t1) + v * t2 (the association of THE SHADING
+ *  NORMAL).  If s or t is not finite, A_c = albedo_c(m).  The wrap is repeat: fs = s - floorf(s); if fs >= 1.0f (a tiny
+ *  negative s, whose subtraction rounds to 1) fs = 0.0f.  ft likewise from t.  W, H = the texture's width and height.
+ *  Nearest.  ix = min((uint32_t)(fs * (float)W), W - 1), iy = min((uint32_t)(ft * (float)H), H - 1); one tap, val_c its channel.
+ *  Bilinear.  x = fs * (float)W - 0.5f, x0 = floorf(x), fx = x - x0, ix0 = (int)x0, ix1 = ix0 + 1; ix0 == -1 becomes W - 1 and
+ *  ix1 == W becomes 0.  y, y0, fy, iy0, iy1 the same from ft and H.  With c00 = the channel of tap (ix0, iy0), c10 of
+ *  (ix1, iy0), c01 of (ix0, iy1), c11 of (ix1, iy1): top = c00 + fx * (c10 - c00), bot = c01 + fx * (c11 - c01),
+ *  val_c = top + fy * (bot - top).
+ *  Texel decode.  Tap (ix, iy) is word offset + iy * W + ix of the texel array; its channel byte c8 (R bits 0..7, G 8..15,
+ *  B 16..23) decodes as (float)c8 / 255.0f (one IEEE division) for TRX_TEX_RGBA8_UNORM and as trx_texture_srgb_table's entry
+ *  c8 for TRX_TEX_RGBA8_SRGB.  Alpha is read and ignored.
+ *  The albedo.  A_c = albedo_c(m) * val_c.
+ * trx_surface_albedo_dev writes A_c of n_records records in any layout - d_hits and d_attr as a trace and its attribute pass
+ * (or a caller) wrote them; it is elementwise - into three planes, plane c at c * n_records.  u and v are used as they are,
+ * whatever they hold (CALLER RECORDS, above: a record whose prim is no triangle of the scene is background, every index formed
+ * from a record stays inside its table).  It takes a launch slot as the attribute pass does: a table swap or a refit called
+ * afterwards waits for it.  Texcoords and textures are optional: without them it writes the plain albedo.  Refused
+ * (TRX_ERR_INVALID): null arguments, n_records == 0 or beyond 2^31 - 1, a scene without materials. */
+int trx_surface_albedo_dev(trx_scene *scene, const trx_hit *d_hits, const trx_hit_attr *d_attr, uint64_t n_records,
+                           float *d_albedo_rgb, void *stream);
+
+/* trx_material_compose_dev with albedo_c(m) read from an albedo plane: for a surface record (the same rule)
+ * colour_c = emission_c(m) + A_c * (E + I_c), A_c = d_albedo_rgb[c * n_records + r] - the same association, each operation
+ * rounded once; emission_c(m) + A_c * E with d_indirect_rgb == NULL; +0.0f in all three planes for any other record.
+ * d_colour_rgb may be d_indirect_rgb: each lane reads before it writes.  On planes trx_surface_albedo_dev wrote for a scene
+ * without a texture set this is trx_material_compose_dev bit for bit.  Refusals as trx_material_compose_dev, plus a null
+ * albedo plane. */
+int trx_albedo_compose_dev(trx_scene *scene, const trx_hit *d_primary, const float *d_albedo_rgb, const float *d_direct,
+                           const float *d_indirect_rgb, uint64_t n_records, float *d_colour_rgb, void *stream);
+
+/* THE TEXTURED RGB INDIRECT TERM.  One entry point for the four RGB modes of the indirect pass, with albedo_c(m) of rules 5c
+ * and 5e replaced by A_c of THE TEXTURED ALBEDO sampled at the bounce hit: prim = bounce_hit_f.prim, u and v those of the
+ * bounce hit's attribute record (what trx_hit_attributes_rays_dev writes for the bounce ray, its hit and its instance id).
+ * The rules are otherwise word for word: 5c is A_c = A_c + (A_c(bounce f) * s_f + emission_c(m)), 5e is
+ * A_c = A_c + A_c(bounce f) * (s_f + X_c).  Bounce rays, hits, shadow rays, s_f, wgeo and the selected emitters are the
+ * existing passes' bit for bit; only the gather differs, and on a scene without a texcoord table or without a texture set the
+ * pass runs the existing kernels and is the existing entry point bit for bit.
+ *  stride       1: the dense pass over `shard` (trx_trace_indirect_rgb_dev's layout and planes); 2..TRX_MAX_AO_STRIDE: the
+ *               sparse pass at (stride, phase) over the whole image - shard must be {0, 1, TRX_LAYOUT_IMAGE} - with
+ *               trx_trace_indirect_rgb_sparse_dev's low-grid planes.  phase < stride * stride (0 with stride 1).
+ *  use_emitters 0: rule 5c, emitter_eps is ignored and n_lights >= 1; 1: rule 5e with emitter_eps, n_lights may be 0 and the
+ *               scene needs a current emitter table.  Anything else is refused.
+ * It refuses what the corresponding existing entry point refuses. */
+int trx_trace_indirect_rgb_textured_dev(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, trx_shard shard,
+                                        uint32_t stride, uint32_t phase, uint32_t semantics, uint32_t ray_mask,
+                                        const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples,
+                                        float bounce_eps, float shadow_eps, uint32_t use_emitters, float emitter_eps,
+                                        const trx_hit *d_primary, const uint32_t *d_primary_inst, float *d_value_rgb,
+                                        void *stream);
+
+/* trx_render_image_colour, _colour_smooth and _colour_emitters in one call, textured (synchronous).  emitter_samples == 0
+ * means no emitter sampling (trx_render_image_colour's chain; n_lights >= 1, emitter_eps ignored), otherwise
+ * trx_render_image_colour_emitters' chain; smooth (0 / 1) inserts trx_shading_normals_primary_dev after the attribute pass as
+ * trx_render_image_colour_smooth does.  Three changes to those chains: trx_surface_albedo_dev runs after the attribute pass
+ * (u and v are the same with or without shading normals); the indirect pass is trx_trace_indirect_rgb_textured_dev; the
+ * compose is trx_albedo_compose_dev.  The albedo multiplies in the compose, after upsample and filter, so a textured primary
+ * albedo stays sharp at any bounce_stride.  On a scene without texcoords or textures the image is the untextured call's byte
+ * for byte.  Refusals: those of the chain it stands for, and smooth > 1. */
+int trx_render_image_colour_textured(trx_scene *scene, const trx_view *view, uint32_t width, uint32_t height, uint32_t semantics,
+                                     uint32_t ray_mask, const trx_light *lights, uint32_t n_lights, uint32_t frame0,
+                                     uint32_t light_samples, float shadow_eps, float ambient, uint32_t ao_samples, float ao_eps,
+                                     float ao_radius, uint32_t filter_radius, float depth_tol, float normal_cos,
+                                     uint32_t bounce_samples, float bounce_eps, uint32_t bounce_filter_levels,
+                                     float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride,
+                                     uint32_t bounce_phase, uint32_t bounce_upsample_radius, uint32_t emitter_samples,
+                                     float emitter_eps, uint32_t smooth, uint8_t *out_rgba, float *out_ms);
+
+/* Stand-in tables for the generated scenes (host; trx_free'd by the caller).
+ * trx_standin_texcoords: box mapping of the mesh as given (verts: n_tris x 9 floats, out_uvs: n_tris x 6).  Per triangle, in
+ * binary32 without contraction: e1 = v1 - v0, e2 = v2 - v0, n = cross(e1, e2) (n.x = e1.y * e2.z - e1.z * e2.y and cyclic); the
+ * dominant axis is the one with the largest |n| component, ties going to the lower axis (a NaN component loses to any number; all NaN: x); (s, t) of
+ * each corner are its other two coordinates in ascending axis order (axis x: (y, z); y: (x, z); z: (x, y)), bit for bit.  The
+ * name is not looked at today.
+ * trx_standin_textures: one 64 x 64 TRX_TEX_RGBA8_UNORM, TRX_TEX_BILINEAR checker - texel (x, y) has R = G = B = 255 where
+ * ((x >> 3) + (y >> 3)) & 1, otherwise 128, alpha 255 - attached to material 0 only (every other material: TRX_NO_TEXTURE).
+ * Refused (TRX_ERR_INVALID): null arguments, n_materials == 0. */
+int trx_standin_texcoords(const char *name, const float *verts, uint64_t n_tris, float *out_uvs);
+int trx_standin_textures(const char *name, uint32_t n_materials, trx_texture_desc **out_descs, uint32_t *out_n_textures,
+                         uint32_t **out_texels, uint64_t *out_n_texels, uint32_t **out_material_texture);
+
+/* trx_load_model with the model's texture coordinates: the same verts and object counts, byte for byte, plus six floats per
+ * triangle in that triangle order, (s0, t0, s1, t1, s2, t2) (all trx_free'd by the caller).  OBJ: `vt` records are read (two
+ * numbers; a missing second one is +0; nothing is refused - any float is a legal texcoord); the second index of a face corner's
+ * v/vt or v/vt/vn names one, relative to the `vt` records read so far when negative.  A corner with no such index (v, v//vn), or
+ * with one out of range at that point of the file, gets +0, +0.  A quad's two triangles take corners 0,1,2 and 0,2,3, as for
+ * positions.  A JSON model gets +0 everywhere.  *out_has_texcoords is 1 when any corner got a `vt`, else 0.  Refused with
+ * TRX_ERR_INVALID: null arguments; TRX_ERR_IO: an unreadable model. */
+int trx_load_model_texcoords(const char *path, float **out_verts, uint64_t *out_n_tris, uint64_t **out_object_counts,
+                             uint32_t *out_n_objects, float **out_uvs, uint32_t *out_has_texcoords);
+
+/* The `map_Kd` file name of every material of the model, in trx_load_model_materials' material order: *out_names (trx_free'd by
+ * the caller) holds *out_n_materials NUL-terminated strings back to back.  An empty string means the material names no map;
+ * material 0, the default, never does; a JSON model or an OBJ without readable mtl files gives one empty string.  The name is
+ * the last blank-separated word of the `map_Kd` line as it stands in the file (relative to the OBJ's directory by convention):
+ * options before it (-s 1 1 1, -clamp on, ...) are skipped, and the last `map_Kd` of a material wins.  The library opens no image
+ * file: decoding is the caller's (the command line's --textures).  Refusals as trx_load_model_materials. */
+int trx_load_model_material_maps(const char *path, char **out_names, uint32_t *out_n_materials);
 
 /* Status of the most recent trace on this scene (stack overflow is detected
  * in-kernel and latched in device memory).  Synchronises `stream`. */

@@ -244,6 +244,23 @@ SIGNATURES = {
     "trx_compute_vertex_normals": (_i, [_P, _u64, _f, _P]),
     "trx_load_model_normals": (_i, [C.c_char_p, C.POINTER(C.POINTER(_f)), C.POINTER(_u64), C.POINTER(C.POINTER(_u64)), C.POINTER(_u32),
                                     C.POINTER(C.POINTER(_f)), C.POINTER(_u32)]),
+    "trx_scene_set_texcoords": (_i, [_P, _P, _u64]),
+    "trx_scene_get_texcoords": (_i, [_P, _P, _u64]),
+    "trx_scene_set_textures": (_i, [_P, _P, _u32, _P, _u64, _P, _u32]),
+    "trx_scene_get_textures": (_i, [_P, _P, C.POINTER(_u32), _P, C.POINTER(_u64), _P, C.POINTER(_u32)]),
+    "trx_scene_remove_textures": (_i, [_P]),
+    "trx_texture_srgb_table": (None, [_P]),
+    "trx_surface_albedo_dev": (_i, [_P, _P, _P, _u64, _P, _P]),
+    "trx_albedo_compose_dev": (_i, [_P, _P, _P, _P, _P, _u64, _P, _P]),
+    "trx_trace_indirect_rgb_textured_dev": (_i, [_P, C.POINTER(View), _u32, _u32, Shard, _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f,
+                                                 _u32, _f, _P, _P, _P, _P]),
+    "trx_render_image_colour_textured": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _u32, _f, _f, _u32,
+                                              _f, _f, _u32, _f, _u32, _f, _f, _u32, _u32, _u32, _u32, _f, _u32, _P, C.POINTER(_f)]),
+    "trx_standin_texcoords": (_i, [C.c_char_p, _P, _u64, _P]),
+    "trx_standin_textures": (_i, [C.c_char_p, _u32, C.POINTER(_P), C.POINTER(_u32), C.POINTER(_P), C.POINTER(_u64), C.POINTER(_P)]),
+    "trx_load_model_texcoords": (_i, [C.c_char_p, C.POINTER(C.POINTER(_f)), C.POINTER(_u64), C.POINTER(C.POINTER(_u64)), C.POINTER(_u32),
+                                      C.POINTER(C.POINTER(_f)), C.POINTER(_u32)]),
+    "trx_load_model_material_maps": (_i, [C.c_char_p, C.POINTER(_P), C.POINTER(_u32)]),
     "trx_debug_indirect_phases": (_i, [_P, C.POINTER(View), _u32, _u32, _u32, _u32, _P, _u32, _u32, _u32, _f, _f, _f, _P, _P, _P, _P,
                                        C.POINTER(_f)]),
     "trx_debug_ao_scratch_cap": (_u64, [_u64]),

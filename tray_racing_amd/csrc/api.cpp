@@ -298,6 +298,10 @@ uint64_t trx_scene_device_bytes(const trx_scene *s) {
     bytes += s->materials.count() * sizeof(trx_material) + s->tri_material.count() * sizeof(uint16_t);
     bytes += s->emitters.count() * sizeof(float4) + s->emitter_cdf.count() * sizeof(float); // the emitter table (trx_scene_build_emitters; swapped under mu)
     bytes += s->vertex_normals.count() * sizeof(float4); // the vertex normals, 48 B per triangle (trx_scene_set_vertex_normals; swapped under mu)
+    bytes += s->texcoords.count() * sizeof(float2); // the texture coordinates, 24 B per triangle (trx_scene_set_texcoords; swapped under mu)
+    // the texture set (trx_scene_set_textures; swapped under mu): descriptors, texels, the per-material index, the sRGB table
+    bytes += s->tex_descs.count() * sizeof(uint4) + (s->texels.count() + s->material_texture.count()) * sizeof(uint32_t) +
+             s->tex_srgb.count() * sizeof(float);
     bytes += s->image_thr.count() * sizeof(float); // the shade's code thresholds (api_image.cpp)
     for (const Slot &sl : s->slots) {
         bytes += sl.spill.count() * sizeof(uint2) + sl.ctr.count() * sizeof(SlotCounters);
@@ -341,6 +345,31 @@ static hipError_t retire(DevBuf<T> &old, hipError_t waited) {
     else (void)old.release();
     return waited;
 }
+
+// A scene's texture set (trx_scene_set_textures) on its way in or out: the four device tables, which are swapped and retired
+// together.  Call take_from / give_to with s->mu held.
+struct TextureSet {
+    DevBuf<uint4> descs;
+    DevBuf<uint32_t> texels, material_texture;
+    DevBuf<float> srgb;
+    std::vector<trx_texture_desc> h_descs;
+    std::vector<uint32_t> h_texels, h_material_texture;
+    void take_from(trx_scene *s) { // (no-throw: moves and swaps only; the scene is left without a set)
+        descs = std::move(s->tex_descs), texels = std::move(s->texels);
+        material_texture = std::move(s->material_texture), srgb = std::move(s->tex_srgb);
+        h_descs.swap(s->h_tex_descs), h_texels.swap(s->h_texels), h_material_texture.swap(s->h_material_texture);
+        s->h_tex_descs.clear(), s->h_texels.clear(), s->h_material_texture.clear();
+    }
+    void give_to(trx_scene *s) {
+        s->tex_descs = std::move(descs), s->texels = std::move(texels);
+        s->material_texture = std::move(material_texture), s->tex_srgb = std::move(srgb);
+        s->h_tex_descs.swap(h_descs), s->h_texels.swap(h_texels), s->h_material_texture.swap(h_material_texture);
+    }
+    hipError_t retire_all(hipError_t waited) {
+        (void)retire(descs, waited), (void)retire(texels, waited), (void)retire(material_texture, waited);
+        return retire(srgb, waited);
+    }
+};
 
 extern "C" {
 
@@ -531,6 +560,7 @@ int trx_scene_set_materials(trx_scene *s, const trx_material *materials, uint32_
     // old tables in full.
     DevBuf<trx_material> old_mat;
     DevBuf<uint16_t> old_idx;
+    TextureSet old_tex;
     e = hipSuccess;
     {
         std::lock_guard<std::mutex> lock(s->mu);
@@ -541,10 +571,13 @@ int trx_scene_set_materials(trx_scene *s, const trx_material *materials, uint32_
         s->h_materials.swap(host_mat);
         s->h_tri_material.swap(host_idx);
         s->emitters_stale = true; // (the emitter table was chosen by, and indexes, the old materials)
+        // (the texture set is keyed by material: one index per material of the table it was set for)
+        if (s->material_texture && s->h_material_texture.size() != n_materials) old_tex.take_from(s);
         if (old_mat)
             for (Slot &sl : s->slots)
                 if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
     }
+    (void)old_tex.retire_all(e);
     (void)retire(old_idx, e);
     if (retire(old_mat, e) != hipSuccess) // (the old tables are kept rather than freed under a kernel that may still read them)
         return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
@@ -622,6 +655,175 @@ int trx_scene_get_vertex_normals(const trx_scene *s, float *out_normals, uint64_
     if (n_tris != s->n_tris)
         return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
     if (n_tris) std::memcpy(out_normals, s->h_vertex_normals.data(), (size_t)n_tris * 9 * sizeof(float));
+    return TRX_OK;
+}
+
+// Texture coordinates (include/trx.h, "texture coordinates and albedo textures"): read by the albedo pass under s->mu, owned
+// like the vertex normals.  Any float is legal: the sampling rule handles what is not finite.
+int trx_scene_set_texcoords(trx_scene *s, const float *uvs, uint64_t n_tris) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    const bool remove = !uvs || n_tris == 0;
+    if (!remove && n_tris != s->n_tris)
+        return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<float> host_copy;
+    DevBuf<float2> fresh;
+    if (!remove) {
+        try {
+            host_copy.assign(uvs, uvs + n_tris * 6);
+        } catch (const std::exception &) {
+            return fail(TRX_ERR_OOM, "host allocation failed");
+        }
+        HIP_TRY(fresh.alloc(n_tris * 3));
+        const hipError_t e = hipMemcpy(fresh.get(), host_copy.data(), host_copy.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the texture coordinates failed: %s", hipGetErrorString(e));
+    }
+    // Swapped under the launch mutex (the albedo pass reads the pointer there); the old table is freed once every launch
+    // slot's last kernel has finished - trx_scene_set_instance_masks' statement.
+    DevBuf<float2> old;
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        old = std::move(s->texcoords);
+        s->texcoords = std::move(fresh);
+        s->h_texcoords.swap(host_copy);
+        if (old)
+            for (Slot &sl : s->slots)
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
+    }
+    if (retire(old, e) != hipSuccess) // (the old table is kept rather than freed under a kernel that may still read it)
+        return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    return TRX_OK;
+}
+
+int trx_scene_get_texcoords(const trx_scene *s, float *out_uvs, uint64_t n_tris) {
+    if (!s || !out_uvs) return fail(TRX_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
+    if (!s->texcoords) return fail(TRX_ERR_INVALID, "the scene has no texture coordinates (trx_scene_set_texcoords)");
+    if (n_tris != s->n_tris)
+        return fail(TRX_ERR_INVALID, "n_tris %llu: the scene has %llu triangles", (unsigned long long)n_tris, (unsigned long long)s->n_tris);
+    if (n_tris) std::memcpy(out_uvs, s->h_texcoords.data(), (size_t)n_tris * 6 * sizeof(float));
+    return TRX_OK;
+}
+
+void trx_texture_srgb_table(float out[256]) {
+    if (!out) return;
+    for (int c = 0; c < 256; c++) {
+        const double x = (double)c / 255.0;
+        out[c] = (float)(x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4));
+    }
+}
+
+// The texture set (include/trx.h, "THE TEXTURE SET"): everything a kernel will index is checked here, on the host, before
+// anything is copied; the four device tables are swapped together under s->mu and owned like the materials.
+int trx_scene_set_textures(trx_scene *s, const trx_texture_desc *descs, uint32_t n_textures, const uint32_t *texels, uint64_t n_texels,
+                           const uint32_t *material_texture, uint32_t n_materials) {
+    if (!s || !descs || !texels || !material_texture) return fail(TRX_ERR_INVALID, "null argument");
+    if (n_textures == 0 || n_textures > TRX_MAX_TEXTURES) return fail(TRX_ERR_INVALID, "n_textures %u outside 1..%u", n_textures, TRX_MAX_TEXTURES);
+    uint64_t sum = 0;
+    for (uint32_t k = 0; k < n_textures; k++) {
+        const trx_texture_desc &d = descs[k];
+        if (d.width == 0 || d.width > TRX_MAX_TEXTURE_SIZE || d.height == 0 || d.height > TRX_MAX_TEXTURE_SIZE)
+            return fail(TRX_ERR_INVALID, "texture %u: %u x %u texels outside 1..%u", k, d.width, d.height, TRX_MAX_TEXTURE_SIZE);
+        if (d.format != TRX_TEX_RGBA8_UNORM && d.format != TRX_TEX_RGBA8_SRGB) return fail(TRX_ERR_INVALID, "texture %u: unknown format %u", k, d.format);
+        if (d.filter != TRX_TEX_NEAREST && d.filter != TRX_TEX_BILINEAR) return fail(TRX_ERR_INVALID, "texture %u: unknown filter %u", k, d.filter);
+        sum += (uint64_t)d.width * d.height; // (at most 65535 * 2^26: no overflow)
+    }
+    if (n_texels != sum) return fail(TRX_ERR_INVALID, "n_texels %llu: the descriptors hold %llu texels", (unsigned long long)n_texels, (unsigned long long)sum);
+    if (n_texels >= 0x80000000ull) return fail(TRX_ERR_INVALID, "n_texels %llu: beyond 2^31 - 1", (unsigned long long)n_texels);
+    for (uint32_t m = 0; m < n_materials; m++)
+        if (material_texture[m] != TRX_NO_TEXTURE && material_texture[m] >= n_textures)
+            return fail(TRX_ERR_INVALID, "material %u: texture index %u of %u textures", m, material_texture[m], n_textures);
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu); // (trx_scene_set_materials holds it too: the count below stays)
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        if (s->h_materials.empty()) return fail(TRX_ERR_INVALID, "the scene has no materials (trx_scene_set_materials)");
+        if (n_materials != s->h_materials.size())
+            return fail(TRX_ERR_INVALID, "n_materials %u: the scene has %zu materials", n_materials, s->h_materials.size());
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    TextureSet fresh;
+    std::vector<uint4> dev_descs;
+    float srgb[256];
+    trx_texture_srgb_table(srgb);
+    try {
+        fresh.h_descs.assign(descs, descs + n_textures);
+        fresh.h_texels.assign(texels, texels + n_texels);
+        fresh.h_material_texture.assign(material_texture, material_texture + n_materials);
+        dev_descs.resize(n_textures);
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "host allocation failed");
+    }
+    uint32_t offset = 0;
+    for (uint32_t k = 0; k < n_textures; k++) {
+        const trx_texture_desc &d = fresh.h_descs[k];
+        dev_descs[k] = make_uint4(offset, d.width, d.height, d.format | d.filter << 8);
+        offset += d.width * d.height;
+    }
+    HIP_TRY(fresh.descs.alloc(n_textures));
+    HIP_TRY(fresh.texels.alloc(n_texels));
+    HIP_TRY(fresh.material_texture.alloc(n_materials));
+    HIP_TRY(fresh.srgb.alloc(256));
+    // (uploaded from the validated host copies: what the kernels index is what was checked)
+    hipError_t e = hipMemcpy(fresh.descs.get(), dev_descs.data(), (size_t)n_textures * sizeof(uint4), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(fresh.texels.get(), fresh.h_texels.data(), (size_t)n_texels * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(fresh.material_texture.get(), fresh.h_material_texture.data(), (size_t)n_materials * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(fresh.srgb.get(), srgb, sizeof(srgb), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(TRX_ERR_NO_DEVICE, "upload of the textures failed: %s", hipGetErrorString(e));
+    TextureSet old;
+    e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        const bool had = (bool)s->material_texture;
+        old.take_from(s);
+        fresh.give_to(s);
+        if (had)
+            for (Slot &sl : s->slots)
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
+    }
+    if (old.retire_all(e) != hipSuccess) // (the old set is kept rather than freed under a kernel that may still read it)
+        return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    return TRX_OK;
+}
+
+int trx_scene_remove_textures(trx_scene *s) {
+    if (!s) return fail(TRX_ERR_INVALID, "null scene");
+    std::lock_guard<std::recursive_mutex> host_lock(s->host_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    TextureSet old;
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        const bool had = (bool)s->material_texture;
+        old.take_from(s);
+        if (had)
+            for (Slot &sl : s->slots)
+                if (sl.used && !sl.pinned && sl.done && e == hipSuccess) e = hipEventSynchronize(sl.done.get());
+    }
+    if (old.retire_all(e) != hipSuccess)
+        return fail(TRX_ERR_NO_DEVICE, "waiting for the scene's launches failed: %s", hipGetErrorString(e));
+    return TRX_OK;
+}
+
+int trx_scene_get_textures(const trx_scene *s, trx_texture_desc *out_descs, uint32_t *inout_n_textures, uint32_t *out_texels,
+                           uint64_t *inout_n_texels, uint32_t *out_material_texture, uint32_t *inout_n_materials) {
+    if (!s || !out_descs || !inout_n_textures || !out_texels || !inout_n_texels || !out_material_texture || !inout_n_materials)
+        return fail(TRX_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lock(const_cast<trx_scene *>(s)->mu);
+    if (!s->material_texture) return fail(TRX_ERR_INVALID, "the scene has no textures (trx_scene_set_textures)");
+    const bool room = *inout_n_textures >= s->h_tex_descs.size() && *inout_n_texels >= s->h_texels.size() &&
+                      *inout_n_materials >= s->h_material_texture.size();
+    *inout_n_textures = (uint32_t)s->h_tex_descs.size();
+    *inout_n_texels = s->h_texels.size();
+    *inout_n_materials = (uint32_t)s->h_material_texture.size();
+    if (!room)
+        return fail(TRX_ERR_INVALID, "too little room: the scene has %u textures, %llu texels, %u materials", *inout_n_textures,
+                    (unsigned long long)*inout_n_texels, *inout_n_materials);
+    std::memcpy(out_descs, s->h_tex_descs.data(), s->h_tex_descs.size() * sizeof(trx_texture_desc));
+    std::memcpy(out_texels, s->h_texels.data(), s->h_texels.size() * sizeof(uint32_t));
+    std::memcpy(out_material_texture, s->h_material_texture.data(), s->h_material_texture.size() * sizeof(uint32_t));
     return TRX_OK;
 }
 

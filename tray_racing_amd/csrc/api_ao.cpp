@@ -399,7 +399,7 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
                   const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps,
                   float albedo, const trx_hit *d_primary, const uint32_t *d_primary_inst, const float *d_base, float *d_value,
                   hipStream_t stream, BouncePhases *phases, const SparseGrid *sparse = nullptr, bool colour = false,
-                  const float *emitter_eps = nullptr) {
+                  const float *emitter_eps = nullptr, bool textured = false) {
     if (!s || !d_primary || !d_value) return fail(TRX_ERR_INVALID, "null argument");
     if (colour) { // (a table once set is only ever replaced: what holds here holds under the pass's lock below)
         std::lock_guard<std::mutex> lock(s->mu);
@@ -529,6 +529,15 @@ int indirect_impl(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, tr
         b.pick = slot->em_pick.get();
         b.has_lights = n_lights ? 1u : 0u;
         b.emitter_eps = *emitter_eps;
+    }
+    // textured (trx_trace_indirect_rgb_textured_dev): with both a texcoord table and a texture set on the scene the gather is
+    // k_bounce_gather_tex; with either missing the pointers stay null and the pass is the colour mode's, kernel for kernel
+    if (textured && colour && s->texcoords && s->material_texture) {
+        b.tex.texcoords = s->texcoords.get();
+        b.tex.descs = s->tex_descs.get();
+        b.tex.texels = s->texels.get();
+        b.tex.material_texture = s->material_texture.get();
+        b.tex.srgb = s->tex_srgb.get();
     }
     // one rays launch on the pass's slot (the slot is this stream's once the first kernel of the chunk is recorded)
     auto walk = [&](TraceParams &p) -> int {
@@ -922,6 +931,28 @@ int trx_trace_indirect_rgb_emitters_sparse_dev(trx_scene *s, const trx_view *vie
     const SparseGrid grid{stride, phase};
     return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
                          1.0f, d_primary, d_primary_inst, nullptr, d_value_rgb_lo, (hipStream_t)stream, nullptr, &grid, true, &emitter_eps);
+}
+
+// ---- the textured RGB indirect term (include/trx.h, "texture coordinates and albedo textures") -----------------------------------------
+
+// One entry point for the four RGB modes: stride 1 is the dense pass over `shard`, stride 2.. the sparse pass over the whole
+// image; use_emitters selects rule 5e.  Everything but the gather is the existing passes' (indirect_impl's `textured`).
+int trx_trace_indirect_rgb_textured_dev(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, trx_shard shard, uint32_t stride,
+                                        uint32_t phase, uint32_t sem, uint32_t ray_mask, const trx_light *lights, uint32_t n_lights,
+                                        uint32_t frame0, uint32_t n_samples, float bounce_eps, float shadow_eps, uint32_t use_emitters,
+                                        float emitter_eps, const trx_hit *d_primary, const uint32_t *d_primary_inst, float *d_value_rgb,
+                                        void *stream) {
+    if (use_emitters > 1u) return fail(TRX_ERR_INVALID, "use_emitters %u: must be 0 or 1", use_emitters);
+    if (int rc = check_sparse(stride, phase)) return rc;
+    const float *eps = use_emitters ? &emitter_eps : nullptr;
+    if (stride == 1u)
+        return indirect_impl(s, view, w, h, shard, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps, 1.0f, d_primary,
+                             d_primary_inst, nullptr, d_value_rgb, (hipStream_t)stream, nullptr, nullptr, true, eps, true);
+    if (shard.index != 0u || shard.count != 1u || shard.layout != TRX_LAYOUT_IMAGE)
+        return fail(TRX_ERR_INVALID, "stride %u: the sparse pass takes the whole image (shard {0, 1, TRX_LAYOUT_IMAGE})", stride);
+    const SparseGrid grid{stride, phase};
+    return indirect_impl(s, view, w, h, trx_shard{0, 1, 0, 0}, sem, ray_mask, lights, n_lights, frame0, n_samples, bounce_eps, shadow_eps,
+                         1.0f, d_primary, d_primary_inst, nullptr, d_value_rgb, (hipStream_t)stream, nullptr, &grid, true, eps, true);
 }
 
 // ---- development surface (include/trx_dev.h) ---------------------------------------------------------------------------

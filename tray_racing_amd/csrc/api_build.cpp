@@ -700,6 +700,59 @@ int trx_standin_materials(const char *name, const float *verts, uint64_t n_tris,
     return TRX_OK;
 }
 
+// Stand-in texture coordinates (include/trx.h, trx_standin_texcoords): box mapping - per triangle the two coordinates other
+// than the dominant axis of its face vector, in binary32 (this file is built without contraction).
+int trx_standin_texcoords(const char *name, const float *verts, uint64_t n_tris, float *out_uvs) {
+    if (!name || ((!verts || !out_uvs) && n_tris)) return fail(TRX_ERR_INVALID, "null argument");
+    for (uint64_t i = 0; i < n_tris; i++) {
+        const float *v = verts + i * 9;
+        const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]}, e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+        const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        int axis = 0;
+        float best = -1.0f;
+        for (int k = 0; k < 3; k++) {
+            const float mag = n[k] != n[k] ? -1.0f : std::fabs(n[k]); // (a NaN component loses to any number)
+            if (mag > best) best = mag, axis = k;
+        }
+        const int a = axis == 0 ? 1 : 0, b = axis == 2 ? 1 : 2;
+        for (int c = 0; c < 3; c++) {
+            out_uvs[i * 6 + 2 * c] = v[3 * c + a];
+            out_uvs[i * 6 + 2 * c + 1] = v[3 * c + b];
+        }
+    }
+    return TRX_OK;
+}
+
+// The stand-in texture set (trx_standin_textures): one 64 x 64 checker on material 0.
+int trx_standin_textures(const char *name, uint32_t n_materials, trx_texture_desc **out_descs, uint32_t *out_n_textures, uint32_t **out_texels,
+                         uint64_t *out_n_texels, uint32_t **out_material_texture) {
+    if (!name || !out_descs || !out_n_textures || !out_texels || !out_n_texels || !out_material_texture) return fail(TRX_ERR_INVALID, "null argument");
+    if (n_materials == 0) return fail(TRX_ERR_INVALID, "n_materials 0");
+    trx_texture_desc *d = static_cast<trx_texture_desc *>(std::calloc(1, sizeof(trx_texture_desc)));
+    uint32_t *tx = static_cast<uint32_t *>(std::calloc(64 * 64, sizeof(uint32_t)));
+    uint32_t *mt = static_cast<uint32_t *>(std::calloc(n_materials, sizeof(uint32_t)));
+    if (!d || !tx || !mt) {
+        std::free(d);
+        std::free(tx);
+        std::free(mt);
+        return fail(TRX_ERR_OOM, "host allocation failed");
+    }
+    *d = trx_texture_desc{64u, 64u, TRX_TEX_RGBA8_UNORM, TRX_TEX_BILINEAR};
+    for (uint32_t y = 0; y < 64u; y++)
+        for (uint32_t x = 0; x < 64u; x++) {
+            const uint32_t g = (((x >> 3) + (y >> 3)) & 1u) ? 255u : 128u;
+            tx[y * 64u + x] = g | g << 8 | g << 16 | 0xFF000000u;
+        }
+    mt[0] = 0u;
+    for (uint32_t m = 1; m < n_materials; m++) mt[m] = TRX_NO_TEXTURE;
+    *out_descs = d;
+    *out_n_textures = 1u;
+    *out_texels = tx;
+    *out_n_texels = 64u * 64u;
+    *out_material_texture = mt;
+    return TRX_OK;
+}
+
 int trx_scene_camera(const char *name, float eye[3], float look_at[3], float *fov) {
     if (!name || !eye || !look_at || !fov) return fail(TRX_ERR_INVALID, "null argument");
     if (!scene_camera(name, eye, look_at, fov)) return fail(TRX_ERR_INVALID, "unknown scene '%s'", name);
@@ -779,6 +832,57 @@ int trx_load_model_normals(const char *path, float **out_verts, uint64_t *out_n,
     }
     *out_normals = nrm;
     *out_has_normals = mn.any ? 1u : 0u;
+    return TRX_OK;
+}
+
+// trx_load_model with the model's texture coordinates (include/trx.h): the same loader call path once more.
+int trx_load_model_texcoords(const char *path, float **out_verts, uint64_t *out_n, uint64_t **out_counts, uint32_t *out_nobj,
+                             float **out_uvs, uint32_t *out_has_texcoords) {
+    if (!path || !out_verts || !out_n || !out_uvs || !out_has_texcoords) return fail(TRX_ERR_INVALID, "null argument");
+    std::vector<float> verts;
+    std::vector<uint64_t> objects;
+    ModelTexcoords mt;
+    try {
+        if (!load_model_texcoords(path, verts, objects, mt)) return fail(TRX_ERR_IO, "Error while loading model file \"%s\"", path);
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "out of memory loading '%s'", path);
+    }
+    float *uvs = static_cast<float *>(std::malloc(std::max<size_t>(mt.uvs.size() * sizeof(float), 4)));
+    if (!uvs) return fail(TRX_ERR_OOM, "host allocation failed");
+    if (!mt.uvs.empty()) std::memcpy(uvs, mt.uvs.data(), mt.uvs.size() * sizeof(float));
+    if (int rc = export_mesh(verts, objects, out_verts, out_n, out_counts, out_nobj)) {
+        std::free(uvs);
+        return rc;
+    }
+    *out_uvs = uvs;
+    *out_has_texcoords = mt.any ? 1u : 0u;
+    return TRX_OK;
+}
+
+// The map_Kd names of trx_load_model_materials' table (include/trx.h): NUL-separated, one per material.
+int trx_load_model_material_maps(const char *path, char **out_names, uint32_t *out_n_materials) {
+    if (!path || !out_names || !out_n_materials) return fail(TRX_ERR_INVALID, "null argument");
+    std::vector<std::string> maps;
+    std::string error;
+    try {
+        if (!load_model_material_maps(path, maps, error)) {
+            if (!error.empty()) return fail(TRX_ERR_INVALID, "%s: %s", path, error.c_str());
+            return fail(TRX_ERR_IO, "Error while loading model file \"%s\"", path);
+        }
+    } catch (const std::exception &) {
+        return fail(TRX_ERR_OOM, "out of memory loading '%s'", path);
+    }
+    size_t bytes = 0;
+    for (const std::string &m : maps) bytes += m.size() + 1;
+    char *out = static_cast<char *>(std::malloc(std::max<size_t>(bytes, 4)));
+    if (!out) return fail(TRX_ERR_OOM, "host allocation failed");
+    char *w = out;
+    for (const std::string &m : maps) {
+        std::memcpy(w, m.c_str(), m.size() + 1);
+        w += m.size() + 1;
+    }
+    *out_names = out;
+    *out_n_materials = (uint32_t)maps.size();
     return TRX_OK;
 }
 

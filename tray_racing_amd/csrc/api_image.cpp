@@ -687,6 +687,58 @@ int trx_shade_rgb_dev(trx_scene *s, const float *d_colour_rgb, uint64_t n, uint8
     });
 }
 
+// ---- the textured albedo (include/trx.h, "texture coordinates and albedo textures") ---------------------------------------------------
+
+// Both passes take a launch slot (enqueue_image): a swap of the materials, the texcoords or the texture set, and a refit,
+// called afterwards wait for the slot's `done` event.
+int trx_surface_albedo_dev(trx_scene *s, const trx_hit *d_hits, const trx_hit_attr *d_attr, uint64_t n, float *d_albedo_rgb, void *stream) {
+    if (!s || !d_hits || !d_attr || !d_albedo_rgb) return fail(TRX_ERR_INVALID, "null argument");
+    if (n == 0 || n > 0x7fffffffull) return fail(TRX_ERR_INVALID, "n_records %llu outside 1..2^31 - 1", (unsigned long long)n);
+    if (int rc = need_materials(s)) return rc;
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        SurfaceAlbedoParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.hits = d_hits;
+        p.attr = d_attr;
+        p.out = d_albedo_rgb;
+        p.materials = s->materials.get(); // (under s->mu: enqueue_image holds it)
+        p.tri_material = s->tri_material.get();
+        p.tex.texcoords = s->texcoords.get(); // (null without a table: the plain albedo)
+        if (s->material_texture) {
+            p.tex.descs = s->tex_descs.get();
+            p.tex.texels = s->texels.get();
+            p.tex.material_texture = s->material_texture.get();
+            p.tex.srgb = s->tex_srgb.get();
+        }
+        p.n_items = (uint32_t)n;
+        p.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull);
+        HIP_TRY(launch_surface_albedo(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
+int trx_albedo_compose_dev(trx_scene *s, const trx_hit *d_primary, const float *d_albedo_rgb, const float *d_direct,
+                           const float *d_indirect_rgb, uint64_t n, float *d_colour_rgb, void *stream) {
+    if (!s || !d_primary || !d_albedo_rgb || !d_direct || !d_colour_rgb) return fail(TRX_ERR_INVALID, "null argument");
+    if (n == 0 || n > 0x7fffffffull) return fail(TRX_ERR_INVALID, "n_records %llu outside 1..2^31 - 1", (unsigned long long)n);
+    if (int rc = need_materials(s)) return rc;
+    return enqueue_image(s, (hipStream_t)stream, false, [&]() -> int {
+        AlbedoComposeParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.primary = d_primary;
+        p.albedo = d_albedo_rgb;
+        p.direct = d_direct;
+        p.indirect = d_indirect_rgb;
+        p.out = d_colour_rgb;
+        p.materials = s->materials.get(); // (under s->mu: enqueue_image holds it)
+        p.tri_material = s->tri_material.get();
+        p.n_items = (uint32_t)n;
+        p.n_tris = (uint32_t)std::min<uint64_t>(s->n_tris, 0xffffffffull);
+        HIP_TRY(launch_albedo_compose(p, (hipStream_t)stream));
+        return TRX_OK;
+    });
+}
+
 } // extern "C"
 
 // trx_render_image_colour (emitter_eps null) and trx_render_image_colour_emitters (include/trx.h, "emitters": emitter_eps set -
@@ -697,7 +749,8 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
                          float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius, float depth_tol,
                          float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels, float bounce_depth_tol,
                          float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase, uint32_t upsample_radius,
-                         uint32_t emitter_samples, const float *emitter_eps, uint8_t *out_rgba, float *out_ms, bool smooth = false) {
+                         uint32_t emitter_samples, const float *emitter_eps, uint8_t *out_rgba, float *out_ms, bool smooth = false,
+                         bool textured = false) {
     // render_lit's refusals in its order, then the bounce's, the filter's and the upsample's where those steps run
     // (no light at all - the emitter form alone: V is what the light term gives for this one light of intensity 0)
     const trx_light none{TRX_LIGHT_DIRECTIONAL, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f, {0u, 0u}};
@@ -752,14 +805,17 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
     }
     // the image scratch: the AO filter's terms, the image, the light term's values, two sets of three planes (the indirect
     // term's steps alternate between them: a low grid holds at most n cells), the value filter's work plane, the lights' planes
-    HIP_TRY(s->scratch_img.grow(n * 4 * 10 + n * (unlit ? 1u : n_lights)));
+    // (textured: three albedo planes more, ahead of the lights' planes)
+    const uint64_t lit_at = n * 4 * (textured ? 13 : 10);
+    HIP_TRY(s->scratch_img.grow(lit_at + n * (unlit ? 1u : n_lights)));
     auto d_term = [&] { return reinterpret_cast<trx_ao_term *>(s->scratch_img.get()); };
     auto d_rgba = [&] { return s->scratch_img.get() + n * 4; };
     auto d_value = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 8); };
     auto d_a = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 12); };
     auto d_b = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 24); };
     auto d_work = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 36); };
-    auto d_lit = [&] { return s->scratch_img.get() + n * 40; };
+    auto d_albedo = [&] { return reinterpret_cast<float *>(s->scratch_img.get() + n * 40); }; // (textured only)
+    auto d_lit = [&] { return s->scratch_img.get() + lit_at; };
     auto d_counts = [&] { return reinterpret_cast<uint8_t *>(s->scratch_b.get()); };
     return host_call(
         s, n, nullptr, 0, n, out_ms,
@@ -771,6 +827,10 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
             if (smooth) {
                 rc = trx_shading_normals_primary_dev(s, view, w, h, whole, s->scratch_a.get(), s->scratch_ia.get(), s->scratch_attr.get(),
                                                      s->scratch_attr.get(), nullptr);
+                if (rc) return rc;
+            }
+            if (textured) { // (u and v are the attribute pass's with or without the shading normals)
+                rc = trx_surface_albedo_dev(s, s->scratch_a.get(), s->scratch_attr.get(), n, d_albedo(), nullptr);
                 if (rc) return rc;
             }
             if (unlit) HIP_TRY(hipMemsetAsync(d_lit(), 0, n, nullptr)); // (a light of intensity 0 adds +0 whatever its plane counts)
@@ -792,8 +852,15 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
             if (bounce_samples != 0) {
                 float *other = d_b();
                 planes = d_a();
+                // (textured: one entry point for the four modes - stride 1 is its dense pass)
+                auto textured_pass = [&](uint32_t stride, uint32_t phase) {
+                    return trx_trace_indirect_rgb_textured_dev(s, view, w, h, whole, stride, phase, sem, ray_mask, lights, n_lights, frame0, bounce_samples,
+                                                               bounce_eps, shadow_eps, emitter_eps ? 1u : 0u, emitter_eps ? *emitter_eps : 0.0f,
+                                                               s->scratch_a.get(), s->scratch_ia.get(), planes, nullptr);
+                };
                 if (sparse) {
-                    rc = emitter_eps ? trx_trace_indirect_rgb_emitters_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights,
+                    rc = textured ? textured_pass(bounce_stride, bounce_phase)
+                         : emitter_eps ? trx_trace_indirect_rgb_emitters_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights,
                                                                                   n_lights, frame0, bounce_samples, bounce_eps, shadow_eps,
                                                                                   *emitter_eps, s->scratch_a.get(), s->scratch_ia.get(), planes, nullptr)
                                      : trx_trace_indirect_rgb_sparse_dev(s, view, w, h, bounce_stride, bounce_phase, sem, ray_mask, lights, n_lights,
@@ -809,7 +876,8 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
                     }
                     std::swap(planes, other);
                 } else {
-                    rc = emitter_eps ? trx_trace_indirect_rgb_emitters_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples,
+                    rc = textured ? textured_pass(1u, 0u)
+                         : emitter_eps ? trx_trace_indirect_rgb_emitters_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples,
                                                                            bounce_eps, shadow_eps, *emitter_eps, s->scratch_a.get(),
                                                                            s->scratch_ia.get(), planes, nullptr)
                                      : trx_trace_indirect_rgb_dev(s, view, w, h, whole, sem, ray_mask, lights, n_lights, frame0, bounce_samples,
@@ -833,7 +901,8 @@ static int render_colour(trx_scene *s, const trx_view *view, uint32_t w, uint32_
                 if (rc) return rc;
                 planes = colour;
             }
-            rc = trx_material_compose_dev(s, s->scratch_a.get(), d_value(), planes, n, colour, nullptr);
+            rc = textured ? trx_albedo_compose_dev(s, s->scratch_a.get(), d_albedo(), d_value(), planes, n, colour, nullptr)
+                          : trx_material_compose_dev(s, s->scratch_a.get(), d_value(), planes, n, colour, nullptr);
             if (rc) return rc;
             return trx_shade_rgb_dev(s, colour, n, d_rgba(), nullptr);
         },
@@ -877,6 +946,22 @@ int trx_render_image_colour_emitters(trx_scene *s, const trx_view *view, uint32_
     return render_colour(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
                          ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, filter_levels, bounce_depth_tol,
                          bounce_normal_cos, bounce_stride, bounce_phase, upsample_radius, emitter_samples, &emitter_eps, out_rgba, out_ms);
+}
+
+// trx_render_image_colour / _smooth / _emitters in one, with the textured albedo (include/trx.h, "texture coordinates and
+// albedo textures"): render_colour's `textured`
+int trx_render_image_colour_textured(trx_scene *s, const trx_view *view, uint32_t w, uint32_t h, uint32_t sem, uint32_t ray_mask,
+                                     const trx_light *lights, uint32_t n_lights, uint32_t frame0, uint32_t light_samples, float shadow_eps,
+                                     float ambient, uint32_t ao_samples, float ao_eps, float ao_radius, uint32_t filter_radius,
+                                     float depth_tol, float normal_cos, uint32_t bounce_samples, float bounce_eps, uint32_t filter_levels,
+                                     float bounce_depth_tol, float bounce_normal_cos, uint32_t bounce_stride, uint32_t bounce_phase,
+                                     uint32_t upsample_radius, uint32_t emitter_samples, float emitter_eps, uint32_t smooth,
+                                     uint8_t *out_rgba, float *out_ms) {
+    if (smooth > 1u) return fail(TRX_ERR_INVALID, "smooth %u: must be 0 or 1", smooth);
+    return render_colour(s, view, w, h, sem, ray_mask, lights, n_lights, frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps,
+                         ao_radius, filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps, filter_levels, bounce_depth_tol,
+                         bounce_normal_cos, bounce_stride, bounce_phase, upsample_radius, emitter_samples,
+                         emitter_samples ? &emitter_eps : nullptr, out_rgba, out_ms, smooth != 0u, true);
 }
 
 } // extern "C"

@@ -17,6 +17,10 @@
 //                    indirect pass's emitter mode (trx_trace_indirect_rgb_emitters_dev / _sparse_dev) in api_ao.cpp; trx_render_image_colour_emitters in api_image.cpp
 //   vertex normals   (include/trx.h, "vertex normals") trx_scene_set_vertex_normals / _get_vertex_normals in api.cpp; trx_shading_normals_primary_dev / _rays_dev (k_shading_normal, kernels.hip) in api_attr.cpp;
 //                    trx_render_image_lit_smooth / _colour_smooth in api_image.cpp; trx_compute_vertex_normals / trx_load_model_normals in api_build.cpp (the welding and the OBJ `vn` reading in scenes.cpp)
+//   textures         (include/trx.h, "texture coordinates and albedo textures") trx_scene_set_texcoords / _get_texcoords / trx_scene_set_textures / _get_textures / _remove_textures /
+//                    trx_texture_srgb_table in api.cpp; trx_surface_albedo_dev / trx_albedo_compose_dev (k_surface_albedo, k_albedo_compose, image.hip; the sampling rule in texture_dev.h)
+//                    in api_image.cpp; trx_standin_texcoords / trx_standin_textures / trx_load_model_texcoords / trx_load_model_material_maps in api_build.cpp (the OBJ `vt` and
+//                    mtl `map_Kd` reading in scenes.cpp); image files are decoded in cli.cpp alone (--textures)
 //   probe.cpp        trx_debug_fetch_rate: the measured ceiling of the node-fetch loop on a scene's buffers
 #ifndef TRX_API_INTERNAL_H
 #define TRX_API_INTERNAL_H
@@ -249,6 +253,18 @@ struct trx_scene {
     // points are refused)
     std::vector<float> h_vertex_normals;
     trxapi::DevBuf<float4> vertex_normals;
+    // texture coordinates (trx_scene_set_texcoords): the caller's six floats per triangle in `prim` order and the device
+    // table of three float2 per triangle, swapped together under mu; empty = no table (the albedo pass writes the plain albedo)
+    std::vector<float> h_texcoords;
+    trxapi::DevBuf<float2> texcoords;
+    // the texture set (trx_scene_set_textures): descriptors, texel words and the per-material texture index as the caller
+    // gave them, and on the device {offset, width, height, format | filter << 8} per texture, the texels, the index and the
+    // sRGB decode table; every index validated on upload, all swapped together under mu; empty = no set
+    std::vector<trx_texture_desc> h_tex_descs;
+    std::vector<uint32_t> h_texels, h_material_texture;
+    trxapi::DevBuf<uint4> tex_descs;
+    trxapi::DevBuf<uint32_t> texels, material_texture;
+    trxapi::DevBuf<float> tex_srgb;
 };
 
 struct trx_bvh {

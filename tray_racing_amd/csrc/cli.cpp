@@ -88,6 +88,10 @@ struct Options { // src/main.rs:65-171 (flags this backend cannot honour are rej
     // file has any, else normals computed from the mesh, welded across edges flatter than DEG degrees (default 45)
     bool smooth = false;
     float smooth_crease = -1.0f; // (not given: 45)
+    // --textures: with --png --colour the image is trx_render_image_colour_textured's - texcoords and albedo textures from the
+    // OBJ's `vt` and the mtl files' map_Kd (binary PPM or 8-bit PNG, taken as sRGB, bilinear) for -i <file.obj>, the stand-in
+    // tables for standin:<name>; goes with --emitters and with --smooth
+    bool textures = false;
     int device = 0;
     unsigned semantics = TRX_SEM_HLSL; // the GPU path of the reference is the HLSL text
 };
@@ -146,6 +150,10 @@ void usage() {
               "  [--emitters 1..64] [--emitter-eps e] (with --png --colour: the emissive triangles sampled as lights - N shadow rays per\n"
               "   pixel and one per bounce ray toward points on them, each stopped e (default 0.001) of its length short of the\n"
               "   emitter; --light becomes optional)\n"
+              "  [--textures] (with --png --colour, also with --emitters or --smooth: albedo textures - the `vt` of -i <file.obj> and the\n"
+              "   map_Kd files of its mtl files, binary PPM (P6, maxval 255) or 8-bit non-interlaced RGB / RGBA PNG, read as sRGB and\n"
+              "   filtered bilinearly; the box mapping and the checker of standin:<name>; not without --colour, with --benchmark or\n"
+              "   with --profile-rt)\n"
               "  [--smooth] [--smooth-crease DEG] (with --png --light or with --colour: shade with interpolated vertex normals - the\n"
               "   `vn` records of -i <file.obj> where it has any, else computed from the mesh, corners welded across edges flatter\n"
               "   than DEG degrees, default 45; rays still start from the geometric normal; not together with --bounce-samples\n"
@@ -308,6 +316,8 @@ Options parse_args(int argc, char **argv) {
         }
         else if (a == "--smooth") {
             o.smooth = true;
+        } else if (a == "--textures") {
+            o.textures = true;
         } else if (a == "--smooth-crease") {
             o.smooth_crease = (float)std::atof(need(i));
             if (!(o.smooth_crease >= 0.0f && o.smooth_crease <= 180.0f)) die("--smooth-crease takes an angle of 0..180 degrees");
@@ -376,6 +386,9 @@ Options parse_args(int argc, char **argv) {
     if (o.bounce_filter >= 0 && o.bounce_samples < 0) die("--bounce-filter filters the term of --bounce-samples N");
     if (o.colour && o.lights.empty() && o.emitters < 0) die("--colour colours the image of --light");
     if (o.colour && o.bounce_albedo >= 0.0f) die("--colour takes the albedo of the materials: not together with --bounce-albedo");
+    if (o.textures && !o.colour) die("--textures textures the image of --colour");
+    if (o.textures && o.benchmark) die("--textures textures the image of --png: not together with --benchmark");
+    if (o.textures && o.profile_rt >= 0) die("--textures textures the colour image: not together with --profile-rt");
     if (!o.smooth && o.smooth_crease >= 0.0f) die("--smooth-crease goes with --smooth");
     if (o.smooth && o.benchmark) die("--smooth shades the image of --png: not together with --benchmark");
     if (o.smooth && o.profile_rt >= 0) die("--smooth shades the lit image: not together with --profile-rt");
@@ -426,6 +439,114 @@ bool write_png(const std::string &path, const std::vector<unsigned char> &rgba, 
     return (bool)f;
 }
 
+// ---- image files for --textures: decoded here, the library stays free of decoders.  Both give RGBA8 words (R in the low
+// byte), row 0 the TOP row of the image as the file has it; false = not such a file (the caller says so and goes on).
+
+// binary PPM: "P6", width, height, maxval 255 (blank-separated, `#` comments to the end of their line), one blank, then RGB bytes
+bool read_ppm(const std::vector<unsigned char> &d, std::vector<uint32_t> &px, uint32_t &w, uint32_t &h) {
+    if (d.size() < 2 || d[0] != 'P' || d[1] != '6') return false;
+    size_t p = 2;
+    unsigned long num[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++) {
+        for (;;) { // blanks and comments
+            while (p < d.size() && (d[p] == ' ' || d[p] == '\t' || d[p] == '\n' || d[p] == '\r')) p++;
+            if (p < d.size() && d[p] == '#') {
+                while (p < d.size() && d[p] != '\n') p++;
+                continue;
+            }
+            break;
+        }
+        const size_t start = p;
+        while (p < d.size() && d[p] >= '0' && d[p] <= '9' && p - start < 9) num[k] = num[k] * 10 + (d[p++] - '0');
+        if (p == start) return false;
+    }
+    if (p >= d.size() || !(d[p] == ' ' || d[p] == '\t' || d[p] == '\n' || d[p] == '\r')) return false;
+    p++;
+    if (num[0] == 0 || num[1] == 0 || num[0] > TRX_MAX_TEXTURE_SIZE || num[1] > TRX_MAX_TEXTURE_SIZE || num[2] != 255) return false;
+    const size_t n = (size_t)num[0] * num[1];
+    if (d.size() - p < n * 3) return false;
+    w = (uint32_t)num[0], h = (uint32_t)num[1];
+    px.resize(n);
+    for (size_t i = 0; i < n; i++) px[i] = d[p + 3 * i] | (uint32_t)d[p + 3 * i + 1] << 8 | (uint32_t)d[p + 3 * i + 2] << 16 | 0xFF000000u;
+    return true;
+}
+
+// PNG: 8 bits per channel, colour type 2 (RGB) or 6 (RGBA), not interlaced; the IDAT chunks are one zlib stream (the zlib this
+// program links for its own PNG), every scanline one filter byte and the five filters of the PNG specification
+bool read_png(const std::vector<unsigned char> &d, std::vector<uint32_t> &px, uint32_t &w, uint32_t &h) {
+    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (d.size() < 8 || std::memcmp(d.data(), sig, 8) != 0) return false;
+    auto be32 = [&](size_t at) { return (uint32_t)d[at] << 24 | (uint32_t)d[at + 1] << 16 | (uint32_t)d[at + 2] << 8 | (uint32_t)d[at + 3]; };
+    size_t p = 8;
+    std::vector<unsigned char> z;
+    uint32_t bpp = 0;
+    bool header = false, end = false;
+    while (!end && d.size() - p >= 12) {
+        const uint32_t len = be32(p);
+        if (len > d.size() - p - 12) return false;
+        const unsigned char *tag = &d[p + 4], *body = &d[p + 8];
+        if (std::memcmp(tag, "IHDR", 4) == 0) {
+            if (len != 13 || header) return false;
+            w = be32(p + 8), h = be32(p + 12);
+            if (w == 0 || h == 0 || w > TRX_MAX_TEXTURE_SIZE || h > TRX_MAX_TEXTURE_SIZE) return false;
+            if (body[8] != 8 || (body[9] != 2 && body[9] != 6) || body[10] != 0 || body[11] != 0 || body[12] != 0) return false;
+            bpp = body[9] == 2 ? 3u : 4u;
+            header = true;
+        } else if (std::memcmp(tag, "IDAT", 4) == 0) {
+            if (!header) return false;
+            z.insert(z.end(), body, body + len);
+        } else if (std::memcmp(tag, "IEND", 4) == 0) {
+            end = true;
+        }
+        p += (size_t)len + 12;
+    }
+    if (!header || !end || z.empty()) return false;
+    const size_t stride = (size_t)w * bpp;
+    std::vector<unsigned char> raw((stride + 1) * h);
+    uLongf got = (uLongf)raw.size();
+    if (uncompress(raw.data(), &got, z.data(), (uLong)z.size()) != Z_OK || got != raw.size()) return false;
+    std::vector<unsigned char> prev(stride, 0), cur(stride);
+    px.resize((size_t)w * h);
+    for (uint32_t y = 0; y < h; y++) {
+        const unsigned char *line = &raw[(stride + 1) * y];
+        const unsigned filter = line[0];
+        if (filter > 4) return false;
+        for (size_t i = 0; i < stride; i++) {
+            const int a = i >= bpp ? cur[i - bpp] : 0, b = prev[i], c = i >= bpp ? prev[i - bpp] : 0; // left, up, up-left
+            int pred = 0;
+            if (filter == 1) pred = a;
+            else if (filter == 2) pred = b;
+            else if (filter == 3) pred = (a + b) / 2;
+            else if (filter == 4) {
+                const int pa = std::abs(b - c), pb = std::abs(a - c), pc = std::abs(a + b - 2 * c);
+                pred = pa <= pb && pa <= pc ? a : pb <= pc ? b : c;
+            }
+            cur[i] = (unsigned char)(line[1 + i] + pred);
+        }
+        for (uint32_t x = 0; x < w; x++) {
+            const unsigned char *q = &cur[(size_t)x * bpp];
+            px[(size_t)y * w + x] = q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (bpp == 4 ? (uint32_t)q[3] << 24 : 0xFF000000u);
+        }
+        prev.swap(cur);
+    }
+    return true;
+}
+
+// an image file of --textures: PPM or PNG by its first bytes; a message on stderr and false for anything else
+bool read_image(const std::string &path, std::vector<uint32_t> &px, uint32_t &w, uint32_t &h) {
+    std::ifstream f(path, std::ios::binary);
+    std::vector<unsigned char> d;
+    if (f) d.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    if (!f || d.empty()) {
+        std::fprintf(stderr, "--textures: cannot read %s: its material stays untextured\n", path.c_str());
+        return false;
+    }
+    if (read_ppm(d, px, w, h) || read_png(d, px, w, h)) return true;
+    std::fprintf(stderr, "--textures: %s is neither a binary PPM (P6, maxval 255) nor an 8-bit non-interlaced RGB / RGBA PNG: its material stays untextured\n",
+                 path.c_str());
+    return false;
+}
+
 // The reference's image: AO term of the primary hit, 1/t where the primary ray missed, gamma 2.2 to u8
 // (src/rt_cpu/rt_cpu.rs:57-85,102-112; the same shading ends the GPU shader, rt_gpu_software.hlsl:47-144).
 void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned frame_count, const std::string &name) {
@@ -450,7 +571,20 @@ void save_png(const Options &o, trx_scene *scene, const trx_view &view, unsigned
         const bool ao = o.ao_samples != 0 || o.ao_radius > 0.0f;
         const unsigned ao_samples = o.ao_samples ? o.ao_samples : ao ? 1u : 0u;
         const float radius = o.ao_radius > 0.0f ? o.ao_radius : std::numeric_limits<float>::infinity();
-        if (o.colour && o.emitters >= 0)
+        if (o.colour && o.textures)
+            // the colour image with the textured albedo: with or without the sampled emitters, with or without smooth normals
+            check(trx_render_image_colour_textured(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
+                                                   o.lights.empty() ? nullptr : o.lights.data(), (uint32_t)o.lights.size(), frame_count,
+                                                   o.light_samples >= 0 ? (uint32_t)o.light_samples : 1u, o.shadow_eps >= 0.0f ? o.shadow_eps : 0.01f,
+                                                   o.ambient >= 0.0f ? o.ambient : 0.1f, ao_samples, 0.0001f, radius,
+                                                   o.ao_filter >= 0 ? (uint32_t)o.ao_filter : 0u, o.ao_depth_tol, o.ao_normal_cos,
+                                                   o.bounce_samples >= 0 ? (uint32_t)o.bounce_samples : 0u, o.bounce_eps >= 0.0f ? o.bounce_eps : 0.01f,
+                                                   o.bounce_filter >= 0 ? (uint32_t)o.bounce_filter : 0u, o.bounce_filter_tol, o.bounce_filter_cos,
+                                                   o.bounce_stride >= 0 ? (uint32_t)o.bounce_stride : 1u, o.bounce_phase >= 0 ? (uint32_t)o.bounce_phase : 0u,
+                                                   o.bounce_upsample >= 0 ? (uint32_t)o.bounce_upsample : 1u, o.emitters >= 0 ? (uint32_t)o.emitters : 0u,
+                                                   o.emitter_eps >= 0.0f ? o.emitter_eps : 0.001f, o.smooth ? 1u : 0u, rgba.data(), &ms),
+                  "png frame");
+        else if (o.colour && o.emitters >= 0)
             // the colour image with the emissive triangles sampled as lights; there may be no --light at all
             check(trx_render_image_colour_emitters(scene, &view, o.width, o.height, o.semantics, o.light_mask >= 0 ? (uint32_t)o.light_mask : 0u,
                                                    o.lights.empty() ? nullptr : o.lights.data(), (uint32_t)o.lights.size(), frame_count,
@@ -580,6 +714,10 @@ Stats render_input(const Options &o, const std::string &input) {
     // --smooth: the vertex normals in the order of verts (permuted like the materials)
     float *normals = nullptr;
     uint32_t has_vn = 0;
+    // --textures: the texcoords in the order of verts (permuted like the materials) and the texture set (keyed by material)
+    std::vector<float> uvs;
+    std::vector<trx_texture_desc> tex_descs;
+    std::vector<uint32_t> texels, material_texture;
     const bool obj = input.size() > 4 && input.compare(input.size() - 4, 4, ".obj") == 0;
     if (input == "demoscene" || input.rfind("standin:", 0) == 0) {
         const std::string name = input == "demoscene" ? "demoscene" : input.substr(8);
@@ -587,6 +725,20 @@ Stats render_input(const Options &o, const std::string &input) {
         check(trx_gen_scene(name.c_str(), 0, 1, &verts, &n_tris, &counts, &n_objects), "scene");
         check(trx_scene_camera(name.c_str(), cam.eye, cam.look_at, &cam.fov), "camera");
         if (o.colour) check(trx_standin_materials(name.c_str(), verts, n_tris, counts, n_objects, &materials, &n_materials, &tri_material), "materials");
+        if (o.textures) {
+            uvs.resize((size_t)n_tris * 6);
+            check(trx_standin_texcoords(name.c_str(), verts, n_tris, uvs.data()), "texcoords");
+            trx_texture_desc *d = nullptr;
+            uint32_t n_tex = 0, *tx = nullptr, *mt = nullptr;
+            uint64_t n_texels = 0;
+            check(trx_standin_textures(name.c_str(), n_materials, &d, &n_tex, &tx, &n_texels, &mt), "textures");
+            tex_descs.assign(d, d + n_tex);
+            texels.assign(tx, tx + n_texels);
+            material_texture.assign(mt, mt + n_materials);
+            trx_free(d);
+            trx_free(tx);
+            trx_free(mt);
+        }
     } else if (obj) {
         // a model file on its own, with the materials of its mtl files: seen from +z, a box diagonal away from the box's centre
         size_t k = input.find_last_of('/');
@@ -601,6 +753,40 @@ Stats render_input(const Options &o, const std::string &input) {
             trx_free(v2);
             trx_free(c2);
             if (n2 != n_tris) die("model normals: the model changed while it was read");
+        }
+        if (o.textures) { // (the same mesh once more with its `vt` records; the map_Kd files from the OBJ's directory)
+            float *v2 = nullptr, *uv = nullptr;
+            uint64_t n2 = 0, *c2 = nullptr;
+            uint32_t o2 = 0, has_vt = 0, n_names = 0;
+            check(trx_load_model_texcoords(input.c_str(), &v2, &n2, &c2, &o2, &uv, &has_vt), "model texcoords");
+            if (n2 != n_tris) die("model texcoords: the model changed while it was read");
+            uvs.assign(uv, uv + (size_t)n_tris * 6);
+            trx_free(v2);
+            trx_free(c2);
+            trx_free(uv);
+            char *names = nullptr;
+            check(trx_load_model_material_maps(input.c_str(), &names, &n_names), "material maps");
+            if (n_names != n_materials) die("material maps: the model changed while it was read");
+            const size_t slash = input.find_last_of('/');
+            const std::string dir = slash == std::string::npos ? std::string() : input.substr(0, slash + 1);
+            material_texture.assign(n_materials, TRX_NO_TEXTURE);
+            const char *nm = names;
+            for (uint32_t m = 0; m < n_materials; m++, nm += std::strlen(nm) + 1) {
+                if (!*nm) continue;
+                std::vector<uint32_t> px;
+                uint32_t tw = 0, th = 0;
+                if (!read_image(nm[0] == '/' ? std::string(nm) : dir + nm, px, tw, th)) continue;
+                if (tex_descs.size() >= TRX_MAX_TEXTURES || texels.size() + px.size() >= 0x80000000ull) {
+                    std::fprintf(stderr, "--textures: %s does not fit the texture set: its material stays untextured\n", nm);
+                    continue;
+                }
+                material_texture[m] = (uint32_t)tex_descs.size();
+                tex_descs.push_back(trx_texture_desc{tw, th, TRX_TEX_RGBA8_SRGB, TRX_TEX_BILINEAR});
+                for (uint32_t y = 0; y < th; y++) // (image files are top-down: row 0 of a texture is the row at t = 0, the bottom one)
+                    texels.insert(texels.end(), px.begin() + (size_t)(th - 1 - y) * tw, px.begin() + (size_t)(th - y) * tw);
+            }
+            trx_free(names);
+            if (!has_vt) std::fprintf(stderr, "--textures: %s has no usable vt: every corner gets 0, 0\n", input.c_str());
         }
         float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
         for (uint64_t i = 0; i < n_tris * 3; i++)
@@ -694,6 +880,15 @@ Stats render_input(const Options &o, const std::string &input) {
         for (uint64_t i = 0; i < flat->n_tris; i++)
             if (flat->tri_source[i] < n_tris) std::memcpy(&by_prim[i * 9], normals + (size_t)flat->tri_source[i] * 9, 9 * sizeof(float));
         check(trx_scene_set_vertex_normals(scene, by_prim.data(), flat->n_tris), "vertex normals");
+    }
+    if (o.textures) { // the texcoords in `prim` order, like the materials; the texture set where any image was read
+        std::vector<float> by_prim((size_t)flat->n_tris * 6, 0.0f);
+        for (uint64_t i = 0; i < flat->n_tris; i++)
+            if (flat->tri_source[i] < n_tris) std::memcpy(&by_prim[i * 6], &uvs[(size_t)flat->tri_source[i] * 6], 6 * sizeof(float));
+        check(trx_scene_set_texcoords(scene, by_prim.data(), flat->n_tris), "texcoords");
+        if (!tex_descs.empty())
+            check(trx_scene_set_textures(scene, tex_descs.data(), (uint32_t)tex_descs.size(), texels.data(), texels.size(), material_texture.data(),
+                                         n_materials), "textures");
     }
     trx_view view;
     check(trx_view_from_camera(cam.eye, cam.look_at, cam.fov, (float)o.width, (float)o.height, &view), "camera");

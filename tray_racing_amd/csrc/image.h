@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/trx.h"
+#include "texture_dev.h"
 
 namespace trx {
 
@@ -124,6 +125,36 @@ struct ShadeRgbParams {
     uint32_t n_items;
 };
 hipError_t launch_shade_rgb(const ShadeRgbParams &p, hipStream_t stream);
+
+// The textured albedo (include/trx.h, "texture coordinates and albedo textures"): both kernels are elementwise over n_items
+// records in any layout, planes at c * n_items.
+//   k_surface_albedo  (trx_surface_albedo_dev) one lane per record: 8 B of hit record and 8 B of u, v read; for a surface record
+//                     of the scene (prim < n_tris) the u16 material index and 12 B of albedo, then - with tables, a textured
+//                     material and finite coordinates - the texture index, the 16 B descriptor, 24 B of texcoords and one or
+//                     four 4 B texels (texture_dev.h); 12 B written: the albedo, +0 for any other record.
+//   k_albedo_compose  (trx_albedo_compose_dev) k_compose with the albedo read from three planes instead of the material:
+//                     emission + A_c * (E + I_c).  Every lane reads before it writes: out may be indirect.
+struct SurfaceAlbedoParams {
+    const trx_hit *hits;
+    const trx_hit_attr *attr;
+    float *out; // three planes
+    const trx_material *materials;
+    const uint16_t *tri_material;
+    TextureTables tex;
+    uint32_t n_items, n_tris;
+};
+hipError_t launch_surface_albedo(const SurfaceAlbedoParams &p, hipStream_t stream);
+struct AlbedoComposeParams {
+    const trx_hit *primary;
+    const float *albedo;           // three planes
+    const float *direct;
+    const float *indirect;         // three planes, or null
+    float *out;                    // three planes
+    const trx_material *materials; // (the emission)
+    const uint16_t *tri_material;
+    uint32_t n_items, n_tris;
+};
+hipError_t launch_albedo_compose(const AlbedoComposeParams &p, hipStream_t stream);
 
 // k_heat: the PROFILE_RT heat map (trx_shade_heat_dev) - one lane per record, 4 bytes of per-ray counts read, 4 bytes
 // {r, g, b, 255} written.  No table in LDS, no pow: the colour is arithmetic on the count.

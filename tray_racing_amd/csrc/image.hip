@@ -536,7 +536,77 @@ __global__ void __launch_bounds__(256) k_rgb_shade(const ShadeRgbParams P) {
     reinterpret_cast<uint32_t *>(P.rgba)[i] = r | g << 8 | b << 16 | 0xFF000000u; // {r, g, b, 255}
 }
 
+// The textured albedo of every record (trx_surface_albedo_dev; include/trx.h, "THE TEXTURED ALBEDO"): one lane per record,
+// planes at c * n_items.  k_compose's surface rule: a record with t < FLT_MAX and prim < n_tris is a surface record of the
+// scene, and every table index formed from it was validated when its table was set; any other record - a caller's too - reads
+// no table and gets +0.  u and v are used as they come (the sampling rule survives any float).  Gathers only: no scratch, no LDS.
+__global__ void __launch_bounds__(256) k_surface_albedo(const SurfaceAlbedoParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    const size_t n = P.n_items;
+    const trx_hit ph = P.hits[i];
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (ph.t < TRX_F32_MAX && ph.prim < P.n_tris) {
+        const uint32_t m = P.tri_material[ph.prim];
+        const float2 *mp = reinterpret_cast<const float2 *>(P.materials + m);
+        const float2 m0 = mp[0]; // {albedo r, g}
+        r = m0.x;
+        g = m0.y;
+        b = P.materials[m].albedo[2];
+        const float2 uv = *reinterpret_cast<const float2 *>(P.attr + i); // {u, v}: the record's first 8 bytes
+        textured_albedo(P.tex, ph.prim, m, uv.x, uv.y, r, g, b);
+    }
+    P.out[i] = r;
+    P.out[n + i] = g;
+    P.out[2u * n + i] = b;
+}
+
+// The colour compose over an albedo plane (trx_albedo_compose_dev): k_compose with albedo_c(m) replaced by the plane's value,
+// the same association and the same background rule.  All of a lane's reads come before its writes, so out may be the indirect
+// planes.
+__global__ void __launch_bounds__(256) k_albedo_compose(const AlbedoComposeParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= P.n_items) return;
+    const size_t n = P.n_items;
+    const trx_hit ph = P.primary[i];
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (ph.t < TRX_F32_MAX && ph.prim < P.n_tris) {
+        const float2 *mp = reinterpret_cast<const float2 *>(P.materials + P.tri_material[ph.prim]);
+        const float2 m1 = mp[1], m2 = mp[2]; // {albedo b, emission r}, {emission g, b}
+        const float Ar = P.albedo[i], Ag = P.albedo[n + i], Ab = P.albedo[2u * n + i];
+        const float E = P.direct[i];
+        float Ir = E, Ig = E, Ib = E;
+        if (P.indirect) {
+            Ir = E + P.indirect[i];
+            Ig = E + P.indirect[n + i];
+            Ib = E + P.indirect[2u * n + i];
+        }
+        r = m1.y + Ar * Ir;
+        g = m2.x + Ag * Ig;
+        b = m2.y + Ab * Ib;
+    }
+    P.out[i] = r;
+    P.out[n + i] = g;
+    P.out[2u * n + i] = b;
+}
+
 } // namespace
+
+hipError_t launch_surface_albedo(const SurfaceAlbedoParams &p, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    if (!p.hits || !p.attr || !p.out || !p.materials || !p.tri_material) return hipErrorInvalidValue;
+    // (a texture set is whole or absent: the kernel reads all four tables once it has seen descs)
+    if (p.tex.descs && (!p.tex.texels || !p.tex.material_texture || !p.tex.srgb)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_surface_albedo, dim3((p.n_items + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_albedo_compose(const AlbedoComposeParams &p, hipStream_t stream) {
+    if (p.n_items == 0) return hipSuccess;
+    if (!p.primary || !p.albedo || !p.direct || !p.out || !p.materials || !p.tri_material) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_albedo_compose, dim3((p.n_items + 255u) / 256u), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_compose(const ComposeParams &p, hipStream_t stream) {
     if (p.n_items == 0) return hipSuccess;

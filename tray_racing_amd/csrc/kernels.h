@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "../../include/trx.h"
+#include "texture_dev.h"
 
 namespace trx {
 
@@ -386,6 +387,11 @@ struct BounceParams {
     uint32_t *pick;
     uint32_t n_emitters, has_lights;
     float emitter_eps;
+    // textures (trx_trace_indirect_rgb_textured_dev; include/trx.h, "THE TEXTURED ALBEDO"; last yet again: the fields above keep
+    // their offsets): with tex.texcoords and tex.descs set launch_bounce_gather runs k_bounce_gather_tex<EMITTERS> in place of
+    // k_bounce_gather_rgb / k_bounce_emitter_gather - the same rule with albedo_c(m) sampled at the bounce hit from
+    // bounce_attr[index].  Null pointers: the kernels above.
+    TextureTables tex;
 };
 hipError_t launch_bounce_emitter_rays(const BounceParams &p, hipStream_t stream);
 hipError_t launch_bounce_light_rays(const BounceParams &p, hipStream_t stream);

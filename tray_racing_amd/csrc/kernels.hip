@@ -1724,6 +1724,61 @@ __global__ void __launch_bounds__(256) k_bounce_emitter_gather(const BounceParam
     P.acc[2u * lanes + item] = Ab;
 }
 
+// k_bounce_gather_rgb (EMITTERS false, rule 5c) and k_bounce_emitter_gather (EMITTERS true, rule 5e) with albedo_c(m) replaced
+// by THE TEXTURED ALBEDO (include/trx.h) sampled at the bounce hit: u, v of bounce_attr[index], the texcoords of bounce_hit.prim,
+// the texture of its material (textured_albedo, texture_dev.h: the statement k_surface_albedo shares).  Everything else is those
+// kernels' word for word - the same reads, the same order of the float sums.  Launched only with a texcoord table and a
+// texture set on the scene (BounceParams::tex); per sample the 8 B of u, v, and for a textured material the descriptor, 24 B of
+// texcoords and one or four texels, are gathers on top of theirs.  No scratch, no LDS.
+template <bool EMITTERS>
+__global__ void __launch_bounds__(256) k_bounce_gather_tex(const BounceParams P) {
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lanes = P.n_tiles * 64u;
+    if (item >= lanes) return;
+    const uint32_t lt = item >> 6, k = item & 63u;
+    const uint32_t from = lt * P.n_samples * 64u + k;
+    float Ar = 0.0f, Ag = 0.0f, Ab = 0.0f;
+    if (!P.first) {
+        Ar = P.acc[item];
+        Ag = P.acc[lanes + item];
+        Ab = P.acc[2u * lanes + item];
+    }
+    for (uint32_t s = 0; s < P.n_samples; s++) {
+        const uint32_t index = from + s * 64u;
+        const float sf = !EMITTERS || P.has_lights ? P.sum[index] : 0.0f;
+        const float tmax = P.bounce_rays[index].tmax;
+        const trx_hit bh = P.bounce_hits[index];
+        if (tmax < 0.0f || !surface_record(bh, P.n_tris)) continue;
+        const uint32_t m = P.tri_material[bh.prim];
+        const float2 *mp = reinterpret_cast<const float2 *>(P.materials + m);
+        const float2 m0 = mp[0], m1 = mp[1], m2 = mp[2]; // {albedo r, g}, {albedo b, emission r}, {emission g, b}
+        const float2 uv = *reinterpret_cast<const float2 *>(P.bounce_attr + index); // {u, v}: the record's first 8 bytes
+        float ar = m0.x, ag = m0.y, ab = m1.x;
+        textured_albedo(P.tex, bh.prim, m, uv.x, uv.y, ar, ag, ab);
+        if (EMITTERS) {
+            float Xr = 0.0f, Xg = 0.0f, Xb = 0.0f;
+            const float wg = P.wgeo[index];
+            const uint32_t j = P.pick[index];
+            if (wg > 0.0f && P.flags[index] == 0u && j < P.n_emitters) {
+                const trx_material *ep = P.materials + __float_as_uint(P.emitters[(size_t)j * 4 + 1].w);
+                Xr = wg * ep->emission[0];
+                Xg = wg * ep->emission[1];
+                Xb = wg * ep->emission[2];
+            }
+            Ar = Ar + ar * (sf + Xr);
+            Ag = Ag + ag * (sf + Xg);
+            Ab = Ab + ab * (sf + Xb);
+        } else {
+            Ar = Ar + (ar * sf + m1.y);
+            Ag = Ag + (ag * sf + m2.x);
+            Ab = Ab + (ab * sf + m2.y);
+        }
+    }
+    P.acc[item] = Ar;
+    P.acc[lanes + item] = Ag;
+    P.acc[2u * lanes + item] = Ab;
+}
+
 } // namespace
 
 // (the sparse form of the bounce kernels exists for the scratch layout of a whole image only: what bounds their cell -> pixel
@@ -1819,6 +1874,16 @@ hipError_t launch_bounce_gather(const BounceParams &p, hipStream_t stream) {
     if (p.n_tiles > 0x3ffffffu) return hipErrorInvalidValue;
     if (p.materials) {
         if (!p.tri_material || !p.scratch) return hipErrorInvalidValue;
+        if (p.tex.texcoords && p.tex.descs) { // the textured gathers (a texture set is whole or absent; the attributes are read)
+            if (!p.tex.texels || !p.tex.material_texture || !p.tex.srgb || !p.bounce_attr) return hipErrorInvalidValue;
+            if (p.emitters) {
+                if (!bounce_emitters_ok(p)) return hipErrorInvalidValue;
+                hipLaunchKernelGGL(k_bounce_gather_tex<true>, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+            } else {
+                hipLaunchKernelGGL(k_bounce_gather_tex<false>, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);
+            }
+            return hipGetLastError();
+        }
         if (p.emitters) {
             if (!bounce_emitters_ok(p)) return hipErrorInvalidValue;
             hipLaunchKernelGGL(k_bounce_emitter_gather, dim3((p.n_tiles * 64u + 255u) / 256u), dim3(256), 0, stream, p);

@@ -712,7 +712,7 @@ std::string line_rest(const char *p) {
 
 // One mtl file into names / table (6 floats per material: Kd, a missing one 0.8 each; Ke, a missing one 0).  A file that cannot
 // be opened adds nothing.  false (mm.error set): a negative or non-finite Kd or Ke, more than 65535 named materials.
-bool load_mtl(const std::string &path, std::vector<std::string> &names, ModelMaterials &mm) {
+bool load_mtl(const std::string &path, std::vector<std::string> &names, ModelMaterials &mm, std::vector<std::string> *maps = nullptr) {
     FILE *f = std::fopen(path.c_str(), "rb");
     if (!f) return true;
     char line[4096];
@@ -729,7 +729,13 @@ bool load_mtl(const std::string &path, std::vector<std::string> &names, ModelMat
             names.push_back(line_rest(p + 6));
             const float fresh[6] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.0f};
             mm.table.insert(mm.table.end(), fresh, fresh + 6);
+            if (maps) maps->push_back(std::string());
             open = true;
+        } else if (maps && open && std::strncmp(p, "map_Kd", 6) == 0 && (p[6] == ' ' || p[6] == '\t')) {
+            // the file name is the last blank-separated word: options (-s 1 1 1, -bm 0.5, -clamp on ...) come before it
+            const std::string rest = line_rest(p + 6);
+            const size_t cut = rest.find_last_of(" \t");
+            maps->back() = cut == std::string::npos ? rest : rest.substr(cut + 1);
         } else if (open && (p[0] == 'K') && (p[1] == 'd' || p[1] == 'e') && (p[2] == ' ' || p[2] == '\t')) {
             float c[3] = {0, 0, 0};
             const int got = std::sscanf(p + 2, "%f %f %f", &c[0], &c[1], &c[2]);
@@ -751,8 +757,11 @@ bool load_mtl(const std::string &path, std::vector<std::string> &names, ModelMat
 // mn (optional): the vertex normals of trx_load_model_normals - `vn` records, and the third index of a face corner's
 // v/vt/vn or v//vn (relative when negative, against the `vn` records read so far); a corner without one, or with one out of
 // range, gets +0.  The mesh is the same with and without it.
+// mt (optional): the texture coordinates of trx_load_model_texcoords - `vt` records (two numbers; a missing second one is +0), and
+// the second index of a face corner's v/vt or v/vt/vn, relative when negative; a corner without a usable one gets +0, +0.
+// maps (optional, with mm): the map_Kd name per material of mm's table.
 bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelMaterials *mm = nullptr,
-              ModelNormals *mn = nullptr) {
+              ModelNormals *mn = nullptr, ModelTexcoords *mt = nullptr, std::vector<std::string> *maps = nullptr) {
     FILE *f = std::fopen(path.c_str(), "rb");
     if (!f) return false;
     std::vector<std::string> names, uses; // the mtl files' materials in file order; the names given to usemtl
@@ -762,7 +771,8 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
         const float fresh[6] = {0.8f, 0.8f, 0.8f, 0.0f, 0.0f, 0.0f};
         mm->table.assign(fresh, fresh + 6);
     }
-    std::vector<float> pos, nrm;
+    std::vector<float> pos, nrm, tex;
+    if (maps) maps->assign(1, std::string());
     uint64_t open_start = 0;
     bool any_object = false;
     auto close_object = [&]() {
@@ -789,13 +799,18 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
             nrm.push_back(x);
             nrm.push_back(y);
             nrm.push_back(z);
+        } else if (mt && line[0] == 'v' && line[1] == 't' && (line[2] == ' ' || line[2] == '\t')) {
+            float s = 0, u = 0;
+            std::sscanf(line + 3, "%f %f", &s, &u);
+            tex.push_back(s);
+            tex.push_back(u);
         } else if (line[0] == 'o' && (line[1] == ' ' || line[1] == '\t')) {
             if (any_object || verts.size() / 9 > open_start) close_object();
             any_object = true;
         } else if (mm && std::strncmp(line, "mtllib", 6) == 0 && (line[6] == ' ' || line[6] == '\t')) {
             const size_t slash = path.find_last_of('/');
             const std::string dir = slash == std::string::npos ? std::string() : path.substr(0, slash + 1);
-            if (!load_mtl(dir + line_rest(line + 6), names, *mm)) {
+            if (!load_mtl(dir + line_rest(line + 6), names, *mm, maps)) {
                 std::fclose(f);
                 return false;
             }
@@ -803,7 +818,7 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
             uses.push_back(line_rest(line + 6));
             use = (uint32_t)uses.size();
         } else if (line[0] == 'f' && (line[1] == ' ' || line[1] == '\t')) {
-            long idx[4], nidx[4] = {-1, -1, -1, -1}; // (nidx: the corner's `vn`, -1 = none)
+            long idx[4], nidx[4] = {-1, -1, -1, -1}, tidx[4] = {-1, -1, -1, -1}; // (nidx, tidx: the corner's `vn` and `vt`, -1 = none)
             int n = 0;
             char *p = line + 2;
             for (;;) { // n counts every vertex of the polygon; the first four are kept
@@ -816,6 +831,14 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
                 if (n < 4) idx[n] = v - 1;
                 n++;
                 p = end;
+                if (mt && n <= 4 && *p == '/') { // v/vt or v/vt/vn: the second index
+                    char *tend;
+                    long vt = std::strtol(p + 1, &tend, 10);
+                    if (tend != p + 1) {
+                        if (vt < 0) vt = (long)(tex.size() / 2) + vt + 1; // relative index
+                        tidx[n - 1] = vt - 1;
+                    }
+                }
                 if (mn && n <= 4 && *p == '/') { // v/vt/vn or v//vn: the third index
                     const char *q = p + 1;
                     while (*q && *q != '/' && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;
@@ -846,6 +869,13 @@ bool load_obj(const std::string &path, std::vector<float> &verts, std::vector<ui
                         const bool have = i >= 0 && i < (long)(nrm.size() / 3);
                         mn->any = mn->any || have;
                         for (int j = 0; j < 3; j++) mn->normals.push_back(have ? nrm[3 * i + j] : 0.0f);
+                    }
+                if (mt)
+                    for (int k : {ka, kb, kc}) {
+                        const long i = tidx[k];
+                        const bool have = i >= 0 && i < (long)(tex.size() / 2);
+                        mt->any = mt->any || have;
+                        for (int j = 0; j < 2; j++) mt->uvs.push_back(have ? tex[2 * i + j] : 0.0f);
                     }
             };
             // the reference reads vertices 0,1,2 and, for quads only, 0,2,3 (src/main.rs:536-553)
@@ -942,6 +972,30 @@ bool load_model_normals(const std::string &path, std::vector<float> &verts, std:
         return true;
     }
     return load_obj(path, verts, objects, nullptr, &mn);
+}
+
+bool load_model_texcoords(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelTexcoords &mt) {
+    mt = ModelTexcoords();
+    if (path.find("json") != std::string::npos && path.rfind('.') != std::string::npos &&
+        path.substr(path.rfind('.')).find("json") != std::string::npos) {
+        if (!load_json(path, verts, objects)) return false;
+        mt.uvs.assign(verts.size() / 9 * 6, 0.0f);
+        return true;
+    }
+    return load_obj(path, verts, objects, nullptr, nullptr, &mt);
+}
+
+bool load_model_material_maps(const std::string &path, std::vector<std::string> &maps, std::string &error) {
+    std::vector<float> verts;
+    std::vector<uint64_t> objects;
+    maps.assign(1, std::string());
+    if (path.find("json") != std::string::npos && path.rfind('.') != std::string::npos &&
+        path.substr(path.rfind('.')).find("json") != std::string::npos)
+        return load_json(path, verts, objects);
+    ModelMaterials mm;
+    const bool ok = load_obj(path, verts, objects, &mm, nullptr, nullptr, &maps);
+    error = mm.error;
+    return ok;
 }
 
 // Vertex normals from the mesh alone (include/trx.h, trx_compute_vertex_normals).  Every operation in binary64, rounded

@@ -28,6 +28,17 @@ struct ModelNormals {
     std::string error;
 };
 bool load_model_normals(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelNormals &mn);
+// load_model with the model's texture coordinates (trx_load_model_texcoords): the same verts and objects, six floats per
+// triangle in the order of verts (an OBJ corner's `vt`, +0, +0 where it names none or one out of range; all +0 for a JSON
+// model) and whether any corner got one.  false: unreadable.
+struct ModelTexcoords {
+    std::vector<float> uvs;
+    bool any = false;
+};
+bool load_model_texcoords(const std::string &path, std::vector<float> &verts, std::vector<uint64_t> &objects, ModelTexcoords &mt);
+// The `map_Kd` file name of every material of load_model_materials' table, in its order (trx_load_model_material_maps): an empty
+// string where a material names none; material 0 never does.  false with `error` set: a mtl file the loader refuses.
+bool load_model_material_maps(const std::string &path, std::vector<std::string> &maps, std::string &error);
 // Vertex normals from the mesh alone (include/trx.h, trx_compute_vertex_normals): nine floats per triangle into out.
 void compute_vertex_normals(const float *verts, uint64_t n_tris, double crease_cos, float *out);
 // A scene file of the reference (assets/scenes/*.ron: model_path, camera(eye, look_at, fov)): the model's path resolved by

@@ -22,6 +22,11 @@ AO_TERM_DTYPE = np.dtype([("unoccluded", "<u2"), ("samples", "<u2")])
 RAY_COST_DTYPE = np.dtype([("n_node", "<u2"), ("n_tri", "<u2")])
 # trx_material: diffuse albedo and emission, linear RGB
 MATERIAL_DTYPE = np.dtype([("albedo", "<f4", 3), ("emission", "<f4", 3)])
+# trx_texture_desc: one texture of a scene's texture set
+TEXTURE_DESC_DTYPE = np.dtype([("width", "<u4"), ("height", "<u4"), ("format", "<u4"), ("filter", "<u4")])
+TEX_RGBA8_UNORM, TEX_RGBA8_SRGB = 0, 1
+TEX_NEAREST, TEX_BILINEAR = 0, 1
+NO_TEXTURE = 0xFFFFFFFF
 MISS_PRIM = 0xFFFFFFFF
 
 
@@ -65,6 +70,37 @@ def standin_materials(name, verts, counts):
     return mats, idx
 
 
+def standin_texcoords(name, verts):
+    """[n_tris, 6] f32 (s0, t0, s1, t1, s2, t2): trx_standin_texcoords - box mapping of the mesh as given (per triangle the two
+    coordinates other than the dominant axis of its face vector), in the order of verts."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 9)
+    out = np.zeros((v.shape[0], 6), dtype=np.float32)
+    L.check(L.load().trx_standin_texcoords(name.encode(), _ptr(v), v.shape[0], _ptr(out)))
+    return out
+
+
+def standin_textures(name, n_materials):
+    """(descs [n] TEXTURE_DESC_DTYPE, texels [n_texels] uint32, material_texture [n_materials] uint32): trx_standin_textures -
+    one 64 x 64 UNORM bilinear checker on material 0, NO_TEXTURE everywhere else."""
+    lib = L.load()
+    dp, tp, mp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    n, nt = C.c_uint32(), C.c_uint64()
+    L.check(lib.trx_standin_textures(name.encode(), n_materials, C.byref(dp), C.byref(n), C.byref(tp), C.byref(nt), C.byref(mp)))
+    descs = np.frombuffer(C.string_at(dp.value, n.value * TEXTURE_DESC_DTYPE.itemsize), dtype=TEXTURE_DESC_DTYPE).copy()
+    texels = np.frombuffer(C.string_at(tp.value, nt.value * 4), dtype=np.uint32).copy()
+    mat_tex = np.frombuffer(C.string_at(mp.value, n_materials * 4), dtype=np.uint32).copy()
+    for p in (dp, tp, mp):
+        lib.trx_free(p)
+    return descs, texels, mat_tex
+
+
+def texture_srgb_table():
+    """[256] f32: trx_texture_srgb_table - the sRGB decode of every byte, computed in binary64 and rounded once."""
+    out = np.zeros(256, dtype=np.float32)
+    L.load().trx_texture_srgb_table(_ptr(out))
+    return out
+
+
 def load_meshs(path):
     """load_meshs (src/main.rs:494-561): OBJ or JSON -> (verts [n,9], triangles per object)."""
     lib = L.load()
@@ -104,6 +140,35 @@ def load_model_normals(path):
     lib.trx_free(C.cast(np_, C.c_void_p))
     verts, counts = _take_mesh(vp, n, cp, nobj)
     return verts, counts, normals, bool(has.value)
+
+
+def load_model_texcoords(path):
+    """(verts [n,9], triangles per object, uvs [n,6] f32, has_texcoords): trx_load_model_texcoords - load_meshs' mesh with the
+    OBJ's `vt` record of every corner (v/vt, v/vt/vn; +0, +0 for a corner that names none or one out of range, and for every
+    corner of a JSON model); has_texcoords says whether any corner got one."""
+    lib = L.load()
+    vp, cp, up = C.POINTER(C.c_float)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_float)()
+    n, nobj, has = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    L.check(lib.trx_load_model_texcoords(str(path).encode(), C.byref(vp), C.byref(n), C.byref(cp), C.byref(nobj), C.byref(up), C.byref(has)))
+    uvs = np.ctypeslib.as_array(up, shape=(max(n.value, 1), 6))[: n.value].copy()
+    lib.trx_free(C.cast(up, C.c_void_p))
+    verts, counts = _take_mesh(vp, n, cp, nobj)
+    return verts, counts, uvs, bool(has.value)
+
+
+def load_model_material_maps(path):
+    """[n_materials] list of str: trx_load_model_material_maps - the map_Kd file name of every material in
+    load_model_materials' order, "" where a material names none (material 0 never does)."""
+    lib = L.load()
+    p, n = C.c_void_p(), C.c_uint32()
+    L.check(lib.trx_load_model_material_maps(str(path).encode(), C.byref(p), C.byref(n)))
+    out, at = [], p.value
+    for _ in range(n.value):
+        s = C.string_at(at)
+        out.append(s.decode("latin-1"))
+        at += len(s) + 1
+    lib.trx_free(p)
+    return out
 
 
 def compute_vertex_normals(verts, crease_cos=0.70710678):
@@ -467,6 +532,48 @@ class Scene:
         L.check(self._lib.trx_scene_get_vertex_normals(self._h, _ptr(out), out.shape[0]))
         return out
 
+    def set_texcoords(self, uvs):
+        """trx_scene_set_texcoords: six floats per triangle ([n_tris, 6] f32: s, t of vertices 0, 1, 2) in `prim` order (the
+        order of flat.tri_verts; coordinates in mesh order go through flat.tri_source); None removes the table.  Any float is
+        legal.  Replaces an earlier table after the scene's launches in flight.  A refit keeps it."""
+        if uvs is None:
+            L.check(self._lib.trx_scene_set_texcoords(self._h, None, 0))
+            return
+        uv = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 6)
+        L.check(self._lib.trx_scene_set_texcoords(self._h, _ptr(uv), uv.shape[0]))
+
+    def get_texcoords(self):
+        """[n_tris, 6] f32 as set, bit for bit; refused on a scene without a table."""
+        out = np.zeros((self.flat.tri_verts.shape[0], 6), dtype=np.float32)
+        L.check(self._lib.trx_scene_get_texcoords(self._h, _ptr(out), out.shape[0]))
+        return out
+
+    def set_textures(self, descs, texels, material_texture):
+        """trx_scene_set_textures: descs ([n] TEXTURE_DESC_DTYPE, or [n, 4] integers: width, height, format, filter), the RGBA8
+        words of all textures back to back (row 0 at t = 0), and one texture index or NO_TEXTURE per material; None for descs
+        removes the set (trx_scene_remove_textures).  Validated on the host; needs materials."""
+        if descs is None:
+            L.check(self._lib.trx_scene_remove_textures(self._h))
+            return
+        d = np.ascontiguousarray(descs)
+        if d.dtype != TEXTURE_DESC_DTYPE:
+            d = np.ascontiguousarray(d, dtype=np.uint32).reshape(-1, 4)
+        tx = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+        mt = np.ascontiguousarray(material_texture, dtype=np.uint32).reshape(-1)
+        L.check(self._lib.trx_scene_set_textures(self._h, _ptr(d), d.shape[0], _ptr(tx), tx.size, _ptr(mt), mt.size))
+
+    def get_textures(self):
+        """(descs [n] TEXTURE_DESC_DTYPE, texels uint32, material_texture uint32) as set; refused on a scene without a set."""
+        nt, nx, nm = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        one = np.zeros(4, dtype=np.uint32)
+        rc = self._lib.trx_scene_get_textures(self._h, _ptr(one), C.byref(nt), _ptr(one), C.byref(nx), _ptr(one), C.byref(nm))
+        if nt.value == 0:   # (no set: the refusal; otherwise the call above reported the counts and refused for room)
+            L.check(rc)
+        d = np.zeros(nt.value, dtype=TEXTURE_DESC_DTYPE)
+        tx, mt = np.zeros(nx.value, dtype=np.uint32), np.zeros(nm.value, dtype=np.uint32)
+        L.check(self._lib.trx_scene_get_textures(self._h, _ptr(d), C.byref(nt), _ptr(tx), C.byref(nx), _ptr(mt), C.byref(nm)))
+        return d, tx, mt
+
     def refit(self, tri_verts):
         """New vertices for every triangle record, in record order ([n_tris, 9] f32; record_order_verts maps object-order
         vertices): trx_scene_refit for a numpy array, trx_scene_refit_dev on torch.cuda.current_stream() for a tensor on
@@ -785,6 +892,25 @@ class Scene:
                                                            bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, bounce_stride,
                                                            bounce_phase, bounce_upsample_radius, emitter_samples, emitter_eps, _ptr(rgba),
                                                            C.byref(ms)))
+        return rgba, ms.value
+
+    def render_image_colour_textured(self, view, width, height, lights=(), emitter_samples=0, emitter_eps=0.001, smooth=False,
+                                     bounce_samples=0, bounce_stride=1, bounce_phase=0, bounce_upsample_radius=1, bounce_filter_levels=0,
+                                     bounce_depth_tol=0.1, bounce_normal_cos=0.9, bounce_eps=0.01, sem=L.SEM_HLSL, ray_mask=0, frame0=0,
+                                     light_samples=1, shadow_eps=0.01, ambient=0.0, ao_samples=0, ao_eps=0.01, ao_radius=float("inf"),
+                                     filter_radius=0, depth_tol=0.02, normal_cos=0.9):
+        """(uint8 image [height, width, 4], ms): trx_render_image_colour_textured - render_image_colour (emitter_samples 0),
+        render_image_colour_emitters (emitter_samples >= 1) and, with smooth, the shading-normal pass, with the textured
+        albedo: surface_albedo_dev after the attribute pass, trace_indirect_rgb_textured_dev, albedo_compose_dev."""
+        arr = light_array(lights)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        ms = C.c_float()
+        L.check(self._lib.trx_render_image_colour_textured(self._h, C.byref(view), width, height, sem, ray_mask, arr if len(arr) else None,
+                                                           len(arr), frame0, light_samples, shadow_eps, ambient, ao_samples, ao_eps, ao_radius,
+                                                           filter_radius, depth_tol, normal_cos, bounce_samples, bounce_eps,
+                                                           bounce_filter_levels, bounce_depth_tol, bounce_normal_cos, bounce_stride,
+                                                           bounce_phase, bounce_upsample_radius, emitter_samples, emitter_eps,
+                                                           1 if smooth else 0, _ptr(rgba), C.byref(ms)))
         return rgba, ms.value
 
     def render_heat_image(self, view, width, height, which=L.HEAT_NODES, scale=None, sem=L.SEM_HLSL):
@@ -1131,6 +1257,29 @@ class Scene:
         surface record of the scene."""
         L.check(self._lib.trx_material_compose_dev(self._h, C.c_void_p(d_primary), C.c_void_p(d_direct), C.c_void_p(d_indirect_rgb), n,
                                                    C.c_void_p(d_colour_rgb), C.c_void_p(stream)))
+
+    def surface_albedo_dev(self, d_hits, d_attr, n, d_albedo_rgb, stream=0):
+        """trx_surface_albedo_dev: three planes of n floats at d_albedo_rgb - the albedo of every hit record's material, times
+        the material's texture sampled at the record's interpolated texcoords where the scene has both tables (THE TEXTURED
+        ALBEDO, include/trx.h); +0 where the record is no surface record of the scene."""
+        L.check(self._lib.trx_surface_albedo_dev(self._h, C.c_void_p(d_hits), C.c_void_p(d_attr), n, C.c_void_p(d_albedo_rgb),
+                                                 C.c_void_p(stream)))
+
+    def albedo_compose_dev(self, d_primary, d_albedo_rgb, d_direct, n, d_colour_rgb, d_indirect_rgb=0, stream=0):
+        """trx_albedo_compose_dev: material_compose_dev with the albedo read from the planes surface_albedo_dev wrote."""
+        L.check(self._lib.trx_albedo_compose_dev(self._h, C.c_void_p(d_primary), C.c_void_p(d_albedo_rgb), C.c_void_p(d_direct),
+                                                 C.c_void_p(d_indirect_rgb), n, C.c_void_p(d_colour_rgb), C.c_void_p(stream)))
+
+    def trace_indirect_rgb_textured_dev(self, view, width, height, lights, d_primary, d_value_rgb, n_samples=1, stride=1, phase=0,
+                                        use_emitters=False, sem=L.SEM_HLSL, ray_mask=0, frame0=0, bounce_eps=0.01, shadow_eps=0.01,
+                                        emitter_eps=0.001, d_primary_inst=0, shard=(0, 1), stream=0):
+        """trx_trace_indirect_rgb_textured_dev: the four RGB modes of the indirect pass (stride 1: dense over `shard`; stride
+        2..: sparse at (stride, phase); use_emitters: rule 5e) with the albedo of every bounce hit sampled from its texture."""
+        arr = light_array(lights)
+        L.check(self._lib.trx_trace_indirect_rgb_textured_dev(self._h, C.byref(view), width, height, L.Shard(*shard), stride, phase, sem,
+                                                              ray_mask, arr if len(arr) else None, len(arr), frame0, n_samples, bounce_eps,
+                                                              shadow_eps, 1 if use_emitters else 0, emitter_eps, C.c_void_p(d_primary),
+                                                              C.c_void_p(d_primary_inst), C.c_void_p(d_value_rgb), C.c_void_p(stream)))
 
     def shade_rgb_dev(self, d_colour_rgb, n, d_rgba, stream=0):
         """trx_shade_rgb_dev: three planes of n floats as RGBA8, every channel through shade_value_dev's code table."""
